@@ -103,7 +103,14 @@ def main() -> None:
     ap.add_argument("--sets", type=int, default=0, help="steps kept in flight (sets of batches used in turn); 0 = 2 on one GPU, 4 sharded")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N > 1: strong = --docs in total, split N ways (default); weak = --docs per GPU (BASELINE config 4: 8 x 100 M)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (per stratum: rowids, weights, counts, total_found, status) "
+                         "as DIR/<name>.npy, float64; one GPU only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("MRK_FORCE_DIST")):
+        ap.error("--dump-outputs: one GPU only (sharded runs hold each query's merged rows on one rank)")
 
     # (MRK_FORCE_DIST=1 with --gpus 1 rehearses the same parent -> ranks -> JSON relay with ONE rank: the only multi-rank
     # path a one-GPU box can run)
@@ -307,6 +314,9 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:  # (before the cc batch of set 0 is reused below)
+        last = (state["i"] - 1) % n_sets
+        dump_outputs(args.dump_outputs, {g: sets[last][g].results() for g, _ in groups})
 
     # sharded runs scan all strata in one launch: time the cc launch on its own (outside the timed region) for the
     # roofline fields
@@ -538,6 +548,36 @@ def main() -> None:
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+DUMP_LIMIT = 64 << 20  # bytes of .npy data --dump-outputs may write
+
+
+def dump_outputs(out_dir: str, results: dict) -> None:
+    """Write what the timed path returned to its caller in its last step: per stratum, every query's rowids and weights
+    (concatenated in query order), its row count, total_found and status, float64 (rowids exceed float32's exact range).
+    If that would exceed DUMP_LIMIT, a fixed, seeded sample of each stratum's queries is written instead and
+    <stratum>_query.npy names them."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_stratum = (DUMP_LIMIT - 4096) // max(1, len(results))  # (less the .npy headers)
+    for g, res in results.items():
+        sel = np.arange(len(res))
+        rows = sum(len(r.rowid) for r in res)
+        if 8 * (2 * rows + 4 * len(res)) > per_stratum:
+            cap = max(1, max(len(r.rowid) for r in res))
+            keep = max(1, per_stratum // (8 * (2 * cap + 4)))
+            sel = np.sort(np.random.default_rng(0x5EED0003).choice(len(res), size=min(keep, len(res)), replace=False))
+        picked = [res[i] for i in sel]
+        arrays = {
+            "rowid": np.concatenate([r.rowid for r in picked] + [np.zeros(0, np.uint32)]),
+            "weight": np.concatenate([r.weight for r in picked] + [np.zeros(0, np.int32)]),
+            "count": np.array([len(r.rowid) for r in picked]),
+            "total_found": np.array([r.total_found for r in picked]),
+            "status": np.array([r.status for r in picked]),
+            "query": sel,
+        }
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, f"{g}_{name}.npy"), a.astype(np.float64))
 
 
 def config5_queries(m, strata, n, K, total_docs, global_docs, fw):

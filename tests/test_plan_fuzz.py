@@ -16,14 +16,14 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc builds the host-only objects")
 def test_planner_under_sanitizers(tmp_path):
-    flags = ["-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    flags = ["-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined"]
     objs = []
     for src in (os.path.join(ROOT, "manticoresearch_amd", "csrc", "mrk_plan.cpp"), os.path.join(HERE, "cpp", "fuzz_plan.cpp")):
         obj = str(tmp_path / (os.path.basename(src) + ".o"))
         subprocess.check_call([HIPCC] + flags + ["-c", src, "-o", obj])
         objs.append(obj)
     exe = str(tmp_path / "fuzz_plan")
-    subprocess.check_call([HIPCC, "-fsanitize=address,undefined"] + objs + ["-o", exe])
+    subprocess.check_call([HIPCC, "-fsanitize=address,undefined", "-fno-gpu-sanitize"] + objs + ["-o", exe])
     for seed in ("11", "12"):
         out = subprocess.run([exe, "250000", seed], capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, (out.stdout[-500:], out.stderr[-3000:])

@@ -2,7 +2,7 @@
 # tools/final_run.sh -- the end-of-round measurement set on the GPU box: GPU tests, the bench line, BASELINE config 2, and the bench under
 # rocprofv3 --kernel-trace --stats (whose per-kernel averages must agree with the bench's HIP-event times).  Output under gpurun_out/.
 set -e
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 cd $ROOT
 python -m pytest tests -x -q -m gpu > $OUT/fin_tests.log 2>&1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/final_run2.sh -- the rest of the end-of-round set: one-eighth shard (12.5 M docs) bench lines, unsharded and as ONE rank of the
 # sharded path; their kernel timelines; config 3 by kernel (stats + SQ counters + HBM traffic); config 5 by kernel.  Output: gpurun_out/.
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 cd $ROOT
 python bench.py --docs 12500000 --no-config3 --no-config5 --no-cpu-baseline > $OUT/fin_b12.json 2> $OUT/fin_b12.err; echo "b12 done"

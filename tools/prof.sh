@@ -4,7 +4,7 @@
 #   pass 2,3: --pmc (own runs, no trace domains) -> gpurun_out/prof_TAG/pmc{1,2}
 set -e
 TAG=$1; DOCS=$2; STRATA=${3:-cc}
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

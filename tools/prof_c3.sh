@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/prof_c3.sh DOCS -- SQ counters of the config-3 leg (3-term mixes, PROXIMITY_BM25) of bench.py
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_c3
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

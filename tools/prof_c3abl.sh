@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/prof_c3abl.sh SHAPE LIB... -- scan_bt_kernel / rank_kernel times of one config-3 query shape under kernel-experiment libraries
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 SHAPE=$1; shift
 cd /tmp && export TMPDIR=/tmp
 for lib in "$@"; do

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/prof_c3k.sh -- the config-3 launch alone (tools/c3_time.py): kernel stats, then two SQ counter passes, then the four query shapes one by one
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_c3k
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/prof_c3s.sh SHAPE -- kernel stats of one query shape of the config-3 launch (tools/c3_time.py --shape)
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_c3s$1
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

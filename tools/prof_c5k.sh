@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/prof_c5k.sh KIND -- kernel stats of one query kind (and2 | mix3 | phrase | all) of the config-5 launch (tools/c5_time.py)
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_c5k_$1
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/sets_sweep.sh DOCS -- the bench step at DOCS docs with 2 / 3 / 4 steps kept in flight (--sets)
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 for s in 2 3 4; do
   python $ROOT/bench.py --docs $1 --no-config3 --no-config5 --no-cpu-baseline --latency-samples 0 --sets $s 2>/dev/null > /tmp/sets_$s.json
   python3 - $s <<'PY'

@@ -4,7 +4,7 @@
 # between the scan stream and the selection / exchange streams can be read off.  Output: gpurun_out/tl_TAG/{stats.csv,timeline.txt}
 set -e
 TAG=$1; DOCS=$2; shift 2
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/tl_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/trace_dist.sh DOCS -- kernel trace of the sharded bench path with ONE rank (no launcher: env rendezvous)
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/trace_dist
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

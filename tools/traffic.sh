@@ -13,7 +13,7 @@
 # Prints the JSON for profiles/rNN_traffic.json (bench.py reads profiles/traffic.json).
 set -e
 DOCS=$1; TAG=${2:-traffic}
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -6,7 +6,7 @@
 # device format's bytes the planner counts for the same queries.
 set -e
 TAG=${1:-traffic_c3}
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
