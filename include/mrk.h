@@ -107,7 +107,8 @@ typedef struct {
   uint64_t total_docs;          /* m_iTotalDocuments */
   uint32_t skiplist_block_size; /* index setting; 32 (default) or 128 */
   uint32_t hit_format;          /* MRK_HITFMT_* */
-  uint32_t n_fields;            /* schema full-text fields (<= 32 on the device path) */
+  uint32_t n_fields;            /* schema full-text fields (<= 32 on the device path; the packed path covers all 32, with one extra
+                                   plane of field masks above 8 fields) */
   uint32_t rowid_base;          /* global docid = rowid_base + rowid for shard merges */
 } mrk_segment_desc;
 

@@ -49,6 +49,8 @@ struct DevSegment {
   const uint32_t* attrs;    // row-wise attributes (.spa rows, attr_stride dwords each) or NULL
   uint32_t attr_stride;
   const uint8_t* blobs;     // blob pool (.spb / m_dBlobs) for MVA filters or NULL; every row's blob row was bounds-checked at load
+  const uint32_t* pk_fmask; // segments with 9-32 fields: per doc slot (block*128 + i, like pk_hit) the doc's field mask -- pk_attr's
+                            // field bytes are zero there; NULL = a segment of <= 8 fields (the masks are in pk_attr)
 };
 
 struct DevFilter { // mrk_filter with the values inline

@@ -349,6 +349,7 @@ static void mrk_segment_destroy_impl(mrk_segment* s) {
   if (s->d_pk_hbase) (void)hipFree(s->d_pk_hbase);
   if (s->d_pk_attr1) (void)hipFree(s->d_pk_attr1);
   if (s->d_pk_attr2) (void)hipFree(s->d_pk_attr2);
+  if (s->d_pk_fmask) (void)hipFree(s->d_pk_fmask);
   if (s->d_dead) (void)hipFree(s->d_dead);
   if (s->d_attrs) (void)hipFree(s->d_attrs);
   if (s->d_blobs) (void)hipFree(s->d_blobs);
@@ -586,7 +587,7 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
   }
 
   // ---- packed doclists: lossless transcode of every term's .spd run (mrk_pack.cpp)
-  std::vector<uint32_t> pk_base, pk_doff, pk_delta, pk_attr, pk_hit;
+  std::vector<uint32_t> pk_base, pk_doff, pk_delta, pk_attr, pk_hit, pk_fmask;
   std::vector<uint64_t> pk_hbase;
   std::vector<uint8_t> pk_w;
   std::vector<uint64_t> pk_exc;
@@ -594,9 +595,11 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
   std::vector<uint8_t> pk_attr1;
   std::vector<uint16_t> pk_attr2; // (indexed like pk_hit; holds zeros for keywords without a bitmap, cut after the last keyword with one)
   size_t attr2_end = 0;
-  bool attr2_ok = ctx->attr_seq != 0;
+  // 9-32 fields: the wide layout, one more plane of field masks (pk_fmask); the bitmap kernels' planes are not built
+  const bool wide = d->n_fields > 8;
+  bool attr2_ok = ctx->attr_seq != 0 && !wide;
   bool attr1_ok = ctx->attr_nibbles && d->n_fields <= 4;
-  bool packed = ctx->pack && d->n_fields <= 8;
+  bool packed = ctx->pack && d->n_fields <= 32;
   if (!packed) { // no transcode, no walk by pack_term: validate every doclist before any of it reaches the VLB kernel
     const int rcv = validate_doclists(d, {});
     if (rcv != MRK_OK) {
@@ -619,7 +622,8 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
         // dense terms also get a bitmap of their doc set (the two-bitmap AND kernel, mrk_scan_bm.hip)
         const bool dense = ctx->bitmap_inv > 0 && d->total_docs > 0 && d->total_docs < (1ull << 32) &&
                            (uint64_t)d->dict[t].docs * (uint64_t)ctx->bitmap_inv >= d->total_docs;
-        if (!pack_term(d->spd, d->spd_len, d->dict[t], inl, dense ? d->total_docs : 0, pt[t], errs[t], d->total_docs, d->spp ? d->spp_len : 0)) bad = true;
+        if (!pack_term(d->spd, d->spd_len, d->dict[t], inl, dense ? d->total_docs : 0, pt[t], errs[t], d->total_docs, d->spp ? d->spp_len : 0, wide))
+          bad = true;
       }
     };
     std::vector<std::thread> th;
@@ -661,6 +665,7 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
         pk_base.reserve(nblk), pk_doff.reserve(nblk), pk_w.reserve(nblk);
         pk_delta.reserve(nd + 64), pk_attr.reserve(nblk * 64), pk_exc.reserve(ne + 1);
         pk_hit.reserve(nblk * 128), pk_hbase.reserve(nblk);
+        if (wide) pk_fmask.reserve(nblk * 128);
         for (uint32_t t = 0; t < d->n_terms; ++t) {
           PackedTerm& x = pt[t];
           HostTerm& h = s->terms[t];
@@ -676,6 +681,7 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
           pk_attr.insert(pk_attr.end(), x.attr.begin(), x.attr.end());
           pk_exc.insert(pk_exc.end(), x.exc.begin(), x.exc.end());
           pk_hit.insert(pk_hit.end(), x.hit.begin(), x.hit.end());
+          pk_fmask.insert(pk_fmask.end(), x.fmask.begin(), x.fmask.end());
           attr1_ok = attr1_ok && x.attr1_ok;
           if (attr1_ok) pk_attr1.insert(pk_attr1.end(), x.attr1.begin(), x.attr1.end());
           pk_hbase.insert(pk_hbase.end(), x.hbase.begin(), x.hbase.end());
@@ -709,7 +715,8 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
         (rc = upload(&s->d_pk_attr, pk_attr.data(), pk_attr.size() * 4, 64, ctx->stream)) != MRK_OK ||
         (rc = upload(&s->d_pk_exc, pk_exc.data(), pk_exc.size() * 8, 64, ctx->stream)) != MRK_OK ||
         (rc = upload(&s->d_pk_hit, pk_hit.data(), pk_hit.size() * 4, 64, ctx->stream)) != MRK_OK ||
-        (rc = upload(&s->d_pk_hbase, pk_hbase.data(), pk_hbase.size() * 8, 64, ctx->stream)) != MRK_OK) {
+        (rc = upload(&s->d_pk_hbase, pk_hbase.data(), pk_hbase.size() * 8, 64, ctx->stream)) != MRK_OK ||
+        (wide && (rc = upload(&s->d_pk_fmask, pk_fmask.data(), pk_fmask.size() * 4, 64, ctx->stream)) != MRK_OK)) {
       mrk_segment_destroy_impl(s);
       return rc;
     }
@@ -738,7 +745,8 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
       s->device_bytes += bm_words.size() * 4 + bm_dir.size() * 4;
     }
     s->has_packed = true;
-    s->device_bytes += pk_base.size() * 17 + pk_delta.size() * 4 + pk_attr.size() * 4 + pk_exc.size() * 8 + pk_hit.size() * 4;
+    s->wide = wide;
+    s->device_bytes += pk_base.size() * 17 + pk_delta.size() * 4 + pk_attr.size() * 4 + pk_exc.size() * 8 + pk_hit.size() * 4 + pk_fmask.size() * 4;
   }
   if ((rc = upload(&s->d_spd, d->spd, d->spd_len, 64, ctx->stream)) != MRK_OK ||
       (rc = upload(&s->d_spp, d->spp, d->spp ? d->spp_len : 0, 64, ctx->stream)) != MRK_OK ||
@@ -764,6 +772,7 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
   s->dev.pk_hbase = (const uint64_t*)s->d_pk_hbase;
   s->dev.pk_attr1 = (const uint8_t*)s->d_pk_attr1;
   s->dev.pk_attr2 = (const uint16_t*)s->d_pk_attr2;
+  s->dev.pk_fmask = (const uint32_t*)s->d_pk_fmask;
   s->dev.bm = (const uint32_t*)s->d_bm;
   s->dev.bm_dir = (const uint32_t*)s->d_bm_dir;
   s->dev.n_windows = (uint32_t)((d->total_docs + 2047) / 2048);
@@ -913,7 +922,8 @@ static uint64_t pass_max_matches(const DevQuery& P) {
 // size the batch's match queues for `chunks[q]` chunks (0 = queue unused) and point the scan arguments at them
 static int bind_match_queues(mrk_batch* b, const uint64_t chunks[3], mrk::ScanArgs& sa) {
   for (int i = 0; i < 3; ++i) {
-    const int planes = i == 2 ? mrk::MQ_GEN_PLANES : mrk::MQ_PLANES;
+    // (a segment with 9-32 fields: queues 0 / 1 carry the doc's whole field mask in one more plane)
+    const int planes = i == 2 ? mrk::MQ_GEN_PLANES : mrk::MQ_PLANES + (sa.seg.pk_fmask ? 1 : 0);
     sa.mq[i] = mrk::MatchQueue{};
     sa.mq[i].count = b->d_mq_count.p + mrk::MQ_SHARDS * i;
     if (!chunks[i]) continue;

@@ -81,6 +81,8 @@ struct mrk_segment {
   void* d_pk_hbase = nullptr;
   void* d_pk_attr1 = nullptr;
   void* d_pk_attr2 = nullptr;
+  void* d_pk_fmask = nullptr;
+  bool wide = false; // packed in the layout for 9-32 fields (pk_fmask): the scan kernel's WIDE instances, no bitmap-driven kernels
   void* d_dead = nullptr;
   void* d_attrs = nullptr; // .spa rows (mrk_segment_set_attrs)
   void* d_blobs = nullptr; // blob pool (mrk_segment_set_blobs)
@@ -119,5 +121,9 @@ int plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, b
                uint32_t qi, uint64_t& algo_bytes, uint64_t& dev_bytes, uint64_t& cand_total, bool& prox_out, bool& tree_out,
                std::vector<mrk::GenProg>& gen_progs, uint32_t rowid_max = 0xFFFFFFFFu); // gen_progs: programs of the generic evaluator (DevQuery::gen_prog indexes it); their
                                                       // work items go to items_bm with kind 2, already cut
+
+// Least and largest field-weight sum over the masks of the first nwf (<= 32) fields, the empty mask counting as 1
+// (ExtRanker_WeightSum_c's "just fake it"): the pruning bins of the weight-sum rankers.
+void weight_sum_range(const int32_t* weights, uint32_t nwf, int64_t& rmin, int64_t& rmax);
 
 } // namespace mrk

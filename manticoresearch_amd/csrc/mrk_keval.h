@@ -55,13 +55,17 @@ struct GenRes { // one node, one doc
 
 __device__ __forceinline__ uint32_t gen_pwf(uint32_t hitpos) { return hitpos & ~(1u << 23); } // HITMAN::GetPosWithField
 
-// the doc's entry in a keyword's packed arrays: hit count, field mask, its first hit
+// the doc's entry in a keyword's packed arrays: hit count, field mask (WIDE: from pk_fmask), its first hit
+template <bool WIDE = false>
 __device__ __forceinline__ void gen_open(const DevSegment& seg, const DevTerm& T, uint32_t ref, uint32_t row, uint64_t& sp, uint32_t& sc, uint32_t& tf,
                                          uint32_t& fl) {
   const uint32_t gblk = T.blk_first + ((ref >> 7) & 0xFFFFFFu), idx = ref & 127u;
   const uint32_t aw = seg.pk_attr[(uint64_t)gblk * 64 + (idx & 63u)], sh = (idx >> 6) * 8u;
   tf = (aw >> sh) & 0xffu;
-  fl = (aw >> (16u + sh)) & 0xffu;
+  if constexpr (WIDE)
+    fl = seg.pk_fmask[(uint64_t)gblk * DEVBLK + idx];
+  else
+    fl = (aw >> (16u + sh)) & 0xffu;
   if (tf == 255u) tf = exc_tf(seg, T, row);
   const uint32_t hv = seg.pk_hit[(uint64_t)gblk * DEVBLK + idx];
   sp = 0, sc = 0;
@@ -81,12 +85,13 @@ __device__ __forceinline__ GenHit gen_hit(uint32_t hitpos, uint32_t qpos, uint32
 
 // ExtTerm_T (+ ExtConditional_T for a position modifier: the doc stays as the term emitted it -- fields, tfidf of ALL its
 // hits -- once one hit is acceptable; only the acceptable hits travel on)
+template <bool WIDE = false>
 __device__ inline void gen_term(const DevSegment& seg, const DevTerm& T, uint32_t ref, uint32_t row, GenAlloc& A, GenRes& R) {
   R.p = nullptr, R.n = 0, R.tfidf = 0.0f, R.fields = 0, R.ok = false;
   if (ref == GEN_NOREF) return;
   uint64_t sp;
   uint32_t sc, tf, fl;
-  gen_open(seg, T, ref, row, sp, sc, tf, fl);
+  gen_open<WIDE>(seg, T, ref, row, sp, sc, tf, fl);
   GenHit* out = A.take(tf);
   if (!out) return;
   uint32_t n = 0;
@@ -119,6 +124,7 @@ __device__ inline void gen_merge(GenHit* out, uint32_t& n_out, const GenHit* L, 
 
 // One doc through the program.  refs[k] = the doc's place in keyword slot k's packed arrays (GEN_NOREF: not there).
 // Returns false when the root does not hold the doc; else tfidf / fields of the root and, for the state rankers, rk.
+template <bool WIDE = false>
 __device__ inline bool gen_eval(const DevSegment& seg, const DevQuery* __restrict__ Q, const GenProg* __restrict__ P, const uint32_t* refs, uint32_t row,
                                 GenAlloc& A, bool state_ranker, bool dupes, const int32_t* fw, uint32_t nw, uint32_t* qflags, float& tfidf_out,
                                 uint32_t& fields_out, int& rk_out, uint32_t near_fq_in = 65535u, uint32_t* near_m_out = nullptr) {
@@ -130,7 +136,7 @@ __device__ inline bool gen_eval(const DevSegment& seg, const DevQuery* __restric
     GenRes R;
     R.p = nullptr, R.n = 0, R.tfidf = 0.0f, R.fields = 0, R.ok = false;
     switch (N.kind) {
-      case GN_TERM: gen_term(seg, Q->t[N.kid[0]], refs[N.kid[0]], row, A, R); break;
+      case GN_TERM: gen_term<WIDE>(seg, Q->t[N.kid[0]], refs[N.kid[0]], row, A, R); break;
       case GN_MULTIAND: {
         // ExtMultiAnd_T: every keyword holds the doc; tfidf adds up in node order; the hits are the keywords' streams merged by
         // (position, query position).  The MergeHits3 quirk is kept: once one of three streams runs dry the two-stream merge tests
@@ -146,7 +152,7 @@ __device__ inline bool gen_eval(const DevSegment& seg, const DevQuery* __restric
         for (uint32_t i = 0; i < k; ++i) {
           const DevTerm& T = Q->t[N.kid[i]];
           uint32_t tf, fl;
-          gen_open(seg, T, refs[N.kid[i]], row, sp[i], sc[i], tf, fl);
+          gen_open<WIDE>(seg, T, refs[N.kid[i]], row, sp[i], sc[i], tf, fl);
           total += tf;
           mask |= fl & T.queried32;
           t += term_tfidf(tf, T.idf);
@@ -261,7 +267,7 @@ __device__ inline bool gen_eval(const DevSegment& seg, const DevQuery* __restric
         if (!(L.ok && Rr.ok)) break;
         GenRes D;
         D.p = nullptr, D.n = 0, D.ok = false;
-        if (N.aux[0] != 0xFFu) gen_term(seg, Q->t[N.aux[0]], refs[N.aux[0]], row, A, D);
+        if (N.aux[0] != 0xFFu) gen_term<WIDE>(seg, Q->t[N.aux[0]], refs[N.aux[0]], row, A, D);
         if (A.failed) break;
         GenHit* out = A.take(L.n + Rr.n);
         if (!out) break;
@@ -613,7 +619,7 @@ __device__ inline bool gen_eval(const DevSegment& seg, const DevQuery* __restric
         uint32_t have = 0, total = 0;
         bool bad = false;
         for (uint32_t i = 0; i < k; ++i) {
-          gen_term(seg, Q->t[N.kid[i]], refs[N.kid[i]], row, A, kr[i]);
+          gen_term<WIDE>(seg, Q->t[N.kid[i]], refs[N.kid[i]], row, A, kr[i]);
           if (kr[i].ok) ++have, total += kr[i].n;
           bad = bad || A.failed;
         }
@@ -731,7 +737,7 @@ __device__ inline bool gen_eval(const DevSegment& seg, const DevQuery* __restric
   rk_out = 0;
   if (state_ranker) {
     if (!root.n) return false; // ExtRanker_State_T::GetMatches: a doc without hits is never flushed (sphinxsearch.cpp:1198-1315)
-    RankState X;
+    RankStateT<WIDE ? 32 : 8> X;
     X.reset();
     for (uint32_t i = 0; i < root.n; ++i) {
       const GenHit h = root.p[i];

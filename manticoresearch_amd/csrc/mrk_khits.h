@@ -240,16 +240,53 @@ struct PhraseFsm {
 //   MATCHANY                    RankerState_MatchAny_fn                  :1577-1616  LCS + matched query positions per field
 //   WORDCOUNT                   RankerState_Wordcount_fn                 :1620-1643  field weight per hit
 //   FIELDMASK                   RankerState_Fieldmask_fn                 :1647-1668  fields that hold a hit
-// m_uLCS[field] / m_uMatchMask[field] are one byte per field in a u64 (<= 8 fields on this path).
+// m_uLCS[field] / m_uMatchMask[field] are one byte per field, eight fields per u64: NF = 8 for segments of <= 8 fields, 32 for the
+// wide ones (the instances that serve segments with 9-32 fields).
 // A doc starts from the post-Finalize state; SPH04's m_uMinExpPos survives Finalize in the reference, which cannot
 // change a doc's first hit (it either fails the delta test or both branches agree), so every doc starts it afresh.
-struct RankState {
-  uint64_t lcs, mmask;
+// one byte per field, eight fields per u64; named words, not an array: the hit pass's own small arrays stay in registers
+template <int NL> struct FieldBytes;
+template <> struct FieldBytes<1> {
+  uint64_t w0;
+  __device__ __forceinline__ void clear() { w0 = 0; }
+  __device__ __forceinline__ uint32_t get(uint32_t f) const { return (uint32_t)((w0 >> (8 * f)) & 0xffu); }
+  __device__ __forceinline__ void set(uint32_t f, uint32_t v) { w0 = (w0 & ~(0xffull << (8 * f))) | ((uint64_t)v << (8 * f)); }
+  __device__ __forceinline__ void bor(uint32_t f, uint32_t v) { w0 |= (uint64_t)v << (8 * f); }
+};
+template <> struct FieldBytes<4> {
+  uint64_t w0, w1, w2, w3;
+  __device__ __forceinline__ void clear() { w0 = w1 = w2 = w3 = 0; }
+  __device__ __forceinline__ uint32_t get(uint32_t f) const {
+    const uint32_t q = f >> 3;
+    const uint64_t w = q == 0 ? w0 : q == 1 ? w1 : q == 2 ? w2 : w3;
+    return (uint32_t)((w >> (8 * (f & 7u))) & 0xffu);
+  }
+  __device__ __forceinline__ void set(uint32_t f, uint32_t v) {
+    const uint32_t q = f >> 3, sh = 8 * (f & 7u);
+    const uint64_t m = ~(0xffull << sh), x = (uint64_t)v << sh;
+    w0 = q == 0 ? (w0 & m) | x : w0;
+    w1 = q == 1 ? (w1 & m) | x : w1;
+    w2 = q == 2 ? (w2 & m) | x : w2;
+    w3 = q == 3 ? (w3 & m) | x : w3;
+  }
+  __device__ __forceinline__ void bor(uint32_t f, uint32_t v) {
+    const uint32_t q = f >> 3;
+    const uint64_t x = (uint64_t)v << (8 * (f & 7u));
+    w0 |= q == 0 ? x : 0ull;
+    w1 |= q == 1 ? x : 0ull;
+    w2 |= q == 2 ? x : 0ull;
+    w3 |= q == 3 ? x : 0ull;
+  }
+};
+
+template <int NF = 8>
+struct RankStateT {
+  FieldBytes<NF / 8> lcs, mmask;
   uint32_t cur_lcs, min_exp_pos, head, exact, fmask;
   int exp_delta, last_pwf, wc;
   bool first;
   __device__ __forceinline__ void reset() {
-    lcs = 0, mmask = 0, cur_lcs = 0, min_exp_pos = 0, head = 0, exact = 0, fmask = 0;
+    lcs.clear(), mmask.clear(), cur_lcs = 0, min_exp_pos = 0, head = 0, exact = 0, fmask = 0;
     exp_delta = -1, last_pwf = -1, wc = 0, first = true;
   }
   // one hit: hp = position with field (no end bit), is_end = its end-of-field marker, hq = query position,
@@ -294,7 +331,7 @@ struct RankState {
         }
         exact = 0;
         fmask = hp;
-        if (f < 8 && (uint32_t)((lcs >> (8 * f)) & 0xffu) < hw) lcs = (lcs & ~(0xffull << (8 * f))) | ((uint64_t)(hw & 0xffu) << (8 * f));
+        if (f < (uint32_t)NF && lcs.get(f) < hw) lcs.set(f, hw & 0xffu);
       }
       exact |= (uint32_t)(1ull << (hq & 63u)); // 1UL << qpos stored into a DWORD: positions 32..63 add no bit
       const int dd = (int)(fmask - min_exp_pos);
@@ -303,14 +340,14 @@ struct RankState {
         min_exp_pos = fmask;
         cur_lcs = (cur_lcs + hw) & 0xffu;
         exact = 0;
-        if (f < 8 && cur_lcs > (uint32_t)((lcs >> (8 * f)) & 0xffu)) lcs = (lcs & ~(0xffull << (8 * f))) | ((uint64_t)cur_lcs << (8 * f));
+        if (f < (uint32_t)NF && cur_lcs > lcs.get(f)) lcs.set(f, cur_lcs);
       }
       return;
     } else { // the proximity family
       if (pwf > last_pwf) cur_lcs = (((delta == exp_delta) ? cur_lcs : 0u) + hw) & 0xffu;
-      if (ranker == MRK_RANK_MATCHANY && f < 8) mmask |= (uint64_t)((1u << ((hq - 1u) & 31u)) & 0xffu) << (8 * f);
+      if (ranker == MRK_RANK_MATCHANY && f < (uint32_t)NF) mmask.bor(f, (1u << ((hq - 1u) & 31u)) & 0xffu);
     }
-    if (f < 8 && cur_lcs > (uint32_t)((lcs >> (8 * f)) & 0xffu)) lcs = (lcs & ~(0xffull << (8 * f))) | ((uint64_t)cur_lcs << (8 * f));
+    if (f < (uint32_t)NF && cur_lcs > lcs.get(f)) lcs.set(f, cur_lcs);
     last_pwf = pwf;
     exp_delta = delta + (int)hspan;
   }
@@ -323,18 +360,19 @@ struct RankState {
       for (uint32_t f = 0; f < nw; ++f) wsum += weights[f];
       const int phrase_k = wsum * n_qwords; // sum of the field weights x query words
       for (uint32_t f = 0; f < nw; ++f) {
-        const uint32_t mm = (uint32_t)(mmask >> (8 * f)) & 0xffu;
-        if (mm) rk += (int)(__popc(mm) + ((int)((lcs >> (8 * f)) & 0xffu) - 1) * phrase_k) * weights[f];
+        const uint32_t mm = mmask.get(f);
+        if (mm) rk += (int)(__popc(mm) + ((int)lcs.get(f) - 1) * phrase_k) * weights[f];
       }
       return rk;
     }
     for (uint32_t f = 0; f < nw; ++f) {
-      const int l = (int)((lcs >> (8 * f)) & 0xffu);
+      const int l = (int)lcs.get(f);
       rk += (ranker == MRK_RANK_SPH04 ? 4 * l + 2 * (int)((head >> f) & 1u) + (int)((exact >> f) & 1u) : l) * weights[f];
     }
     return rk;
   }
 };
+using RankState = RankStateT<8>;
 
 // one value of the boolean-tree evaluation stack, for the two docs a lane owns
 struct TreeEnt {
@@ -386,7 +424,8 @@ __device__ __forceinline__ void notnear_filter(const uint8_t* __restrict__ spp, 
 
 // One doc's hit pass.  ref0..ref3 = where the doc sits in each keyword's packed arrays (block within the keyword << 7 |
 // slot, bit 31 = its one hit was inlined), smask = keyword slots whose hits take part, pmask = slots forming the
-// phrase (0 = none), rank = feed the state ranker (else: stop at the first phrase occurrence).
+// phrase (0 = none), rank = feed the state ranker (else: stop at the first phrase occurrence).  NF: fields of the ranker state.
+template <int NF = 8>
 __device__ __forceinline__ void hit_pass(const HitCtx& C, uint32_t ref0, uint32_t ref1, uint32_t ref2, uint32_t ref3, uint32_t smask,
                                          uint32_t pmask, bool rank, bool& ph_found, uint32_t& ph_field, int& rk_out, bool nn_partner = false) {
   // .spp cursor (0 = inlined hit / exhausted), current Hitpos_t (0 = exhausted), query position, field limit
@@ -452,7 +491,7 @@ __device__ __forceinline__ void hit_pass(const HitCtx& C, uint32_t ref0, uint32_
   uint32_t oe0 = 0, oe1 = 0, oe2 = 0, oe3 = 0;                                     // flushed run waiting for the ranker
   uint32_t olen_l = 0, olen_r = 0, opos_l = 0, opos_r = 0, ofield = 0xFFFFFFFFu, opend_i = 0, opend_n = 0, pq = C.ap0 & 0xFFFFu;
   bool pend_is_end = false;
-  RankState X;
+  RankStateT<NF> X;
   X.reset();
   const uint32_t dmask = smask & ~pmask; // keywords whose hits reach the ranker as they are
   const uint32_t cmpmask = C.quorum_hits ? ~(1u << 23) : 0xFFFFFFFFu; // ExtQuorum_c sorts its hits without the end flag
@@ -695,6 +734,7 @@ __device__ __forceinline__ void hs_advance(const uint8_t* __restrict__ spp, uint
 // under a state ranker, the bulk of hit-ranked traffic: the keywords' streams merged by (hitpos, qpos) straight into the
 // ranker.  No word state machines, run trackers or acceptors: about half the registers of hit_pass, which is what
 // lets rank_kernel keep many docs in flight per SIMD.
+template <int NF = 8>
 __device__ __forceinline__ int hit_rank_plain(const HitCtx& C, uint32_t ref0, uint32_t ref1, uint32_t ref2, uint32_t ref3, uint32_t smask) {
   uint64_t sp[MAX_PROX_TERMS];
   uint32_t sc[MAX_PROX_TERMS], sq[MAX_PROX_TERMS], sm[MAX_PROX_TERMS];
@@ -732,7 +772,7 @@ __device__ __forceinline__ int hit_rank_plain(const HitCtx& C, uint32_t ref0, ui
 #pragma unroll
   for (int t = 0; t < MAX_PROX_TERMS; ++t)
     if (on[t] && !lone[t]) hs_advance(C.spp, sp[t], sc[t], w0[t], w1[t], w2[t], w3[t], so[t]);
-  RankState X;
+  RankStateT<NF> X;
   X.reset();
   const uint32_t cmpmask = C.quorum_hits ? ~(1u << 23) : 0xFFFFFFFFu; // ExtQuorum_c sorts its hits without the end flag
   // MergeHits3 quirk (searchnode.cpp:3072-3077 + 3052-3054), as in hit_pass

@@ -10,7 +10,9 @@
 //          (offsets cost ~4 more bits per doc than deltas; the scan kernel is issue-bound, not
 //          HBM-bound, and two wave-wide prefix sums per block cost more than those bits)
 //   attrs  one word per lane: tf[l] | tf[l+64] << 8 | fields[l] << 16 | fields[l+64] << 24
-//          (tf >= 255 is stored as 255 and listed in the term's exception array; needs <= 8 fields)
+//          (tf >= 255 is stored as 255 and listed in the term's exception array; <= 8 fields)
+//   fmask  segments with 9-32 fields (the wide layout): one word per doc slot, the doc's whole field mask; the attr
+//          words then carry the tf bytes only
 // rowid[i] = base + o[i].  Everything the BM25 / NONE rankers read survives
 // exactly: rowid, hit count, low field-mask bits.
 #include "mrk_pack.h"
@@ -101,7 +103,7 @@ bool validate_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e
 }
 
 bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bool inline_hits, uint64_t bitmap_rows,
-               PackedTerm& out, std::string& err, uint64_t total_rows, uint64_t spp_len) {
+               PackedTerm& out, std::string& err, uint64_t total_rows, uint64_t spp_len, bool wide) {
   out = PackedTerm();
   if (!e.docs) return true;
   if (e.doclist_off == 0 || e.doclist_off > spd_len || e.doclist_len > spd_len - e.doclist_off) {
@@ -123,6 +125,7 @@ bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bo
   out.hit.assign((size_t)nblk * 128, 0);
   out.attr1.assign((size_t)nblk * 128, 0);
   if (bitmap_rows) out.attr2.assign((size_t)nblk * 128, 0);
+  if (wide) out.fmask.assign((size_t)nblk * 128, 0);
   out.hbase.reserve(nblk);
   uint64_t hit_position = 0; // m_uHitPosition / m_iHitlistPos (sphinx.cpp:534, 542)
   out.delta.reserve((size_t)nblk * 32 + 8);
@@ -202,7 +205,9 @@ bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bo
         err = "corrupt: truncated doclist entry";
         return false;
       }
-      if (fields > 0xFFu) {
+      if (wide)
+        out.fmask[(size_t)b * 128 + i] = fields, fields = 0; // (the attr bytes below stay zero)
+      else if (fields > 0xFFu) {
         err = "field mask wider than 8 bits";
         return false;
       }
@@ -257,7 +262,7 @@ bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bo
     err = "corrupt: doclist longer than the dictionary's doc count";
     return false;
   }
-  out.packed_bytes = out.delta.size() * 4 + out.attr.size() * 4 + (uint64_t)nblk * 9;
+  out.packed_bytes = out.delta.size() * 4 + out.attr.size() * 4 + out.fmask.size() * 4 + (uint64_t)nblk * 9;
   out.last_rowid = rowid;
   if (!want_bm) {
     out.bm.clear();

@@ -27,6 +27,8 @@ struct PackedTerm {
   std::vector<uint32_t> hit;   // 128 per block: the inlined Hitpos_t (inline format, tf == 1) or the doc's
                                // hitlist offset in .spp relative to hbase[block]
   std::vector<uint64_t> hbase; // per block: .spp position of the block's first hitlist
+  std::vector<uint32_t> fmask; // wide layout only (9-32 fields): 128 per block, the doc's field mask per slot (indexed like hit);
+                               // the attr words' field bytes stay zero
   uint64_t packed_bytes = 0;   // bytes a scan of the whole term reads (deltas + attrs + block index)
   // dense terms only (bitmap_rows != 0): the doc set as a bitmap over [0, bitmap_rows), one 2048-rowid
   // window = 64 words, plus a rank directory (docs before each group of 8 words = 256 rowids).
@@ -40,15 +42,15 @@ constexpr uint32_t BM_GROUP = 256;   // rowids per rank-directory entry
 
 // returns false and sets err on input it cannot pack; err starts with "corrupt:" when the bytes are malformed (truncated
 // entries, descending rowids, rowids >= total_rows, hitlist offsets >= spp_len; the last two only when the limit is
-// given) -- as opposed to well-formed input beyond the packed format (field masks wider than 8 bits)
+// given) -- as opposed to well-formed input beyond the packed format (field masks wider than 8 bits in the narrow layout)
 // bitmap_rows: 0 = no bitmap; else the segment's row count (every rowid of the term must be below it)
+// wide: the layout of a segment with 9-32 fields -- every mask fits, it goes to out.fmask
 bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bool inline_hits, uint64_t bitmap_rows,
-               PackedTerm& out, std::string& err, uint64_t total_rows = 0, uint64_t spp_len = 0);
+               PackedTerm& out, std::string& err, uint64_t total_rows = 0, uint64_t spp_len = 0, bool wide = false);
 
 // Validate-only walk of one term's doclist: every entry decodes, rowids ascend and stay below total_rows, hitlist
 // offsets stay below spp_len, the terminator sits where the dictionary's doc count says.  false + err ("corrupt: ...")
-// otherwise.  mrk_segment_create runs it on every doclist pack_term did not walk to the end (segments with > 8 fields,
-// pack = 0, a packing decline half way): nothing unvalidated reaches a kernel.
+// otherwise.  mrk_segment_create runs it on every doclist pack_term did not walk to the end (pack = 0, a packing decline half way): nothing unvalidated reaches a kernel.
 bool validate_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bool inline_hits, uint64_t total_rows,
                    uint64_t spp_len, std::string& err);
 

@@ -687,6 +687,36 @@ static int64_t sat_add(int64_t a, int64_t b) {
   return (int64_t)(v > lim ? lim : v < -lim ? -lim : v);
 }
 
+void mrk::weight_sum_range(const int32_t* weights, uint32_t nwf, int64_t& rmin, int64_t& rmax) {
+  rmin = INT64_MAX, rmax = INT64_MIN;
+  if (nwf <= 8) {
+    for (uint32_t m = 0; m < (1u << nwf); ++m) { // (every mask of the segment's fields; bits beyond them change nothing)
+      int64_t r = 0;
+      if (!m)
+        r = 1;
+      else
+        for (uint32_t f = 0; f < nwf; ++f)
+          if (m & (1u << f)) r += weights[f];
+      rmin = std::min(rmin, r);
+      rmax = std::max(rmax, r);
+    }
+    return;
+  }
+  // 2^nwf masks are too many to walk: the least non-empty sum takes every negative weight (or, with none, the smallest single
+  // weight), the largest every positive one (or, with none, the largest single weight); the empty mask weighs 1
+  int64_t neg = 0, pos = 0, wmin = INT64_MAX, wmax = INT64_MIN;
+  bool any_neg = false, any_pos = false;
+  for (uint32_t f = 0; f < nwf && f < 32; ++f) {
+    const int64_t w = weights[f];
+    if (w < 0) neg += w, any_neg = true;
+    if (w > 0) pos += w, any_pos = true;
+    wmin = std::min(wmin, w);
+    wmax = std::max(wmax, w);
+  }
+  rmin = std::min<int64_t>(1, any_neg ? neg : wmin);
+  rmax = std::max<int64_t>(1, any_pos ? pos : wmax);
+}
+
 // returns MRK_OK, or MRK_E_UNSUPPORTED / MRK_E_INVAL with the message set.  dq = the query's head pass
 // (index qi); further passes go to `extra` and get pass indices n_queries + position.
 int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq,
@@ -1045,7 +1075,7 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
     hi = std::isfinite(hi) ? std::min(hi, 1e12) : 1e12;
     const int64_t bm_lo = (int64_t)floor((lo + 0.5) * 1000.0) - 2, bm_hi = (int64_t)ceil((hi + 0.5) * 1000.0) + 2;
     int64_t rmin = INT64_MAX, rmax = INT64_MIN;
-    const uint32_t nwf = std::min<uint32_t>(dq.n_weights, 8u);
+    const uint32_t nwf = std::min<uint32_t>(dq.n_weights, seg->wide ? 32u : 8u);
     if (prox) {
       // sum_f LCS[f] * w[f] with 0 <= LCS[f] <= number of keywords (hit weight 1, unique keywords)
       // (a phrase occurrence weighs its word count; back-to-back occurrences can add up -- beyond 2n the bins clamp)
@@ -1068,16 +1098,7 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
       }
       if (ranker == MRK_RANK_FIELDMASK) rmin = 0, rmax = (1ll << nwf) - 1;
     } else
-      for (uint32_t m = 0; m < (1u << nwf); ++m) { // (every mask of the segment's fields; bits beyond them change nothing)
-        int64_t r = 0;
-        if (!m)
-          r = 1;
-        else
-          for (uint32_t f = 0; f < nwf; ++f)
-            if (m & (1u << f)) r += dq.weights[f];
-        rmin = std::min(rmin, r);
-        rmax = std::max(rmax, r);
-      }
+      weight_sum_range(dq.weights, nwf, rmin, rmax);
     const bool with_bm = ranker == MRK_RANK_BM25 || ranker == MRK_RANK_PROXIMITY_BM25 || ranker == MRK_RANK_SPH04;
     const int64_t iw = (int32_t)dq.index_weight;
     const int64_t sc = with_bm ? 1000 : 1, b0 = with_bm ? bm_lo : 0, b1 = with_bm ? bm_hi : 0;
@@ -1112,7 +1133,7 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
   tree_out = tree_out || !pure_and;
 
   // two dense keywords: the bitmap kernel (mrk_scan_bm.hip) walks 2048-rowid windows instead of blocks
-  if (use_packed && pure_and && !T.phrase && n == 2 && !filtered && q.n_weight_filters == 0 && (ranker == MRK_RANK_NONE || ranker == MRK_RANK_BM25) && seg->dev.bm &&
+  if (use_packed && pure_and && !T.phrase && n == 2 && !filtered && q.n_weight_filters == 0 && (ranker == MRK_RANK_NONE || ranker == MRK_RANK_BM25) && seg->dev.bm && !seg->wide &&
       seg->ctx->bitmap_inv > 0 && seg->terms[T.kws[0].term_id].bm_off != ~0ull && seg->terms[T.kws[1].term_id].bm_off != ~0ull) {
     dq.n_terms = 2;
     for (int i = 0; i < 2; ++i) fill_term(seg, T.kws[i], dq.t[i]);
@@ -1138,7 +1159,7 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
   // is then "the keyword holds the doc"); sparse keywords are fine, their window words are assembled from a block cursor.
   {
     const uint32_t all_fields = seg->n_fields >= 32 ? 0xFFFFFFFFu : (1u << seg->n_fields) - 1u;
-    bool ok = use_packed && seg->dev.bm && seg->ctx->bitmap_inv > 0 && seg->ctx->bt_cover_inv > 0 && !T.gen && !T.phrase && !T.ph_leaf && !T.quorum && !T.order &&
+    bool ok = use_packed && seg->dev.bm && !seg->wide && seg->ctx->bitmap_inv > 0 && seg->ctx->bt_cover_inv > 0 && !T.gen && !T.phrase && !T.ph_leaf && !T.quorum && !T.order &&
               !T.termpos && !T.notnear && !filtered && q.n_weight_filters == 0 && n <= MAX_PROX_TERMS && seg->total_docs < (1ull << 32) && T.nodes.size() <= 16;
     uint64_t cover_docs = 0;
     for (int k : cover) cover_docs += (uint64_t)T.kws[k].docs;
@@ -1285,7 +1306,7 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
     // at -- comes off the doc-set bitmaps, 8192 rowids per step (scan_bt_kernel), instead of the rarest word's blocks one by one
     // with a probe per doc and word; the candidates travel through the same queue to the same hit pass (rank_kernel<1>).
     // Config 5's phrase fifth spent 20 of its 36 ms per launch in the block walk.
-    if (T.phrase && p == 0 && cover.size() == 1 && use_packed && seg->dev.bm && seg->ctx->bitmap_inv > 0 && seg->ctx->bt_cover_inv > 0 && seg->ctx->bt_phrase &&
+    if (T.phrase && p == 0 && cover.size() == 1 && use_packed && seg->dev.bm && !seg->wide && seg->ctx->bitmap_inv > 0 && seg->ctx->bt_cover_inv > 0 && seg->ctx->bt_phrase &&
         pure_and && !got_dupes && !T.gen && !T.termpos && !T.notnear && !T.order && !T.quorum && !filtered && q.n_weight_filters == 0 && n >= 2 && n <= MAX_PROX_TERMS &&
         seg->total_docs < (1ull << 32) && T.nodes.size() <= 16 && (uint64_t)T.kws[cover[0]].docs * (uint64_t)seg->ctx->bt_cover_inv >= seg->total_docs) {
       const uint32_t all_fields = seg->n_fields >= 32 ? 0xFFFFFFFFu : (1u << seg->n_fields) - 1u;

@@ -15,27 +15,32 @@ namespace mrk {
 
 constexpr int RK_CBUF = 128; // candidates a wave collects before it publishes them
 
+template <int NF>
 struct __align__(16) RkWaveLds {
   uint64_t cbuf[RK_CBUF];
-  int32_t fw[8]; // the current query's per-field weights
+  int32_t fw[NF]; // the current query's per-field weights
 };
 
+template <int NF>
 struct __align__(16) RkSmem {
-  RkWaveLds w[WAVES];
+  RkWaveLds<NF> w[WAVES];
   uint32_t hist[NBINS]; // publishing scratch, one per workgroup behind hist_lock (as in scan_bm_kernel)
   uint32_t hist_lock;
   uint32_t pre[MQ_SHARDS + 1]; // chunks in the shards before shard s (filled prefixes laid end to end)
 };
 
 // MODE 0: lean (hit_rank_plain / hit_rank_prox), 1: FAT (hit_pass with the word state machines), 2: GEN (gen_eval)
-template <int MODE>
+// WIDE: a segment with 9-32 fields -- 32 field weights and ranker bytes; queues 0 / 1 carry the doc's whole field mask in one more
+// plane behind the narrow entry (the generic evaluator reads it from pk_fmask itself)
+template <int MODE, bool WIDE = false>
 __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   constexpr bool FAT = MODE == 1, GEN = MODE == 2;
-  constexpr int NP = GEN ? MQ_GEN_PLANES : MQ_PLANES; // planes of a queue entry
-  __shared__ RkSmem s;
+  constexpr int NF = WIDE ? 32 : 8;
+  constexpr int NP = GEN ? MQ_GEN_PLANES : MQ_PLANES + (WIDE ? 1 : 0); // planes of a queue entry
+  __shared__ RkSmem<NF> s;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const MatchQueue MQ = a.mq[MODE];
-  RkWaveLds& L = s.w[wave];
+  RkWaveLds<NF>& L = s.w[wave];
   if (!tid) s.hist_lock = 0;
   static_assert(MQ_SHARDS == 64, "one shard per lane of the prefix sum");
   if (wave == 0) {
@@ -190,7 +195,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
       auto U = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
       const uint32_t oq = U(Q->out_q);
       qc_nterms = U(Q->n_terms), qc_ranker = U(Q->ranker), qc_flags = U(Q->tree_flags), qc_index_weight = U(Q->index_weight);
-      qc_nw = U(Q->n_weights < 8u ? Q->n_weights : 8u);
+      qc_nw = U(Q->n_weights < (uint32_t)NF ? Q->n_weights : (uint32_t)NF);
       qc_max_qpos = U(Q->max_qpos), qc_n_qwords = U(Q->n_qwords);
       qc_gen_prog = GEN ? U(Q->gen_prog) : 0u;
       qc_nwf = U(Q->n_wfilters);
@@ -208,7 +213,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
       }
       const uint32_t k_ = U(Q->k), bm_ = U(Q->bin_mode), bs_ = U(Q->bin_shift), bl_ = U((uint32_t)Q->bin_lo), cc_ = U(Q->cand_cap);
       const uint64_t co_ = ((uint64_t)U((uint32_t)(Q->cand_off >> 32)) << 32) | U((uint32_t)Q->cand_off);
-      const int32_t wl = lane < 8 ? Q->weights[lane] : 0;
+      const int32_t wl = lane < (uint32_t)NF ? Q->weights[lane] : 0;
       if (oq != cur_oq) {
         leave_query();
         cur_oq = oq;
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
         tau_bin = 0;
       }
       wave_lds_fence();
-      if (lane < 8) L.fw[lane] = wl;
+      if (lane < (uint32_t)NF) L.fw[lane] = wl;
       wave_lds_fence();
     }
     {
@@ -259,7 +264,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
     float tfidf = GEN ? 0.0f : __uint_as_float(cur[1]);
     const uint32_t r0 = GEN ? 0u : cur[3], r1 = GEN ? 0u : cur[4], r2 = GEN ? 0u : cur[5], r3 = GEN ? 0u : cur[6];
     bool is_live = valid;
-    uint32_t fields = fa & 0xffu;
+    uint32_t fields = WIDE && !GEN ? cur[MQ_PLANES < NP ? MQ_PLANES : 0] : fa & 0xffu;
     int rk = 0;
     if (GEN) {
       if (valid) {
@@ -278,7 +283,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
         if (probe && !nearn)
           is_live = false;
         else
-          is_live = gen_eval(a.seg, a.queries + cur_pass, a.gen.progs + qc_gen_prog, refs, rowid, GA, prox_ranker, HC.dupes, L.fw, nw, a.q_flags + cur_oq, tfidf,
+          is_live = gen_eval<WIDE>(a.seg, a.queries + cur_pass, a.gen.progs + qc_gen_prog, refs, rowid, GA, prox_ranker, HC.dupes, L.fw, nw, a.q_flags + cur_oq, tfidf,
                              fields, rk, fq, &m_ins);
         if (probe) {
           if (nearn && m_ins < 64u) atomicMin(tab + m_ins, rowid);
@@ -296,7 +301,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
         const uint32_t pmask = phrase ? all_slots : (ph_leaf && (smask & ph_mask) == ph_mask) ? ph_mask : 0u;
         bool found = false;
         uint32_t ffield = 0;
-        hit_pass(HC, r0, r1, r2, r3, smask, pmask, prox_ranker, found, ffield, rk, ((fa >> 16) & 1u) != 0);
+        hit_pass<NF>(HC, r0, r1, r2, r3, smask, pmask, prox_ranker, found, ffield, rk, ((fa >> 16) & 1u) != 0);
         if (phrase) {
           is_live = found;
           fields = 1u << ffield; // the doc's field mask comes from its first occurrence (searchnode.cpp:3836)
@@ -306,7 +311,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
           rk = nterms == 2 ? hit_rank_prox<2>(HC, r0, r1, r2, r3, smask) : nterms == 3 ? hit_rank_prox<3>(HC, r0, r1, r2, r3, smask)
                                                                                        : hit_rank_prox<4>(HC, r0, r1, r2, r3, smask);
         else
-          rk = hit_rank_plain(HC, r0, r1, r2, r3, smask);
+          rk = hit_rank_plain<NF>(HC, r0, r1, r2, r3, smask);
     }
     // the match: weight, pruning bin, candidate buffer (emit_match of scan_pk_kernel)
     bool push = false;
@@ -358,7 +363,14 @@ void launch_rank(const ScanArgs& a, int which, void* stream) {
   // persistent grid: enough workgroups to fill every CU at the kernel's occupancy; late ones find the cursor past the
   // count and leave at once
   const dim3 grid(256 * 8), block(WG);
-  if (which == 2)
+  if (a.seg.pk_fmask) { // a segment with 9-32 fields
+    if (which == 2)
+      hipLaunchKernelGGL((rank_kernel<2, true>), dim3(GEN_GRID), block, 0, (hipStream_t)stream, a);
+    else if (which)
+      hipLaunchKernelGGL((rank_kernel<1, true>), grid, block, 0, (hipStream_t)stream, a);
+    else
+      hipLaunchKernelGGL((rank_kernel<0, true>), grid, block, 0, (hipStream_t)stream, a);
+  } else if (which == 2)
     hipLaunchKernelGGL(rank_kernel<2>, dim3(GEN_GRID), block, 0, (hipStream_t)stream, a);
   else if (which)
     hipLaunchKernelGGL(rank_kernel<1>, grid, block, 0, (hipStream_t)stream, a);

@@ -14,6 +14,8 @@
 #include "mrk_kpk.h"
 #include "mrk_kmq.h"
 
+#include <type_traits>
+
 #ifndef MRK_EXP
 #define MRK_EXP 0
 #endif
@@ -29,22 +31,26 @@ namespace mrk {
 constexpr int CBUF = MRK_CBUF; // candidates a wave collects before it publishes them
 constexpr int MQCAP = 128;     // matched docs a wave queues for the hit pass (processed 64 at a time)
 
-template <bool PROX, bool TREE, int NREF = MAX_PROX_TERMS>
+// WIDE: the instance for segments with 9-32 fields -- field masks come from the pk_fmask plane instead of pk_attr's bytes
+template <bool PROX, bool TREE, int NREF = MAX_PROX_TERMS, bool WIDE = false>
 struct __align__(16) PkWaveLds {
+  using Fmask = typename std::conditional<WIDE, uint32_t, uint8_t>::type;
   uint64_t cbuf[CBUF];  // candidates not yet published to the query's global list
   // proximity rankers: where each matched doc sits in the other terms' blocks (block<<7 | slot, bit 31 = lone hit)
   uint32_t href[PROX ? NREF - 1 : 1][PROX ? DEVBLK : 1];
   uint32_t tj_rowid[DEVBLK];
   uint32_t tj_attr[64];
+  uint32_t tj_fm[WIDE ? DEVBLK : 0]; // WIDE: the decoded other-term block's field masks, by slot (none in the other instances)
   // boolean trees: what each keyword contributes to each doc of the driver block (tfidf term, field bits)
   // hit rankers / PHRASE: matched docs wait here until 64 of them can go through the hit pass with every lane busy
   // (row, tfidf sum, fields | contributing keywords << 8, one hit reference per keyword)
   uint32_t mq_row[PROX ? MQCAP : 1];
   float mq_acc[PROX ? MQCAP : 1];
   uint32_t mq_fa[PROX ? MQCAP : 1];
+  uint32_t mq_fm[PROX && WIDE ? MQCAP : 0]; // WIDE: the doc's whole field mask (one more queue plane)
   uint32_t mq_ref[PROX ? NREF : 1][PROX ? MQCAP : 1];
   float kv[TREE ? MRK_MAX_AND_TERMS : 1][TREE ? DEVBLK : 4];
-  uint8_t kf[TREE ? MRK_MAX_AND_TERMS : 1][TREE ? DEVBLK : 16];
+  Fmask kf[TREE ? MRK_MAX_AND_TERMS : 1][TREE ? DEVBLK : 16];
   union {
     uint8_t map[MAPCAP];  // rowid offset -> slot of the decoded other-term block
     uint32_t hist[NBINS]; // publishing scratch: per-bin counts of the candidates being flushed
@@ -52,10 +58,10 @@ struct __align__(16) PkWaveLds {
 };
 static_assert(NBINS * 4 <= MAPCAP, "hist must fit the map area");
 
-template <bool PROX, bool TREE, int NREF = MAX_PROX_TERMS>
+template <bool PROX, bool TREE, int NREF = MAX_PROX_TERMS, bool WIDE = false>
 struct __align__(16) PkSmem {
-  PkWaveLds<PROX, TREE, NREF> w[WAVES];
-  uint32_t rank[256];
+  PkWaveLds<PROX, TREE, NREF, WIDE> w[WAVES];
+  uint32_t rank[WIDE ? 4 : 1][256]; // field-weight sum per mask; WIDE: per mask byte (the four add up)
   float tfidf[1][256]; // really [n_terms][256]: the tail lives in dynamic LDS right behind this struct
 };
 
@@ -63,11 +69,16 @@ struct __align__(16) PkSmem {
 // leaner instance (the extra code costs the three-keyword proximity mixes ~7 % even when it never executes)
 // NREF: keyword slots whose packed-array references travel with a match (more than MAX_PROX_TERMS: the instance that
 // feeds the generic evaluator's queue -- candidates, not matches, with one reference per keyword)
-template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS>
+// WIDE: segments with 9-32 fields (pk_fmask): masks from the plane, 32 field weights, and matches queued for the hit pass carry
+// the whole mask in one more plane
+template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false>
 __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
+  constexpr int NF = WIDE ? 32 : 8;
   constexpr bool GEN = NREF > MAX_PROX_TERMS;
   extern __shared__ __align__(16) uint8_t smem_raw[];
-  PkSmem<PROX, TREE, NREF>& s = *reinterpret_cast<PkSmem<PROX, TREE, NREF>*>(smem_raw);
+  using Smem = PkSmem<PROX, TREE, NREF, WIDE>;
+  using Fmask = typename PkWaveLds<PROX, TREE, NREF, WIDE>::Fmask;
+  Smem& s = *reinterpret_cast<Smem*>(smem_raw);
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   if (blockIdx.x >= a.n_items) return;
   const DevItem item = a.items[blockIdx.x];
@@ -76,7 +87,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   // its remaining work items are not worth their time -- least of all when the queue they would write to is full
   if (__hip_atomic_load(a.q_flags + Q->out_q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & QF_OVERFLOW) return;
   const uint32_t nterms = Q->n_terms, K = Q->k, ranker = Q->ranker;
-  const uint32_t nw = Q->n_weights < 8u ? Q->n_weights : 8u;
+  const uint32_t nw = Q->n_weights < (WIDE ? 32u : 8u) ? Q->n_weights : (WIDE ? 32u : 8u);
   const uint32_t index_weight = Q->index_weight;
   const DevTerm T0 = Q->t[0];
   const DevTerm T1 = Q->t[nterms > 1 ? 1 : 0];
@@ -86,7 +97,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
                                         ? nterms > 1
                                         : (ranker == MRK_RANK_WORDCOUNT || ranker == MRK_RANK_MATCHANY ||
                                            ranker == MRK_RANK_FIELDMASK || ranker == MRK_RANK_SPH04));
-  PkWaveLds<PROX, TREE, NREF>& L = s.w[wave];
+  PkWaveLds<PROX, TREE, NREF, WIDE>& L = s.w[wave];
   const uint32_t oq = Q->out_q; // logical query: several passes (driver keywords) may feed one result
   const uint32_t req_mask = TREE ? Q->req_mask : 0u, excl_mask = TREE ? Q->excl_mask : 0u;
   const uint32_t n_nodes = TREE ? Q->n_nodes : 0u;
@@ -102,15 +113,31 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
                  ap3 = PROX ? Q->ph_atoms[3] : 0u;
   // per-workgroup tables: tfidf(tf) per term, field-weight sum per mask
   for (uint32_t j = 0; j < nterms; ++j) s.tfidf[j][tid] = term_tfidf(tid, Q->t[j].idf);
-  {
+  if constexpr (!WIDE) {
     uint32_t rk = 0;
     if (!tid)
       rk = 1; // empty mask: "just fake it" (sphinxsearch.cpp:1114-1118)
     else
       for (uint32_t f = 0; f < nw; ++f)
         if (tid & (1u << f)) rk += (uint32_t)Q->weights[f];
-    s.rank[tid] = rk;
+    s.rank[0][tid] = rk;
+  } else {
+    // four tables, one per byte of the mask; the empty mask's 1 is applied where the sum is taken (rank_of)
+#pragma unroll
+    for (uint32_t by = 0; by < 4; ++by) {
+      uint32_t rk = 0;
+      for (uint32_t f = 8 * by; f < nw && f < 8 * by + 8; ++f)
+        if (tid & (1u << (f - 8 * by))) rk += (uint32_t)Q->weights[f];
+      s.rank[by][tid] = rk;
+    }
   }
+  // field-weight sum of a mask (ExtRanker_WeightSum_c, sphinxsearch.cpp:1112-1129); integer sums: the order does not matter
+  auto rank_of = [&](uint32_t m) -> uint32_t {
+    if constexpr (!WIDE)
+      return s.rank[0][m];
+    else
+      return m ? s.rank[0][m & 0xffu] + s.rank[1][(m >> 8) & 0xffu] + s.rank[2][(m >> 16) & 0xffu] + s.rank[3][m >> 24] : 1u;
+  };
   const uint32_t bin_mode = Q->bin_mode, bin_shift = Q->bin_shift;
   const int32_t bin_lo = Q->bin_lo;
   const uint32_t cand_cap = Q->cand_cap;
@@ -200,11 +227,11 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
         const int32_t bm = (int32_t)((tfidf + 0.5f) * 1000.0f);
         weight = (ranker == MRK_RANK_PROXIMITY_BM25 || ranker == MRK_RANK_SPH04) ? (uint32_t)bm + (uint32_t)rk * 1000u : (uint32_t)rk;
       } else if (ranker == MRK_RANK_PROXIMITY) {
-        weight = s.rank[fields]; // single keyword: ExtRanker_WeightSum_c<> without BM25 (sphinxsearch.cpp:4216-4217, 1131)
+        weight = rank_of(fields); // single keyword: ExtRanker_WeightSum_c<> without BM25 (sphinxsearch.cpp:4216-4217, 1131)
       } else {
         // ExtRanker_WeightSum_c<BM25>, sphinxsearch.cpp:1070, 1112-1129
         const int32_t bm = (int32_t)((tfidf + 0.5f) * 1000.0f);
-        weight = (uint32_t)bm + s.rank[fields] * 1000u;
+        weight = (uint32_t)bm + rank_of(fields) * 1000u;
       }
       weight *= index_weight; // MatchExtended, sphinx.cpp:12220
       if (EXT && Q->n_wfilters && !weight_passes_filters(Q->wfilters, Q->n_wfilters, (int32_t)weight)) is_live = false; // m_pWeightFilter (:12223-12227)
@@ -245,7 +272,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
     const MatchQueue& MQ = a.mq[GEN ? 2 : fat_q ? 1 : 0];
     const uint32_t c = mq_take(MQ, mqw);
     if (c != 0xFFFFFFFFu) {
-      uint32_t* __restrict__ d = MQ.data + (uint64_t)c * ((GEN ? MQ_GEN_PLANES : MQ_PLANES) * 64) + lane;
+      uint32_t* __restrict__ d = MQ.data + (uint64_t)c * ((GEN ? MQ_GEN_PLANES : MQ_PLANES + (WIDE ? 1 : 0)) * 64) + lane;
       const uint32_t e = from + lane; // (entries past n are stale slots; the header's count masks them)
       d[0] = L.mq_row[e];
       if (GEN) {
@@ -256,6 +283,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
         d[128] = L.mq_fa[e];
 #pragma unroll
         for (int t = 0; t < MAX_PROX_TERMS; ++t) d[192 + 64 * t] = L.mq_ref[t][e];
+        if constexpr (WIDE) d[64 * MQ_PLANES] = L.mq_fm[e];
       }
       if (lane == 0) MQ.hdr[c] = item.query | (n << 24);
     } else if (lane == 0)
@@ -336,10 +364,16 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
       uint32_t fld[2];
       float acc[2];
       bool live[2];
+      uint32_t fm0[2] = {0u, 0u};
+      if constexpr (WIDE) {
+        const uint32_t* __restrict__ fmp = a.seg.pk_fmask + (uint64_t)(T0.blk_first + b) * DEVBLK + lane;
+        fm0[0] = ok[0] ? fmp[0] : 0u;
+        fm0[1] = ok[1] ? fmp[64] : 0u;
+      }
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const uint32_t tf = (cur0.attr >> (8 * r)) & 0xffu;
-        fld[r] = (cur0.attr >> (16 + 8 * r)) & 0xffu & T0.queried32; // FitsFields
+        fld[r] = (WIDE ? fm0[r] : (cur0.attr >> (16 + 8 * r)) & 0xffu) & T0.queried32; // FitsFields
         live[r] = ok[r] && fld[r] != 0;
         float t = s.tfidf[0][tf];
         if (tf == 255u && live[r]) t = term_tfidf(exc_tf(a.seg, T0, row[r]), T0.idf);
@@ -352,7 +386,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
         for (int r = 0; r < 2; ++r) {
           pres[r] = live[r] ? 1u : 0u;
           L.kv[0][lane + 64 * r] = acc[r];
-          L.kf[0][lane + 64 * r] = (uint8_t)fld[r];
+          L.kf[0][lane + 64 * r] = (Fmask)fld[r];
         }
       }
 
@@ -405,23 +439,24 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
             present[r] = inb[r] && ((word >> bit) & 1u);
             rk[r] = cnt + (uint32_t)__popc(word & ((1u << bit) - 1u));
           }
-          uint32_t aw[2];
+          uint32_t aw[2], fw[2] = {0u, 0u};
 #pragma unroll
           for (int r = 0; r < 2; ++r) {
             const uint32_t q = present[r] ? rk[r] : 0u;
             aw[r] = a.seg.pk_attr[(uint64_t)(Tj.blk_first + (q >> 7)) * 64 + (q & 63u)];
+            if (WIDE) fw[r] = a.seg.pk_fmask[(uint64_t)(Tj.blk_first + (q >> 7)) * DEVBLK + (q & 127u)];
           }
 #pragma unroll
           for (int r = 0; r < 2; ++r) {
             const uint32_t sh = ((rk[r] >> 6) & 1u) * 8u;
             const uint32_t tfq = (aw[r] >> sh) & 0xffu;
-            const uint32_t fq = (aw[r] >> (16u + sh)) & 0xffu & Tj.queried32;
+            const uint32_t fq = (WIDE ? fw[r] : (aw[r] >> (16u + sh)) & 0xffu) & Tj.queried32;
             if (present[r] && fq != 0) {
               hit[r] = true;
               const float tvx = tfq == 255u ? term_tfidf(exc_tf(a.seg, Tj, row[r]), Tj.idf) : s.tfidf[j][tfq];
               if (TREE) {
                 L.kv[j][lane + 64 * r] = tvx;
-                L.kf[j][lane + 64 * r] = (uint8_t)fq;
+                L.kf[j][lane + 64 * r] = (Fmask)fq;
               } else {
                 acc[r] = acc[r] + tvx;
                 fld[r] |= fq;
@@ -507,6 +542,11 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
               L.tj_rowid[lane] = k0 ? e0 : INF_ROWID;
               L.tj_rowid[lane + 64] = k1 ? e1 : INF_ROWID;
               L.tj_attr[lane] = rj.attr;
+              if constexpr (WIDE) {
+                const uint32_t* __restrict__ fmp = a.seg.pk_fmask + (uint64_t)(Tj.blk_first + kj) * DEVBLK + lane;
+                L.tj_fm[lane] = k0 ? fmp[0] : 0u;
+                L.tj_fm[lane + 64] = k1 ? fmp[64] : 0u;
+              }
               if (slot_map) {
                 if (k0) L.map[f0] = (uint8_t)lane;
                 if (k1) L.map[f1] = (uint8_t)(lane + 64);
@@ -557,7 +597,10 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
               for (int r = 0; r < 2; ++r) {
                 const uint32_t sh = (pos[r] >> 6) * 8;
                 tfj[r] = (aw[r] >> sh) & 0xffu;
-                fj[r] = (aw[r] >> (16 + sh)) & 0xffu & Tj.queried32;
+                if constexpr (WIDE)
+                  fj[r] = L.tj_fm[pos[r]] & Tj.queried32;
+                else
+                  fj[r] = (aw[r] >> (16 + sh)) & 0xffu & Tj.queried32;
                 hp[r] = inr[r] && rid[r] == row[r] && fj[r] != 0;
               }
               float tv[2];
@@ -570,7 +613,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
                   const float tvx = tfj[r] == 255u ? term_tfidf(exc_tf(a.seg, Tj, row[r]), Tj.idf) : tv[r];
                   if (TREE) {
                     L.kv[j][lane + 64 * r] = tvx;
-                    L.kf[j][lane + 64 * r] = (uint8_t)fj[r];
+                    L.kf[j][lane + 64 * r] = (Fmask)fj[r];
                   } else {
                     acc[r] = acc[r] + tvx;
                     fld[r] |= fj[r];
@@ -629,7 +672,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
           if (live[r] && (pres[r] & ph_mask) == ph_mask) {
             int unused = 0;
             const uint32_t dref = ((inline_hits && ((cur0.attr >> (8 * r)) & 0xffu) == 1u) ? 0x80000000u : 0u) | (b << 7) | (lane + 64 * r);
-            hit_pass(HC, dref, L.href[0][lane + 64 * r], L.href[1][lane + 64 * r], L.href[2][lane + 64 * r], ph_mask, ph_mask, false,
+            hit_pass<NF>(HC, dref, L.href[0][lane + 64 * r], L.href[1][lane + 64 * r], L.href[2][lane + 64 * r], ph_mask, ph_mask, false,
                      ph_ok[r], ph_fld[r], unused);
           }
       }
@@ -801,6 +844,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
               L.mq_row[pos] = row[r];
               L.mq_acc[pos] = acc[r];
               // (bit 16: the doc also holds the NOTNEAR node's not-keyword -- its hits filter the must side's in the final pass)
+              if constexpr (WIDE) L.mq_fm[pos] = fld[r];
               L.mq_fa[pos] = (fld[r] & 0xffu) | ((TREE ? act[r] & 0xffu : 0xffu) << 8) | ((notnear && ((pres[r] >> HC.nn_b) & 1u)) ? 1u << 16 : 0u);
               L.mq_ref[0][pos] = ((inline_hits && ((cur0.attr >> (8 * r)) & 0xffu) == 1u) ? 0x80000000u : 0u) | (b << 7) | (lane + 64 * r);
 #pragma unroll
@@ -832,9 +876,9 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   }
 }
 
-template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS>
+template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false>
 static void launch_pk(const ScanArgs& a, size_t tail, hipStream_t st) {
-  hipLaunchKernelGGL((scan_pk_kernel<PROX, TREE, EXT, NREF>), dim3(a.n_items), dim3(WG), sizeof(PkSmem<PROX, TREE, NREF>) + tail, st, a);
+  hipLaunchKernelGGL((scan_pk_kernel<PROX, TREE, EXT, NREF, WIDE>), dim3(a.n_items), dim3(WG), sizeof(PkSmem<PROX, TREE, NREF, WIDE>) + tail, st, a);
 }
 
 void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen) {
@@ -842,7 +886,16 @@ void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree,
   if (max_terms < 1) max_terms = 1;
   const size_t tail = (size_t)(max_terms - 1) * 256 * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (gen) // candidates of the generic evaluator: the tree kernel without the in-scan hit passes, a reference per keyword
+  if (a.seg.pk_fmask) { // a segment with 9-32 fields: the same choice among the WIDE instances
+    if (gen)
+      launch_pk<true, true, true, MRK_MAX_AND_TERMS, true>(a, tail, st);
+    else if (ext)
+      launch_pk<true, true, true, MAX_PROX_TERMS, true>(a, tail, st);
+    else if (tree)
+      prox ? launch_pk<true, true, false, MAX_PROX_TERMS, true>(a, tail, st) : launch_pk<false, true, false, MAX_PROX_TERMS, true>(a, tail, st);
+    else
+      prox ? launch_pk<true, false, false, MAX_PROX_TERMS, true>(a, tail, st) : launch_pk<false, false, false, MAX_PROX_TERMS, true>(a, tail, st);
+  } else if (gen) // candidates of the generic evaluator: the tree kernel without the in-scan hit passes, a reference per keyword
     launch_pk<true, true, true, MRK_MAX_AND_TERMS>(a, tail, st);
   else if (ext) // filters alone may come with a plain AND: the EXT instance is the full tree + hit-stream kernel
     launch_pk<true, true, true>(a, tail, st);

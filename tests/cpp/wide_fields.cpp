@@ -1,0 +1,306 @@
+// wide_fields.cpp -- the host half of segments with 9-32 fields, under AddressSanitizer + UBSan on the CPU:
+//   pack    pack_term's wide layout (pk_fmask) gives back every entry's field mask, tf and rowid from the .spd bytes, in both hit
+//           formats; the narrow layout still declines such a doclist; a truncated doclist fails "corrupt:" in both layouts
+//   range   weight_sum_range equals a walk over every mask for up to 16 fields (the planner's closed form beyond 8)
+//   plan    plan_query on a 32-field stand-in segment accepts and declines exactly what it does on an 8-field twin (every shape and
+//           ranker on the same terms), never plans the bitmap kernels there, and trips no sanitizer (1u << 32 would)
+// Built and run by tests/test_wide_fields_cpu.py; no GPU, no libmrk.so: the three library symbols the planner calls are stubbed.
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../manticoresearch_amd/csrc/mrk_host_int.h"
+#include "../../manticoresearch_amd/csrc/mrk_pack.h"
+
+static char g_err[512];
+int mrk_fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof g_err, fmt, ap);
+  va_end(ap);
+  return code;
+}
+extern "C" const char* mrk_last_error(void) { return g_err; }
+extern "C" float mrk_idf(int64_t docs, int64_t total, int, int, int, float boost) { // (values do not matter here)
+  if (docs <= 0 || total <= 0) return 0.0f;
+  return logf((float)(total - docs + 1) / (float)docs) / (2.0f * logf((float)(1 + total))) * boost;
+}
+
+static uint64_t g_s = 0x9E3779B97F4A7C15ull;
+static uint64_t rnd() {
+  g_s += 0x9E3779B97F4A7C15ull;
+  uint64_t z = g_s;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+static uint32_t below(uint32_t n) { return n ? (uint32_t)(rnd() % n) : 0u; }
+
+static int g_fail = 0;
+#define CHECK(c, ...)                  \
+  do {                                 \
+    if (!(c)) {                        \
+      fprintf(stderr, __VA_ARGS__);    \
+      fprintf(stderr, "\n");           \
+      if (++g_fail > 20) exit(2);      \
+    }                                  \
+  } while (0)
+
+static void put_vlb(std::vector<uint8_t>& o, uint64_t v) { // most significant group first (sphinx.cpp's ZipInt)
+  uint8_t g[10];
+  int n = 0;
+  do g[n++] = (uint8_t)(v & 0x7f), v >>= 7;
+  while (v);
+  while (n--) o.push_back((uint8_t)(g[n] | (n ? 0x80 : 0)));
+}
+
+struct Doc {
+  uint32_t rowid, tf, mask;
+};
+
+// one doclist in either hit format; returns its dictionary entry (the doclist starts at offset 1 of spd)
+static mrk_dict_entry write_doclist(const std::vector<Doc>& docs, bool inl, std::vector<uint8_t>& spd) {
+  spd.assign(1, 0);
+  uint32_t prev = 0xFFFFFFFFu;
+  uint64_t hitpos = 0;
+  for (const Doc& d : docs) {
+    put_vlb(spd, d.rowid - prev);
+    prev = d.rowid;
+    const uint64_t hit_delta = 1 + below(50);
+    if (inl) {
+      put_vlb(spd, d.tf);
+      if (d.tf == 1) {
+        put_vlb(spd, 1 + below(1000));                          // the inlined hit's position
+        put_vlb(spd, ((uint32_t)__builtin_ctz(d.mask) << 1) | below(2)); // field << 1 | end flag
+      } else {
+        put_vlb(spd, d.mask);
+        put_vlb(spd, hit_delta);
+        hitpos += hit_delta;
+      }
+    } else {
+      put_vlb(spd, hit_delta);
+      hitpos += hit_delta;
+      put_vlb(spd, d.mask);
+      put_vlb(spd, d.tf);
+    }
+  }
+  put_vlb(spd, 0);
+  mrk_dict_entry e;
+  memset(&e, 0, sizeof e);
+  e.doclist_off = 1;
+  e.doclist_len = spd.size() - 1;
+  e.docs = (uint32_t)docs.size();
+  return e;
+}
+
+static void test_pack(int iters) {
+  for (int it = 0; it < iters; ++it) {
+    const bool inl = it & 1;
+    const uint32_t n_fields = 9 + below(24);
+    const uint32_t n = 1 + below(700);
+    std::vector<Doc> docs(n);
+    uint32_t row = below(3);
+    bool any_wide = false;
+    for (uint32_t i = 0; i < n; ++i) {
+      Doc& d = docs[i];
+      d.rowid = row;
+      row += 1 + (below(4) == 0 ? below(100000) : below(5));
+      d.tf = below(10) == 0 ? 255 + below(1000) : 1 + below(6);
+      if (inl && d.tf == 1)
+        d.mask = 1u << below(n_fields);
+      else {
+        d.mask = (uint32_t)rnd() & (n_fields >= 32 ? 0xFFFFFFFFu : (1u << n_fields) - 1u);
+        if (!d.mask) d.mask = 1u << (n_fields - 1);
+      }
+      any_wide = any_wide || d.mask > 0xFFu;
+    }
+    std::vector<uint8_t> spd;
+    const mrk_dict_entry e = write_doclist(docs, inl, spd);
+    const uint64_t rows = (uint64_t)row + 1;
+    mrk::PackedTerm pt;
+    std::string err;
+    const bool ok = mrk::pack_term(spd.data(), spd.size(), e, inl, 0, pt, err, rows, 1ull << 40, true);
+    CHECK(ok, "iteration %d: wide pack_term failed: %s", it, err.c_str());
+    if (!ok) continue;
+    const uint32_t nblk = (n + 127) / 128;
+    CHECK(pt.fmask.size() == (size_t)nblk * 128 && pt.hit.size() == pt.fmask.size(), "iteration %d: fmask plane of %zu", it, pt.fmask.size());
+    size_t exc = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t b = i / 128, sl = i % 128;
+      CHECK(pt.fmask[i] == docs[i].mask, "iteration %d doc %u: mask %08x, want %08x", it, i, pt.fmask[i], docs[i].mask);
+      const uint32_t aw = pt.attr[(size_t)b * 64 + (sl & 63)], sh = (sl >> 6) * 8;
+      CHECK(((aw >> sh) & 0xffu) == (docs[i].tf < 255 ? docs[i].tf : 255u), "iteration %d doc %u: tf byte", it, i);
+      CHECK(((aw >> (16 + sh)) & 0xffu) == 0, "iteration %d doc %u: field byte of the wide layout", it, i);
+      if (docs[i].tf >= 255) {
+        CHECK(exc < pt.exc.size() && pt.exc[exc] == (((uint64_t)docs[i].rowid << 32) | docs[i].tf), "iteration %d doc %u: tf exception", it, i);
+        ++exc;
+      }
+      // the rowid out of the bit-packed offsets: slot 2l + r holds doc l + 64r
+      const uint32_t w = pt.w[b], l = sl & 63, r = sl >> 6;
+      const uint32_t* dl = pt.delta.data() + pt.doff[b];
+      uint32_t off;
+      if (w == 0xFF)
+        off = dl[sl];
+      else {
+        const uint64_t bit = (uint64_t)(2 * l + r) * w;
+        const uint64_t v = (uint64_t)dl[bit >> 5] | ((uint64_t)dl[(bit >> 5) + 1] << 32);
+        off = w ? (uint32_t)((v >> (bit & 31)) & ((1ull << w) - 1)) : 0u;
+      }
+      CHECK(pt.base[b] + off == docs[i].rowid, "iteration %d doc %u: rowid %u, want %u", it, i, pt.base[b] + off, docs[i].rowid);
+    }
+    CHECK(exc == pt.exc.size(), "iteration %d: %zu tf exceptions, want %zu", it, pt.exc.size(), exc);
+    // the narrow layout: unchanged (declines a mask beyond 8 bits, packs the rest without a mask plane)
+    mrk::PackedTerm pn;
+    std::string errn;
+    const bool okn = mrk::pack_term(spd.data(), spd.size(), e, inl, 0, pn, errn, rows, 1ull << 40);
+    CHECK(okn == !any_wide && pn.fmask.empty(), "iteration %d: narrow pack_term %d (%s)", it, (int)okn, errn.c_str());
+    if (any_wide) CHECK(errn == "field mask wider than 8 bits", "iteration %d: narrow decline '%s'", it, errn.c_str());
+    // a truncated doclist: the same "corrupt:" answer in both layouts and from the validate-only walk
+    mrk_dict_entry et = e;
+    et.doclist_len = 1 + below((uint32_t)e.doclist_len - 1);
+    std::string ew, en, ev;
+    mrk::PackedTerm scratch;
+    const bool rw = mrk::pack_term(spd.data(), spd.size(), et, inl, 0, scratch, ew, rows, 1ull << 40, true);
+    const bool rv = mrk::validate_term(spd.data(), spd.size(), et, inl, rows, 1ull << 40, ev);
+    CHECK(!rw && !rv && ew.compare(0, 8, "corrupt:") == 0 && ev.compare(0, 8, "corrupt:") == 0, "iteration %d: truncated: wide '%s', validate '%s'", it,
+          ew.c_str(), ev.c_str());
+    (void)en;
+  }
+}
+
+static void test_range(int iters) {
+  static const int32_t wild[] = {0, 1, -1, 2, -7, 100, INT32_MAX, INT32_MIN, 1000, -1000};
+  for (int it = 0; it < iters; ++it) {
+    const uint32_t nwf = below(17);
+    int32_t w[32];
+    for (int f = 0; f < 32; ++f) w[f] = below(4) == 0 ? wild[below(10)] : (int32_t)below(21) - 10;
+    int64_t lo, hi, blo = INT64_MAX, bhi = INT64_MIN;
+    mrk::weight_sum_range(w, nwf, lo, hi);
+    for (uint32_t m = 0; m < (1u << nwf); ++m) {
+      int64_t r = m ? 0 : 1;
+      for (uint32_t f = 0; f < nwf; ++f)
+        if (m >> f & 1u) r += w[f];
+      if (r < blo) blo = r;
+      if (r > bhi) bhi = r;
+    }
+    CHECK(lo == blo && hi == bhi, "nwf %u: [%lld, %lld], every mask gives [%lld, %lld]", nwf, (long long)lo, (long long)hi, (long long)blo, (long long)bhi);
+  }
+  int32_t w[32];
+  for (int f = 0; f < 32; ++f) w[f] = f & 1 ? INT32_MIN : INT32_MAX;
+  int64_t lo, hi;
+  mrk::weight_sum_range(w, 32, lo, hi);
+  CHECK(lo == 16ll * INT32_MIN && hi == 16ll * INT32_MAX, "32 extreme weights: [%lld, %lld]", (long long)lo, (long long)hi);
+}
+
+static void test_plan(int iters, int& n_ok, int& n_uns) {
+  mrk_ctx ctx;
+  mrk_segment S;
+  static uint32_t dummy[16];
+  S.ctx = &ctx;
+  S.total_docs = 1000000;
+  S.n_fields = 32;
+  S.has_packed = true;
+  S.wide = true;
+  uint32_t blk = 0;
+  for (int t = 0; t < 20; ++t) {
+    HostTerm h;
+    h.docs = (uint32_t)(S.total_docs / (uint64_t)(t + 2));
+    h.hits = h.docs * 2;
+    h.nblocks = (h.docs + 127) / 128;
+    h.blk_first = blk;
+    blk += h.nblocks;
+    h.doclist_off = 1 + (uint64_t)t * 100000;
+    h.doclist_len = h.docs * 3ull;
+    h.packed_bytes = h.docs * 6ull;
+    h.last_rowid = (uint32_t)S.total_docs - 1 - (uint32_t)t;
+    if (t < 8) h.bm_off = (uint64_t)t * 4096, h.dir_off = (uint64_t)t * 64; // dense keywords keep their bitmaps (the scan kernel probes them)
+    S.terms.push_back(h);
+  }
+  S.dev.n_windows = (uint32_t)((S.total_docs + 2047) / 2048);
+  S.dev.pk_attr = S.dev.pk_hit = S.dev.bm = S.dev.pk_fmask = dummy;
+  mrk_segment N = S; // the narrow twin
+  N.n_fields = 8;
+  N.wide = false;
+  N.dev.pk_fmask = nullptr;
+  static const int rankers[] = {MRK_RANK_NONE, MRK_RANK_BM25, MRK_RANK_PROXIMITY, MRK_RANK_PROXIMITY_BM25, MRK_RANK_WORDCOUNT, MRK_RANK_MATCHANY,
+                                MRK_RANK_FIELDMASK, MRK_RANK_SPH04};
+  static const int ops[] = {MRK_OP_AND, MRK_OP_OR, MRK_OP_MAYBE, MRK_OP_ANDNOT, MRK_OP_PHRASE, MRK_OP_QUORUM};
+  for (int it = 0; it < iters; ++it) {
+    const int op = ops[below(6)];
+    const int nk = op == MRK_OP_ANDNOT ? 2 : op == MRK_OP_AND ? 1 + (int)below(4) : 2 + (int)below(3);
+    std::vector<mrk_node> nodes((size_t)nk + 1);
+    std::vector<int32_t> children;
+    for (int i = 0; i < nk; ++i) {
+      mrk_node& N = nodes[(size_t)i];
+      memset(&N, 0, sizeof N);
+      N.op = MRK_OP_TERM;
+      N.term_id = (int32_t)((below(5) + 5 * i) % 20); // (distinct keywords: a repeated one keeps a quorum off the device)
+      N.atom_pos = i + 1;
+      N.boost = 1.0f;
+      const uint32_t lims[] = {0xFFFFFFFFu, 1u << 8, 1u << 20, 1u << 31, (1u << 3) | (1u << 30), (uint32_t)rnd()};
+      N.field_mask = op == MRK_OP_QUORUM ? 0xFFFFFFFFu : lims[below(6)]; // (field-limited keywords in a quorum stay off the device)
+      N.term_pos = 0;
+      children.push_back(i);
+    }
+    mrk_node& R = nodes[(size_t)nk];
+    memset(&R, 0, sizeof R);
+    R.op = op;
+    R.n_children = nk;
+    R.first_child = 0;
+    R.field_mask = 0xFFFFFFFFu;
+    R.boost = 1.0f;
+    R.opt = op == MRK_OP_QUORUM ? 1 + (int)below((uint32_t)nk) : 0;
+    R.term_pos = 0;
+    int32_t fw[32];
+    for (int f = 0; f < 32; ++f) fw[f] = below(5) == 0 ? -(int32_t)below(100) : (int32_t)below(1000);
+    mrk_query q;
+    memset(&q, 0, sizeof q);
+    q.nodes = nodes.data();
+    q.n_nodes = nk + 1;
+    q.children = children.data();
+    q.root = nk;
+    const int ranker = rankers[below(8)];
+    q.ranker = ranker;
+    q.max_matches = 1 + (int)below(1000);
+    q.field_weights = fw;
+    q.n_weights = below(2) ? 32 : (int)below(33);
+    q.index_weight = 1 + (int)below(3);
+    DevQuery dq, dn;
+    std::vector<DevQuery> extra, extra_n;
+    std::vector<DevItem> items, items_bm, items_n, items_bm_n;
+    std::vector<mrk::GenProg> progs, progs_n;
+    uint64_t ab = 0, db = 0, ct = 0, abn = 0, dbn = 0, ctn = 0;
+    bool prox = false, tree = false, prox_n = false, tree_n = false;
+    const int rc = mrk::plan_query(&S, q, 128 << 10, true, dq, extra, 1, items, items_bm, 0, ab, db, ct, prox, tree, progs);
+    const std::string err_w = g_err;
+    const int rc_n = mrk::plan_query(&N, q, 128 << 10, true, dn, extra_n, 1, items_n, items_bm_n, 0, abn, dbn, ctn, prox_n, tree_n, progs_n);
+    CHECK(rc == rc_n, "iteration %d: ranker %d op %d over %d keywords: %d on the wide segment (%s), %d on the narrow one (%s)", it, ranker, op, nk, rc,
+          err_w.c_str(), rc_n, g_err);
+    if (rc == MRK_OK) {
+      ++n_ok;
+      CHECK(prox == prox_n && dq.ranker == dn.ranker, "iteration %d: a different ranker plan", it); // (the narrow twin may take the bitmap kernels)
+      for (const DevItem& I : items_bm) // (the generic evaluator's work items travel there too, kind 2)
+        CHECK(I.kind == 2, "iteration %d: bitmap kernels planned for a wide segment", it);
+      CHECK(dq.n_weights == 32, "iteration %d: %u weights", it, dq.n_weights);
+    } else {
+      ++n_uns;
+      CHECK(rc == MRK_E_UNSUPPORTED, "iteration %d: rc %d (%s)", it, rc, err_w.c_str());
+    }
+  }
+}
+
+int main(int argc, char** argv) {
+  const int iters = argc > 1 ? atoi(argv[1]) : 2000;
+  if (argc > 2) g_s = strtoull(argv[2], nullptr, 0);
+  test_pack(iters);
+  test_range(iters);
+  int n_ok = 0, n_uns = 0;
+  test_plan(iters * 5, n_ok, n_uns);
+  printf("ok %d unsupported %d failures %d\n", n_ok, n_uns, g_fail);
+  return g_fail ? 1 : 0;
+}
