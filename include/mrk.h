@@ -206,6 +206,7 @@ typedef struct {
   uint64_t n_items_bm;    /* of n_items: work items of the two-bitmap AND kernel (dense keywords) */
   float plan_ms;          /* host: query planning inside mrk_batch_submit */
   float submit_ms;        /* host: whole mrk_batch_submit call */
+  uint32_t n_rerun;       /* queries the last mrk_batch_wait ran again alone (their match queue or candidate list was full) */
 } mrk_batch_stats;
 
 const char* mrk_last_error(void);
@@ -307,7 +308,8 @@ int mrk_batch_create(mrk_ctx* ctx, uint32_t max_queries, mrk_batch** out);
 void mrk_batch_destroy(mrk_batch* b);
 /* plan on host, copy descriptors, launch kernels, start the result copy; returns at once */
 int mrk_batch_submit(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n_queries);
-/* block until the results of the last submit are in host memory */
+/* block until the results of the last submit are in host memory; a query that fails here (its result's status != MRK_OK,
+   e.g. out of generic-evaluator memory) leaves the reason in mrk_last_error() */
 int mrk_batch_wait(mrk_batch* b);
 /* has the device finished the last submit?  MRK_OK = yes (mrk_batch_wait returns without blocking), 1 = not yet.  A stream
    query on the CALLING thread (no hop to the submission thread: a polling loop must not queue behind other callers'

@@ -1532,6 +1532,7 @@ static int mrk_batch_wait_impl(mrk_batch* b) {
   if (hipEventElapsedTime(&ms, b->ev_scan0, b->ev_scan1) == hipSuccess) b->stats.scan_ms = ms;
   if (hipEventElapsedTime(&ms, b->ev_scan1, b->ev_merge1) == hipSuccess) b->stats.merge_ms = ms;
   b->stats.n_cands = 0;
+  b->stats.n_rerun = 0;
   if (b->packed_run)
     for (uint32_t i = 0; i < b->n_queries; ++i) b->stats.n_cands += b->h_cand_n.p[i];
   if (b->packed_run)
@@ -1545,6 +1546,7 @@ static int mrk_batch_wait_impl(mrk_batch* b) {
       else if (b->h_flags.p[i] & QF_OVERFLOW) {
         // more matches tied at the pruning threshold than the candidate list holds (e.g. millions of docs with the
         // very same weight): run the query again, alone, with room for every doc its drivers can deliver
+        ++b->stats.n_rerun;
         const int rc = rerun_overflowed(b, i);
         if (rc != MRK_OK) b->status[i] = rc;
       }
@@ -1774,7 +1776,8 @@ struct mrk_worker {
   }
 };
 
-// run f (-> int status) on the context's worker and hand back its status; the worker's error text travels with it
+// run f (-> int status) on the context's worker and hand back its status; the worker's error text travels with it -- also
+// when f succeeds but set one (a query that failed inside mrk_batch_wait: its status says so, mrk_last_error() says why)
 template <typename F>
 static int on_worker(mrk_ctx* c, F&& f) {
   mrk_worker* w = c ? c->worker : nullptr;
@@ -1788,8 +1791,9 @@ static int on_worker(mrk_ctx* c, F&& f) {
   {
     std::lock_guard<std::mutex> lk(w->mu);
     w->q.emplace_back([&] {
+      g_err[0] = 0;
       rc = f();
-      if (rc != MRK_OK) memcpy(err, g_err, sizeof err);
+      if (g_err[0]) memcpy(err, g_err, sizeof err);
       std::lock_guard<std::mutex> lk2(m);
       done = true;
       cv.notify_one();
@@ -1800,7 +1804,7 @@ static int on_worker(mrk_ctx* c, F&& f) {
     std::unique_lock<std::mutex> lk(m);
     cv.wait(lk, [&] { return done; });
   }
-  if (rc != MRK_OK) memcpy(g_err, err, sizeof g_err);
+  if (err[0]) memcpy(g_err, err, sizeof g_err);
   return rc;
 }
 
