@@ -7,7 +7,13 @@ selective x selective thirds.  The query file holds 10 000 queries (SURVEY 8(d),
 cut into sets of 3 x 256; a "step" = one set: one batch (kernel launch) per stratum, the sets taken
 in turn.  Index segments are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--docs D] [--queries Q]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--docs D] [--queries Q] [--full]
+
+A plain run does what the headline needs: it builds the corpus and the query file, warms up, times the steps, writes
+--dump-outputs if asked and prints the JSON line (with the per-stratum figures of the timed launches and the segment's
+footprint).  --full adds what takes work of its own after the timed region: the roofline (the cc sets run once more,
+their bytes counted on the host, the committed traffic measurement), single-query latency, BASELINE configs 3 and 5 and
+the CPU baseline.
 
 N > 1, one rank per GPU: the corpus is split into N rowid-range shards (strong scaling: total docs
 fixed; `--scaling weak` keeps --docs per GPU instead), every rank scans its shard, partial top-K
@@ -40,6 +46,19 @@ SELECTIVE = (1e-4, 3e-3)   # ... of "selective" terms
 QUERY_SEED = 0x5EED0002
 CORPUS_SEED = 0x5EED0001
 QUERY_FILE = 10_000        # queries per config; the steps cycle through them
+
+
+def usable_cpus() -> int:
+    """CPUs this process may really use: its affinity, capped by a cgroup CPU quota.  The corpus generator runs this many
+    threads (its postings do not depend on the count); its default, the machine's core count, may be many times the quota."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        q, p = open("/sys/fs/cgroup/cpu.max").read().split()
+        if q != "max":
+            n = max(1, min(n, int(q) // int(p)))
+    except (OSError, ValueError):
+        pass
+    return n
 
 
 def zipf_c() -> float:
@@ -89,15 +108,17 @@ def main() -> None:
     ap.add_argument("--queries", type=int, default=256, help="queries per stratum per step")
     ap.add_argument("--item-bytes", type=int, default=0)
     ap.add_argument("--skiplist-block", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the oracle timing sample")
-    ap.add_argument("--latency-samples", type=int, default=96)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline, single-query latency, configs 3 and 5 and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the oracle timing sample (--full)")
+    ap.add_argument("--latency-samples", type=int, default=96, help="single-query latency samples (--full)")
     ap.add_argument("--strata", default="cc,sc,ss", help="subset of strata to run (profiling aid; the metric uses all three)")
     ap.add_argument("--path", type=int, default=0, help="0 = packed doclists (default), 1 = VLB-direct")
     ap.add_argument("--attr-nibbles", action="store_true", help="build the one-byte tf/field plane (ctx key attr_nibbles)")
     ap.add_argument("--ctx", action="append", default=[], metavar="KEY=VALUE", help="context tunable (mrk_ctx_set), e.g. attr_seq=0")
-    ap.add_argument("--no-config3", action="store_true", help="skip the extra 3-term AND/OR mix leg (BASELINE config 3)")
-    ap.add_argument("--no-config5", action="store_true", help="skip the extra Zipf-mix leg with PHRASE + field weights, 1024 queries per launch (BASELINE config 5, one GPU's share)")
+    ap.add_argument("--no-config3", action="store_true", help="--full without the extra 3-term AND/OR mix leg (BASELINE config 3)")
+    ap.add_argument("--no-config5", action="store_true", help="--full without the extra Zipf-mix leg with PHRASE + field weights, 1024 queries per launch (BASELINE config 5, one GPU's share)")
     ap.add_argument("--config5-docs", type=int, default=125_000_000, help="docs of the config-5 leg's corpus (one eighth of 1 B)")
     ap.add_argument("--query-file", type=int, default=QUERY_FILE, help="queries in the query file the steps cycle through")
     ap.add_argument("--sets", type=int, default=0, help="steps kept in flight (sets of batches used in turn); 0 = 2 on one GPU, 4 sharded")
@@ -158,9 +179,11 @@ def main() -> None:
     corpus_docs = args.docs * world if args.scaling == "weak" else args.docs
     row0 = rank * corpus_docs // world
     shard_docs = (rank + 1) * corpus_docs // world - row0
-    hi = m.synth_index(shard_docs, probs, seed=CORPUS_SEED, rowid_base=row0, skiplist_block_size=args.skiplist_block)
+    hi = m.synth_index(shard_docs, probs, seed=CORPUS_SEED, rowid_base=row0, skiplist_block_size=args.skiplist_block,
+                       n_threads=usable_cpus())
     t_gen = time.time() - t_setup
 
+    t_dev = time.time()
     ctx = m.Context(local_rank)
     # the main corpus is written WITHOUT field-end flags, config 5's with the flag on the hit at a field's last position whatever the
     # word (what the reference's indexer writes): in both, hits at one position reach the ranker in query-position order and the tighter of
@@ -174,6 +197,7 @@ def main() -> None:
     for kv in args.ctx:
         ctx.set(kv.split("=")[0], int(kv.split("=")[1]))
     seg = m.Segment(ctx, hi, rowid_base=row0)
+    t_dev = time.time() - t_dev
     batch = m.Batch(ctx, args.queries)
     sharded = world > 1 or force_dist
     state = {"i": 0, "pending": [], "rec": [False] * 8}
@@ -318,135 +342,115 @@ def main() -> None:
         last = (state["i"] - 1) % n_sets
         dump_outputs(args.dump_outputs, {g: sets[last][g].results() for g, _ in groups})
 
-    # sharded runs scan all strata in one launch: time the cc launch on its own (outside the timed region) for the
-    # roofline fields
-    if "cc" not in names:
-        prepared["cc"] = [m.prepare([mkq(a, b) for a, b in qset("cc", k_)]) for k_ in range(n_qsets)]
-        per.setdefault("cc", {"scan_ms": 0.0, "merge_ms": 0.0, "algo_bytes": 0, "n": 0})
-    if sharded or "cc" not in names:
-        for k_ in range(min(n_qsets, 4)):
-            batch.submit_prepared(seg, prepared["cc"][k_], nq)
-            batch.wait()
-            record_stats("cc", batch.stats())
-    # every cc set once more for its results: 8 B per returned match are output bytes, total_found checks the host-side count
-    res_cc_sets = []
-    for k_ in range(n_qsets):
-        batch.submit_prepared(seg, prepared["cc"][k_], nq)
-        batch.wait()
-        res_cc_sets.append(batch.results())
-
-    # single-query latency (batch of one), p50 over a stratified sample
-    lat = []
-    if rank == 0 and world == 1 and args.latency_samples > 0:
-        sample = []
-        per_s = max(1, args.latency_samples // 3)
-        for s in names:
-            sample += [mkq(a, b) for a, b in strata[s][:per_s]]
-        singles = [m.prepare([q]) for q in sample]
-        for cq in singles[:3]:
-            batch.submit_prepared(seg, cq, 1)
-            batch.wait()
-        for cq in singles:
-            t1 = time.perf_counter()
-            batch.submit_prepared(seg, cq, 1)
-            batch.wait()
-            lat.append((time.perf_counter() - t1) * 1e3)
-
     total_queries = len(names) * nq * args.steps
     qps = total_queries / elapsed
-    cc = per["cc"]
-    scan_ms = cc["scan_ms"] / max(1, cc["n"])
-    # which kernel carried the cc launch: the two-bitmap AND kernel (dense keywords) or the block scan
-    bm_share = cc.get("n_items_bm", 0) / max(1, cc.get("n_items", 1))
-    kernel_tag = "bm" if bm_share > 0.5 else ("pk" if cc.get("packed") else "vlb")
-    # algorithmic bytes of the launch = SUM over its queries of min(B_ref(q), B_dev(q)):
-    #   B_ref(q) = the two doclists in the reference's VLB format (CSphDictEntry::m_iDoclistLength) + 8 B per returned match
-    #   B_dev(q) = what the device format makes the kernel read: both bitmaps (256 B per 2048-rowid window each) + the
-    #              128-byte lines of tf / field words the MATCHED docs' slots touch in each keyword's packed array
-    #              (counted on the host from the two doclists, mrk_host_index_pair_stats) + 8 B per returned match
-    algo_detail = None
-    out_bytes = sum(8 * len(r.rowid) for rs in res_cc_sets for r in rs) / max(1, len(res_cc_sets))
-    if kernel_tag == "bm" and rank == 0:
-        # per launch = the AVERAGE over the query file's cc sets (every one of them was timed in the loop, the same number of times
-        # when --steps is a multiple of the set count)
-        t_ps = time.time()
-        nwin = (shard_docs + 2047) // 2048
-        seq_plane = not args.attr_nibbles and not any(kv.startswith("attr_seq=0") for kv in args.ctx)
-        tot = {"algo": 0, "ref": 0, "dev": 0, "ref_smaller": 0, "bitmap": 0, "lines": 0, "full": 0}
-        for k_ in range(n_qsets):
-            pairs_k, res_k = qset("cc", k_), res_cc_sets[k_]
-            ps = m.pair_stats(hi, pairs_k)
-            b_ref = [int(hi.dict[a]["doclist_len"]) + int(hi.dict[b]["doclist_len"]) + 8 * len(r.rowid) for (a, b), r in zip(pairs_k, res_k)]
-            # the 128-byte lines the matched docs' slots touch in the plane the launched kernel gathers from: the slot-ordered
-            # two-byte plane (default), the one-byte plane (--attr-nibbles) or the block decoder's interleaved words (attr_seq=0)
-            line = [(p[5] + p[6]) if args.attr_nibbles else (p[7] + p[8]) if seq_plane else (p[3] + p[4]) for p in ps]
-            b_dev = [2 * nwin * 256 + 128 * ln + 8 * len(r.rowid) for ln, r in zip(line, res_k)]
-            if not os.environ.get("MRK_LIB_PATH"):  # (kernel-experiment libraries may skip the scoring step)
-                assert all(p[0] == r.total_found for p, r in zip(ps, res_k)), "host intersection and device total_found disagree"
-            tot["algo"] += sum(min(x, y) for x, y in zip(b_ref, b_dev))
-            tot["ref"] += sum(b_ref)
-            tot["dev"] += sum(b_dev)
-            tot["ref_smaller"] += sum(x < y for x, y in zip(b_ref, b_dev))
-            tot["bitmap"] += 2 * nwin * 256 * len(ps)
-            tot["lines"] += 128 * sum(line)
-            tot["full"] += sum(((p[1] + 127) // 128 + (p[2] + 127) // 128) * (128 if args.attr_nibbles else 256) for p in ps)
-        algo = tot["algo"] / n_qsets
-        algo_detail = {"sets_averaged": n_qsets, "sum_min_per_query": int(algo), "sum_B_ref": int(tot["ref"] / n_qsets), "sum_B_dev": int(tot["dev"] / n_qsets),
-                       "queries_where_ref_is_smaller_per_set": round(tot["ref_smaller"] / n_qsets, 1),
-                       "bitmap_bytes": int(tot["bitmap"] / n_qsets), "attr_line_bytes_touched": int(tot["lines"] / n_qsets),
-                       "attr_plane": "one byte per posting" if args.attr_nibbles else "two bytes per posting, slot order" if seq_plane else "interleaved block words",
-                       "attr_bytes_if_every_word_were_read": int(tot["full"] / n_qsets), "host_count_s": round(time.time() - t_ps, 1)}
-    else:
-        algo = min(cc["algo_bytes"], cc.get("dev_bytes", cc["algo_bytes"])) / max(1, cc["n"]) + out_bytes
-    achieved = algo / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
-    traffic, traffic_src, measured_strata = None, None, {}
-    kernel_name = {"bm": "mrk::scan_bm_kernel", "pk": "mrk::scan_pk_kernel", "vlb": "mrk::scan_kernel"}[kernel_tag]
-    device_format = {"bm": "doc-set bitmaps (2048-rowid windows) + packed tf/field bytes gathered by rank",
-                     "pk": "packed 128-doc blocks (bit-packed rowid offsets + tf/field bytes)",
-                     "vlb": "reference .spd VLB"}[kernel_tag]
-    tr_path = os.path.join(ROOT, "profiles", "traffic.json")
-    ksha = kernel_sources_sha()
-    if os.path.exists(tr_path):
-        try:
-            tj = json.load(open(tr_path))
-            if (tj.get("docs") == args.docs and tj.get("queries") == nq and tj.get("skiplist_block") == args.skiplist_block
-                    and tj.get("kernel_tag") == kernel_tag and not args.attr_nibbles):
-                if tj.get("kernel_sources_sha") == ksha:
-                    traffic = tj.get("traffic_bytes_per_launch")
-                    traffic_src = ("profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this configuration and of THESE kernel sources "
-                                   f"(sha {ksha}; tools/traffic.sh), calibrated on known-size kernels in this kernel's access patterns; "
-                                   "a PMC pass cannot run inside this process")
-                    measured_strata = tj.get("strata", {})
-                else:  # measured on other kernel sources: not this run's kernel -- say so instead of reporting it
-                    traffic_src = (f"profiles/traffic.json was measured at kernel sources {tj.get('kernel_sources_sha')}, this run has {ksha}: "
-                                   "stale, not reported (re-run tools/traffic.sh)")
-        except Exception:
-            traffic = None
 
-    out = {
-        "metric": "queries/sec, 2-term AND BM25 top-1000 (p50 latency in p50_latency_ms)",
-        "value": round(qps, 1),
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "u8 postings -> u32 rowids, f32 BM25, i32 weights",
-        "data": "synthetic",
-        "config": {
-            "workload": f"{corpus_docs // 1_000_000}M docs (Zipf s=1, V=2^20, {AVG_TERMS_PER_DOC:.0f} terms/doc), 2-term AND, "
-                        f"SPH_RANK_BM25, top-{K}, {3 * nq} queries/step in 3 strata (cc/sc/ss) out of a {n_qsets * 3 * nq}-query file, "
-                        f"skiplist_block_size={args.skiplist_block}, inline hits",
-            "docs": corpus_docs,
-            "shards": world,
-            "queries_per_step": 3 * nq,
-            "k": K,
-            "query_file": f"{n_qsets * 3 * nq} queries (seed {QUERY_SEED:#x}) in {n_qsets} sets of 3 x {nq}; step i runs set i mod {n_qsets}",
-        },
-        "roofline": {
+    # --full: the roofline of the cc launch, single-query latency (work of their own after the timed region); a plain run
+    # reports neither
+    roofline, measured_strata, lat = None, {}, []
+    if args.full:
+        # sharded runs scan all strata in one launch: time the cc launch on its own (outside the timed region) for the
+        # roofline fields
+        if "cc" not in names:
+            prepared["cc"] = [m.prepare([mkq(a, b) for a, b in qset("cc", k_)]) for k_ in range(n_qsets)]
+            per.setdefault("cc", {"scan_ms": 0.0, "merge_ms": 0.0, "algo_bytes": 0, "n": 0})
+        if sharded or "cc" not in names:
+            for k_ in range(min(n_qsets, 4)):
+                batch.submit_prepared(seg, prepared["cc"][k_], nq)
+                batch.wait()
+                record_stats("cc", batch.stats())
+        # every cc set once more for its results: 8 B per returned match are output bytes, total_found checks the host-side count
+        res_cc_sets = []
+        for k_ in range(n_qsets):
+            batch.submit_prepared(seg, prepared["cc"][k_], nq)
+            batch.wait()
+            res_cc_sets.append(batch.results())
+
+        # single-query latency (batch of one), p50 over a stratified sample
+        if rank == 0 and world == 1 and args.latency_samples > 0:
+            sample = []
+            per_s = max(1, args.latency_samples // 3)
+            for s in names:
+                sample += [mkq(a, b) for a, b in strata[s][:per_s]]
+            singles = [m.prepare([q]) for q in sample]
+            for cq in singles[:3]:
+                batch.submit_prepared(seg, cq, 1)
+                batch.wait()
+            for cq in singles:
+                t1 = time.perf_counter()
+                batch.submit_prepared(seg, cq, 1)
+                batch.wait()
+                lat.append((time.perf_counter() - t1) * 1e3)
+
+        cc = per["cc"]
+        scan_ms = cc["scan_ms"] / max(1, cc["n"])
+        # which kernel carried the cc launch: the two-bitmap AND kernel (dense keywords) or the block scan
+        bm_share = cc.get("n_items_bm", 0) / max(1, cc.get("n_items", 1))
+        kernel_tag = "bm" if bm_share > 0.5 else ("pk" if cc.get("packed") else "vlb")
+        # algorithmic bytes of the launch = SUM over its queries of min(B_ref(q), B_dev(q)):
+        #   B_ref(q) = the two doclists in the reference's VLB format (CSphDictEntry::m_iDoclistLength) + 8 B per returned match
+        #   B_dev(q) = what the device format makes the kernel read: both bitmaps (256 B per 2048-rowid window each) + the
+        #              128-byte lines of tf / field words the MATCHED docs' slots touch in each keyword's packed array
+        #              (counted on the host from the two doclists, mrk_host_index_pair_stats) + 8 B per returned match
+        algo_detail = None
+        out_bytes = sum(8 * len(r.rowid) for rs in res_cc_sets for r in rs) / max(1, len(res_cc_sets))
+        if kernel_tag == "bm" and rank == 0:
+            # per launch = the AVERAGE over the query file's cc sets (every one of them was timed in the loop, the same number of times
+            # when --steps is a multiple of the set count)
+            t_ps = time.time()
+            nwin = (shard_docs + 2047) // 2048
+            seq_plane = not args.attr_nibbles and not any(kv.startswith("attr_seq=0") for kv in args.ctx)
+            tot = {"algo": 0, "ref": 0, "dev": 0, "ref_smaller": 0, "bitmap": 0, "lines": 0, "full": 0}
+            for k_ in range(n_qsets):
+                pairs_k, res_k = qset("cc", k_), res_cc_sets[k_]
+                ps = m.pair_stats(hi, pairs_k)
+                b_ref = [int(hi.dict[a]["doclist_len"]) + int(hi.dict[b]["doclist_len"]) + 8 * len(r.rowid) for (a, b), r in zip(pairs_k, res_k)]
+                # the 128-byte lines the matched docs' slots touch in the plane the launched kernel gathers from: the slot-ordered
+                # two-byte plane (default), the one-byte plane (--attr-nibbles) or the block decoder's interleaved words (attr_seq=0)
+                line = [(p[5] + p[6]) if args.attr_nibbles else (p[7] + p[8]) if seq_plane else (p[3] + p[4]) for p in ps]
+                b_dev = [2 * nwin * 256 + 128 * ln + 8 * len(r.rowid) for ln, r in zip(line, res_k)]
+                if not os.environ.get("MRK_LIB_PATH"):  # (kernel-experiment libraries may skip the scoring step)
+                    assert all(p[0] == r.total_found for p, r in zip(ps, res_k)), "host intersection and device total_found disagree"
+                tot["algo"] += sum(min(x, y) for x, y in zip(b_ref, b_dev))
+                tot["ref"] += sum(b_ref)
+                tot["dev"] += sum(b_dev)
+                tot["ref_smaller"] += sum(x < y for x, y in zip(b_ref, b_dev))
+                tot["bitmap"] += 2 * nwin * 256 * len(ps)
+                tot["lines"] += 128 * sum(line)
+                tot["full"] += sum(((p[1] + 127) // 128 + (p[2] + 127) // 128) * (128 if args.attr_nibbles else 256) for p in ps)
+            algo = tot["algo"] / n_qsets
+            algo_detail = {"sets_averaged": n_qsets, "sum_min_per_query": int(algo), "sum_B_ref": int(tot["ref"] / n_qsets), "sum_B_dev": int(tot["dev"] / n_qsets),
+                           "queries_where_ref_is_smaller_per_set": round(tot["ref_smaller"] / n_qsets, 1),
+                           "bitmap_bytes": int(tot["bitmap"] / n_qsets), "attr_line_bytes_touched": int(tot["lines"] / n_qsets),
+                           "attr_plane": "one byte per posting" if args.attr_nibbles else "two bytes per posting, slot order" if seq_plane else "interleaved block words",
+                           "attr_bytes_if_every_word_were_read": int(tot["full"] / n_qsets), "host_count_s": round(time.time() - t_ps, 1)}
+        else:
+            algo = min(cc["algo_bytes"], cc.get("dev_bytes", cc["algo_bytes"])) / max(1, cc["n"]) + out_bytes
+        achieved = algo / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
+        traffic, traffic_src = None, None
+        kernel_name = {"bm": "mrk::scan_bm_kernel", "pk": "mrk::scan_pk_kernel", "vlb": "mrk::scan_kernel"}[kernel_tag]
+        device_format = {"bm": "doc-set bitmaps (2048-rowid windows) + packed tf/field bytes gathered by rank",
+                         "pk": "packed 128-doc blocks (bit-packed rowid offsets + tf/field bytes)",
+                         "vlb": "reference .spd VLB"}[kernel_tag]
+        tr_path = os.path.join(ROOT, "profiles", "traffic.json")
+        ksha = kernel_sources_sha()
+        if os.path.exists(tr_path):
+            try:
+                tj = json.load(open(tr_path))
+                if (tj.get("docs") == args.docs and tj.get("queries") == nq and tj.get("skiplist_block") == args.skiplist_block
+                        and tj.get("kernel_tag") == kernel_tag and not args.attr_nibbles):
+                    if tj.get("kernel_sources_sha") == ksha:
+                        traffic = tj.get("traffic_bytes_per_launch")
+                        traffic_src = ("profiles/traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this configuration and of THESE kernel sources "
+                                       f"(sha {ksha}; tools/traffic.sh), calibrated on known-size kernels in this kernel's access patterns; "
+                                       "a PMC pass cannot run inside this process")
+                        measured_strata = tj.get("strata", {})
+                    else:  # measured on other kernel sources: not this run's kernel -- say so instead of reporting it
+                        traffic_src = (f"profiles/traffic.json was measured at kernel sources {tj.get('kernel_sources_sha')}, this run has {ksha}: "
+                                       "stale, not reported (re-run tools/traffic.sh)")
+            except Exception:
+                traffic = None
+        roofline = {
             "bound": "hbm",
             "achieved": round(achieved, 1),
             "peak": HBM_PEAK_GBS,
@@ -464,9 +468,36 @@ def main() -> None:
             "launch_ms": round(scan_ms, 4),
             "timed": ("cc launch timed after the loop: the sharded loop scans all strata in one launch per rank" if sharded
                       else "cc launches inside the timed region (HIP events on the scan stream)"),
+        }
+
+    out = {
+        "metric": "queries/sec, 2-term AND BM25 top-1000 (p50 latency in p50_latency_ms)",
+        "value": round(qps, 1),
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "u8 postings -> u32 rowids, f32 BM25, i32 weights",
+        "data": "synthetic",
+        "full": args.full,
+        "config": {
+            "workload": f"{corpus_docs // 1_000_000}M docs (Zipf s=1, V=2^20, {AVG_TERMS_PER_DOC:.0f} terms/doc), 2-term AND, "
+                        f"SPH_RANK_BM25, top-{K}, {3 * nq} queries/step in 3 strata (cc/sc/ss) out of a {n_qsets * 3 * nq}-query file, "
+                        f"skiplist_block_size={args.skiplist_block}, inline hits",
+            "docs": corpus_docs,
+            "shards": world,
+            "queries_per_step": 3 * nq,
+            "k": K,
+            "query_file": f"{n_qsets * 3 * nq} queries (seed {QUERY_SEED:#x}) in {n_qsets} sets of 3 x {nq}; step i runs set i mod {n_qsets}",
         },
-        # sc / ss: galloping over the block index reads less than the algorithmic bytes ("skip-assisted"): their
-        # algorithmic rate may exceed the HBM peak and is never folded into the headline; measured bytes next to it
+        "roofline": roofline,  # (--full)
+        # the timed launches' own figures.  sc / ss: galloping over the block index reads less than the algorithmic bytes
+        # ("skip-assisted"): their algorithmic rate may exceed the HBM peak and is never folded into the headline;
+        # measured bytes next to it (--full)
         "strata": {
             s: {"label": "headline (no skipping possible: algorithmic ~ read bytes)" if s == "cc" else "skip-assisted" if s in ("sc", "ss") else "all strata in one launch",
                 "algo_GBps": round(min(per[s]["algo_bytes"], per[s].get("dev_bytes", per[s]["algo_bytes"])) / max(1e-9, per[s]["scan_ms"] * 1e-3) / 1e9, 1),
@@ -477,15 +508,16 @@ def main() -> None:
                 "host_plan_ms": round(per[s].get("plan_ms", 0.0) / max(1, per[s]["n"]), 4),
                 "host_submit_ms": round(per[s].get("submit_ms", 0.0) / max(1, per[s]["n"]), 4)} for s in (names + ["all"]) if per[s]["n"]},
         "strata_run": names,
-        "p50_latency_ms": round(float(np.percentile(lat, 50)), 4) if lat else None,
+        "p50_latency_ms": round(float(np.percentile(lat, 50)), 4) if lat else None,  # (--full)
         "p95_latency_ms": round(float(np.percentile(lat, 95)), 4) if lat else None,
-        "setup_s": {"generate": round(t_gen, 1), "index_MB": round((hi.spd.size + hi.spp.size + hi.spe.size) / 1e6, 1)},
+        "setup_s": {"generate": round(t_gen, 1), "segment": round(t_dev, 1), "index_MB": round((hi.spd.size + hi.spp.size + hi.spe.size) / 1e6, 1)},
     }
 
     out["host_ms_per_step"] = {k_: round(v / max(1, host_ms["n"]), 4) for k_, v in host_ms.items() if k_ != "n"}
-    # BASELINE config 3 on the same corpus, outside the timed region: 3-term mixes a b c / (a|b) c / a (b|c) / a b -c under
+    # --full: BASELINE config 3 on the same corpus, outside the timed region: 3-term mixes a b c / (a|b) c / a (b|c) / a b -c under
     # SPH_RANK_PROXIMITY_BM25 (hitlist decode); a = selective keyword, b and c = common ones.  Extra information only.
-    if rank == 0 and world == 1 and not sharded and not args.no_config3 and args.path == 0 and set(names) == {"cc", "sc", "ss"}:
+    if (args.full and rank == 0 and world == 1 and not sharded and not args.no_config3 and args.path == 0
+            and set(names) == {"cc", "sc", "ss"}):
         c3 = config3_queries(m, strata, nq, K, total_docs, global_docs)
         cq3 = m.prepare(c3)
         b3 = [m.Batch(ctx, nq), m.Batch(ctx, nq)]
@@ -523,16 +555,18 @@ def main() -> None:
             "projection_note": f"bytes per posting x {AVG_TERMS_PER_DOC:.0f} postings per doc x {shard_docs} docs: an upper estimate (the materialised terms "
                                "are the query terms: dense keywords, whose bitmaps and second tf/field plane cost most per posting, are over-represented)",
         }
-    # BASELINE config 5 on one GPU's share (1 B docs / 8): Zipf query mix incl. PHRASE, field weights (10,5,2,1), SPH_RANK_PROXIMITY_BM25,
-    # 1024 queries per launch.  Its own corpus (4 fields, field-end markers); outside the timed region.  Extra information only.
-    if rank == 0 and world == 1 and not sharded and not args.no_config5 and args.path == 0 and set(names) == {"cc", "sc", "ss"}:
+    # --full: BASELINE config 5 on one GPU's share (1 B docs / 8): Zipf query mix incl. PHRASE, field weights (10,5,2,1),
+    # SPH_RANK_PROXIMITY_BM25, 1024 queries per launch.  Its own corpus (4 fields, field-end markers); outside the timed region.
+    # Extra information only.
+    if (args.full and rank == 0 and world == 1 and not sharded and not args.no_config5 and args.path == 0
+            and set(names) == {"cc", "sc", "ss"}):
         try:
             out["config5"] = config5_leg(m, ctx, args, c, K)
         except Exception as e:  # (the headline line must not die with the extra leg)
             out["config5"] = {"error": f"{type(e).__name__}: {e}"}
     if merger is not None and merger.timing:
         out["dist_timing_ms_per_call"] = {k_: round(v / max(1, merger.timing["calls"]), 4) for k_, v in merger.timing.items() if k_ != "calls"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(hi, strata, total_docs, K, args.cpu_seconds)
     elif rank == 0:
         out["cpu_baseline"] = None
@@ -615,7 +649,8 @@ def config5_leg(m, ctx, args, c, K):
     nq5, fw = 1024, (10, 5, 2, 1)
     ranks, strata = make_queries(c, 342)
     probs = [min(0.5, c / r) for r in ranks]
-    hi5 = m.synth_index(args.config5_docs, probs, seed=CORPUS_SEED + 5, n_fields=4, end_markers=2, skiplist_block_size=args.skiplist_block)
+    hi5 = m.synth_index(args.config5_docs, probs, seed=CORPUS_SEED + 5, n_fields=4, end_markers=2, skiplist_block_size=args.skiplist_block,
+                        n_threads=usable_cpus())
     t_gen = time.time() - t0
     # (config 5's corpus carries field-end flags the way the reference's indexer writes them -- on the hit at a field's last position,
     # whatever the word: end_markers=2 -- so the statement made for the main corpus holds here too)

@@ -4,8 +4,8 @@
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 cd $ROOT
-python bench.py --docs 12500000 --no-config3 --no-config5 --no-cpu-baseline > $OUT/fin_b12.json 2> $OUT/fin_b12.err; echo "b12 done"
-MRK_FORCE_DIST=1 python bench.py --gpus 1 --docs 12500000 --no-cpu-baseline > $OUT/fin_d12.json 2> $OUT/fin_d12.err; echo "d12 done"
+python bench.py --full --docs 12500000 --no-config3 --no-config5 --no-cpu-baseline > $OUT/fin_b12.json 2> $OUT/fin_b12.err; echo "b12 done"
+MRK_FORCE_DIST=1 python bench.py --full --gpus 1 --docs 12500000 --no-cpu-baseline > $OUT/fin_d12.json 2> $OUT/fin_d12.err; echo "d12 done"
 bash tools/timeline.sh fin_12M5 12500000 > $OUT/fin_tl12.log 2>&1; echo "tl12 done"
 DIST=1 bash tools/timeline.sh fin_12M5_dist 12500000 > $OUT/fin_tl12d.log 2>&1; echo "tl12d done"
 bash tools/prof_c3k.sh > $OUT/fin_c3k.log 2>&1; echo "c3k done"
