@@ -207,6 +207,7 @@ typedef struct {
   float plan_ms;          /* host: query planning inside mrk_batch_submit */
   float submit_ms;        /* host: whole mrk_batch_submit call */
   uint32_t n_rerun;       /* queries the last mrk_batch_wait ran again alone (their match queue or candidate list was full) */
+  uint32_t n_bm_groups[4]; /* "bm_group": groups of 1, 2, 3 and 4 two-bitmap AND queries the last submit ran in one workgroup each */
 } mrk_batch_stats;
 
 const char* mrk_last_error(void);
@@ -233,6 +234,8 @@ int mrk_ctx_destroy(mrk_ctx* ctx);
    128: since work items of different queries interleave -- "item_order", a mask: 1 block scan, 2 bitmap AND, 4 bitmap trees, 8 also in
    batches that feed the hit pass; default 7 -- small items are the fast ones); "pk_min_items" (a batch with fewer block-scan work items
    has its block ranges cut finer, default 2048);
+   "bm_group" (1 = a batch's two-bitmap AND queries that share a keyword run in one workgroup, a wave per member, so the shared
+   keyword's bitmap and tf/field lines are fetched once per CU; 0 = a workgroup per query; default 1; read at submit);
    "prox_prune" (1 = proximity rankers: matches whose weight upper bound cannot reach the top K skip the hit pass, default);
    "prox_bound_keywords" (0 = that bound takes a proximity run to be as long as the field's hits allow: always sound, default;
    1 = as long as the number of keywords in the field -- tighter, and sound where hits of different keywords at ONE position reach

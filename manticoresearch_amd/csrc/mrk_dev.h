@@ -278,6 +278,23 @@ struct DevItem {
   uint32_t kind;      // window-range items: 0 = scan_bm_kernel, 1 = scan_bt_kernel
 };
 
+// A group of scan_bm queries that share a keyword (mrk_batch_submit, "bm_group"): the work items of the grouped kernel
+// instance name one of these in DevItem::query.  `per` waves serve each member over the item's window range, splitting it:
+// per = WAVES for a lone query (today's layout: the four waves split one query's range), else one or two waves per member,
+// so that partners walk the same windows on one CU at nearly the same time and one fetch of a shared line serves them all.
+constexpr int BM_GROUP_MAX = WAVES;
+constexpr int BM_GROUP_TABS = BM_GROUP_MAX + 1; // every member holds the group's seed keyword: at most 5 distinct keywords
+struct BmGroup {
+  uint32_t q[BM_GROUP_MAX]; // members' pass indices
+  uint32_t n;               // members (1 .. BM_GROUP_MAX)
+  uint32_t per;             // waves per member (WAVES / n, rounded down)
+  uint32_t ntab;            // distinct keywords = tfidf tables
+  uint32_t tab_idx;         // member m's keywords A / B use tables (tab_idx >> 6m) & 7 / (tab_idx >> (6m + 3)) & 7
+  uint32_t tab_src[BM_GROUP_TABS]; // table j is keyword (tab_src & 1) of member (tab_src >> 1)
+  uint32_t pad[3];
+};
+static_assert(sizeof(BmGroup) % sizeof(DevItem) == 0, "groups ride behind the work items in the items buffer");
+
 // candidate key: bigger = better under MatchRelevanceLt_fn (weight desc, rowid asc)
 __host__ __device__ inline uint64_t make_key(int32_t weight, uint32_t rowid) {
   return ((uint64_t)((uint32_t)weight ^ 0x80000000u) << 32) | (uint32_t)(~rowid);
@@ -357,6 +374,7 @@ struct ScanArgs {
   uint32_t* q_tau_lb;  // [n_queries * QSTRIDE]: (threshold bin << 10) | threshold slot of the second level
   MatchQueue mq[3];    // [0] plain boolean trees, [1] queries with PHRASE / PROXIMITY / BEFORE nodes or position modifiers, [2] TF_GEN
   GenArgs gen;
+  const BmGroup* bm_groups; // scan_bm work items name a group (grouped kernel instance); NULL = an item names its query
 };
 
 // Top-K selection over the candidate lists (mrk_select.hip), three launches on the batch's stream:

@@ -300,6 +300,11 @@ extern "C" int mrk_ctx_set(mrk_ctx* c, const char* key, int64_t value) {
     c->pk_min_items = (int)value;
     return MRK_OK;
   }
+  if (!strcmp(key, "bm_group")) {
+    if (value < 0 || value > 1) return mrk_fail(MRK_E_INVAL, "bm_group must be 0 or 1");
+    c->bm_group = (int)value;
+    return MRK_OK;
+  }
   if (!strcmp(key, "bm_min_windows")) {
     if (value < 16 || value > 4096) return mrk_fail(MRK_E_INVAL, "bm_min_windows must be 16 .. 4096");
     c->bm_min_windows = (int)value;
@@ -1020,6 +1025,71 @@ static void sel_rowid_range(const mrk_segment* seg, mrk::SelectArgs& se) {
   se.rowid_hi = (uint32_t)(seg->dev.rowid_base + docs - 1);
 }
 
+// The batch's scan_bm queries (items_bm entries of kind 0, one whole window range each) in groups, and per group the items_bm
+// entry of its first member (a group's members share the window range)
+static void group_bm_items(const mrk_batch* b, const mrk_segment* seg, const std::vector<DevItem>& items_bm, const std::vector<DevQuery>& extra,
+                           uint32_t n, std::vector<BmGroup>& groups, std::vector<uint32_t>& group_item) {
+  auto pass = [&](uint32_t p) -> const DevQuery& { return p < n ? b->h_queries.p[p] : extra[p - n]; };
+  const bool nib = seg->dev.pk_attr1 != nullptr;
+  auto tkey = [](const DevTerm& T) { // (bitmap, idf): one key = one tfidf table
+    uint32_t idf;
+    memcpy(&idf, &T.idf, 4);
+    return std::make_pair(T.bm_off, idf);
+  };
+  std::vector<std::pair<uint64_t, uint32_t>> keys;
+  for (const DevItem& it : items_bm)
+    if (it.kind == 0) keys.push_back(tkey(pass(it.query).t[0])), keys.push_back(tkey(pass(it.query).t[1]));
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  std::vector<uint32_t> ent; // items_bm index of member i
+  std::vector<BmMember> mem;
+  std::vector<uint32_t> cls_rep; // per class: a member's entry
+  for (uint32_t e = 0; e < items_bm.size(); ++e) {
+    const DevItem& it = items_bm[e];
+    if (it.kind != 0) continue;
+    const DevQuery& P = pass(it.query);
+    const uint32_t nw = std::min<uint32_t>(P.n_weights, 8u);
+    BmMember x{};
+    x.cls = ~0u;
+    for (uint32_t c = 0; c < cls_rep.size() && x.cls == ~0u; ++c) { // same windows, same field-weight table
+      const DevItem& r = items_bm[cls_rep[c]];
+      const DevQuery& R = pass(r.query);
+      if (r.blk_begin == it.blk_begin && r.blk_end == it.blk_end && std::min<uint32_t>(R.n_weights, 8u) == nw &&
+          !memcmp(R.weights, P.weights, nw * sizeof(int32_t)))
+        x.cls = c;
+    }
+    if (x.cls == ~0u) x.cls = (uint32_t)cls_rep.size(), cls_rep.push_back(e);
+    for (int t = 0; t < 2; ++t) {
+      x.key[t] = (uint64_t)(std::lower_bound(keys.begin(), keys.end(), tkey(P.t[t])) - keys.begin());
+      x.bytes[t] = (uint64_t)(it.blk_end - it.blk_begin) * 256 + (uint64_t)P.t[t].nblocks * (nib ? 128 : 256);
+    }
+    ent.push_back(e), mem.push_back(x);
+  }
+  std::vector<uint32_t> order, sizes;
+  plan_bm_groups(mem, order, sizes);
+  groups.clear(), group_item.clear();
+  size_t o = 0;
+  for (uint32_t sz : sizes) {
+    BmGroup g{};
+    g.n = sz;
+    g.per = WAVES / sz;
+    uint64_t tab_key[BM_GROUP_TABS];
+    for (uint32_t j = 0; j < sz; ++j) {
+      const uint32_t i = order[o + j];
+      g.q[j] = items_bm[ent[i]].query;
+      for (uint32_t t = 0; t < 2; ++t) {
+        uint32_t k = 0;
+        while (k < g.ntab && tab_key[k] != mem[i].key[t]) ++k;
+        if (k == g.ntab) tab_key[g.ntab] = mem[i].key[t], g.tab_src[g.ntab++] = j << 1 | t; // (<= 5: every member holds the seed)
+        g.tab_idx |= k << (6 * j + 3 * t);
+      }
+    }
+    groups.push_back(g);
+    group_item.push_back(ent[order[o]]);
+    o += sz;
+  }
+}
+
 static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n) {
   if (!b || !seg || (!queries && n)) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: NULL argument");
   if (n > b->max_queries) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: %u queries > batch capacity %u", n, b->max_queries);
@@ -1130,6 +1200,8 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   // items; each kind's whole-range entries are cut once the batch's total is known (a wave's fixed costs -- tables, final
   // publish, atomics on the query's counters -- want long runs of windows)
   size_t n_items_kind[3] = {0, 0, 0};
+  std::vector<BmGroup> groups; // the grouped bitmap kernel's groups (uploaded behind the work items) ...
+  std::vector<uint32_t> bm_group_item; // ... and per group its first member's whole-range entry in items_bm
   for (uint32_t kind = 0; kind < 2; ++kind) {
     uint64_t total_win = 0;
     for (const DevItem& it : items_bm)
@@ -1144,7 +1216,28 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     // atomics on one address serialize at the memory side (~70 ns each), about 0.1 ms per query whatever the shard size --
     // hidden behind 100 M docs, the whole launch at 12.5 M (12288 work items: 0.85 ms; 4096: 0.39 ms, same bytes).
     const size_t before = items.size();
-    if (!(b->ctx->item_order & (kind == 0 ? 2 : 4)) || (kind == 1 && any_prox && !(b->ctx->item_order & 8))) { // query-major (experiments; trees that feed the match queue)
+    if (kind == 0 && b->ctx->bm_group && (b->ctx->item_order & 2)) {
+      // Queries that share a keyword run in one workgroup, a wave (or two) per member over the same windows: the shared
+      // keyword's bitmap words and tf / field lines are then fetched once per CU instead of once per query
+      group_bm_items(b, seg, items_bm, extra, n, groups, bm_group_item);
+      for (const BmGroup& g : groups) ++b->stats.n_bm_groups[g.n - 1];
+      for (uint64_t piece = 0;; ++piece) {
+        bool any = false;
+        for (uint32_t g = 0; g < groups.size(); ++g) {
+          const DevItem& whole = items_bm[bm_group_item[g]];
+          const uint64_t gw = wpi * groups[g].per / WAVES; // a wave walks wpi / WAVES windows, as in the ungrouped layout
+          const uint64_t w = whole.blk_begin + piece * gw;
+          if (w >= whole.blk_end) continue;
+          any = true;
+          DevItem it = whole;
+          it.query = g;
+          it.blk_begin = (uint32_t)w;
+          it.blk_end = (uint32_t)std::min<uint64_t>(whole.blk_end, w + gw);
+          items.push_back(it);
+        }
+        if (!any) break;
+      }
+    } else if (!(b->ctx->item_order & (kind == 0 ? 2 : 4)) || (kind == 1 && any_prox && !(b->ctx->item_order & 8))) { // query-major (experiments; trees that feed the match queue)
       for (const DevItem& whole : items_bm)
         if (whole.kind == kind)
           for (uint64_t w = whole.blk_begin; w < whole.blk_end; w += wpi) {
@@ -1197,10 +1290,12 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   b->stats.n_items = n_items;
   b->stats.n_items_bm = n_items_bm;
   int rc;
-  if ((rc = b->h_items.reserve(n_items + 1)) || (rc = b->d_items.reserve(n_items + 1)) ||
+  const size_t n_group_slots = groups.size() * (sizeof(BmGroup) / sizeof(DevItem)); // (the groups ride behind the work items)
+  if ((rc = b->h_items.reserve(n_items + n_group_slots + 1)) || (rc = b->d_items.reserve(n_items + n_group_slots + 1)) ||
       (rc = b->d_item_cand.reserve((n_items + 1) * KCAP)) || (rc = b->d_item_cnt.reserve(n_items + 1)))
     return rc;
   if (n_items) memcpy(b->h_items.p, items.data(), n_items * sizeof(DevItem));
+  if (n_group_slots) memcpy((void*)(b->h_items.p + n_items), groups.data(), groups.size() * sizeof(BmGroup));
   const size_t n_pass = (size_t)n + extra.size();
   if ((rc = b->h_queries.reserve_keep(n_pass, n)) || (rc = b->d_queries.reserve(n_pass))) return rc;
   if (!extra.empty()) memcpy(b->h_queries.p + n, extra.data(), extra.size() * sizeof(DevQuery));
@@ -1219,7 +1314,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     static_assert(sizeof(DevQuery) % 4 == 0 && sizeof(DevItem) % 4 == 0, "descriptors are copied dword-wise");
     mrk::PrepArgs pa{};
     pa.dst[0] = (uint32_t*)b->d_queries.p, pa.src[0] = (const uint32_t*)b->h_queries.p, pa.n4[0] = (uint32_t)(n_pass * sizeof(DevQuery) / 4);
-    pa.dst[1] = (uint32_t*)b->d_items.p, pa.src[1] = (const uint32_t*)b->h_items.p, pa.n4[1] = (uint32_t)(n_items * sizeof(DevItem) / 4);
+    pa.dst[1] = (uint32_t*)b->d_items.p, pa.src[1] = (const uint32_t*)b->h_items.p, pa.n4[1] = (uint32_t)((n_items + n_group_slots) * sizeof(DevItem) / 4);
     // totals, thresholds, counters (+ the pruning histograms of the queries in use)
     pa.zero = (uint32_t*)b->d_state.p;
     pa.zero_n4 = (uint32_t)(((size_t)b->max_queries * STATE_BYTES + (use_packed ? (size_t)n * NBINS * 4 : 0)) / 4);
@@ -1286,6 +1381,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
       ScanArgs sb = sa;
       sb.items = b->d_items.p + n_items_pk;
       sb.n_items = (uint32_t)n_items_kind[0];
+      sb.bm_groups = n_group_slots ? (const BmGroup*)(b->d_items.p + n_items) : nullptr;
       launch_scan_bm(sb, st);
     }
   } else

@@ -35,6 +35,7 @@ struct mrk_ctx {
   int attr_nibbles = 0;           // also build the one-byte tf/field plane the bitmap kernel can gather from (<= 4 fields)
   int bm_target_items = 1 << 20;  // two-bitmap AND kernel: cap of the work items per launch ...
   int bm_min_windows = 128;       // ... and the least windows per work item (a wave's fixed costs show on short runs)
+  int bm_group = 1;               // two-bitmap AND kernel: queries that share a keyword run in one workgroup, a wave per member (0 = a workgroup per query)
   int pk_min_items = 2048;        // block-scan kernel: a batch with fewer work items has its block ranges cut finer (>= one block per wave)
   int exchange_part = 1;          // mrk_shard_exchange partitions the merge by query (all-to-all of row slices); 0 = all-gather, every rank merges everything
   int prox_prune = 1;             // proximity rankers: matches whose weight upper bound cannot reach the top K skip the hit pass (counted, not ranked)
@@ -121,6 +122,20 @@ int plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, b
                uint32_t qi, uint64_t& algo_bytes, uint64_t& dev_bytes, uint64_t& cand_total, bool& prox_out, bool& tree_out,
                std::vector<mrk::GenProg>& gen_progs, uint32_t rowid_max = 0xFFFFFFFFu); // gen_progs: programs of the generic evaluator (DevQuery::gen_prog indexes it); their
                                                       // work items go to items_bm with kind 2, already cut
+
+// Groups of a batch's scan_bm queries for the grouped bitmap kernel ("bm_group", mrk_batch_submit).  A member names its two
+// keywords (key: bitmap offset + idf bits, so that members sharing a key share its tfidf table too), the bytes a walk of each
+// costs, and a class: only members of one class may share a group (same window range and field weights).  Deterministic
+// greedy, per class: seed a group with the key held by the most members left (ties: the smaller key), then add, up to
+// BM_GROUP_MAX, the holder of the seed that adds the fewest bytes of keys new to the group (ties: the lower index).  Members
+// whose keys no other member left holds stay alone.  A key's bytes are taken per class (they depend on the window range).
+// Per-key holder lists and counts: about O(members + groups x keys).  Out: the members, group by group, and each group's size.
+struct BmMember {
+  uint64_t key[2];
+  uint64_t bytes[2];
+  uint32_t cls;
+};
+void plan_bm_groups(const std::vector<BmMember>& m, std::vector<uint32_t>& order, std::vector<uint32_t>& sizes);
 
 // Least and largest field-weight sum over the masks of the first nwf (<= 32) fields, the empty mask counting as 1
 // (ExtRanker_WeightSum_c's "just fake it"): the pruning bins of the weight-sum rankers.

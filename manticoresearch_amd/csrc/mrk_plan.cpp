@@ -1362,3 +1362,93 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
 }
 
 // ----------------------------------------------------------------------------------------
+
+void mrk::plan_bm_groups(const std::vector<BmMember>& m, std::vector<uint32_t>& order, std::vector<uint32_t>& sizes) {
+  order.clear(), sizes.clear();
+  const uint32_t n = (uint32_t)m.size();
+  // classes in the order of their first member; each class's members ascending
+  std::vector<uint32_t> by_cls(n);
+  for (uint32_t i = 0; i < n; ++i) by_cls[i] = i;
+  std::vector<uint32_t> cls_rank(n, ~0u); // class rank by first appearance (cls values are arbitrary)
+  {
+    std::vector<std::pair<uint32_t, uint32_t>> seen; // (cls, rank)
+    std::vector<uint32_t> rank(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      uint32_t r = ~0u;
+      for (const auto& c : seen)
+        if (c.first == m[i].cls) r = c.second;
+      if (r == ~0u) r = (uint32_t)seen.size(), seen.emplace_back(m[i].cls, r);
+      rank[i] = r;
+    }
+    std::stable_sort(by_cls.begin(), by_cls.end(), [&](uint32_t a, uint32_t b) { return rank[a] < rank[b]; });
+    for (uint32_t i = 0; i < n; ++i) cls_rank[i] = rank[i];
+  }
+  std::vector<uint64_t> keys;
+  std::vector<uint32_t> ka, kb, cnt, have, hold_first, hold;
+  std::vector<uint64_t> kbytes;
+  std::vector<uint8_t> done;
+  for (uint32_t c0 = 0; c0 < n;) {
+    uint32_t c1 = c0;
+    while (c1 < n && cls_rank[by_cls[c1]] == cls_rank[by_cls[c0]]) ++c1;
+    const uint32_t* mem = by_cls.data() + c0; // the class's members, ascending
+    const uint32_t nm = c1 - c0;
+    // dense key ids of the class, in key order (ties of the greedy go to the smaller key); a key's bytes are the class's
+    keys.clear();
+    for (uint32_t j = 0; j < nm; ++j) keys.push_back(m[mem[j]].key[0]), keys.push_back(m[mem[j]].key[1]);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    const size_t nk = keys.size();
+    ka.assign(nm, 0), kb.assign(nm, 0), done.assign(nm, 0);
+    cnt.assign(nk, 0), have.assign(nk, 0), kbytes.assign(nk, 0), hold_first.assign(nk + 1, 0);
+    for (uint32_t j = 0; j < nm; ++j) {
+      const BmMember& x = m[mem[j]];
+      ka[j] = (uint32_t)(std::lower_bound(keys.begin(), keys.end(), x.key[0]) - keys.begin());
+      kb[j] = (uint32_t)(std::lower_bound(keys.begin(), keys.end(), x.key[1]) - keys.begin());
+      kbytes[ka[j]] = x.bytes[0], kbytes[kb[j]] = x.bytes[1];
+      ++cnt[ka[j]];
+      if (kb[j] != ka[j]) ++cnt[kb[j]];
+    }
+    // holder lists (members ascending): hold[hold_first[k] .. hold_first[k + 1])
+    for (size_t k = 0; k < nk; ++k) hold_first[k + 1] = hold_first[k] + cnt[k];
+    hold.assign(hold_first[nk], 0);
+    {
+      std::vector<uint32_t> fill(hold_first.begin(), hold_first.end() - 1);
+      for (uint32_t j = 0; j < nm; ++j) {
+        hold[fill[ka[j]]++] = j;
+        if (kb[j] != ka[j]) hold[fill[kb[j]]++] = j;
+      }
+    }
+    uint32_t stamp = 0;
+    for (;;) {
+      // cnt[k] = holders of k not yet placed: the seed is the key most of them hold (ties: the smaller key)
+      uint32_t best = 0;
+      for (uint32_t k = 1; k < nk; ++k)
+        if (cnt[k] > cnt[best]) best = k;
+      if (nk == 0 || cnt[best] < 2) break;
+      ++stamp;
+      have[best] = stamp;
+      const size_t g0 = order.size();
+      while (order.size() - g0 < (size_t)BM_GROUP_MAX) {
+        // the seed's holder that adds the fewest bytes of keys new to the group (ties: the lower index)
+        uint32_t pick = ~0u;
+        uint64_t pick_cost = 0;
+        for (uint32_t h = hold_first[best]; h < hold_first[best + 1]; ++h) {
+          const uint32_t j = hold[h];
+          if (done[j]) continue;
+          const uint64_t cost = (have[ka[j]] == stamp ? 0 : kbytes[ka[j]]) + (have[kb[j]] == stamp || kb[j] == ka[j] ? 0 : kbytes[kb[j]]);
+          if (pick == ~0u || cost < pick_cost) pick = j, pick_cost = cost;
+        }
+        if (pick == ~0u) break;
+        done[pick] = 1;
+        have[ka[pick]] = have[kb[pick]] = stamp;
+        --cnt[ka[pick]];
+        if (kb[pick] != ka[pick]) --cnt[kb[pick]];
+        order.push_back(mem[pick]);
+      }
+      sizes.push_back((uint32_t)(order.size() - g0));
+    }
+    for (uint32_t j = 0; j < nm; ++j) // no key of theirs is held by another member left: alone
+      if (!done[j]) order.push_back(mem[j]), sizes.push_back(1);
+    c0 = c1;
+  }
+}

@@ -16,6 +16,12 @@
 // packed scan kernel, then the pruning histogram / candidate list shared with it (mrk_kprune.h).
 // Field-limited keywords are honoured at scoring time (a doc counts for a keyword only if
 // fields & queried != 0, searchnode.cpp:1925-1939), so totals are counted there too.
+//
+// GROUP instance: a work item names a BmGroup of queries that share a keyword (mrk_batch_submit).  Wave w serves member
+// w / per over the item's windows (a lone query: per = 4, the waves split its range as above), so the members' bitmap words,
+// dead-row words and tf / field lines are requested by the waves of one CU at nearly the same time and a shared keyword's
+// lines come from L2 for all but the first of them.  All per-query state is per wave; the tfidf tables are one per distinct
+// keyword of the group, the field-weight table one per workgroup (members have the same field weights).
 #include "mrk_kcommon.h"
 #include "mrk_kprune.h"
 
@@ -32,8 +38,12 @@ constexpr int BM_WORDS = 64; // words per window
 #endif
 constexpr int BM_BURST = MRK_BM_BURST;
 constexpr int BM_WQCAP = 128; // word queue entries per wave (unpacked in batches of 64)
+#ifndef MRK_BM_GSYNC
+#define MRK_BM_GSYNC 0 // experiment: the grouped instance's waves meet at a workgroup barrier every N bursts (0 = never)
+#endif
+constexpr int BM_GSYNC = MRK_BM_GSYNC;
 
-// (4 x (896 + 3072) B of wave queues + 3 KB of tables)
+// (4 x (896 + 3072 + 256) B of wave queues + 3 KB of tables; GROUP: + 3 KB more tables, 23040 B: still 7 workgroups per CU)
 struct __align__(16) BmWaveLds {
   uint64_t cbuf[BM_CBUF];
   // word queue: the windows' non-empty match words wait here until 64 of them can be unpacked with every lane busy
@@ -42,36 +52,58 @@ struct __align__(16) BmWaveLds {
   uint16_t wpre[BM_WQCAP]; // final drain: matches held by the queue entries before this one (<= 128 x 32)
 };
 
+template <bool GROUP>
 struct __align__(16) BmSmem {
   BmWaveLds w[WAVES];
   uint32_t rank[256];
-  float tfidf[2][256];
+  float tfidf[GROUP ? BM_GROUP_TABS : 2][256];
 };
 
 // SEQ: the segment holds the dense keywords' tf / field bytes in slot order (DevSegment::pk_attr2) and the gathers read those
-template <bool SEQ>
+template <bool SEQ, bool GROUP>
 __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
-  __shared__ BmSmem s;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  __shared__ BmSmem<GROUP> s;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  const uint32_t wave = GROUP ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6; // (GROUP: the wave's query is read with scalar loads)
   if (blockIdx.x >= a.n_items) return;
   const DevItem item = a.items[blockIdx.x];
-  const DevQuery* __restrict__ Q = a.queries + item.query;
+  // the wave's query and its share of the item's windows: part `sub` of `per`
+  uint32_t qi = item.query, per = WAVES, sub = wave, ia = 0, ib = 1, member = 0, n_members = 1;
+  if (GROUP) {
+    const BmGroup* __restrict__ G = a.bm_groups + item.query;
+    per = G->per, n_members = G->n;
+    member = wave / per, sub = wave - member * per;
+    if (member >= n_members) member = 0; // (an idle wave: it fills its share of the tables, then leaves)
+    qi = G->q[member];
+    ia = (G->tab_idx >> (6u * member)) & 7u, ib = (G->tab_idx >> (6u * member + 3u)) & 7u;
+    for (uint32_t j = 0; j < G->ntab; ++j) {
+      const uint32_t src = G->tab_src[j];
+      s.tfidf[j][tid] = term_tfidf(tid, a.queries[G->q[src >> 1]].t[src & 1u].idf);
+    }
+  }
+  const DevQuery* __restrict__ Q = a.queries + qi;
+  const DevQuery* __restrict__ QR = GROUP ? a.queries + a.bm_groups[item.query].q[0] : Q; // (the members' field weights are the same)
   const uint32_t K = Q->k, ranker = Q->ranker, oq = Q->out_q;
   const uint32_t nw = Q->n_weights < 8u ? Q->n_weights : 8u;
   const uint32_t index_weight = Q->index_weight;
   const DevTerm TA = Q->t[0], TB = Q->t[1]; // ExtMultiAnd_T node order: tfidf = 0 + A + B
   BmWaveLds& L = s.w[wave];
-  s.tfidf[0][tid] = term_tfidf(tid, TA.idf);
-  s.tfidf[1][tid] = term_tfidf(tid, TB.idf);
+  if (!GROUP) {
+    s.tfidf[0][tid] = term_tfidf(tid, TA.idf);
+    s.tfidf[1][tid] = term_tfidf(tid, TB.idf);
+  }
   {
+    const uint32_t nwr = GROUP ? (QR->n_weights < 8u ? QR->n_weights : 8u) : nw;
     uint32_t rk = 0;
     if (!tid)
       rk = 1; // empty mask: "just fake it" (sphinxsearch.cpp:1114-1118)
     else
-      for (uint32_t f = 0; f < nw; ++f)
-        if (tid & (1u << f)) rk += (uint32_t)Q->weights[f];
+      for (uint32_t f = 0; f < nwr; ++f)
+        if (tid & (1u << f)) rk += (uint32_t)QR->weights[f];
     s.rank[tid] = rk;
   }
+  const float* __restrict__ tabA = s.tfidf[ia];
+  const float* __restrict__ tabB = s.tfidf[ib];
   const uint32_t bin_mode = Q->bin_mode, bin_shift = Q->bin_shift;
   const int32_t bin_lo = Q->bin_lo;
   const uint32_t cand_cap = Q->cand_cap;
@@ -92,10 +124,16 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
   const bool none_fast = ranker == MRK_RANK_NONE && (TA.queried32 & field_all) == field_all && (TB.queried32 & field_all) == field_all;
 
   const uint32_t nwin = item.blk_end - item.blk_begin;
-  const uint32_t per = (nwin + WAVES - 1) / WAVES;
-  const uint32_t w0 = item.blk_begin + wave * per;
-  const uint32_t w1 = w0 + per < item.blk_end ? w0 + per : item.blk_end;
-  __syncthreads(); // tables ready; the waves never meet again
+  const uint32_t part = (nwin + per - 1) / per;
+  const uint32_t w0 = item.blk_begin + sub * part;
+  uint32_t w1 = w0 + part < item.blk_end ? w0 + part : item.blk_end;
+  __syncthreads(); // tables ready; the waves never meet again (unless gsync)
+  constexpr bool gsync = GROUP && BM_GSYNC > 0; // (then every wave, an idle one too, runs the same number of bursts)
+  if (GROUP && wave >= n_members * per) {
+    if (!gsync) return;
+    w1 = w0;
+  }
+  const uint32_t nburst = (part + BM_BURST - 1) / BM_BURST;
 
   uint32_t total = 0, tau_bin = 0, cn = 0;
   // running ranks at the start of the next window (uniform)
@@ -159,7 +197,7 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
       fa = (wa >> ((SEQ ? 8u : 16u) + sa)) & 0xffu & TA.queried32, fb = (wb >> ((SEQ ? 8u : 16u) + sb)) & 0xffu & TB.queried32; // FitsFields
     }
     const bool live = valid && (none_fast || (fa != 0 && fb != 0));
-    float ta = s.tfidf[0][tfa], tb = s.tfidf[1][tfb];
+    float ta = tabA[tfa], tb = tabB[tfb];
     if (tfa == 255u && live) ta = term_tfidf(exc_tf(a.seg, TA, row), TA.idf);
     if (tfb == 255u && live) tb = term_tfidf(exc_tf(a.seg, TB, row), TB.idf);
     float acc = 0.0f + ta; // ExtMultiAnd_T::GetTFIDF: nodes in ascending-docs order
@@ -242,9 +280,10 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
     return (uint32_t)__popcll(bal);
   };
 
-  for (uint32_t wb = w0; wb < w1; wb += BM_BURST) {
+  for (uint32_t wb = w0, it = 0; gsync ? it < nburst : wb < w1; wb += BM_BURST, ++it) {
     // BM_BURST windows requested back to back (one memory round trip per burst)
-    const uint32_t nb = w1 - wb < (uint32_t)BM_BURST ? w1 - wb : (uint32_t)BM_BURST;
+    const uint32_t nb = (gsync && wb >= w1) ? 0u : w1 - wb < (uint32_t)BM_BURST ? w1 - wb : (uint32_t)BM_BURST;
+    if (gsync && it % (BM_GSYNC > 0 ? BM_GSYNC : 1) == 0 && it) __syncthreads();
     uint32_t av[BM_BURST], bv[BM_BURST], dv[BM_BURST];
 #pragma unroll
     for (int i = 0; i < BM_BURST; ++i) {
@@ -359,10 +398,10 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
 
 void launch_scan_bm(const ScanArgs& a, void* stream) {
   if (!a.n_items) return;
-  if (a.seg.pk_attr2 && !a.seg.pk_attr1)
-    hipLaunchKernelGGL(scan_bm_kernel<true>, dim3(a.n_items), dim3(WG), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(scan_bm_kernel<false>, dim3(a.n_items), dim3(WG), 0, (hipStream_t)stream, a);
+  const bool seq = a.seg.pk_attr2 && !a.seg.pk_attr1;
+  void (*k)(ScanArgs) = a.bm_groups ? (seq ? scan_bm_kernel<true, true> : scan_bm_kernel<false, true>)
+                                    : (seq ? scan_bm_kernel<true, false> : scan_bm_kernel<false, false>);
+  hipLaunchKernelGGL(k, dim3(a.n_items), dim3(WG), 0, (hipStream_t)stream, a);
 }
 
 } // namespace mrk
