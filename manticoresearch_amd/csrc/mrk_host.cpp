@@ -161,7 +161,6 @@ struct mrk_batch {
   DevBuf<unsigned long long> d_gen_used;
   DevBuf<uint32_t> d_gen_near; // GenArgs::near_tab
   std::vector<mrk::GenProg> gen_progs;
-  bool last_fat = false;
   // decoded results
   std::vector<uint32_t> rowid;
   std::vector<int32_t> weight;
@@ -898,32 +897,6 @@ static int mrk_batch_create_impl(mrk_ctx* ctx, uint32_t max_queries, mrk_batch**
   return MRK_OK;
 }
 
-// mirrors scan_pk_kernel: matches of these passes leave through the match queue (state rankers over more than one
-// keyword, whole-query PHRASE); `fat` = the queue whose consumer carries the word state machines
-static bool pass_queues_matches(const DevQuery& P, bool& fat) {
-  const uint32_t rk = P.ranker;
-  if (P.tree_flags & mrk::TF_GEN) return fat = false, true; // (queue 2: see queue_of)
-  const bool prox_ranker = (rk == MRK_RANK_PROXIMITY_BM25 || rk == MRK_RANK_PROXIMITY)
-                               ? P.n_terms > 1
-                               : (rk == MRK_RANK_WORDCOUNT || rk == MRK_RANK_MATCHANY || rk == MRK_RANK_FIELDMASK || rk == MRK_RANK_SPH04);
-  fat = (P.tree_flags & mrk::TF_FAT) != 0;
-  return prox_ranker || (P.tree_flags & mrk::TF_PHRASE) != 0;
-}
-
-static int queue_of(const DevQuery& P, bool fat) { return (P.tree_flags & mrk::TF_GEN) ? 2 : fat ? 1 : 0; }
-
-// upper bound of the docs a pass can match: its driver's docs; the common docs for the two-bitmap AND; any keyword's docs for
-// a tree evaluated on bitmap words
-static uint64_t pass_max_matches(const DevQuery& P) {
-  if (P.tree_flags & mrk::TF_BITMAP) return std::min<uint64_t>(P.t[0].docs, P.t[1].docs);
-  if (P.tree_flags & mrk::TF_BTREE) {
-    uint64_t d = 0, least = ~0ull;
-    for (uint32_t k = 0; k < P.n_terms && k < (uint32_t)MRK_MAX_AND_TERMS; ++k) d += P.t[k].docs, least = std::min<uint64_t>(least, P.t[k].docs);
-    return (P.tree_flags & mrk::TF_MULTIAND) && P.n_terms ? least : d; // (an AND of keywords holds no more docs than its rarest one)
-  }
-  return P.t[0].docs;
-}
-
 // size the batch's match queues for `chunks[q]` chunks (0 = queue unused) and point the scan arguments at them
 static int bind_match_queues(mrk_batch* b, const uint64_t chunks[3], mrk::ScanArgs& sa) {
   for (int i = 0; i < 3; ++i) {
@@ -1016,78 +989,78 @@ static int cutoff_probe(mrk_batch* b, mrk_segment* seg, const mrk_query* queries
   return MRK_OK;
 }
 
-// the selection's sub-bin geometry: the segment's largest global rowid and the bits its rowid range needs
-static void sel_rowid_range(const mrk_segment* seg, mrk::SelectArgs& se) {
+// the scan state of a batch as the scan kernels see it: descriptors, work items, per-query state, candidate arena (a retry
+// batch never reserves the VLB path's per-item lists: null there)
+static void bind_scan(const mrk_batch* b, const mrk_segment* seg, mrk::ScanArgs& sa) {
+  sa.seg = seg->dev;
+  sa.queries = b->d_queries.p;
+  sa.items = b->d_items.p;
+  sa.item_cand = b->d_item_cand.p;
+  sa.item_cnt = b->d_item_cnt.p;
+  sa.q_total = b->d_q_total.p;
+  sa.q_tau = b->d_q_tau.p;
+  sa.q_hist = b->d_q_hist.p;
+  sa.q_cand_n = b->d_q_cand_n.p;
+  sa.q_flags = b->d_q_flags.p;
+  sa.q_tau_bin = b->d_q_tau_bin.p;
+  sa.cand = b->d_cand.p;
+}
+
+// The packed path's kernels over a laid-out item array (sa.items: block-scan items, then kinds 0, 1, 2): block scan, tree
+// kernel and generic-evaluator candidates, the rank launches of the queues in use, then the two-bitmap AND kernel
+// (bm_groups: its group records on the device, or null)
+static int launch_packed(mrk::ScanArgs sa, size_t n_items_pk, const size_t n_items_kind[3], const uint64_t mq_chunks[3], uint32_t max_terms, bool prox,
+                         bool tree, bool ext, bool nearn, const BmGroup* bm_groups, hipStream_t st) {
+  const DevItem* items = sa.items;
+  sa.n_items = (uint32_t)n_items_pk;
+  launch_scan_pk(sa, max_terms, prox, tree, ext, st);
+  if (n_items_kind[1]) { // before the rank kernels: it feeds the match queue too
+    ScanArgs sb = sa;
+    sb.items = items + n_items_pk + n_items_kind[0];
+    sb.n_items = (uint32_t)n_items_kind[1];
+    launch_scan_bt(sb, st);
+  }
+  if (n_items_kind[2]) { // candidates of the generic evaluator
+    ScanArgs sg = sa;
+    sg.items = items + n_items_pk + n_items_kind[0] + n_items_kind[1];
+    sg.n_items = (uint32_t)n_items_kind[2];
+    launch_scan_pk(sg, max_terms, true, true, true, st, true);
+  }
+  // the queued matches of hit-ranked queries: hit pass + state rankers (mrk_rank.hip), behind the scans on the same stream
+  if (mq_chunks[0]) launch_rank(sa, 0, st);
+  if (mq_chunks[1]) launch_rank(sa, 1, st);
+  int rc;
+  if (mq_chunks[2] && (rc = launch_gen_rank(sa, nearn, st))) return rc;
+  if (n_items_kind[0]) {
+    ScanArgs sb = sa;
+    sb.items = items + n_items_pk;
+    sb.n_items = (uint32_t)n_items_kind[0];
+    sb.bm_groups = bm_groups;
+    launch_scan_bm(sb, st);
+  }
+  return MRK_OK;
+}
+
+// the top-K selection of n_queries over a batch's candidate arena of cand_total slots (d_sel reserved for them); the sub-bin
+// geometry: the segment's largest global rowid and the bits its rowid range needs
+static void bind_select(const mrk_batch* b, const mrk_segment* seg, uint32_t n_queries, uint64_t cand_total, mrk::SelectArgs& se) {
+  se.queries = b->d_queries.p;
+  se.q_hist = b->d_q_hist.p;
+  se.q_cand_n = b->d_q_cand_n.p;
+  se.cand = b->d_cand.p;
+  se.n_queries = n_queries;
+  se.rowid_base = seg->dev.rowid_base;
+  se.out_keys = b->d_out_keys.p;
+  se.out_cnt = b->d_out_cnt.p;
+  se.sel_tau = b->d_sel.p;
+  se.sel_nslice = b->d_sel.p + n_queries;
+  se.slice_cnt = b->d_sel.p + 2 * (size_t)n_queries;
+  se.max_slices = (uint32_t)std::min<uint64_t>(mrk::sel_slice_slots(cand_total, n_queries), 1u << 30);
   const uint64_t docs = std::max<uint64_t>(seg->total_docs, 1);
   uint32_t bits = 1;
   while (bits < 32 && ((docs - 1) >> bits)) ++bits;
   se.rowid_bits = bits;
   se.rowid_hi = (uint32_t)(seg->dev.rowid_base + docs - 1);
-}
-
-// The batch's scan_bm queries (items_bm entries of kind 0, one whole window range each) in groups, and per group the items_bm
-// entry of its first member (a group's members share the window range)
-static void group_bm_items(const mrk_batch* b, const mrk_segment* seg, const std::vector<DevItem>& items_bm, const std::vector<DevQuery>& extra,
-                           uint32_t n, std::vector<BmGroup>& groups, std::vector<uint32_t>& group_item) {
-  auto pass = [&](uint32_t p) -> const DevQuery& { return p < n ? b->h_queries.p[p] : extra[p - n]; };
-  const bool nib = seg->dev.pk_attr1 != nullptr;
-  auto tkey = [](const DevTerm& T) { // (bitmap, idf): one key = one tfidf table
-    uint32_t idf;
-    memcpy(&idf, &T.idf, 4);
-    return std::make_pair(T.bm_off, idf);
-  };
-  std::vector<std::pair<uint64_t, uint32_t>> keys;
-  for (const DevItem& it : items_bm)
-    if (it.kind == 0) keys.push_back(tkey(pass(it.query).t[0])), keys.push_back(tkey(pass(it.query).t[1]));
-  std::sort(keys.begin(), keys.end());
-  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-  std::vector<uint32_t> ent; // items_bm index of member i
-  std::vector<BmMember> mem;
-  std::vector<uint32_t> cls_rep; // per class: a member's entry
-  for (uint32_t e = 0; e < items_bm.size(); ++e) {
-    const DevItem& it = items_bm[e];
-    if (it.kind != 0) continue;
-    const DevQuery& P = pass(it.query);
-    const uint32_t nw = std::min<uint32_t>(P.n_weights, 8u);
-    BmMember x{};
-    x.cls = ~0u;
-    for (uint32_t c = 0; c < cls_rep.size() && x.cls == ~0u; ++c) { // same windows, same field-weight table
-      const DevItem& r = items_bm[cls_rep[c]];
-      const DevQuery& R = pass(r.query);
-      if (r.blk_begin == it.blk_begin && r.blk_end == it.blk_end && std::min<uint32_t>(R.n_weights, 8u) == nw &&
-          !memcmp(R.weights, P.weights, nw * sizeof(int32_t)))
-        x.cls = c;
-    }
-    if (x.cls == ~0u) x.cls = (uint32_t)cls_rep.size(), cls_rep.push_back(e);
-    for (int t = 0; t < 2; ++t) {
-      x.key[t] = (uint64_t)(std::lower_bound(keys.begin(), keys.end(), tkey(P.t[t])) - keys.begin());
-      x.bytes[t] = (uint64_t)(it.blk_end - it.blk_begin) * 256 + (uint64_t)P.t[t].nblocks * (nib ? 128 : 256);
-    }
-    ent.push_back(e), mem.push_back(x);
-  }
-  std::vector<uint32_t> order, sizes;
-  plan_bm_groups(mem, order, sizes);
-  groups.clear(), group_item.clear();
-  size_t o = 0;
-  for (uint32_t sz : sizes) {
-    BmGroup g{};
-    g.n = sz;
-    g.per = WAVES / sz;
-    uint64_t tab_key[BM_GROUP_TABS];
-    for (uint32_t j = 0; j < sz; ++j) {
-      const uint32_t i = order[o + j];
-      g.q[j] = items_bm[ent[i]].query;
-      for (uint32_t t = 0; t < 2; ++t) {
-        uint32_t k = 0;
-        while (k < g.ntab && tab_key[k] != mem[i].key[t]) ++k;
-        if (k == g.ntab) tab_key[g.ntab] = mem[i].key[t], g.tab_src[g.ntab++] = j << 1 | t; // (<= 5: every member holds the seed)
-        g.tab_idx |= k << (6 * j + 3 * t);
-      }
-    }
-    groups.push_back(g);
-    group_item.push_back(ent[order[o]]);
-    o += sz;
-  }
 }
 
 static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n) {
@@ -1117,26 +1090,19 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
 
   // ---- plan
   const auto t_submit0 = std::chrono::steady_clock::now();
-  std::vector<DevItem> items, items_bm;
-  items.reserve(n * 4);
-  uint64_t algo_bytes = 0, dev_bytes = 0, cand_total = 0;
+  mrk::BatchPlan plan;
+  plan.items.reserve(n * 4);
   uint32_t max_terms = 1;
-  bool any_prox = false, any_tree = false, any_ext = false; // ext: position modifiers, BEFORE, attribute filters
+  bool any_ext = false; // position modifiers, BEFORE, attribute filters
   if (b->ctx->path == 2 && !seg->has_packed) return mrk_fail(MRK_E_UNSUPPORTED, "path=packed but the segment has no packed doclists");
   const bool use_packed = seg->has_packed && b->ctx->path != 1;
-  std::vector<DevQuery> extra; // passes beyond the first of tree queries; pass index = n + position
-  b->gen_progs.clear();
   for (uint32_t i = 0; i < n; ++i) {
-    const size_t extra0 = extra.size(), items0 = items.size(), items_bm0 = items_bm.size(), gen0 = b->gen_progs.size();
-    int rc = plan_query(seg, queries[i], b->ctx->item_bytes, use_packed, b->h_queries.p[i], extra, n, items, items_bm, i, algo_bytes,
-                        dev_bytes, cand_total, any_prox, any_tree, b->gen_progs, rowid_max.empty() ? 0xFFFFFFFFu : rowid_max[i]);
+    const mrk::BatchPlan::Mark before = plan.mark();
+    int rc = plan_query(seg, queries[i], b->ctx->item_bytes, use_packed, b->h_queries.p[i], n, i, plan, rowid_max.empty() ? 0xFFFFFFFFu : rowid_max[i]);
     b->status[i] = rc;
     if (rc == MRK_E_INVAL) return rc;
     if (rc != MRK_OK) { // unsupported: reported per query, runs no device work
-      items.resize(items0);
-      items_bm.resize(items_bm0);
-      extra.resize(extra0);
-      b->gen_progs.resize(gen0);
+      plan.rewind(before);
       b->h_queries.p[i].n_items = 0;
       b->h_queries.p[i].n_terms = 0;
     }
@@ -1147,155 +1113,31 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     b->h_list_n.p[i] = b->h_queries.p[i].n_items;
     b->h_kq.p[i] = b->h_queries.p[i].k ? b->h_queries.p[i].k : 1;
   }
-  // A small batch (one-eighth shards, selective keywords, a lone query): the planner cuts a driver doclist into ~item_bytes
-  // pieces whatever the batch holds, and 280 workgroups that each walk 70 blocks per wave one after the other leave the chip
-  // idle for 0.1 ms.  Cut the block ranges finer until the launch has pk_min_items work items (never under one block per wave).
-  if (use_packed && !items.empty() && items.size() < (size_t)b->ctx->pk_min_items) {
-    uint64_t total_blocks = 0;
-    for (const DevItem& it : items) total_blocks += it.blk_end - it.blk_begin;
-    uint64_t per = (total_blocks + (uint64_t)b->ctx->pk_min_items - 1) / (uint64_t)b->ctx->pk_min_items;
-    per = std::max<uint64_t>(T0_BLOCKS, (per + T0_BLOCKS - 1) / T0_BLOCKS * T0_BLOCKS);
-    std::vector<DevItem> cut;
-    cut.reserve(items.size() + (size_t)(total_blocks / per) + 1);
-    std::vector<uint32_t> per_pass((size_t)n + extra.size(), 0);
-    for (const DevItem& whole : items)
-      for (uint64_t x = whole.blk_begin; x < whole.blk_end; x += per) {
-        DevItem it = whole;
-        it.blk_begin = (uint32_t)x;
-        it.blk_end = (uint32_t)std::min<uint64_t>(whole.blk_end, x + per);
-        cut.push_back(it);
-        if (it.query < per_pass.size()) ++per_pass[it.query];
-      }
-    items.swap(cut);
-    // (the counts feed the match-queue sizing below; the VLB path's per-query list ranges are not built from a packed plan)
-    for (uint32_t i = 0; i < n; ++i)
-      if (per_pass[i]) b->h_queries.p[i].n_items = per_pass[i];
-    for (size_t e = 0; e < extra.size(); ++e)
-      if (per_pass[n + e]) extra[e].n_items = per_pass[n + e];
-  }
-  // ... and in piece-major order, for the reason given at the window-range items below: concurrent workgroups should belong
-  // to different queries (the planner emits a query's items back to back; only the VLB path needs them that way)
-  // (not for batches whose matches travel through the match queue to the hit pass: config 3 measured 6.6 ms query-major, 7.1 ms
-  // interleaved -- the rank kernel likes a query's chunks in rowid order)
-  if (use_packed && items.size() > 1 && (b->ctx->item_order & 1) && (!any_prox || (b->ctx->item_order & 8))) {
-    std::vector<DevItem> rr;
-    rr.reserve(items.size());
-    std::vector<size_t> run_begin, run_end; // runs of items of one pass
-    for (size_t i = 0; i < items.size();) {
-      size_t j = i + 1;
-      while (j < items.size() && items[j].query == items[i].query) ++j;
-      run_begin.push_back(i), run_end.push_back(j);
-      i = j;
-    }
-    if (run_begin.size() > 1) {
-      for (size_t k = 0; rr.size() < items.size(); ++k)
-        for (size_t r = 0; r < run_begin.size(); ++r)
-          if (run_begin[r] + k < run_end[r]) rr.push_back(items[run_begin[r] + k]);
-      items.swap(rr);
-    }
-  }
-  const float plan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_submit0).count();
-  const size_t n_items_pk = items.size();
-  // window-range work items (two-bitmap AND kernel, then the window-driven tree kernel) ride behind the block work
-  // items; each kind's whole-range entries are cut once the batch's total is known (a wave's fixed costs -- tables, final
-  // publish, atomics on the query's counters -- want long runs of windows)
-  size_t n_items_kind[3] = {0, 0, 0};
-  std::vector<BmGroup> groups; // the grouped bitmap kernel's groups (uploaded behind the work items) ...
-  std::vector<uint32_t> bm_group_item; // ... and per group its first member's whole-range entry in items_bm
-  for (uint32_t kind = 0; kind < 2; ++kind) {
-    uint64_t total_win = 0;
-    for (const DevItem& it : items_bm)
-      if (it.kind == kind) total_win += it.blk_end - it.blk_begin;
-    if (!total_win) continue;
-    const uint64_t unit = 4 * WAVES; // one burst per wave
-    uint64_t wpi = (total_win / (uint64_t)(kind == 0 ? b->ctx->bm_target_items : b->ctx->bt_target_items) / unit) * unit;
-    wpi = std::min<uint64_t>(std::max<uint64_t>(wpi, kind == 0 ? (uint64_t)b->ctx->bm_min_windows / unit * unit : 4 * unit), 4096); // (short runs: a wave's fixed costs show -- 12.5 M docs, 8192 items: 0.55 vs 0.47 ms)
-    // Piece-major order: the k-th piece of every query, then the (k+1)-th ...  Workgroups that run at the same time then
-    // belong to DIFFERENT queries.  Query-major order put a query's 20-50 workgroups on the chip together, all of them adding
-    // to the one candidate counter, the same few histogram bins and the one threshold word of that query: device-scope
-    // atomics on one address serialize at the memory side (~70 ns each), about 0.1 ms per query whatever the shard size --
-    // hidden behind 100 M docs, the whole launch at 12.5 M (12288 work items: 0.85 ms; 4096: 0.39 ms, same bytes).
-    const size_t before = items.size();
-    if (kind == 0 && b->ctx->bm_group && (b->ctx->item_order & 2)) {
-      // Queries that share a keyword run in one workgroup, a wave (or two) per member over the same windows: the shared
-      // keyword's bitmap words and tf / field lines are then fetched once per CU instead of once per query
-      group_bm_items(b, seg, items_bm, extra, n, groups, bm_group_item);
-      for (const BmGroup& g : groups) ++b->stats.n_bm_groups[g.n - 1];
-      for (uint64_t piece = 0;; ++piece) {
-        bool any = false;
-        for (uint32_t g = 0; g < groups.size(); ++g) {
-          const DevItem& whole = items_bm[bm_group_item[g]];
-          const uint64_t gw = wpi * groups[g].per / WAVES; // a wave walks wpi / WAVES windows, as in the ungrouped layout
-          const uint64_t w = whole.blk_begin + piece * gw;
-          if (w >= whole.blk_end) continue;
-          any = true;
-          DevItem it = whole;
-          it.query = g;
-          it.blk_begin = (uint32_t)w;
-          it.blk_end = (uint32_t)std::min<uint64_t>(whole.blk_end, w + gw);
-          items.push_back(it);
-        }
-        if (!any) break;
-      }
-    } else if (!(b->ctx->item_order & (kind == 0 ? 2 : 4)) || (kind == 1 && any_prox && !(b->ctx->item_order & 8))) { // query-major (experiments; trees that feed the match queue)
-      for (const DevItem& whole : items_bm)
-        if (whole.kind == kind)
-          for (uint64_t w = whole.blk_begin; w < whole.blk_end; w += wpi) {
-            DevItem it = whole;
-            it.blk_begin = (uint32_t)w;
-            it.blk_end = (uint32_t)std::min<uint64_t>(whole.blk_end, w + wpi);
-            items.push_back(it);
-          }
-    } else
-    for (uint64_t piece = 0;; ++piece) {
-      bool any = false;
-      for (const DevItem& whole : items_bm) {
-        if (whole.kind != kind) continue;
-        const uint64_t w = whole.blk_begin + piece * wpi;
-        if (w >= whole.blk_end) continue;
-        any = true;
-        DevItem it = whole;
-        it.blk_begin = (uint32_t)w;
-        it.blk_end = (uint32_t)std::min<uint64_t>(whole.blk_end, w + wpi);
-        items.push_back(it);
-      }
-      if (!any) break;
-    }
-    n_items_kind[kind] = items.size() - before;
-  }
-  for (const DevItem& it : items_bm) // the generic evaluator's candidates: block ranges, cut by the planner
-    if (it.kind == 2) items.push_back(it), ++n_items_kind[2];
-  // match queues: a pass hands over at most one entry per doc it can match, plus one partial chunk per wave of its items
-  uint64_t mq_chunks[3] = {0, 0, 0};
-  if (use_packed && any_prox) {
-    bool bt_feeds[3] = {false, false, false};
-    auto account = [&](const DevQuery& P) {
-      bool fat = false;
-      if (!P.n_items || !pass_queues_matches(P, fat)) return;
-      const bool bt = (P.tree_flags & mrk::TF_BTREE) != 0;
-      mq_chunks[queue_of(P, fat)] += pass_max_matches(P) / 64 + (bt ? 0 : 4ull * (mrk::MQ_BATCH + 1) * P.n_items) + 1;
-      bt_feeds[queue_of(P, fat)] = bt_feeds[queue_of(P, fat)] || bt;
-    };
-    for (uint32_t i = 0; i < n; ++i) account(b->h_queries.p[i]);
-    for (const DevQuery& P : extra) account(P);
-    for (int i = 0; i < 2; ++i) // per wave one partial chunk + the unused rest of a reservation (its work items were only cut just now)
-      if (bt_feeds[i]) mq_chunks[i] += 4ull * (mrk::MQ_BATCH + 1) * n_items_kind[1];
-    for (int i = 0; i < 3; ++i) mq_chunks[i] = std::min<uint64_t>(mq_chunks[i], (uint64_t)b->ctx->mq_max_chunks);
-  }
-  const size_t n_items_bm = items.size() - n_items_pk;
-  const size_t n_items = items.size();
-  b->stats.algo_bytes = algo_bytes;
-  b->stats.dev_bytes = dev_bytes;
+  const bool any_prox = plan.any_prox, any_tree = plan.any_tree;
+  const std::vector<DevQuery>& extra = plan.extra; // passes beyond the first of tree queries; pass index = n + position
+  b->gen_progs.swap(plan.gen_progs); // (copied to the device below: they live until the next submit)
+  // ---- launch layout (mrk_plan.cpp): the items in launch order, the scan_bm groups, the match queues' sizes
+  const mrk_ctx* c = b->ctx;
+  const mrk::LayoutKnobs knobs{c->pk_min_items, c->item_order, c->bm_target_items, c->bm_min_windows, c->bt_target_items, c->bm_group, c->mq_max_chunks};
+  mrk::BatchLayout lay;
+  mrk::layout_batch(b->h_queries.p, n, plan, use_packed, seg->dev.pk_attr1 != nullptr, knobs, lay);
+  const float plan_ms = std::chrono::duration<float, std::milli>(lay.t_block_items - t_submit0).count(); // (up to the block-scan section in order)
+  const size_t n_items = lay.items.size(), n_items_pk = lay.n_items_pk;
+  const uint64_t cand_total = plan.cand_total;
+  memcpy(b->stats.n_bm_groups, lay.n_bm_groups, sizeof lay.n_bm_groups);
+  b->stats.algo_bytes = plan.algo_bytes;
+  b->stats.dev_bytes = plan.dev_bytes;
   b->stats.packed = use_packed ? 1 : 0;
   b->stats.n_items = n_items;
-  b->stats.n_items_bm = n_items_bm;
+  b->stats.n_items_bm = n_items - n_items_pk;
+  // ---- reserve + stage
   int rc;
-  const size_t n_group_slots = groups.size() * (sizeof(BmGroup) / sizeof(DevItem)); // (the groups ride behind the work items)
+  const size_t n_group_slots = lay.groups.size() * (sizeof(BmGroup) / sizeof(DevItem)); // (the groups ride behind the work items)
   if ((rc = b->h_items.reserve(n_items + n_group_slots + 1)) || (rc = b->d_items.reserve(n_items + n_group_slots + 1)) ||
       (rc = b->d_item_cand.reserve((n_items + 1) * KCAP)) || (rc = b->d_item_cnt.reserve(n_items + 1)))
     return rc;
-  if (n_items) memcpy(b->h_items.p, items.data(), n_items * sizeof(DevItem));
-  if (n_group_slots) memcpy((void*)(b->h_items.p + n_items), groups.data(), groups.size() * sizeof(BmGroup));
+  if (n_items) memcpy(b->h_items.p, lay.items.data(), n_items * sizeof(DevItem));
+  if (n_group_slots) memcpy((void*)(b->h_items.p + n_items), lay.groups.data(), lay.groups.size() * sizeof(BmGroup));
   const size_t n_pass = (size_t)n + extra.size();
   if ((rc = b->h_queries.reserve_keep(n_pass, n)) || (rc = b->d_queries.reserve(n_pass))) return rc;
   if (!extra.empty()) memcpy(b->h_queries.p + n, extra.data(), extra.size() * sizeof(DevQuery));
@@ -1327,19 +1169,8 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   }
 
   ScanArgs sa{};
-  sa.seg = seg->dev;
-  sa.queries = b->d_queries.p;
-  sa.items = b->d_items.p;
-  sa.item_cand = b->d_item_cand.p;
-  sa.item_cnt = b->d_item_cnt.p;
-  sa.q_total = b->d_q_total.p;
-  sa.q_tau = b->d_q_tau.p;
-  sa.n_items = (uint32_t)(use_packed ? n_items_pk : n_items);
-  sa.q_hist = b->d_q_hist.p;
-  sa.q_cand_n = b->d_q_cand_n.p;
-  sa.q_flags = b->d_q_flags.p;
-  sa.q_tau_bin = b->d_q_tau_bin.p;
-  sa.cand = b->d_cand.p;
+  bind_scan(b, seg, sa);
+  sa.n_items = (uint32_t)n_items; // (the VLB path's one launch; launch_packed sets its sections')
   bool any_nearn = false;
   if (use_packed && any_prox && b->ctx->prox_prune) { // pruning in front of the hit pass (mrk_kprune.h, prox_bounds)
     const size_t words = (size_t)n * (2 * NBINS + mrk::QSTRIDE);
@@ -1349,6 +1180,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     sa.q_hist_lb2 = b->d_lb.p + (size_t)n * NBINS;
     sa.q_tau_lb = b->d_lb.p + (size_t)n * 2 * NBINS;
   }
+  const uint64_t* mq_chunks = lay.mq_chunks;
   if ((rc = bind_match_queues(b, mq_chunks, sa))) return rc;
   if (mq_chunks[0] || mq_chunks[1] || mq_chunks[2]) HIP_TRY(hipMemsetAsync(b->d_mq_count.p, 0, 3 * mrk::MQ_SHARDS * 4, st));
   if (!b->gen_progs.empty()) {
@@ -1360,62 +1192,18 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   lap("h2d+memset");
   HIP_TRY(hipEventRecord(b->ev_scan0, st));
   if (use_packed) {
-    launch_scan_pk(sa, max_terms, any_prox, any_tree, any_ext, st);
-    if (n_items_kind[1]) { // before the rank kernels: it feeds the match queue too
-      ScanArgs sb = sa;
-      sb.items = b->d_items.p + n_items_pk + n_items_kind[0];
-      sb.n_items = (uint32_t)n_items_kind[1];
-      launch_scan_bt(sb, st);
-    }
-    if (n_items_kind[2]) { // candidates of the generic evaluator
-      ScanArgs sg = sa;
-      sg.items = b->d_items.p + n_items_pk + n_items_kind[0] + n_items_kind[1];
-      sg.n_items = (uint32_t)n_items_kind[2];
-      launch_scan_pk(sg, max_terms, true, true, true, st, true);
-    }
-    // the queued matches of hit-ranked queries: hit pass + state rankers (mrk_rank.hip), behind the scans on the same stream
-    if (mq_chunks[0]) launch_rank(sa, 0, st);
-    if (mq_chunks[1]) launch_rank(sa, 1, st);
-    if (mq_chunks[2] && (rc = launch_gen_rank(sa, any_nearn, st))) return rc;
-    if (n_items_kind[0]) {
-      ScanArgs sb = sa;
-      sb.items = b->d_items.p + n_items_pk;
-      sb.n_items = (uint32_t)n_items_kind[0];
-      sb.bm_groups = n_group_slots ? (const BmGroup*)(b->d_items.p + n_items) : nullptr;
-      launch_scan_bm(sb, st);
-    }
+    if ((rc = launch_packed(sa, n_items_pk, lay.n_items_kind, mq_chunks, max_terms, any_prox, any_tree, any_ext, any_nearn,
+                            n_group_slots ? (const BmGroup*)(b->d_items.p + n_items) : nullptr, st)))
+      return rc;
   } else
     launch_scan(sa, st);
   HIP_TRY(hipEventRecord(b->ev_scan1, st));
   lap("scan launched");
   HIP_TRY(hipStreamWaitEvent(st2, b->ev_scan1, 0));
 
-  MergeArgs ma{};
-  ma.in_keys = b->d_item_cand.p;
-  ma.in_cnt = b->d_item_cnt.p;
-  ma.list_first = b->d_list_first.p;
-  ma.list_n = b->d_list_n.p;
-  ma.n_lists = 0;
-  ma.n_queries = n;
-  ma.k_per_query = b->d_kq.p;
-  ma.k = KCAP;
-  ma.out_keys = b->d_out_keys.p;
-  ma.out_cnt = b->d_out_cnt.p;
   if (use_packed) {
     SelectArgs se{};
-    se.queries = b->d_queries.p;
-    se.q_hist = b->d_q_hist.p;
-    se.q_cand_n = b->d_q_cand_n.p;
-    se.cand = b->d_cand.p;
-    se.n_queries = n;
-    se.rowid_base = seg->dev.rowid_base;
-    se.out_keys = b->d_out_keys.p;
-    se.out_cnt = b->d_out_cnt.p;
-    se.sel_tau = b->d_sel.p;
-    se.sel_nslice = b->d_sel.p + n;
-    se.slice_cnt = b->d_sel.p + 2 * (size_t)n;
-    se.max_slices = (uint32_t)std::min<uint64_t>(mrk::sel_slice_slots(cand_total, n), 1u << 30);
-    sel_rowid_range(seg, se);
+    bind_select(b, seg, n, cand_total, se);
     // results straight into the batch's pinned host memory (a batch with a standing rows destination feeds a shard merge:
     // its own lists stay on the device unless mrk_batch_result asks for them)
     se.q_total = b->d_q_total.p;
@@ -1427,8 +1215,20 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     se.rows_dst = b->rows_dst;
     se.declined = nullptr;
     launch_select(se, st2);
-  } else
+  } else {
+    MergeArgs ma{};
+    ma.in_keys = b->d_item_cand.p;
+    ma.in_cnt = b->d_item_cnt.p;
+    ma.list_first = b->d_list_first.p;
+    ma.list_n = b->d_list_n.p;
+    ma.n_lists = 0;
+    ma.n_queries = n;
+    ma.k_per_query = b->d_kq.p;
+    ma.k = KCAP;
+    ma.out_keys = b->d_out_keys.p;
+    ma.out_cnt = b->d_out_cnt.p;
     launch_merge(ma, st2);
+  }
   HIP_TRY(hipEventRecord(b->ev_merge1, st2));
   {
     bool any = false;
@@ -1510,7 +1310,7 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
       (bm ? items_bm : bt ? items_bt : (P.tree_flags & TF_GEN) ? items_gen : items_pk).push_back(it);
     }
   }
-  const size_t n_pk = items_pk.size(), n_bm = items_bm.size(), n_bt = items_bt.size(), n_gen = items_gen.size();
+  const size_t n_pk = items_pk.size(), n_kind[3] = {items_bm.size(), items_bt.size(), items_gen.size()};
   items_pk.insert(items_pk.end(), items_bm.begin(), items_bm.end());
   items_pk.insert(items_pk.end(), items_bt.begin(), items_bt.end());
   items_pk.insert(items_pk.end(), items_gen.begin(), items_gen.end());
@@ -1525,66 +1325,22 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   if (n_items) HIP_TRY(hipMemcpyAsync(r->d_items.p, r->h_items.p, n_items * sizeof(DevItem), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(r->d_state.p, 0, (size_t)r->max_queries * STATE_BYTES + (size_t)NBINS * 4, st));
   ScanArgs sa{};
-  sa.seg = seg->dev;
-  sa.queries = r->d_queries.p;
-  sa.items = r->d_items.p;
-  sa.q_total = r->d_q_total.p;
-  sa.q_tau = r->d_q_tau.p;
-  sa.n_items = (uint32_t)n_pk;
-  sa.q_hist = r->d_q_hist.p;
-  sa.q_cand_n = r->d_q_cand_n.p;
-  sa.q_flags = r->d_q_flags.p;
-  sa.q_tau_bin = r->d_q_tau_bin.p;
-  sa.cand = r->d_cand.p;
-  {
-    uint64_t chunks[3] = {0, 0, 0};
-    for (size_t p = 0; p < passes.size(); ++p) {
-      bool fat = false;
-      if (pass_queues_matches(passes[p], fat)) chunks[queue_of(passes[p], fat)] += pass_max_matches(passes[p]) / 64 + 4ull * (mrk::MQ_BATCH + 1) * n_items + 1;
-    }
-    for (int i = 0; i < 3; ++i)
-      if (chunks[i] > (1ull << 25)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: match queue for the rerun too large", qi);
-    if ((rc = bind_match_queues(r, chunks, sa))) return rc;
-    if (chunks[0] || chunks[1] || chunks[2]) HIP_TRY(hipMemsetAsync(r->d_mq_count.p, 0, 3 * mrk::MQ_SHARDS * 4, st));
-    const bool nearn = (passes[0].tree_flags & TF_GEN_NEARN) != 0;
-    if (n_gen && (rc = bind_gen(r, b, sa, st, 1, nearn))) return rc; // (the programs are the submit's, still on the device)
-    launch_scan_pk(sa, b->last_max_terms, b->last_prox, b->last_tree, b->last_ext, st);
-    if (n_gen) {
-      ScanArgs sg = sa;
-      sg.items = r->d_items.p + n_pk + n_bm + n_bt;
-      sg.n_items = (uint32_t)n_gen;
-      launch_scan_pk(sg, b->last_max_terms, true, true, true, st, true);
-    }
-    if (n_bt) {
-      ScanArgs sb = sa;
-      sb.items = r->d_items.p + n_pk + n_bm;
-      sb.n_items = (uint32_t)n_bt;
-      launch_scan_bt(sb, st);
-    }
-    if (chunks[0]) launch_rank(sa, 0, st);
-    if (chunks[1]) launch_rank(sa, 1, st);
-    if (chunks[2] && (rc = launch_gen_rank(sa, nearn, st))) return rc;
+  bind_scan(r, seg, sa);
+  // match queues for every doc a pass can match (no cap: this run must not overflow), every pass charged the whole rerun's items
+  uint64_t chunks[3] = {0, 0, 0};
+  for (const DevQuery& P : passes) {
+    bool fat = false;
+    if (pass_queues_matches(P, fat)) chunks[queue_of(P, fat)] += pass_max_matches(P) / 64 + 4ull * (mrk::MQ_BATCH + 1) * n_items + 1;
   }
-  if (n_bm) {
-    ScanArgs sb = sa;
-    sb.items = r->d_items.p + n_pk;
-    sb.n_items = (uint32_t)n_bm;
-    launch_scan_bm(sb, st);
-  }
+  for (int i = 0; i < 3; ++i)
+    if (chunks[i] > (1ull << 25)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: match queue for the rerun too large", qi);
+  if ((rc = bind_match_queues(r, chunks, sa))) return rc;
+  if (chunks[0] || chunks[1] || chunks[2]) HIP_TRY(hipMemsetAsync(r->d_mq_count.p, 0, 3 * mrk::MQ_SHARDS * 4, st));
+  const bool nearn = (passes[0].tree_flags & TF_GEN_NEARN) != 0;
+  if (n_kind[2] && (rc = bind_gen(r, b, sa, st, 1, nearn))) return rc; // (the programs are the submit's, still on the device)
+  if ((rc = launch_packed(sa, n_pk, n_kind, chunks, b->last_max_terms, b->last_prox, b->last_tree, b->last_ext, nearn, nullptr, st))) return rc;
   SelectArgs se{};
-  se.queries = r->d_queries.p;
-  se.q_hist = r->d_q_hist.p;
-  se.q_cand_n = r->d_q_cand_n.p;
-  se.cand = r->d_cand.p;
-  se.n_queries = 1;
-  se.rowid_base = seg->dev.rowid_base;
-  se.out_keys = r->d_out_keys.p;
-  se.out_cnt = r->d_out_cnt.p;
-  se.sel_tau = r->d_sel.p;
-  se.sel_nslice = r->d_sel.p + 1;
-  se.slice_cnt = r->d_sel.p + 2;
-  se.max_slices = (uint32_t)std::min<uint64_t>(mrk::sel_slice_slots(cap, 1), 1u << 30);
-  sel_rowid_range(seg, se);
+  bind_select(r, seg, 1, cap, se);
   launch_select(se, st);
   HIP_TRY(hipGetLastError());
   uint32_t flags = 0;

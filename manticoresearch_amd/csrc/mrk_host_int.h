@@ -1,9 +1,10 @@
-// mrk_host_int.h -- host-side objects shared by mrk_host.cpp (segments, batches, C-ABI) and mrk_plan.cpp (query planner).
+// mrk_host_int.h -- host-side objects shared by mrk_host.cpp (segments, batches, C-ABI) and mrk_plan.cpp (query planner, launch layout).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <atomic>
+#include <chrono>
 #include <vector>
 
 #include "mrk_dev.h"
@@ -113,15 +114,27 @@ hipEvent_t mrk_comm_rows_ready_event(mrk_ctx* ctx);
 
 namespace mrk {
 
+// What the planning loop of one batch accumulates: plan_query appends a query's passes, work items and byte counts to it, and
+// layout_batch turns it into the launch's item array.
+struct BatchPlan {
+  std::vector<DevQuery> extra;     // passes beyond a query's head pass; pass index = n_queries + position
+  std::vector<DevItem> items;      // block-scan work items, a query's back to back
+  std::vector<DevItem> items_bm;   // one whole window range per scan_bm (kind 0) / scan_bt (kind 1) pass; the generic evaluator's block items (kind 2), already cut
+  std::vector<GenProg> gen_progs;  // programs of the generic evaluator (DevQuery::gen_prog indexes it)
+  uint64_t algo_bytes = 0, dev_bytes = 0, cand_total = 0;
+  bool any_prox = false, any_tree = false;
+  // a declined query runs no device work: what it appended is taken back (the byte counts and flags stay as plan_query left them)
+  struct Mark { size_t extra, items, items_bm, gen_progs; };
+  Mark mark() const { return Mark{extra.size(), items.size(), items_bm.size(), gen_progs.size()}; }
+  void rewind(const Mark& m) { extra.resize(m.extra), items.resize(m.items), items_bm.resize(m.items_bm), gen_progs.resize(m.gen_progs); }
+};
+
 // Plans one query of a batch: validates it, builds the reference-shaped evaluation tree, computes IDFs, pruning
-// histogram geometry and candidate capacity, and emits the query's passes and work items.  Returns MRK_OK, or
+// histogram geometry and candidate capacity, and emits the query's passes and work items into `plan`.  Returns MRK_OK, or
 // MRK_E_UNSUPPORTED / MRK_E_INVAL with the message set.  dq = the query's head pass (index qi); further passes go to
-// `extra` and get pass indices n_queries + position; bitmap-kernel work goes to items_bm as one whole-range entry.
-int plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq,
-               std::vector<DevQuery>& extra, uint32_t n_queries, std::vector<DevItem>& items, std::vector<DevItem>& items_bm,
-               uint32_t qi, uint64_t& algo_bytes, uint64_t& dev_bytes, uint64_t& cand_total, bool& prox_out, bool& tree_out,
-               std::vector<mrk::GenProg>& gen_progs, uint32_t rowid_max = 0xFFFFFFFFu); // gen_progs: programs of the generic evaluator (DevQuery::gen_prog indexes it); their
-                                                      // work items go to items_bm with kind 2, already cut
+// plan.extra and get pass indices n_queries + position.
+int plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
+               BatchPlan& plan, uint32_t rowid_max = 0xFFFFFFFFu);
 
 // Groups of a batch's scan_bm queries for the grouped bitmap kernel ("bm_group", mrk_batch_submit).  A member names its two
 // keywords (key: bitmap offset + idf bits, so that members sharing a key share its tfidf table too), the bytes a walk of each
@@ -136,6 +149,33 @@ struct BmMember {
   uint32_t cls;
 };
 void plan_bm_groups(const std::vector<BmMember>& m, std::vector<uint32_t>& order, std::vector<uint32_t>& sizes);
+
+// mirrors scan_pk_kernel: matches of these passes leave through the match queue (state rankers over more than one
+// keyword, whole-query PHRASE); `fat` = the queue whose consumer carries the word state machines
+bool pass_queues_matches(const DevQuery& P, bool& fat);
+int queue_of(const DevQuery& P, bool fat);
+// upper bound of the docs a pass can match: its driver's docs; the common docs for the two-bitmap AND; any keyword's docs for
+// a tree evaluated on bitmap words
+uint64_t pass_max_matches(const DevQuery& P);
+
+// The launch layout of a planned batch on the packed path (host arithmetic only): block ranges cut finer for small batches,
+// the whole window ranges of scan_bm / scan_bt cut into pieces, each section in query-major or piece-major order, scan_bm
+// queries that share a keyword put in groups, the match queues sized.
+struct LayoutKnobs { // the context's settings of the same names
+  int pk_min_items, item_order, bm_target_items, bm_min_windows, bt_target_items, bm_group, mq_max_chunks;
+};
+struct BatchLayout {
+  std::vector<DevItem> items;       // launch order: block-scan items, then kind 0 (scan_bm), kind 1 (scan_bt), kind 2 (generic evaluator)
+  size_t n_items_pk = 0;            // ... the first section's length
+  size_t n_items_kind[3] = {0, 0, 0}; // ... and the others'
+  std::vector<BmGroup> groups;      // grouped scan_bm: a kind-0 item's `query` indexes it (empty: it is a pass index)
+  uint32_t n_bm_groups[BM_GROUP_MAX] = {}; // groups of 1 .. BM_GROUP_MAX members
+  uint64_t mq_chunks[3] = {0, 0, 0}; // chunks of each match queue (0 = unused)
+  std::chrono::steady_clock::time_point t_block_items; // when the block-scan section was in order (mrk_batch_stats::plan_ms ends there)
+};
+// head[0 .. n) = the queries' head passes; takes plan.items, and writes the piece counts of the passes it cut to their n_items
+// (head and plan.extra).  nibble_plane: the segment has the one-byte tf/field plane (it halves what a keyword's walk costs a group).
+void layout_batch(DevQuery* head, uint32_t n, BatchPlan& plan, bool use_packed, bool nibble_plane, const LayoutKnobs& knobs, BatchLayout& out);
 
 // Least and largest field-weight sum over the masks of the first nwf (<= 32) fields, the empty mask counting as 1
 // (ExtRanker_WeightSum_c's "just fake it"): the pruning bins of the weight-sum rankers.

@@ -717,15 +717,10 @@ void mrk::weight_sum_range(const int32_t* weights, uint32_t nwf, int64_t& rmin, 
   rmax = std::max<int64_t>(1, any_pos ? pos : wmax);
 }
 
-// returns MRK_OK, or MRK_E_UNSUPPORTED / MRK_E_INVAL with the message set.  dq = the query's head pass
-// (index qi); further passes go to `extra` and get pass indices n_queries + position.
-int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq,
-                      std::vector<DevQuery>& extra, uint32_t n_queries, std::vector<DevItem>& items,
-                      std::vector<DevItem>& items_bm, uint32_t qi,
-                      uint64_t& algo_bytes, uint64_t& dev_bytes, uint64_t& cand_total, bool& prox_out, bool& tree_out, std::vector<mrk::GenProg>& gen_progs,
-                      uint32_t rowid_max) {
+int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
+                    BatchPlan& plan, uint32_t rowid_max) {
   memset(&dq, 0, sizeof dq);
-  dq.item_first = (uint32_t)items.size();
+  dq.item_first = (uint32_t)plan.items.size();
   dq.out_q = qi;
   if (!q.nodes || q.n_nodes <= 0 || q.root < 0 || q.root >= q.n_nodes) return mrk_fail(MRK_E_INVAL, "query %u: bad tree", qi);
   for (int i = 0; i < q.n_nodes; ++i) // (ExtHit_t::m_uQuerypos is a WORD, sphinxint.h:733; the arithmetic on positions below assumes as much)
@@ -1119,18 +1114,18 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
     for (int k : cover) cap += (uint64_t)T.kws[k].docs;
     cap = std::min<uint64_t>(std::max<uint64_t>(cap, 1), (uint64_t)1 << 20);
     dq.cand_cap = (uint32_t)cap;
-    dq.cand_off = cand_total;
-    cand_total += cap;
+    dq.cand_off = plan.cand_total;
+    plan.cand_total += cap;
   }
   if (empty) {
     dq.n_terms = (uint32_t)n;
     dq.n_items = 0;
     return MRK_OK;
   }
-  algo_bytes += bytes;
-  dev_bytes += use_packed ? pbytes : bytes;
-  prox_out = prox_out || prox || T.phrase || T.ph_leaf || T.termpos || T.notnear || T.gen; // (every generic-path candidate goes through the queue)
-  tree_out = tree_out || !pure_and;
+  plan.algo_bytes += bytes;
+  plan.dev_bytes += use_packed ? pbytes : bytes;
+  plan.any_prox = plan.any_prox || prox || T.phrase || T.ph_leaf || T.termpos || T.notnear || T.gen; // (every generic-path candidate goes through the queue)
+  plan.any_tree = plan.any_tree || !pure_and;
 
   // two dense keywords: the bitmap kernel (mrk_scan_bm.hip) walks 2048-rowid windows instead of blocks
   if (use_packed && pure_and && !T.phrase && n == 2 && !filtered && q.n_weight_filters == 0 && (ranker == MRK_RANK_NONE || ranker == MRK_RANK_BM25) && seg->dev.bm && !seg->wide &&
@@ -1138,18 +1133,18 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
     dq.n_terms = 2;
     for (int i = 0; i < 2; ++i) fill_term(seg, T.kws[i], dq.t[i]);
     dq.tree_flags = TF_MULTIAND | TF_BITMAP;
-    dq.item_first = (uint32_t)items_bm.size();
+    dq.item_first = (uint32_t)plan.items_bm.size();
     const uint64_t nwin = seg->dev.n_windows;
     // bitmaps + tf / field bytes of the docs (one byte each where the segment has the nibble plane, else the attr words)
     const uint64_t bm_bytes = 2 * nwin * 256 + ((uint64_t)dq.t[0].nblocks + dq.t[1].nblocks) * (seg->dev.pk_attr1 ? 128 : 256);
-    dev_bytes += bm_bytes - pbytes; // (pbytes was added above)
+    plan.dev_bytes += bm_bytes - pbytes; // (pbytes was added above)
     // one entry for the whole window range; mrk_batch_submit cuts it once the batch's total is known (a wave's
     // fixed costs -- tables, final publish, atomics on the query's counters -- want long runs of windows)
     DevItem it{};
     it.query = qi;
     it.blk_begin = 0;
     it.blk_end = (uint32_t)nwin;
-    items_bm.push_back(it);
+    plan.items_bm.push_back(it);
     dq.n_items = 1;
     return MRK_OK;
   }
@@ -1185,7 +1180,7 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
         const PlanNode& pn = T.nodes[i];
         dq.prog[i] = pn.op | ((uint32_t)(pn.l < 0 ? 0 : pn.l) << 8) | ((uint32_t)(pn.r < 0 ? 0 : pn.r) << 16) | ((uint32_t)(pn.kw < 0 ? 0 : pn.kw) << 24);
       }
-      dq.item_first = (uint32_t)items_bm.size();
+      dq.item_first = (uint32_t)plan.items_bm.size();
       const uint64_t nwin = seg->dev.n_windows;
       uint64_t bt_bytes = 0; // bitmaps of the dense keywords + packed blocks of the sparse ones + every keyword's tf / field words
       for (int k = 0; k < n; ++k)
@@ -1193,13 +1188,13 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
           const HostTerm& h = seg->terms[T.kws[k].term_id];
           bt_bytes += h.bm_off != ~0ull ? nwin * 256 + (uint64_t)h.nblocks * 256 : h.packed_bytes;
         }
-      dev_bytes += bt_bytes - pbytes; // (pbytes was added above)
+      plan.dev_bytes += bt_bytes - pbytes; // (pbytes was added above)
       DevItem it{};
       it.query = qi;
       it.blk_begin = 0;
       it.blk_end = (uint32_t)nwin;
       it.kind = 1;
-      items_bm.push_back(it);
+      plan.items_bm.push_back(it);
       dq.n_items = 1;
       return MRK_OK;
     }
@@ -1212,12 +1207,12 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
     DevQuery* P = &dq;
     uint32_t pass_index = qi;
     if (p > 0) {
-      extra.push_back(base);
-      P = &extra.back();
-      pass_index = n_queries + (uint32_t)extra.size() - 1;
-      P->item_first = (uint32_t)items.size();
+      plan.extra.push_back(base);
+      P = &plan.extra.back();
+      pass_index = n_queries + (uint32_t)plan.extra.size() - 1;
+      P->item_first = (uint32_t)plan.items.size();
     }
-    if (T.gen) P->item_first = (uint32_t)items_bm.size(), P->n_items = 0;
+    if (T.gen) P->item_first = (uint32_t)plan.items_bm.size(), P->n_items = 0;
     // keyword order of this pass: driver, then required keywords by ascending docs, then the rest
     IntVec order;
     const int drv = cover[p];
@@ -1251,8 +1246,8 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
           for (int k = 0; k < g.n_words; ++k) g.aux[k] = (uint8_t)slot[g.aux[k]];
         if (g.kind == GN_UNIT && g.aux[0] != 0xFF) g.aux[0] = (uint8_t)slot[g.aux[0]];
       }
-      P->gen_prog = (uint32_t)gen_progs.size();
-      gen_progs.push_back(gp);
+      P->gen_prog = (uint32_t)plan.gen_progs.size();
+      plan.gen_progs.push_back(gp);
     }
     P->nn_a = T.notnear ? (uint32_t)slot[T.nn_a] : 0u, P->nn_b = T.notnear ? (uint32_t)slot[T.nn_b] : 0u, P->nn_dist = (uint32_t)T.nn_dist;
     P->px_dist = (uint32_t)T.px_dist;
@@ -1319,20 +1314,20 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
       for (const PlanNode& pn : T.nodes) sp += pn.op == PN_TERM ? 1 : -1, deep = std::max(deep, sp);
       if (ok && n_dense > 0 && deep <= TREE_STACK) {
         P->tree_flags |= TF_BTREE | TF_MULTIAND;
-        P->item_first = (uint32_t)items_bm.size();
+        P->item_first = (uint32_t)plan.items_bm.size();
         const uint64_t nwin = seg->dev.n_windows;
         uint64_t bt_bytes = 0;
         for (int k = 0; k < n; ++k) {
           const HostTerm& h = seg->terms[T.kws[k].term_id];
           bt_bytes += h.bm_off != ~0ull ? nwin * 256 + (uint64_t)h.nblocks * 256 : h.packed_bytes;
         }
-        dev_bytes += bt_bytes - pbytes; // (pbytes was added above)
+        plan.dev_bytes += bt_bytes - pbytes; // (pbytes was added above)
         DevItem it{};
         it.query = pass_index;
         it.blk_begin = 0;
         it.blk_end = (uint32_t)nwin;
         it.kind = 1;
-        items_bm.push_back(it);
+        plan.items_bm.push_back(it);
         P->n_items = 1;
         continue;
       }
@@ -1350,13 +1345,13 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
         it.blk_end = (uint32_t)std::min<uint64_t>(nb0, b + bpi);
         if (T.gen) { // its own launch (the scan instance that hands over a reference per keyword), behind the block items
           it.kind = 2;
-          items_bm.push_back(it);
+          plan.items_bm.push_back(it);
           ++P->n_items;
         } else
-          items.push_back(it);
+          plan.items.push_back(it);
       }
     }
-    if (!T.gen) P->n_items = (uint32_t)items.size() - P->item_first;
+    if (!T.gen) P->n_items = (uint32_t)plan.items.size() - P->item_first;
   }
   return MRK_OK;
 }
@@ -1450,5 +1445,230 @@ void mrk::plan_bm_groups(const std::vector<BmMember>& m, std::vector<uint32_t>& 
     for (uint32_t j = 0; j < nm; ++j) // no key of theirs is held by another member left: alone
       if (!done[j]) order.push_back(mem[j]), sizes.push_back(1);
     c0 = c1;
+  }
+}
+
+bool mrk::pass_queues_matches(const DevQuery& P, bool& fat) {
+  const uint32_t rk = P.ranker;
+  if (P.tree_flags & mrk::TF_GEN) return fat = false, true; // (queue 2: see queue_of)
+  const bool prox_ranker = (rk == MRK_RANK_PROXIMITY_BM25 || rk == MRK_RANK_PROXIMITY)
+                               ? P.n_terms > 1
+                               : (rk == MRK_RANK_WORDCOUNT || rk == MRK_RANK_MATCHANY || rk == MRK_RANK_FIELDMASK || rk == MRK_RANK_SPH04);
+  fat = (P.tree_flags & mrk::TF_FAT) != 0;
+  return prox_ranker || (P.tree_flags & mrk::TF_PHRASE) != 0;
+}
+
+int mrk::queue_of(const DevQuery& P, bool fat) { return (P.tree_flags & mrk::TF_GEN) ? 2 : fat ? 1 : 0; }
+
+uint64_t mrk::pass_max_matches(const DevQuery& P) {
+  if (P.tree_flags & mrk::TF_BITMAP) return std::min<uint64_t>(P.t[0].docs, P.t[1].docs);
+  if (P.tree_flags & mrk::TF_BTREE) {
+    uint64_t d = 0, least = ~0ull;
+    for (uint32_t k = 0; k < P.n_terms && k < (uint32_t)MRK_MAX_AND_TERMS; ++k) d += P.t[k].docs, least = std::min<uint64_t>(least, P.t[k].docs);
+    return (P.tree_flags & mrk::TF_MULTIAND) && P.n_terms ? least : d; // (an AND of keywords holds no more docs than its rarest one)
+  }
+  return P.t[0].docs;
+}
+
+// The batch's scan_bm queries (items_bm entries of kind 0, one whole window range each) in groups, and per group the items_bm
+// entry of its first member (a group's members share the window range)
+static void group_bm_items(const DevQuery* head, uint32_t n, const std::vector<DevQuery>& extra, const std::vector<DevItem>& items_bm, bool nib,
+                           std::vector<BmGroup>& groups, std::vector<uint32_t>& group_item) {
+  auto pass = [&](uint32_t p) -> const DevQuery& { return p < n ? head[p] : extra[p - n]; };
+  auto tkey = [](const DevTerm& T) { // (bitmap, idf): one key = one tfidf table
+    uint32_t idf;
+    memcpy(&idf, &T.idf, 4);
+    return std::make_pair(T.bm_off, idf);
+  };
+  std::vector<std::pair<uint64_t, uint32_t>> keys;
+  for (const DevItem& it : items_bm)
+    if (it.kind == 0) keys.push_back(tkey(pass(it.query).t[0])), keys.push_back(tkey(pass(it.query).t[1]));
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  std::vector<uint32_t> ent; // items_bm index of member i
+  std::vector<BmMember> mem;
+  std::vector<uint32_t> cls_rep; // per class: a member's entry
+  for (uint32_t e = 0; e < items_bm.size(); ++e) {
+    const DevItem& it = items_bm[e];
+    if (it.kind != 0) continue;
+    const DevQuery& P = pass(it.query);
+    const uint32_t nw = std::min<uint32_t>(P.n_weights, 8u);
+    BmMember x{};
+    x.cls = ~0u;
+    for (uint32_t c = 0; c < cls_rep.size() && x.cls == ~0u; ++c) { // same windows, same field-weight table
+      const DevItem& r = items_bm[cls_rep[c]];
+      const DevQuery& R = pass(r.query);
+      if (r.blk_begin == it.blk_begin && r.blk_end == it.blk_end && std::min<uint32_t>(R.n_weights, 8u) == nw &&
+          !memcmp(R.weights, P.weights, nw * sizeof(int32_t)))
+        x.cls = c;
+    }
+    if (x.cls == ~0u) x.cls = (uint32_t)cls_rep.size(), cls_rep.push_back(e);
+    for (int t = 0; t < 2; ++t) {
+      x.key[t] = (uint64_t)(std::lower_bound(keys.begin(), keys.end(), tkey(P.t[t])) - keys.begin());
+      x.bytes[t] = (uint64_t)(it.blk_end - it.blk_begin) * 256 + (uint64_t)P.t[t].nblocks * (nib ? 128 : 256);
+    }
+    ent.push_back(e), mem.push_back(x);
+  }
+  std::vector<uint32_t> order, sizes;
+  plan_bm_groups(mem, order, sizes);
+  groups.clear(), group_item.clear();
+  size_t o = 0;
+  for (uint32_t sz : sizes) {
+    BmGroup g{};
+    g.n = sz;
+    g.per = WAVES / sz;
+    uint64_t tab_key[BM_GROUP_TABS];
+    for (uint32_t j = 0; j < sz; ++j) {
+      const uint32_t i = order[o + j];
+      g.q[j] = items_bm[ent[i]].query;
+      for (uint32_t t = 0; t < 2; ++t) {
+        uint32_t k = 0;
+        while (k < g.ntab && tab_key[k] != mem[i].key[t]) ++k;
+        if (k == g.ntab) tab_key[g.ntab] = mem[i].key[t], g.tab_src[g.ntab++] = j << 1 | t; // (<= 5: every member holds the seed)
+        g.tab_idx |= k << (6 * j + 3 * t);
+      }
+    }
+    groups.push_back(g);
+    group_item.push_back(ent[order[o]]);
+    o += sz;
+  }
+}
+
+// Walks the pieces 0, 1, ... of ranges 0 .. n_ranges (piece(r, k) emits piece k of range r, or returns false past the range's
+// end): query-major, a range's pieces back to back, or piece-major, the k-th piece of every range, then the (k+1)-th ...
+template <class Piece>
+static void for_pieces(size_t n_ranges, bool piece_major, Piece piece) {
+  if (!piece_major) {
+    for (size_t r = 0; r < n_ranges; ++r)
+      for (uint64_t k = 0; piece(r, k); ++k) {}
+    return;
+  }
+  for (uint64_t k = 0;; ++k) {
+    bool any = false;
+    for (size_t r = 0; r < n_ranges; ++r) any = piece(r, k) || any;
+    if (!any) break;
+  }
+}
+
+// piece k of `whole` cut into pieces of `len`, appended to `out`; false past its end
+static bool cut_piece(const DevItem& whole, uint64_t len, uint64_t k, std::vector<DevItem>& out) {
+  const uint64_t x = whole.blk_begin + k * len;
+  if (x >= whole.blk_end) return false;
+  DevItem it = whole;
+  it.blk_begin = (uint32_t)x;
+  it.blk_end = (uint32_t)std::min<uint64_t>(whole.blk_end, x + len);
+  out.push_back(it);
+  return true;
+}
+
+void mrk::layout_batch(DevQuery* head, uint32_t n, BatchPlan& plan, bool use_packed, bool nibble_plane, const LayoutKnobs& knobs, BatchLayout& out) {
+  std::vector<DevQuery>& extra = plan.extra;
+  const std::vector<DevItem>& items_bm = plan.items_bm;
+  const bool any_prox = plan.any_prox;
+  out = BatchLayout{};
+  std::vector<DevItem>& items = out.items;
+  items.swap(plan.items);
+  // A small batch (one-eighth shards, selective keywords, a lone query): the planner cuts a driver doclist into ~item_bytes
+  // pieces whatever the batch holds, and 280 workgroups that each walk 70 blocks per wave one after the other leave the chip
+  // idle for 0.1 ms.  Cut the block ranges finer until the launch has pk_min_items work items (never under one block per wave).
+  if (use_packed && !items.empty() && items.size() < (size_t)knobs.pk_min_items) {
+    uint64_t total_blocks = 0;
+    for (const DevItem& it : items) total_blocks += it.blk_end - it.blk_begin;
+    uint64_t per = (total_blocks + (uint64_t)knobs.pk_min_items - 1) / (uint64_t)knobs.pk_min_items;
+    per = std::max<uint64_t>(T0_BLOCKS, (per + T0_BLOCKS - 1) / T0_BLOCKS * T0_BLOCKS);
+    std::vector<DevItem> cut;
+    cut.reserve(items.size() + (size_t)(total_blocks / per) + 1);
+    std::vector<uint32_t> per_pass((size_t)n + extra.size(), 0);
+    for_pieces(items.size(), false, [&](size_t r, uint64_t k) {
+      if (!cut_piece(items[r], per, k, cut)) return false;
+      if (items[r].query < per_pass.size()) ++per_pass[items[r].query];
+      return true;
+    });
+    items.swap(cut);
+    // (the counts feed the match-queue sizing below; the VLB path's per-query list ranges are not built from a packed plan)
+    for (uint32_t i = 0; i < n; ++i)
+      if (per_pass[i]) head[i].n_items = per_pass[i];
+    for (size_t e = 0; e < extra.size(); ++e)
+      if (per_pass[n + e]) extra[e].n_items = per_pass[n + e];
+  }
+  // ... and in piece-major order, for the reason given at the window-range items below: concurrent workgroups should belong
+  // to different queries (the planner emits a query's items back to back; only the VLB path needs them that way)
+  // (not for batches whose matches travel through the match queue to the hit pass: config 3 measured 6.6 ms query-major, 7.1 ms
+  // interleaved -- the rank kernel likes a query's chunks in rowid order)
+  if (use_packed && items.size() > 1 && (knobs.item_order & 1) && (!any_prox || (knobs.item_order & 8))) {
+    std::vector<size_t> run_begin, run_end; // runs of items of one pass: its ranges, their pieces the items
+    for (size_t i = 0; i < items.size();) {
+      size_t j = i + 1;
+      while (j < items.size() && items[j].query == items[i].query) ++j;
+      run_begin.push_back(i), run_end.push_back(j);
+      i = j;
+    }
+    std::vector<DevItem> rr;
+    rr.reserve(items.size());
+    for_pieces(run_begin.size(), true, [&](size_t r, uint64_t k) {
+      if (run_begin[r] + k >= run_end[r]) return false;
+      rr.push_back(items[run_begin[r] + k]);
+      return true;
+    });
+    items.swap(rr);
+  }
+  out.t_block_items = std::chrono::steady_clock::now();
+  out.n_items_pk = items.size();
+  // window-range work items (two-bitmap AND kernel, then the window-driven tree kernel) ride behind the block work
+  // items; each kind's whole-range entries are cut once the batch's total is known (a wave's fixed costs -- tables, final
+  // publish, atomics on the query's counters -- want long runs of windows)
+  for (uint32_t kind = 0; kind < 2; ++kind) {
+    uint64_t total_win = 0;
+    for (const DevItem& it : items_bm)
+      if (it.kind == kind) total_win += it.blk_end - it.blk_begin;
+    if (!total_win) continue;
+    const uint64_t unit = 4 * WAVES; // one burst per wave
+    uint64_t wpi = (total_win / (uint64_t)(kind == 0 ? knobs.bm_target_items : knobs.bt_target_items) / unit) * unit;
+    wpi = std::min<uint64_t>(std::max<uint64_t>(wpi, kind == 0 ? (uint64_t)knobs.bm_min_windows / unit * unit : 4 * unit), 4096); // (short runs: a wave's fixed costs show -- 12.5 M docs, 8192 items: 0.55 vs 0.47 ms)
+    std::vector<DevItem> whole; // the ranges to cut ...
+    std::vector<uint64_t> len;  // ... and each one's piece length
+    if (kind == 0 && knobs.bm_group && (knobs.item_order & 2)) {
+      // Queries that share a keyword run in one workgroup, a wave (or two) per member over the same windows: the shared
+      // keyword's bitmap words and tf / field lines are then fetched once per CU instead of once per query
+      std::vector<uint32_t> group_item; // per group its first member's whole-range entry in items_bm
+      group_bm_items(head, n, extra, items_bm, nibble_plane, out.groups, group_item);
+      for (uint32_t g = 0; g < out.groups.size(); ++g) {
+        ++out.n_bm_groups[out.groups[g].n - 1];
+        whole.push_back(items_bm[group_item[g]]);
+        whole.back().query = g;
+        len.push_back(wpi * out.groups[g].per / WAVES); // a wave walks wpi / WAVES windows, as in the ungrouped layout
+      }
+    } else
+      for (const DevItem& it : items_bm)
+        if (it.kind == kind) whole.push_back(it), len.push_back(wpi);
+    // Piece-major order: the k-th piece of every query, then the (k+1)-th ...  Workgroups that run at the same time then
+    // belong to DIFFERENT queries.  Query-major order put a query's 20-50 workgroups on the chip together, all of them adding
+    // to the one candidate counter, the same few histogram bins and the one threshold word of that query: device-scope
+    // atomics on one address serialize at the memory side (~70 ns each), about 0.1 ms per query whatever the shard size --
+    // hidden behind 100 M docs, the whole launch at 12.5 M (12288 work items: 0.85 ms; 4096: 0.39 ms, same bytes).
+    // Query-major: experiments, and trees that feed the match queue (see the block items above).
+    const bool piece_major = (knobs.item_order & (kind == 0 ? 2 : 4)) && !(kind == 1 && any_prox && !(knobs.item_order & 8));
+    const size_t before = items.size();
+    for_pieces(whole.size(), piece_major, [&](size_t r, uint64_t k) { return cut_piece(whole[r], len[r], k, items); });
+    out.n_items_kind[kind] = items.size() - before;
+  }
+  for (const DevItem& it : items_bm) // the generic evaluator's candidates: block ranges, cut by the planner
+    if (it.kind == 2) items.push_back(it), ++out.n_items_kind[2];
+  // match queues: a pass hands over at most one entry per doc it can match, plus one partial chunk per wave of its items
+  uint64_t (&mq_chunks)[3] = out.mq_chunks;
+  if (use_packed && any_prox) {
+    bool bt_feeds[3] = {false, false, false};
+    auto account = [&](const DevQuery& P) {
+      bool fat = false;
+      if (!P.n_items || !pass_queues_matches(P, fat)) return;
+      const bool bt = (P.tree_flags & mrk::TF_BTREE) != 0;
+      mq_chunks[queue_of(P, fat)] += pass_max_matches(P) / 64 + (bt ? 0 : 4ull * (mrk::MQ_BATCH + 1) * P.n_items) + 1;
+      bt_feeds[queue_of(P, fat)] = bt_feeds[queue_of(P, fat)] || bt;
+    };
+    for (uint32_t i = 0; i < n; ++i) account(head[i]);
+    for (const DevQuery& P : extra) account(P);
+    for (int i = 0; i < 2; ++i) // per wave one partial chunk + the unused rest of a reservation (its work items were only cut just now)
+      if (bt_feeds[i]) mq_chunks[i] += 4ull * (mrk::MQ_BATCH + 1) * out.n_items_kind[1];
+    for (int i = 0; i < 3; ++i) mq_chunks[i] = std::min<uint64_t>(mq_chunks[i], (uint64_t)knobs.mq_max_chunks);
   }
 }

@@ -186,14 +186,12 @@ int main(int argc, char** argv) {
 
     const mrk_segment* seg = &segs[below(3)];
     DevQuery dq;
-    std::vector<DevQuery> extra;
-    std::vector<DevItem> items, items_bm;
-    std::vector<mrk::GenProg> progs;
-    uint64_t ab = 0, db = 0, ct = 0;
-    bool prox = false, tree = false;
+    mrk::BatchPlan plan;
+    const std::vector<DevQuery>& extra = plan.extra;
+    const std::vector<DevItem>&items = plan.items, &items_bm = plan.items_bm;
+    const std::vector<mrk::GenProg>& progs = plan.gen_progs;
     const uint32_t n_queries = 1 + below(4), qi = below(n_queries);
-    const int rc = mrk::plan_query(seg, q, 128 << 10, seg->has_packed && chance(90), dq, extra, n_queries, items, items_bm, qi, ab, db, ct, prox, tree, progs,
-                                   chance(90) ? 0xFFFFFFFFu : below(1000000));
+    const int rc = mrk::plan_query(seg, q, 128 << 10, seg->has_packed && chance(90), dq, n_queries, qi, plan, chance(90) ? 0xFFFFFFFFu : below(1000000));
     if (rc == MRK_OK) {
       ++n_ok;
       // what the launch code relies on

@@ -271,20 +271,16 @@ static void test_plan(int iters, int& n_ok, int& n_uns) {
     q.n_weights = below(2) ? 32 : (int)below(33);
     q.index_weight = 1 + (int)below(3);
     DevQuery dq, dn;
-    std::vector<DevQuery> extra, extra_n;
-    std::vector<DevItem> items, items_bm, items_n, items_bm_n;
-    std::vector<mrk::GenProg> progs, progs_n;
-    uint64_t ab = 0, db = 0, ct = 0, abn = 0, dbn = 0, ctn = 0;
-    bool prox = false, tree = false, prox_n = false, tree_n = false;
-    const int rc = mrk::plan_query(&S, q, 128 << 10, true, dq, extra, 1, items, items_bm, 0, ab, db, ct, prox, tree, progs);
+    mrk::BatchPlan plan, plan_n;
+    const int rc = mrk::plan_query(&S, q, 128 << 10, true, dq, 1, 0, plan);
     const std::string err_w = g_err;
-    const int rc_n = mrk::plan_query(&N, q, 128 << 10, true, dn, extra_n, 1, items_n, items_bm_n, 0, abn, dbn, ctn, prox_n, tree_n, progs_n);
+    const int rc_n = mrk::plan_query(&N, q, 128 << 10, true, dn, 1, 0, plan_n);
     CHECK(rc == rc_n, "iteration %d: ranker %d op %d over %d keywords: %d on the wide segment (%s), %d on the narrow one (%s)", it, ranker, op, nk, rc,
           err_w.c_str(), rc_n, g_err);
     if (rc == MRK_OK) {
       ++n_ok;
-      CHECK(prox == prox_n && dq.ranker == dn.ranker, "iteration %d: a different ranker plan", it); // (the narrow twin may take the bitmap kernels)
-      for (const DevItem& I : items_bm) // (the generic evaluator's work items travel there too, kind 2)
+      CHECK(plan.any_prox == plan_n.any_prox && dq.ranker == dn.ranker, "iteration %d: a different ranker plan", it); // (the narrow twin may take the bitmap kernels)
+      for (const DevItem& I : plan.items_bm) // (the generic evaluator's work items travel there too, kind 2)
         CHECK(I.kind == 2, "iteration %d: bitmap kernels planned for a wide segment", it);
       CHECK(dq.n_weights == 32, "iteration %d: %u weights", it, dq.n_weights);
     } else {
