@@ -158,6 +158,24 @@ typedef struct {
   int32_t mva_bits, mva_all, blob_attr_id, n_blob_attrs;
 } mrk_filter;
 
+/* The sorter's order (ISphMatchSorter's comparator, sphinxsort.cpp): relevance = MatchRelevanceLt_fn (weight desc, rowid asc), the
+   default; MRK_SORT_ATTR = ONE row attribute of at most 32 bits first -- SPH_SORT_ATTR_DESC / _ASC (MatchAttrLt_fn / MatchAttrGt_fn,
+   sphinxsort.cpp:4552-4610: then_weight = 1) and SPH_SORT_EXTENDED of the shapes 'attr' and 'attr, weight()' (MatchGeneric1_fn / 2_fn,
+   :4708-4730) --, optionally the weight next, rowid ascending last.  An integer key compares as SphAttr_t does for a zero-extended
+   attribute (unsigned), a float key as the dword read as a float (-0.0 == +0.0 falls through to the next key part).
+   Declined per query with MRK_E_UNSUPPORTED: a blob-stored attribute (bit_offset < 0), a 64-bit one (bit_count 64, dword-aligned, inside
+   the rows the segment holds -- any other 64 is MRK_E_INVAL), a segment without
+   attribute rows, a float column that holds a NaN (no strict weak order), cutoff next to a sort, the VLB-direct path.  Locators outside
+   the row, bit_count 0 or 33..63, unknown kinds / tie rules: MRK_E_INVAL.  Sorted queries run on the packed block-scan path only. */
+enum { MRK_SORT_RELEVANCE = 0, MRK_SORT_ATTR = 1 };
+enum { MRK_SORTKEY_INT = 0, MRK_SORTKEY_FLOAT = 1 };
+typedef struct {
+  int32_t kind;                  /* MRK_SORTKEY_* */
+  int32_t bit_offset, bit_count; /* CSphAttrLocator of a row attribute: 1..32 bits inside one dword */
+  int32_t desc;                  /* 1 = descending */
+  int32_t then_weight;           /* 0 = attribute, rowid asc;  1 = attribute, weight DESC, rowid asc;  2 = attribute, weight ASC, rowid asc */
+} mrk_sort;
+
 /* CSphQuery fields that reach the ranker + the query tree */
 typedef struct {
   const mrk_node* nodes;
@@ -185,6 +203,7 @@ typedef struct {
      the locator fields are ignored.  All must pass. */
   const mrk_filter* weight_filters;
   int32_t n_weight_filters;     /* <= MRK_MAX_FILTERS on the device */
+  const mrk_sort* sort;         /* NULL = (weight desc, rowid asc) */
 } mrk_query;
 
 typedef struct {
@@ -193,6 +212,10 @@ typedef struct {
   const uint32_t* rowid;  /* n entries, valid until the batch is resubmitted/destroyed */
   const int32_t* weight;
   int32_t status;         /* MRK_OK or MRK_E_UNSUPPORTED for this query */
+  const uint32_t* sort_key; /* a query with mrk_query.sort: the primary attribute's raw value (the locator's bits) per returned row; NULL
+                               for relevance queries and for mrk_batcher_search (whose rows land in the caller's buffers).  Read from the
+                               segment's rows when the result is fetched: no mrk_segment_set_attrs between mrk_batch_submit and mrk_batch_result.  weight is the
+                               true weight of every row, also where the weight is no part of the order */
 } mrk_result;
 
 typedef struct {
@@ -322,7 +345,9 @@ int mrk_batch_result(mrk_batch* b, uint32_t q, mrk_result* out);
 int mrk_batch_stats_get(mrk_batch* b, mrk_batch_stats* out);
 /* device-resident partial top-K of the last submit, for shard merges without a host hop:
    keys[q*MRK_MAX_K + i] = ((weight ^ 0x80000000) << 32) | ~(rowid_base + rowid), sorted
-   descending; counts[q]; totals[q].  Valid after mrk_batch_wait. */
+   descending; counts[q]; totals[q].  Valid after mrk_batch_wait.  The keys of a query with mrk_query.sort stand in the
+   sorter's order but are compared by nothing here: merges across shards (mrk_topk_merge*, mrk_shard_exchange) order by
+   (weight, docid) only, so such a query's exchange row leaves with MRK_ROW_DECLINED. */
 int mrk_batch_device_results(mrk_batch* b, const uint64_t** keys, const uint32_t** counts, const uint64_t** totals);
 
 /* copy those three arrays into caller-owned device buffers (e.g. tensors handed to RCCL);

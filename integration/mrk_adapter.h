@@ -16,11 +16,16 @@
 //   MrkCreateRanker      the three calls above in the order sphCreateRanker needs them; nullptr = not for the device,
 //                        keep the ExtRanker_* path.
 //
-// Why the sorter matters.  The device returns ONLY the K best matches by (weight desc, rowid asc) -- MatchRelevanceLt_fn,
-// sphinxsort.cpp:4541-4547 -- not the whole match stream.  Feeding those K rows to any queue whose order is not exactly
-// that (ORDER BY attribute, expressions, group-by, several sorters, random) would silently drop rows the queue wanted, and
-// so would a filter the device did not evaluate (EarlyReject would thin the K rows out).  MrkEligible therefore admits:
-// one sorter, not group-by, not random, relevance order; no packed factors; max_matches and cutoff <= MRK_MAX_K; filters
+// Why the sorter matters.  The device returns ONLY the K best matches under ONE order, not the whole match stream.  Feeding those K
+// rows to a queue whose order is another one would silently drop rows the queue wanted, and so would a filter the device did not
+// evaluate (EarlyReject would thin the K rows out).  The device knows two orders (MrkSorterOrder): (weight desc, rowid asc) --
+// MatchRelevanceLt_fn, sphinxsort.cpp:4541-4547 -- and ONE static row attribute of <= 32 bits first, then optionally the weight, then
+// rowid asc (mrk_query.sort): SPH_SORT_ATTR_DESC / _ASC (MatchAttrLt_fn / MatchAttrGt_fn, :4552-4610) and SPH_SORT_EXTENDED whose
+// comparator state reads [INT|FLOAT attr] [WEIGHT] ROWID asc (MatchGeneric1_fn / 2_fn).  Everything else (strings, expressions and
+// other dynamic or blob locators, 64-bit attributes, weight first of two parts, three and more parts, time segments, group-by,
+// several sorters, random) keeps the CPU ranker.  The frame replay feeds rows by rowid and the sorter re-reads the attribute through
+// the row pointer, so the replay itself does not change.  MrkEligible therefore admits:
+// one sorter, not group-by, not random, one of those orders, no cutoff next to an attribute order; no packed factors; max_matches and cutoff <= MRK_MAX_K; filters
 // (attribute filters: integer VALUES / RANGE, FLOATRANGE, MVA any / all; weight filters) only if FlattenXQ could hand every
 // one of them to the device; a weight filter next to a cutoff stays on the CPU (the cutoff counts matches in rowid order
 // AFTER the weight filter, sphinx.cpp:12223-12267; the device's cutoff probe runs without weights).
@@ -60,6 +65,7 @@ struct MrkFlatQuery_t
 	CSphVector<int64_t>		m_dFilterValues [ MRK_MAX_FILTERS ];
 	mrk_filter				m_dFilters [ MRK_MAX_FILTERS ];
 	CSphVector<int64_t>		m_dWeightFilterValues [ MRK_MAX_FILTERS ];
+	mrk_sort				m_tSort;				///< the sorter's order when it starts with a row attribute (mrk_query.sort points here)
 	mrk_filter				m_dWeightFilters [ MRK_MAX_FILTERS ];	///< filters on @weight / a weight column (CSphQueryContext::m_pWeightFilter)
 	mrk_query				m_tQuery;
 	CSphVector<CSphString>	m_dDictWords;			///< per node (empty for operators), for tMeta.AddStat
@@ -84,11 +90,63 @@ inline bool MrkSorterIsRelevance ( const CSphQuery & tQuery, const ISphMatchSort
 }
 
 
+/// a sort key part over a row attribute the device can order by: static (a row of the index, not a computed column), not blob-stored,
+/// 1..32 bits inside one dword
+inline bool MrkSortLocatorOk ( const CSphAttrLocator & tLoc )
+{
+	return !tLoc.m_bDynamic && !tLoc.IsBlobAttr() && tLoc.m_iBitOffset>=0 && tLoc.m_iBitCount>=1 && tLoc.m_iBitCount<=32
+		&& ( tLoc.m_iBitOffset & 31 ) + tLoc.m_iBitCount<=32;
+}
+
+/// Which device order is this sorter?  0 = none (keep the CPU ranker), 1 = relevance, 2 = attribute first (tSort filled).
+inline int MrkSorterOrder ( const CSphQuery & tQuery, const ISphMatchSorter * pSorter, mrk_sort & tSort )
+{
+	memset ( &tSort, 0, sizeof(tSort) );
+	if ( MrkSorterIsRelevance ( tQuery, pSorter ) )
+		return 1;
+	if ( !pSorter || pSorter->IsGroupby() || pSorter->m_bRandomize )
+		return 0;
+	const CSphMatchComparatorState & tState = pSorter->GetState();
+	const ESphSortKeyPart eKey = tState.m_eKeypart[0];
+	if ( tQuery.m_eSort==SPH_SORT_ATTR_DESC || tQuery.m_eSort==SPH_SORT_ATTR_ASC )
+	{
+		// MatchAttrLt_fn / MatchAttrGt_fn compare SphAttr_t whatever the column's type (a float column by its bits), then weight desc, rowid asc
+		if ( ( eKey!=SPH_KEYPART_INT && eKey!=SPH_KEYPART_FLOAT ) || !MrkSortLocatorOk ( tState.m_tLocator[0] ) )
+			return 0;
+		tSort.kind = MRK_SORTKEY_INT;
+		tSort.desc = tQuery.m_eSort==SPH_SORT_ATTR_DESC ? 1 : 0;
+		tSort.then_weight = 1;
+	} else if ( tQuery.m_eSort==SPH_SORT_EXTENDED )
+	{
+		if ( ( eKey!=SPH_KEYPART_INT && eKey!=SPH_KEYPART_FLOAT ) || !MrkSortLocatorOk ( tState.m_tLocator[0] ) )
+			return 0;
+		if ( eKey==SPH_KEYPART_FLOAT && tState.m_tLocator[0].m_iBitCount!=32 )
+			return 0;
+		tSort.kind = eKey==SPH_KEYPART_FLOAT ? MRK_SORTKEY_FLOAT : MRK_SORTKEY_INT;
+		tSort.desc = ( tState.m_uAttrDesc & 1 ) ? 1 : 0;
+		// [attr] ROWID asc  |  [attr] [WEIGHT] ROWID asc; sphParseSortClause ends every clause with an ascending ROWID part
+		if ( tState.m_eKeypart[1]==SPH_KEYPART_ROWID && ( tState.m_uAttrDesc & 2 )==0 )
+			tSort.then_weight = 0;
+		else if ( tState.m_eKeypart[1]==SPH_KEYPART_WEIGHT && tState.m_eKeypart[2]==SPH_KEYPART_ROWID && ( tState.m_uAttrDesc & 4 )==0 )
+			tSort.then_weight = ( tState.m_uAttrDesc & 2 ) ? 1 : 2;
+		else
+			return 0;
+	} else
+		return 0;
+	tSort.bit_offset = tState.m_tLocator[0].m_iBitOffset;
+	tSort.bit_count = tState.m_tLocator[0].m_iBitCount;
+	return 2;
+}
+
+
 inline bool MrkEligible ( const CSphQuery & tQuery, const CSphQueryContext & tCtx, const VecTraits_T<ISphMatchSorter *> & dSorters,
 	DWORD uPackedFactorFlags, CSphString & sWhy )
 {
 	if ( dSorters.GetLength()!=1 )					{ sWhy = "several sorters"; return false; }
-	if ( !MrkSorterIsRelevance ( tQuery, dSorters[0] ) )	{ sWhy = "sorter order is not (weight desc, rowid asc)"; return false; }
+	mrk_sort tSort;
+	const int iOrder = MrkSorterOrder ( tQuery, dSorters[0], tSort );
+	if ( !iOrder )									{ sWhy = "sorter order is neither (weight desc, rowid asc) nor (row attribute of <= 32 bits [, weight], rowid asc)"; return false; }
+	if ( iOrder==2 && tQuery.m_iCutoff>0 )			{ sWhy = "cutoff next to an attribute order"; return false; }
 	if ( tCtx.m_pWeightFilter && tQuery.m_iCutoff>0 )	{ sWhy = "weight filter next to a cutoff"; return false; }	// sphinx.cpp:12223-12267
 	if ( tQuery.m_iCutoff>MRK_MAX_K )				{ sWhy = "cutoff beyond the device top-K"; return false; }	// sphinx.cpp:12261-12267; smaller ones: mrk_query::cutoff
 	if ( uPackedFactorFlags!=SPH_FACTOR_DISABLE )	{ sWhy = "packed factors"; return false; }
@@ -371,7 +429,8 @@ inline bool MrkFlattenFilter ( const CSphFilterSettings & tFilter, const ISphSch
 
 /// XQQuery_t + CSphQuery + CSphQueryContext -> mrk_query.  false + sWhy = keep the CPU ranker.
 inline bool FlattenXQ ( const XQQuery_t & tXQ, const CSphQuery & tQuery, const CSphQueryContext & tCtx, const ISphQwordSetup & tSetup,
-	const MrkIndexBinding_t & tIndex, const ISphSchema & tIndexSchema, int iIndexWeight, MrkFlatQuery_t & tOut, CSphString & sWhy )
+	const MrkIndexBinding_t & tIndex, const ISphSchema & tIndexSchema, int iIndexWeight, MrkFlatQuery_t & tOut, CSphString & sWhy,
+	const ISphMatchSorter * pSorter = nullptr )
 {
 	if ( !tXQ.m_pRoot || tXQ.m_bEmpty )				{ sWhy = "empty query"; return false; }
 	if ( tXQ.m_dZones.GetLength() )					{ sWhy = "zones"; return false; }
@@ -397,6 +456,9 @@ inline bool FlattenXQ ( const XQQuery_t & tXQ, const CSphQuery & tQuery, const C
 	q.normalized_tfidf = tQuery.m_bNormalizedTFIDF;
 	q.total_docs_override = tCtx.m_iTotalDocs;
 	q.local_docs = tCtx.m_pLocalDocs ? tOut.m_dLocalDocs.Begin() : nullptr;
+	// the sorter's order (CSphMatchComparatorState: m_eKeypart, m_tLocator, m_uAttrDesc); relevance leaves q.sort NULL
+	if ( pSorter && MrkSorterOrder ( tQuery, pSorter, tOut.m_tSort )==2 )
+		q.sort = &tOut.m_tSort;
 	q.cutoff = tQuery.m_iCutoff>0 ? tQuery.m_iCutoff : 0;	// the device hands back the best of the first m_iCutoff matches; MatchExtended's own count then runs out on the last of them
 
 	// filters: every one of them on the device, or the query stays on the CPU (EarlyReject would thin the K rows out).
@@ -524,7 +586,7 @@ public:
 		{
 			m_tIndex = *pNext;
 			CSphScopedPtr<MrkFlatQuery_t> pFlat ( new MrkFlatQuery_t );
-			if ( FlattenXQ ( *m_pXQ, *m_pQuery, *m_pQueryCtx, tSetup, m_tIndex, *m_pIndexSchema, m_iIndexWeight, *pFlat.Ptr(), sWhy ) )
+			if ( FlattenXQ ( *m_pXQ, *m_pQuery, *m_pQueryCtx, tSetup, m_tIndex, *m_pIndexSchema, m_iIndexWeight, *pFlat.Ptr(), sWhy, m_pSorter ) )
 			{
 				m_pFlat = pFlat.LeakPtr();
 				if ( Run ( sWhy ) )
@@ -589,7 +651,7 @@ inline ISphRanker * MrkCreateRanker ( const XQQuery_t & tXQ, const CSphQuery & t
 	if ( !MrkEligible ( tQuery, tCtx, dSorters, uPackedFactorFlags, sWhy ) )
 		return nullptr;
 	CSphScopedPtr<MrkFlatQuery_t> pFlat ( new MrkFlatQuery_t );
-	if ( !FlattenXQ ( tXQ, tQuery, tCtx, tSetup, tIndex, tIndexSchema, iIndexWeight, *pFlat.Ptr(), sWhy ) )
+	if ( !FlattenXQ ( tXQ, tQuery, tCtx, tSetup, tIndex, tIndexSchema, iIndexWeight, *pFlat.Ptr(), sWhy, dSorters[0] ) )
 		return nullptr;
 	MrkFlatQuery_t * pRawFlat = pFlat.LeakPtr();
 	CSphScopedPtr<MrkRankerAdapter_c> pRanker ( new MrkRankerAdapter_c ( pBatch, pBatcher, tIndex, dSorters[0], pRawFlat, tSetup ) );

@@ -51,18 +51,24 @@ class Filter(C.Structure):
                 ("n_blob_attrs", C.c_int32)]
 
 
+class Sort(C.Structure):
+    """mrk_sort (include/mrk.h)"""
+    _fields_ = [("kind", C.c_int32), ("bit_offset", C.c_int32), ("bit_count", C.c_int32), ("desc", C.c_int32), ("then_weight", C.c_int32)]
+
+
 class Query(C.Structure):
     _fields_ = [("nodes", C.POINTER(Node)), ("n_nodes", C.c_int32), ("children", C.POINTER(C.c_int32)),
                 ("root", C.c_int32), ("ranker", C.c_int32), ("max_matches", C.c_int32),
                 ("field_weights", C.POINTER(C.c_int32)), ("n_weights", C.c_int32), ("index_weight", C.c_int32),
                 ("plain_idf", C.c_int32), ("normalized_tfidf", C.c_int32), ("total_docs_override", C.c_int64),
                 ("local_docs", C.POINTER(C.c_int64)), ("cutoff", C.c_int32), ("filters", C.POINTER(Filter)),
-                ("n_filters", C.c_int32), ("weight_filters", C.POINTER(Filter)), ("n_weight_filters", C.c_int32)]
+                ("n_filters", C.c_int32), ("weight_filters", C.POINTER(Filter)), ("n_weight_filters", C.c_int32),
+                ("sort", C.POINTER(Sort))]
 
 
 class Result(C.Structure):
     _fields_ = [("n", C.c_int32), ("total_found", C.c_int64), ("rowid", C.POINTER(C.c_uint32)),
-                ("weight", C.POINTER(C.c_int32)), ("status", C.c_int32)]
+                ("weight", C.POINTER(C.c_int32)), ("status", C.c_int32), ("sort_key", C.POINTER(C.c_uint32))]
 
 
 class BatchStats(C.Structure):

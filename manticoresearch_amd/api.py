@@ -331,6 +331,21 @@ class Filter:
         return d
 
 
+SORTKEY_INT, SORTKEY_FLOAT = 0, 1
+
+
+@dataclass
+class Sort:
+    """The sorter's order when it starts with a row attribute (mrk_sort, include/mrk.h): SPH_SORT_ATTR_DESC / _ASC and
+    SPH_SORT_EXTENDED 'attr' / 'attr, weight()'.  then_weight: 0 = attribute, rowid asc; 1 = attribute, weight DESC, rowid asc;
+    2 = attribute, weight ASC, rowid asc."""
+    bit_offset: int
+    bit_count: int
+    desc: bool = True
+    then_weight: int = 1
+    kind: int = SORTKEY_INT  # SORTKEY_FLOAT: the dword compares as a float
+
+
 @dataclass
 class Query:
     """CSphQuery fields that reach the ranker, plus the parsed tree."""
@@ -346,6 +361,7 @@ class Query:
     cutoff: int = 0
     filters: Optional[Sequence["Filter"]] = None  # CSphQuery::m_dFilters, resolved to attribute locators
     weight_filters: Optional[Sequence["Filter"]] = None  # filters on the match weight (m_pWeightFilter); locator fields unused
+    sort: Optional["Sort"] = None             # None = by relevance (weight desc, rowid asc)
 
 
 class _CQueries:
@@ -416,6 +432,10 @@ class _CQueries:
                 c.filters, c.n_filters = fill(q.filters), len(q.filters)
             if q.weight_filters:
                 c.weight_filters, c.n_weight_filters = fill(q.weight_filters), len(q.weight_filters)
+            if q.sort is not None:
+                cs = _lib.Sort(int(q.sort.kind), int(q.sort.bit_offset), int(q.sort.bit_count), int(bool(q.sort.desc)), int(q.sort.then_weight))
+                c.sort = C.pointer(cs)
+                self.keep.append(cs)
             self.keep += [cn, ch]
 
 
@@ -426,6 +446,7 @@ class Matches:
     weight: np.ndarray
     total_found: int
     status: int = 0
+    sort_key: Optional[np.ndarray] = None  # a sorted query: the primary attribute's raw value per returned row
 
 
 # --------------------------------------------------------------------------- device objects
@@ -505,6 +526,7 @@ class Segment:
     def __init__(self, ctx: Context, hi: HostIndex, rowid_base: int = 0):
         self.ctx = ctx
         self.host = hi
+        self._attrs = None
         d = _segment_desc(hi, rowid_base)
         self._h = C.c_void_p()
         ctx._children.add(self)
@@ -518,10 +540,12 @@ class Segment:
         """Upload the row-wise attribute storage (.spa rows: uint32 [n_rows, stride]) for Query.filters; None drops it."""
         if rows is None:
             check(lib().mrk_segment_set_attrs(self._h, None, 0, 0))
+            self._attrs = None
             return
         a = np.ascontiguousarray(rows, dtype=np.uint32)
         assert a.ndim == 2
         check(lib().mrk_segment_set_attrs(self._h, a.ctypes.data, a.shape[1], a.shape[0]))
+        self._attrs = a  # (Batcher.search reads a sorted query's sort_key from it)
 
     def set_blobs(self, pool: Optional[np.ndarray], n_blob_attrs: int = 0, rows: Optional[np.ndarray] = None) -> None:
         """Upload the blob pool (.spb bytes / an RT segment's m_dBlobs) for MVA filters; rows = the attribute rows given to
@@ -587,7 +611,8 @@ class Batch:
             n = r.n
             rowid = np.ctypeslib.as_array(r.rowid, (max(n, 1),))[:n].copy()
             weight = np.ctypeslib.as_array(r.weight, (max(n, 1),))[:n].copy()
-            out.append(Matches(rowid, weight, int(r.total_found), int(r.status)))
+            sk = np.ctypeslib.as_array(r.sort_key, (max(n, 1),))[:n].copy() if r.sort_key else None
+            out.append(Matches(rowid, weight, int(r.total_found), int(r.status), sk))
         return out
 
     def stats(self) -> dict:
@@ -638,7 +663,12 @@ class Batcher:
         weight = np.empty(cap, np.int32)
         r = _lib.Result()
         check(lib().mrk_batcher_search(self._h, seg._h, cq.arr, rowid.ctypes.data, weight.ctypes.data, cap, C.byref(r)))
-        return Matches(rowid[: r.n].copy(), weight[: r.n].copy(), int(r.total_found), int(r.status))
+        sk = None
+        if query.sort is not None and r.status == 0 and seg._attrs is not None:  # (mrk_batcher_search hands back no sort_key)
+            s = query.sort
+            dw = seg._attrs[rowid[: r.n], s.bit_offset >> 5]
+            sk = dw if s.bit_count >= 32 else (dw >> np.uint32(s.bit_offset & 31)) & np.uint32((1 << s.bit_count) - 1)
+        return Matches(rowid[: r.n].copy(), weight[: r.n].copy(), int(r.total_found), int(r.status), sk)
 
     def stats(self) -> dict:
         s = _lib.BatcherStats()
@@ -669,5 +699,5 @@ def idf(term_docs: int, total_docs: int, plain: bool = False, normalized: bool =
 __all__ = ["open_rt_ram", "open_rt_segment", "SPH_RANK_PROXIMITY_BM25", "SPH_RANK_BM25", "SPH_RANK_NONE", "SPH_RANK_WORDCOUNT", "SPH_RANK_PROXIMITY",
            "SPH_RANK_MATCHANY", "SPH_RANK_FIELDMASK", "SPH_RANK_SPH04",
            "parse_query", "SPH_QUERY_TERM", "SPH_QUERY_AND", "SPH_QUERY_OR", "SPH_QUERY_MAYBE", "SPH_QUERY_ANDNOT", "SPH_QUERY_PHRASE", "SPH_QUERY_PROXIMITY", "SPH_QUERY_QUORUM", "SPH_QUERY_BEFORE", "SPH_QUERY_NEAR", "SPH_QUERY_NOTNEAR", "SPH_QUERY_SENTENCE", "SPH_QUERY_PARAGRAPH",
-           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Matches", "Context",
+           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "Matches", "Context",
            "Segment", "Batch", "Batcher", "prepare", "idf", "MrkError", "validate_index", "pair_stats"]

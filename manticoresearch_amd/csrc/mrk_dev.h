@@ -269,6 +269,16 @@ struct DevQuery {
   DevFilter wfilters[MRK_MAX_FILTERS];
   int32_t weights[32];
   DevTerm t[MRK_MAX_AND_TERMS];
+  // mrk_query.sort (mrk_sortkey.h): the order starts with a row attribute.  Such a query's candidates are 16 bytes each and live
+  // in an arena of their own (ScanArgs::scand); its cand_cap is 0, so the relevance selection sees an empty list, and bin_lo /
+  // bin_shift hold the geometry of the MAPPED KEY's range in the column (bin_lo read as unsigned)
+  uint32_t sort_on;    // 0 = relevance
+  uint32_t sort_item, sort_shift, sort_bits; // the attribute: dword of the row, bit offset inside it, width
+  uint32_t sort_flags; // SORT_FLOAT | SORT_DESC
+  uint32_t sort_tie;   // mrk_sort::then_weight
+  uint32_t sort_cap;   // capacity of the candidate list ...
+  uint32_t sort_pad;
+  uint64_t sort_off;   // ... and its offset in ScanArgs::scand, in candidates
 };
 
 struct DevItem {
@@ -375,7 +385,26 @@ struct ScanArgs {
   MatchQueue mq[3];    // [0] plain boolean trees, [1] queries with PHRASE / PROXIMITY / BEFORE nodes or position modifiers, [2] TF_GEN
   GenArgs gen;
   const BmGroup* bm_groups; // scan_bm work items name a group (grouped kernel instance); NULL = an item names its query
+  uint32_t* s_hist;         // sorted hit-ranked queries: [n_queries][NBINS] attribute bins of the matches the scan queued for the hit pass, and
+  uint32_t* s_tau;          // [n_queries * QSTRIDE] the threshold bin they prove (scan_pk_kernel, pre_prune); NULL = the batch holds no such query
+  uint64_t* scand;          // candidates of the batch's sorted queries: [2 * i] = hi, [2 * i + 1] = lo (mrk_sortkey.h); NULL = the batch holds none
 };
+
+// Top-K of the sorted queries' candidate lists (mrk_sortsel.hip): one workgroup per sorted query, launched behind launch_select on
+// the same stream -- the relevance selection saw an empty list for the query and wrote a count of 0; this one overwrites it.  The rows
+// leave in the relevance format, make_key(true weight, rowid), in the sorter's order.
+struct SortSelArgs {
+  const DevQuery* queries;
+  const uint32_t* q_hist;
+  const uint32_t* q_cand_n;
+  const uint64_t* scand;
+  uint32_t n_queries;
+  uint64_t* out_keys; // [n_queries][KCAP]
+  uint32_t* out_cnt;
+  uint64_t* h_keys;   // pinned host or NULL
+  uint32_t* h_cnt;    // pinned host or NULL
+};
+void launch_sort_select(const SortSelArgs& a, void* stream);
 
 // Top-K selection over the candidate lists (mrk_select.hip), three launches on the batch's stream:
 //   sel_tau_kernel    one wave per query: final threshold bin of its histogram, number of 2048-key slices of its list
@@ -474,13 +503,13 @@ struct PackRowsArgs {
 void launch_pack_rows(const PackRowsArgs& a, void* stream);
 
 void launch_scan(const ScanArgs& a, void* stream);
-void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen = false);
+void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen = false); // a.scand: the instances that carry the sort
 constexpr int MAX_PROX_TERMS = MAX_PROX_TERMS_; // keywords whose hit streams the hit kernel merges per doc
 void launch_scan_bm(const ScanArgs& a, void* stream); // a.items: (query, window range) work items
 void launch_scan_bt(const ScanArgs& a, void* stream); // the same for TF_BTREE passes (mrk_scan_bt.hip)
 // final ranking of the queued matches (mrk_rank.hip): a persistent grid drains queue `which` of a.mq (2 = the generic evaluator)
 constexpr int GEN_GRID = 512; // its workgroups: lane arenas are sized for GEN_GRID * WG lanes
-void launch_rank(const ScanArgs& a, int which, void* stream);
+void launch_rank(const ScanArgs& a, int which, void* stream); // a.scand: the instances that carry the sort
 void launch_select(const SelectArgs& a, void* stream);
 void launch_merge(const MergeArgs& a, void* stream);
 

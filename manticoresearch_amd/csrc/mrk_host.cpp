@@ -50,6 +50,7 @@ int mrk_fail(int code, const char* fmt, ...) {
 // objects
 // ----------------------------------------------------------------------------------------
 #include "mrk_host_int.h"
+#include "mrk_sortkey.h"
 
 template <typename T>
 struct DevBuf {
@@ -146,6 +147,8 @@ struct mrk_batch {
   View<uint32_t> d_q_hist, d_q_cand_n, d_q_flags, d_q_tau_bin;
   PinBuf<uint32_t> h_cand_n;
   DevBuf<uint64_t> d_cand;
+  DevBuf<uint32_t> d_shist;  // sorted hit-ranked queries: the scan's histogram of queued matches' attribute bins [n][NBINS], then the threshold words [n * QSTRIDE]
+  DevBuf<uint64_t> d_scand;  // 16-byte candidates of the sorted queries (two words each); reserved by the first batch that holds one
   PinBuf<uint32_t> h_flags;
   // per query: != 0 when the planner declined it on the last submit's segment; travels in the exchange rows
   PinBuf<uint32_t> h_decl;
@@ -165,6 +168,11 @@ struct mrk_batch {
   std::vector<uint32_t> rowid;
   std::vector<int32_t> weight;
   std::vector<int32_t> status;
+  // sorted queries of the last submit: the locator of the primary attribute (bits 0 = relevance) and the raw values of the returned rows
+  struct SortLoc { uint32_t item = 0, shift = 0, bits = 0; };
+  std::vector<SortLoc> sort_loc;
+  std::vector<uint32_t> sort_key;
+  bool last_sort = false;
   bool decoded = false;
   bool packed_run = false;
   // what a rerun of an overflowed query needs (mrk_batch_wait)
@@ -401,6 +409,17 @@ static int mrk_segment_set_attrs_impl(mrk_segment* s, const uint32_t* rows, uint
   }
   if (s->d_attrs) (void)hipFree(s->d_attrs);
   s->d_attrs = fresh;
+  s->sort_ranges.clear(); // (the cached column ranges of sorted queries belong to the old rows)
+  if (rows) {
+    try {
+      s->h_attrs.assign(rows, rows + (size_t)n_rows * stride);
+    } catch (const std::bad_alloc&) { // the device copy stands (filters work); sorted queries are declined for want of the host rows
+      std::vector<uint32_t>().swap(s->h_attrs);
+      (void)mrk_fail(MRK_E_NOMEM, "mrk_segment_set_attrs: no host memory for the rows' copy (sorted queries need it)");
+      return MRK_E_NOMEM;
+    }
+  } else
+    std::vector<uint32_t>().swap(s->h_attrs);
   s->attr_rows = rows ? n_rows : 0;
   s->dev.attrs = (const uint32_t*)fresh;
   s->dev.attr_stride = rows ? stride : 0;
@@ -842,6 +861,8 @@ static void mrk_batch_destroy_impl(mrk_batch* b) {
 
   b->h_cand_n.release();
   b->d_cand.release();
+  b->d_scand.release();
+  b->d_shist.release();
   b->h_flags.release();
   b->h_decl.release();
   b->d_decl.release();
@@ -892,6 +913,8 @@ static int mrk_batch_create_impl(mrk_ctx* ctx, uint32_t max_queries, mrk_batch**
   }
   b->rowid.resize(nq * KCAP);
   b->weight.resize(nq * KCAP);
+  b->sort_key.resize(nq * KCAP);
+  b->sort_loc.assign(nq, mrk_batch::SortLoc{});
   b->status.assign(nq, MRK_OK);
   *out = b;
   return MRK_OK;
@@ -964,7 +987,7 @@ static int cutoff_probe(mrk_batch* b, mrk_segment* seg, const mrk_query* queries
   std::vector<mrk_query> pq;
   std::vector<uint32_t> who;
   for (uint32_t i = 0; i < n; ++i)
-    if (queries[i].cutoff > 0 && queries[i].cutoff <= MRK_MAX_K && queries[i].n_weight_filters == 0) { // (the others: plan_query says why not)
+    if (queries[i].cutoff > 0 && queries[i].cutoff <= MRK_MAX_K && queries[i].n_weight_filters == 0 && !queries[i].sort) { // (the others: plan_query says why not)
       mrk_query q = queries[i];
       q.ranker = MRK_RANK_NONE;
       q.max_matches = q.cutoff;
@@ -1009,6 +1032,7 @@ static void bind_scan(const mrk_batch* b, const mrk_segment* seg, mrk::ScanArgs&
 // The packed path's kernels over a laid-out item array (sa.items: block-scan items, then kinds 0, 1, 2): block scan, tree
 // kernel and generic-evaluator candidates, the rank launches of the queues in use, then the two-bitmap AND kernel
 // (bm_groups: its group records on the device, or null)
+// (sa.scand set = the batch holds sorted queries: every block-scan and rank launch takes the instance that carries the sort)
 static int launch_packed(mrk::ScanArgs sa, size_t n_items_pk, const size_t n_items_kind[3], const uint64_t mq_chunks[3], uint32_t max_terms, bool prox,
                          bool tree, bool ext, bool nearn, const BmGroup* bm_groups, hipStream_t st) {
   const DevItem* items = sa.items;
@@ -1105,10 +1129,13 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
       plan.rewind(before);
       b->h_queries.p[i].n_items = 0;
       b->h_queries.p[i].n_terms = 0;
+      b->h_queries.p[i].sort_on = 0;
     }
     max_terms = std::max(max_terms, b->h_queries.p[i].n_terms);
     any_ext = any_ext || (b->h_queries.p[i].tree_flags & (mrk::TF_TERMPOS | mrk::TF_ORDER | mrk::TF_PHRASE_LEAF | mrk::TF_NOTNEAR)) != 0 || b->h_queries.p[i].n_filters != 0 || b->h_queries.p[i].n_wfilters != 0 ||
-              b->h_queries.p[i].rowid_max != 0xFFFFFFFFu;
+              b->h_queries.p[i].rowid_max != 0xFFFFFFFFu || b->h_queries.p[i].sort_on != 0;
+    b->sort_loc[i] = mrk_batch::SortLoc{};
+    if (rc == MRK_OK && b->h_queries.p[i].sort_on) b->sort_loc[i] = mrk_batch::SortLoc{b->h_queries.p[i].sort_item, b->h_queries.p[i].sort_shift, b->h_queries.p[i].sort_bits};
     b->h_list_first.p[i] = b->h_queries.p[i].item_first;
     b->h_list_n.p[i] = b->h_queries.p[i].n_items;
     b->h_kq.p[i] = b->h_queries.p[i].k ? b->h_queries.p[i].k : 1;
@@ -1142,6 +1169,8 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   if ((rc = b->h_queries.reserve_keep(n_pass, n)) || (rc = b->d_queries.reserve(n_pass))) return rc;
   if (!extra.empty()) memcpy(b->h_queries.p + n, extra.data(), extra.size() * sizeof(DevQuery));
   if (use_packed && ((rc = b->d_cand.reserve(cand_total + 64)) || (rc = b->d_sel.reserve(2 * (size_t)n + mrk::sel_slice_slots(cand_total, n))))) return rc;
+  const bool any_sort = use_packed && plan.sort_total != 0;
+  if (any_sort && (rc = b->d_scand.reserve(2 * plan.sort_total + 64))) return rc;
 
   static const bool phase_timing = getenv("MRK_SUBMIT_TIMING") != nullptr;
   auto lap = [&](const char* what) {
@@ -1171,6 +1200,14 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   ScanArgs sa{};
   bind_scan(b, seg, sa);
   sa.n_items = (uint32_t)n_items; // (the VLB path's one launch; launch_packed sets its sections')
+  sa.scand = any_sort ? b->d_scand.p : nullptr;
+  if (any_sort && any_prox) { // the attribute bin test in front of the hit pass (scan_pk_kernel, pre_prune)
+    const size_t words = (size_t)n * (NBINS + mrk::QSTRIDE);
+    if ((rc = b->d_shist.reserve(words))) return rc;
+    HIP_TRY(hipMemsetAsync(b->d_shist.p, 0, words * 4, st));
+    sa.s_hist = b->d_shist.p;
+    sa.s_tau = b->d_shist.p + (size_t)n * NBINS;
+  }
   bool any_nearn = false;
   if (use_packed && any_prox && b->ctx->prox_prune) { // pruning in front of the hit pass (mrk_kprune.h, prox_bounds)
     const size_t words = (size_t)n * (2 * NBINS + mrk::QSTRIDE);
@@ -1215,6 +1252,13 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     se.rows_dst = b->rows_dst;
     se.declined = nullptr;
     launch_select(se, st2);
+    if (any_sort) { // the sorted queries' own selection, behind the relevance one (which wrote a count of 0 for them)
+      mrk::SortSelArgs ss{};
+      ss.queries = b->d_queries.p, ss.q_hist = b->d_q_hist.p, ss.q_cand_n = b->d_q_cand_n.p, ss.scand = b->d_scand.p, ss.n_queries = n;
+      ss.out_keys = b->d_out_keys.p, ss.out_cnt = b->d_out_cnt.p;
+      if (!b->rows_dst) ss.h_keys = b->h_keys.p, ss.h_cnt = b->h_cnt.p;
+      mrk::launch_sort_select(ss, st2);
+    }
   } else {
     MergeArgs ma{};
     ma.in_keys = b->d_item_cand.p;
@@ -1232,10 +1276,11 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   HIP_TRY(hipEventRecord(b->ev_merge1, st2));
   {
     bool any = false;
-    for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK;
+    // (a sorted query's row is no answer to a merge by (weight, docid): in the exchange it counts as declined)
+    for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits);
     b->any_declined = any;
     if (any || b->decl_dirty) {
-      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = b->status[i] != MRK_OK ? 1u : 0u;
+      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = (b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits)) ? 1u : 0u;
       HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     }
     b->decl_dirty = any;
@@ -1259,6 +1304,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   b->last_prox = any_prox;
   b->last_tree = any_tree;
   b->last_ext = any_ext;
+  b->last_sort = any_sort;
   lap("select launched");
   // ---- results to pinned host memory: the packed path's selection wrote them itself; the VLB path copies
   b->host_copied = b->rows_dst == nullptr;
@@ -1298,7 +1344,9 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
     DevQuery& P = passes[p];
     P.out_q = 0;
     P.cand_off = 0;
-    P.cand_cap = (uint32_t)cap;
+    P.cand_cap = P.sort_on ? 0u : (uint32_t)cap;
+    P.sort_off = 0;
+    P.sort_cap = P.sort_on ? (uint32_t)cap : 0u;
     const bool bm = (P.tree_flags & TF_BITMAP) != 0, bt = (P.tree_flags & TF_BTREE) != 0;
     const uint32_t n = (bm || bt) ? seg->dev.n_windows : P.t[0].nblocks, step = (bm || bt) ? 1024u : 256u;
     for (uint32_t x = 0; x < n; x += step) {
@@ -1319,6 +1367,8 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   if ((rc = r->h_queries.reserve(passes.size())) || (rc = r->d_queries.reserve(passes.size())) || (rc = r->h_items.reserve(n_items + 1)) ||
       (rc = r->d_items.reserve(n_items + 1)) || (rc = r->d_cand.reserve(cap + 64)) || (rc = r->d_sel.reserve(2 + mrk::sel_slice_slots(cap, 1))))
     return rc;
+  const bool sorted = passes[0].sort_on != 0; // (the query's order travels with its passes: sort_* of the DevQuery planned at submit)
+  if (sorted && (rc = r->d_scand.reserve(2 * cap + 64))) return rc;
   memcpy(r->h_queries.p, passes.data(), passes.size() * sizeof(DevQuery));
   if (n_items) memcpy(r->h_items.p, items_pk.data(), n_items * sizeof(DevItem));
   HIP_TRY(hipMemcpyAsync(r->d_queries.p, r->h_queries.p, passes.size() * sizeof(DevQuery), hipMemcpyHostToDevice, st));
@@ -1326,6 +1376,14 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   HIP_TRY(hipMemsetAsync(r->d_state.p, 0, (size_t)r->max_queries * STATE_BYTES + (size_t)NBINS * 4, st));
   ScanArgs sa{};
   bind_scan(r, seg, sa);
+  sa.scand = sorted ? r->d_scand.p : nullptr;
+  if (sorted && b->last_prox) {
+    const size_t words = NBINS + mrk::QSTRIDE;
+    if ((rc = r->d_shist.reserve(words))) return rc;
+    HIP_TRY(hipMemsetAsync(r->d_shist.p, 0, words * 4, st));
+    sa.s_hist = r->d_shist.p;
+    sa.s_tau = r->d_shist.p + NBINS;
+  }
   // match queues for every doc a pass can match (no cap: this run must not overflow), every pass charged the whole rerun's items
   uint64_t chunks[3] = {0, 0, 0};
   for (const DevQuery& P : passes) {
@@ -1342,6 +1400,12 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   SelectArgs se{};
   bind_select(r, seg, 1, cap, se);
   launch_select(se, st);
+  if (sorted) {
+    mrk::SortSelArgs ss{};
+    ss.queries = r->d_queries.p, ss.q_hist = r->d_q_hist.p, ss.q_cand_n = r->d_q_cand_n.p, ss.scand = r->d_scand.p, ss.n_queries = 1;
+    ss.out_keys = r->d_out_keys.p, ss.out_cnt = r->d_out_cnt.p;
+    mrk::launch_sort_select(ss, st);
+  }
   HIP_TRY(hipGetLastError());
   uint32_t flags = 0;
   HIP_TRY(hipMemcpyAsync(&flags, r->d_q_flags.p, 4, hipMemcpyDeviceToHost, st));
@@ -1428,6 +1492,14 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
         b->rowid[(size_t)i * KCAP + j] = key_rowid(keys[j]) - rb;
         b->weight[(size_t)i * KCAP + j] = key_weight(keys[j]);
       }
+      if (b->sort_loc[i].bits) { // mrk_result.sort_key: the primary attribute of the returned rows, from the host's copy of the rows
+        const mrk_segment* sg = b->last_seg;
+        const mrk_batch::SortLoc& sl = b->sort_loc[i];
+        for (uint32_t j = 0; j < cnt; ++j) {
+          const uint64_t at = (uint64_t)b->rowid[(size_t)i * KCAP + j] * (sg ? sg->dev.attr_stride : 0) + sl.item;
+          b->sort_key[(size_t)i * KCAP + j] = sg && at < sg->h_attrs.size() ? mrk::sort_extract(sg->h_attrs[at], sl.shift, sl.bits) : 0u;
+        }
+      }
     }
     b->decoded = true;
   }
@@ -1436,6 +1508,7 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
   out->total_found = b->status[q] == MRK_OK ? (int64_t)b->h_total.p[q] : 0;
   out->rowid = b->rowid.data() + (size_t)q * KCAP;
   out->weight = b->weight.data() + (size_t)q * KCAP;
+  out->sort_key = b->status[q] == MRK_OK && b->sort_loc[q].bits ? b->sort_key.data() + (size_t)q * KCAP : nullptr;
   return MRK_OK;
 }
 

@@ -90,6 +90,17 @@ struct mrk_segment {
   void* d_blobs = nullptr; // blob pool (mrk_segment_set_blobs)
   uint32_t n_blob_attrs = 0;
   uint64_t attr_rows = 0;
+  // sorted queries (mrk_query.sort): the rows are kept on the host too -- the planner takes the range of a sort column from them
+  // (one pass per locator, cached here until mrk_segment_set_attrs is called again) and mrk_batch_result reads mrk_result.sort_key
+  std::vector<uint32_t> h_attrs;
+  struct SortRange {
+    int32_t bit_offset, bit_count, is_float;
+    uint32_t lo, hi; // least / largest mapped key of the DESCENDING order (mrk_sortkey.h); lo > hi: no rows
+    bool has_nan;
+  };
+  // (written by plan_query through a const segment: planning runs on the context's ONE submission thread; with MRK_INLINE_HIP=1 the
+  // caller must not submit sorted queries against one segment from two threads at once)
+  mutable std::vector<SortRange> sort_ranges;
   void* d_bm = nullptr;
   void* d_bm_dir = nullptr;
 };
@@ -122,6 +133,7 @@ struct BatchPlan {
   std::vector<DevItem> items_bm;   // one whole window range per scan_bm (kind 0) / scan_bt (kind 1) pass; the generic evaluator's block items (kind 2), already cut
   std::vector<GenProg> gen_progs;  // programs of the generic evaluator (DevQuery::gen_prog indexes it)
   uint64_t algo_bytes = 0, dev_bytes = 0, cand_total = 0;
+  uint64_t sort_total = 0;         // 16-byte candidate slots of the batch's sorted queries (mrk_query.sort); 0 = it holds none
   bool any_prox = false, any_tree = false;
   // a declined query runs no device work: what it appended is taken back (the byte counts and flags stay as plan_query left them)
   struct Mark { size_t extra, items, items_bm, gen_progs; };

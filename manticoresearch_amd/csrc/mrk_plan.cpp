@@ -2,6 +2,7 @@
 // items.  Mirrors what sphCreateRanker / ExtNode_i::Create decide on the host in the reference
 // (sphinxsearch.cpp:4167-4378, searchnode.cpp:1599-1811).
 #include "mrk_host_int.h"
+#include "mrk_sortkey.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -735,7 +736,45 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
   if (q.cutoff > MRK_MAX_K) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff %d (device path: <= %d)", qi, q.cutoff, MRK_MAX_K);
   if (q.cutoff > 0 && q.n_weight_filters > 0)
     return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to a weight filter (which rows count depends on their weights)", qi);
-  const bool filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu;
+  // The sorter's order (mrk_query.sort).  Checked before anything is read: a hostile locator ends here.
+  const mrk_segment::SortRange* srange = nullptr;
+  if (q.sort) {
+    const mrk_sort& S = *q.sort;
+    if (S.kind != MRK_SORTKEY_INT && S.kind != MRK_SORTKEY_FLOAT) return mrk_fail(MRK_E_INVAL, "query %u: sort key kind %d", qi, S.kind);
+    if (S.then_weight < 0 || S.then_weight > 2) return mrk_fail(MRK_E_INVAL, "query %u: sort tie rule %d", qi, S.then_weight);
+    if (S.bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sort by a blob-stored or computed attribute (no row locator)", qi);
+    if (S.bit_count == 64 && (S.bit_offset & 31) == 0 && seg->dev.attrs && (uint64_t)S.bit_offset + 64 <= (uint64_t)seg->dev.attr_stride * 32)
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sort by a 64-bit attribute (device path: <= 32 bits)", qi);
+    if (S.bit_count < 1 || S.bit_count > 32 || (S.bit_offset & 31) + S.bit_count > 32)
+      return mrk_fail(MRK_E_INVAL, "query %u: sort locator %d/%d is not 1..32 bits inside one dword", qi, S.bit_offset, S.bit_count);
+    if (S.kind == MRK_SORTKEY_FLOAT && S.bit_count != 32) return mrk_fail(MRK_E_INVAL, "query %u: a float sort key needs a 32-bit attribute", qi);
+    if (!seg->dev.attrs || seg->h_attrs.empty())
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sorting by an attribute needs the segment's attribute rows (mrk_segment_set_attrs)", qi);
+    if ((uint64_t)S.bit_offset + (uint64_t)S.bit_count > (uint64_t)seg->dev.attr_stride * 32)
+      return mrk_fail(MRK_E_INVAL, "query %u: sort locator %d/%d outside the %u-dword row", qi, S.bit_offset, S.bit_count, seg->dev.attr_stride);
+    if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sorted queries run on the packed path only", qi);
+    if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to a sort (which rows count depends on the scan order)", qi);
+    // the column's range of mapped keys, once per (segment, locator): the pruning bins' geometry; a NaN ends the query here
+    for (const mrk_segment::SortRange& r : seg->sort_ranges)
+      if (r.bit_offset == S.bit_offset && r.bit_count == S.bit_count && r.is_float == S.kind) srange = &r;
+    if (!srange) {
+      mrk_segment::SortRange r{S.bit_offset, S.bit_count, S.kind, 0xFFFFFFFFu, 0u, false};
+      const uint32_t stride = seg->dev.attr_stride, item = (uint32_t)S.bit_offset >> 5, shift = (uint32_t)S.bit_offset & 31u;
+      const uint32_t fl = SORT_DESC | (S.kind == MRK_SORTKEY_FLOAT ? SORT_FLOAT : 0u);
+      const uint64_t rows = seg->h_attrs.size() / stride;
+      for (uint64_t i = 0; i < rows; ++i) {
+        const uint32_t v = sort_extract(seg->h_attrs[i * stride + item], shift, (uint32_t)S.bit_count);
+        if (S.kind == MRK_SORTKEY_FLOAT && sort_is_nan(v)) r.has_nan = true;
+        const uint32_t m = sort_map_key(v, fl);
+        r.lo = std::min(r.lo, m), r.hi = std::max(r.hi, m);
+      }
+      seg->sort_ranges.push_back(r);
+      srange = &seg->sort_ranges.back();
+    }
+    if (srange->has_nan) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the float sort column holds a NaN (no strict weak order)", qi);
+  }
+  // (a sorted query reads attribute rows like a filtered one: the packed block scan's EXT instances only)
+  const bool filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || q.sort != nullptr;
 
   // The specialised paths first; a shape they decline goes to the generic per-doc evaluator (mrk_keval.h) when the segment
   // has what it reads (packed doclists + hit references), else the decline stands.
@@ -1109,13 +1148,39 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
       dq.bin_shift = sh;
     }
   }
+  if (q.sort) { // the order starts with the attribute: the bins span the column's range of mapped keys (bin_lo read as unsigned)
+    const mrk_sort& S = *q.sort;
+    dq.sort_on = 1;
+    dq.sort_item = (uint32_t)S.bit_offset >> 5, dq.sort_shift = (uint32_t)S.bit_offset & 31u, dq.sort_bits = (uint32_t)S.bit_count;
+    dq.sort_flags = (S.kind == MRK_SORTKEY_FLOAT ? SORT_FLOAT : 0u) | (S.desc ? SORT_DESC : 0u);
+    dq.sort_tie = (uint32_t)S.then_weight;
+    uint32_t lo = srange->lo, hi = srange->hi;
+    if (lo > hi) lo = hi = 0;
+    if (!S.desc) { // ascending: the keys are complemented
+      const uint32_t l = ~hi, h = ~lo;
+      lo = l, hi = h;
+    }
+    uint32_t sh = 0;
+    while (sh < 31 && ((hi - lo) >> sh) >= (uint32_t)NBINS) ++sh;
+    dq.bin_mode = BIN_WEIGHT;
+    dq.bin_lo = (int32_t)lo;
+    dq.bin_shift = sh;
+  }
   {
     uint64_t cap = 0;
     for (int k : cover) cap += (uint64_t)T.kws[k].docs;
     cap = std::min<uint64_t>(std::max<uint64_t>(cap, 1), (uint64_t)1 << 20);
-    dq.cand_cap = (uint32_t)cap;
-    dq.cand_off = plan.cand_total;
-    plan.cand_total += cap;
+    if (q.sort) { // 16-byte candidates in the arena of the sorted queries; the relevance selection sees an empty list
+      dq.cand_cap = 0;
+      dq.cand_off = plan.cand_total;
+      dq.sort_cap = (uint32_t)cap;
+      dq.sort_off = plan.sort_total;
+      plan.sort_total += cap;
+    } else {
+      dq.cand_cap = (uint32_t)cap;
+      dq.cand_off = plan.cand_total;
+      plan.cand_total += cap;
+    }
   }
   if (empty) {
     dq.n_terms = (uint32_t)n;

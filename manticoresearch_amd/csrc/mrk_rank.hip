@@ -10,20 +10,22 @@
 #include "mrk_khits.h"
 #include "mrk_kprune.h"
 #include "mrk_keval.h"
+#include "mrk_sortkey.h"
 
 namespace mrk {
 
 constexpr int RK_CBUF = 128; // candidates a wave collects before it publishes them
 
-template <int NF>
+template <int NF, bool SORT = false>
 struct __align__(16) RkWaveLds {
   uint64_t cbuf[RK_CBUF];
+  uint64_t cbuf2[SORT ? RK_CBUF : 0]; // sorted queries: the low halves of the 16-byte candidates (mrk_sortkey.h)
   int32_t fw[NF]; // the current query's per-field weights
 };
 
-template <int NF>
+template <int NF, bool SORT = false>
 struct __align__(16) RkSmem {
-  RkWaveLds<NF> w[WAVES];
+  RkWaveLds<NF, SORT> w[WAVES];
   uint32_t hist[NBINS]; // publishing scratch, one per workgroup behind hist_lock (as in scan_bm_kernel)
   uint32_t hist_lock;
   uint32_t pre[MQ_SHARDS + 1]; // chunks in the shards before shard s (filled prefixes laid end to end)
@@ -32,15 +34,16 @@ struct __align__(16) RkSmem {
 // MODE 0: lean (hit_rank_plain / hit_rank_prox), 1: FAT (hit_pass with the word state machines), 2: GEN (gen_eval)
 // WIDE: a segment with 9-32 fields -- 32 field weights and ranker bytes; queues 0 / 1 carry the doc's whole field mask in one more
 // plane behind the narrow entry (the generic evaluator reads it from pk_fmask itself)
-template <int MODE, bool WIDE = false>
+// SORT: the batch holds queries ordered by a row attribute (mrk_query.sort); instances of their own (see scan_pk_kernel)
+template <int MODE, bool WIDE = false, bool SORT = false>
 __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   constexpr bool FAT = MODE == 1, GEN = MODE == 2;
   constexpr int NF = WIDE ? 32 : 8;
   constexpr int NP = GEN ? MQ_GEN_PLANES : MQ_PLANES + (WIDE ? 1 : 0); // planes of a queue entry
-  __shared__ RkSmem<NF> s;
+  __shared__ RkSmem<NF, SORT> s;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const MatchQueue MQ = a.mq[MODE];
-  RkWaveLds<NF>& L = s.w[wave];
+  RkWaveLds<NF, SORT>& L = s.w[wave];
   if (!tid) s.hist_lock = 0;
   static_assert(MQ_SHARDS == 64, "one shard per lane of the prefix sum");
   if (wave == 0) {
@@ -64,6 +67,10 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   uint32_t K = 1, bin_mode = 0, bin_shift = 0, cand_cap = 0;
   int32_t bin_lo = 0;
   uint64_t* cand = nullptr;
+  // a sorted query (uniform per logical query): its 16-byte candidates go to their own arena, binned by the mapped attribute key
+  bool sorted = false;
+  uint32_t so_item = 0, so_shift = 0, so_bits = 32, so_flags = 0, so_tie = 0;
+  uint64_t* scand = nullptr;
   uint32_t *ghist = nullptr, *gcount = nullptr, *gtaubin = nullptr;
 
   auto publish = [&]() {
@@ -85,6 +92,13 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
       wave_lds_fence();
       for (uint32_t i = lane; i < cn; i += 64) {
         const uint64_t key = L.cbuf[i];
+        if constexpr (SORT) {
+          if (sorted) {
+            if (fits) *reinterpret_cast<ulonglong2*>(scand + 2 * (uint64_t)(basep + i)) = make_ulonglong2(key, L.cbuf2[i]);
+            atomicAdd(&s.hist[sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))], 1u);
+            continue;
+          }
+        }
         if (fits) cand[basep + i] = key;
         atomicAdd(&s.hist[bin_of(bin_mode, bin_lo, bin_shift, key_weight(key), key_rowid(key))], 1u);
       }
@@ -214,11 +228,19 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
       const uint32_t k_ = U(Q->k), bm_ = U(Q->bin_mode), bs_ = U(Q->bin_shift), bl_ = U((uint32_t)Q->bin_lo), cc_ = U(Q->cand_cap);
       const uint64_t co_ = ((uint64_t)U((uint32_t)(Q->cand_off >> 32)) << 32) | U((uint32_t)Q->cand_off);
       const int32_t wl = lane < (uint32_t)NF ? Q->weights[lane] : 0;
+      const uint32_t son_ = SORT ? U(Q->sort_on) : 0u, si_ = SORT ? U(Q->sort_item) : 0u, ss_ = SORT ? U(Q->sort_shift) : 0u, sb_ = SORT ? U(Q->sort_bits) : 32u,
+                     sf_ = SORT ? U(Q->sort_flags) : 0u, st_ = SORT ? U(Q->sort_tie) : 0u, sc_ = SORT ? U(Q->sort_cap) : 0u;
+      const uint64_t so_ = SORT ? ((uint64_t)U((uint32_t)(Q->sort_off >> 32)) << 32) | U((uint32_t)Q->sort_off) : 0ull;
       if (oq != cur_oq) {
         leave_query();
         cur_oq = oq;
         K = k_, bin_mode = bm_, bin_shift = bs_, bin_lo = (int32_t)bl_, cand_cap = cc_;
         cand = a.cand + co_;
+        if constexpr (SORT) {
+          sorted = son_ != 0;
+          so_item = si_, so_shift = ss_, so_bits = sb_, so_flags = sf_, so_tie = st_;
+          if (sorted) cand_cap = sc_, scand = a.scand + 2 * so_;
+        }
         ghist = a.q_hist + (uint64_t)oq * NBINS;
         gcount = a.q_cand_n + (size_t)oq * QSTRIDE;
         gtaubin = a.q_tau_bin + (size_t)oq * QSTRIDE;
@@ -315,7 +337,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
     }
     // the match: weight, pruning bin, candidate buffer (emit_match of scan_pk_kernel)
     bool push = false;
-    uint64_t key = 0;
+    uint64_t key = 0, key2 = 0;
     uint32_t weight = 0;
     if (is_live) {
       if (ranker == MRK_RANK_NONE)
@@ -342,7 +364,12 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
     if (is_live) {
       ++total;
       const uint32_t grow = a.seg.rowid_base + rowid;
-      if (bin_of(bin_mode, bin_lo, bin_shift, (int32_t)weight, grow) >= tau_bin) {
+      if (SORT && sorted) { // the order starts with the row's attribute; the weight, final here, only breaks ties
+        const uint32_t mk = sort_map_key(sort_extract(a.seg.attrs[(uint64_t)rowid * a.seg.attr_stride + so_item], so_shift, so_bits), so_flags);
+        key = ((uint64_t)mk << 32) | sort_weight_part(so_tie, (int32_t)weight);
+        key2 = ((uint64_t)(~grow) << 32) | weight;
+        push = sort_bin((uint32_t)bin_lo, bin_shift, mk) >= tau_bin;
+      } else if (bin_of(bin_mode, bin_lo, bin_shift, (int32_t)weight, grow) >= tau_bin) {
         push = true;
         key = make_key((int32_t)weight, grow);
       }
@@ -351,7 +378,11 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
     if (bal) {
       const uint32_t np = (uint32_t)__popcll(bal);
       if (cn + np > (uint32_t)RK_CBUF) publish(); // keys pushed under the older threshold stay valid candidates
-      if (push) L.cbuf[cn + __popcll(bal & ((1ull << lane) - 1ull))] = key;
+      if (push) {
+        const uint32_t at = cn + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        L.cbuf[at] = key;
+        if constexpr (SORT) L.cbuf2[at] = key2;
+      }
       cn += np;
       if (cn >= (uint32_t)RK_CBUF - 64u) publish();
     }
@@ -363,6 +394,23 @@ void launch_rank(const ScanArgs& a, int which, void* stream) {
   // persistent grid: enough workgroups to fill every CU at the kernel's occupancy; late ones find the cursor past the
   // count and leave at once
   const dim3 grid(256 * 8), block(WG);
+  if (a.scand) { // the batch holds sorted queries
+    hipStream_t st = (hipStream_t)stream;
+    if (a.seg.pk_fmask) {
+      if (which == 2)
+        hipLaunchKernelGGL((rank_kernel<2, true, true>), dim3(GEN_GRID), block, 0, st, a);
+      else if (which)
+        hipLaunchKernelGGL((rank_kernel<1, true, true>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((rank_kernel<0, true, true>), grid, block, 0, st, a);
+    } else if (which == 2)
+      hipLaunchKernelGGL((rank_kernel<2, false, true>), dim3(GEN_GRID), block, 0, st, a);
+    else if (which)
+      hipLaunchKernelGGL((rank_kernel<1, false, true>), grid, block, 0, st, a);
+    else
+      hipLaunchKernelGGL((rank_kernel<0, false, true>), grid, block, 0, st, a);
+    return;
+  }
   if (a.seg.pk_fmask) { // a segment with 9-32 fields
     if (which == 2)
       hipLaunchKernelGGL((rank_kernel<2, true>), dim3(GEN_GRID), block, 0, (hipStream_t)stream, a);

@@ -13,6 +13,7 @@
 #include "mrk_khits.h"
 #include "mrk_kpk.h"
 #include "mrk_kmq.h"
+#include "mrk_sortkey.h"
 
 #include <type_traits>
 
@@ -32,10 +33,12 @@ constexpr int CBUF = MRK_CBUF; // candidates a wave collects before it publishes
 constexpr int MQCAP = 128;     // matched docs a wave queues for the hit pass (processed 64 at a time)
 
 // WIDE: the instance for segments with 9-32 fields -- field masks come from the pk_fmask plane instead of pk_attr's bytes
-template <bool PROX, bool TREE, int NREF = MAX_PROX_TERMS, bool WIDE = false>
+// SORT: the instances that carry mrk_query.sort -- a second plane for the low halves of the 16-byte candidates
+template <bool PROX, bool TREE, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false>
 struct __align__(16) PkWaveLds {
   using Fmask = typename std::conditional<WIDE, uint32_t, uint8_t>::type;
   uint64_t cbuf[CBUF];  // candidates not yet published to the query's global list
+  uint64_t cbuf2[SORT ? CBUF : 0]; // sorted queries: ~rowid << 32 | true weight (mrk_sortkey.h)
   // proximity rankers: where each matched doc sits in the other terms' blocks (block<<7 | slot, bit 31 = lone hit)
   uint32_t href[PROX ? NREF - 1 : 1][PROX ? DEVBLK : 1];
   uint32_t tj_rowid[DEVBLK];
@@ -58,9 +61,9 @@ struct __align__(16) PkWaveLds {
 };
 static_assert(NBINS * 4 <= MAPCAP, "hist must fit the map area");
 
-template <bool PROX, bool TREE, int NREF = MAX_PROX_TERMS, bool WIDE = false>
+template <bool PROX, bool TREE, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false>
 struct __align__(16) PkSmem {
-  PkWaveLds<PROX, TREE, NREF, WIDE> w[WAVES];
+  PkWaveLds<PROX, TREE, NREF, WIDE, SORT> w[WAVES];
   uint32_t rank[WIDE ? 4 : 1][256]; // field-weight sum per mask; WIDE: per mask byte (the four add up)
   float tfidf[1][256]; // really [n_terms][256]: the tail lives in dynamic LDS right behind this struct
 };
@@ -71,13 +74,15 @@ struct __align__(16) PkSmem {
 // feeds the generic evaluator's queue -- candidates, not matches, with one reference per keyword)
 // WIDE: segments with 9-32 fields (pk_fmask): masks from the plane, 32 field weights, and matches queued for the hit pass carry
 // the whole mask in one more plane
-template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false>
+// SORT: the batch holds queries ordered by a row attribute (mrk_query.sort); instances of their own, so that the ones relevance-only
+// batches launch stay as they are
+template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false>
 __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   constexpr int NF = WIDE ? 32 : 8;
   constexpr bool GEN = NREF > MAX_PROX_TERMS;
   extern __shared__ __align__(16) uint8_t smem_raw[];
-  using Smem = PkSmem<PROX, TREE, NREF, WIDE>;
-  using Fmask = typename PkWaveLds<PROX, TREE, NREF, WIDE>::Fmask;
+  using Smem = PkSmem<PROX, TREE, NREF, WIDE, SORT>;
+  using Fmask = typename PkWaveLds<PROX, TREE, NREF, WIDE, SORT>::Fmask;
   Smem& s = *reinterpret_cast<Smem*>(smem_raw);
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   if (blockIdx.x >= a.n_items) return;
@@ -97,7 +102,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
                                         ? nterms > 1
                                         : (ranker == MRK_RANK_WORDCOUNT || ranker == MRK_RANK_MATCHANY ||
                                            ranker == MRK_RANK_FIELDMASK || ranker == MRK_RANK_SPH04));
-  PkWaveLds<PROX, TREE, NREF, WIDE>& L = s.w[wave];
+  PkWaveLds<PROX, TREE, NREF, WIDE, SORT>& L = s.w[wave];
   const uint32_t oq = Q->out_q; // logical query: several passes (driver keywords) may feed one result
   const uint32_t req_mask = TREE ? Q->req_mask : 0u, excl_mask = TREE ? Q->excl_mask : 0u;
   const uint32_t n_nodes = TREE ? Q->n_nodes : 0u;
@@ -140,7 +145,12 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   };
   const uint32_t bin_mode = Q->bin_mode, bin_shift = Q->bin_shift;
   const int32_t bin_lo = Q->bin_lo;
-  const uint32_t cand_cap = Q->cand_cap;
+  // a sorted query: 16-byte candidates in their own arena, the pruning bin is the mapped attribute key's
+  const bool sorted = SORT && Q->sort_on != 0;
+  const uint32_t so_item = SORT ? Q->sort_item : 0u, so_shift = SORT ? Q->sort_shift : 0u, so_bits = SORT ? Q->sort_bits : 32u,
+                 so_flags = SORT ? Q->sort_flags : 0u, so_tie = SORT ? Q->sort_tie : 0u;
+  uint64_t* __restrict__ scand = sorted ? a.scand + 2 * Q->sort_off : nullptr;
+  const uint32_t cand_cap = sorted ? Q->sort_cap : Q->cand_cap;
   uint64_t* __restrict__ cand = a.cand + Q->cand_off;
   uint32_t* __restrict__ ghist = a.q_hist + (uint64_t)oq * NBINS;
   uint32_t* __restrict__ gcount = a.q_cand_n + (size_t)oq * QSTRIDE;
@@ -174,6 +184,11 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   uint32_t gt_new = 0;
   __syncthreads(); // tables ready; from here on the waves never meet again
   uint32_t tau_bin = 0, cn = 0, flush_at = 64;
+  // (a sorted query prunes on the attribute alone, which needs no weight: a wave that starts late takes over the threshold the earlier
+  // ones reached -- small batches cut their items down to a block per wave, too short to learn it on the way)
+  if constexpr (SORT) {
+    if (sorted) tau_bin = __hip_atomic_load(gtaubin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 
   // publish the wave's buffered candidates: reserve a slice of the query's list with ONE atomic,
   // write it coalesced, add the per-bin counts to the global histogram, re-read the threshold
@@ -189,6 +204,13 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
       wave_lds_fence();
       for (uint32_t i = lane; i < cn; i += 64) {
         const uint64_t key = L.cbuf[i];
+        if constexpr (SORT) {
+          if (sorted) {
+            if (fits) *reinterpret_cast<ulonglong2*>(scand + 2 * (uint64_t)(basep + i)) = make_ulonglong2(key, L.cbuf2[i]);
+            atomicAdd(&L.hist[sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))], 1u);
+            continue;
+          }
+        }
         if (fits) cand[basep + i] = key;
         atomicAdd(&L.hist[bin_of(bin_mode, bin_lo, bin_shift, key_weight(key), key_rowid(key))], 1u);
       }
@@ -217,7 +239,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   // one match: weight, pruning bin, candidate buffer (all lanes call it; live = this lane holds a match)
   auto emit_match = [&](bool is_live, uint32_t rowid, float tfidf, uint32_t fields, int rk) {
     bool push = false;
-    uint64_t key = 0;
+    uint64_t key = 0, key2 = 0;
     uint32_t weight = 0;
     if (is_live) {
       if (ranker == MRK_RANK_NONE)
@@ -239,19 +261,32 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
     if (is_live) {
       ++total;
       const uint32_t grow = rowid_base + rowid;
-      const uint32_t bin = bin_of(bin_mode, bin_lo, bin_shift, (int32_t)weight, grow);
+      uint32_t bin;
+      if (SORT && sorted) { // the sorter reads the row's attribute (the order's first part); the weight only breaks ties
+        const uint32_t mk = sort_map_key(sort_extract(a.seg.attrs[(uint64_t)rowid * a.seg.attr_stride + so_item], so_shift, so_bits), so_flags);
+        bin = sort_bin((uint32_t)bin_lo, bin_shift, mk);
+        key = ((uint64_t)mk << 32) | sort_weight_part(so_tie, (int32_t)weight);
+        key2 = ((uint64_t)(~grow) << 32) | weight;
+        push = bin >= tau_bin;
+      } else {
+        bin = bin_of(bin_mode, bin_lo, bin_shift, (int32_t)weight, grow);
 #if MRK_EXP != 1 && MRK_EXP != 6 && MRK_EXP != 7
-      if (bin >= tau_bin) {
-        push = true;
-        key = make_key((int32_t)weight, grow);
-      }
+        if (bin >= tau_bin) {
+          push = true;
+          key = make_key((int32_t)weight, grow);
+        }
 #endif
+      }
     }
     const uint64_t bal = __ballot(push);
     if (bal) {
       const uint32_t n = (uint32_t)__popcll(bal);
       if (cn + n > (uint32_t)CBUF) publish(); // keys pushed under the older threshold stay valid candidates
-      if (push) L.cbuf[cn + __popcll(bal & ((1ull << lane) - 1ull))] = key;
+      if (push) {
+        const uint32_t at = cn + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        L.cbuf[at] = key;
+        if constexpr (SORT) L.cbuf2[at] = key2;
+      }
       cn += n;
       if (cn >= flush_at) {
         publish();
@@ -317,6 +352,24 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   HC.dupes = (Q->tree_flags & TF_DUPES) != 0 && (ranker == MRK_RANK_PROXIMITY_BM25 || ranker == MRK_RANK_PROXIMITY);
   const bool notnear = EXT && PROX && TREE && (Q->tree_flags & TF_NOTNEAR) != 0;
   HC.nn_a = notnear ? Q->nn_a : 0u, HC.nn_b = notnear ? Q->nn_b : 0u, HC.nn_dist = notnear ? Q->nn_dist : 0u;
+
+  // Sorted hit-ranked queries whose matches are final at scan time (no whole-query PHRASE, no generic evaluator, no weight filter): the
+  // attribute bin test runs HERE, in front of the match queue -- it needs no hits.  The scan keeps its own histogram of the matches'
+  // attribute bins (a.s_hist; the rank kernel's candidates go to q_hist later and must not be counted twice): K matches at or above bin
+  // T prove that a match below T cannot reach the top K; it is counted (total_found) and its hits are never read.
+  const bool pre_prune = SORT && PROX && sorted && need_hits && !phrase && !GEN && Q->n_wfilters == 0 && a.s_hist != nullptr;
+  uint32_t* __restrict__ shist = pre_prune ? a.s_hist + (uint64_t)oq * NBINS : nullptr;
+  uint32_t* __restrict__ stau = pre_prune ? a.s_tau + (size_t)oq * QSTRIDE : nullptr;
+  uint32_t tau_pre = pre_prune ? __hip_atomic_load(stau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  uint32_t pre_added = 0;
+  auto pre_refresh = [&]() {
+    const uint32_t tb = threshold_bin(shist, K);
+    if (tb > tau_pre) {
+      tau_pre = tb;
+      if (lane == 0) atomicMax(stau, tb);
+    }
+    pre_added = 0;
+  };
 
   for (uint32_t b = wb0; b < wb1; ++b) {
     {
@@ -835,6 +888,25 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
       // phrase is one more stream, of folded hits.  That pass is a chain of dependent loads per doc, so matched docs
       // are queued and go through it 64 at a time, one per lane, instead of the few a single driver block holds.
       if (PROX && need_hits) {
+        if constexpr (SORT) {
+          if (pre_prune) {
+            const uint32_t gt = __hip_atomic_load(stau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (gt > tau_pre) tau_pre = gt;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+              uint32_t bin = 0;
+              if (live[r])
+                bin = sort_bin((uint32_t)bin_lo, bin_shift,
+                               sort_map_key(sort_extract(a.seg.attrs[(uint64_t)row[r] * a.seg.attr_stride + so_item], so_shift, so_bits), so_flags));
+              const bool keep = live[r] && bin >= tau_pre;
+              if (live[r] && !keep) ++total; // a match all the same: it just cannot reach the top K
+              if (keep) atomicAdd(shist + bin, 1u); // (attribute bins scatter: a lane-wise add beats one atomic per distinct bin)
+              pre_added += (uint32_t)__popcll(__ballot(keep));
+              live[r] = keep;
+            }
+            if (pre_added >= 512u) pre_refresh();
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
           const uint64_t bal = __ballot(live[r]);
@@ -864,6 +936,9 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
       }
     }
   }
+  if constexpr (SORT) {
+    if (pre_prune && pre_added) pre_refresh(); // (small batches: a block per wave -- the next waves start from this threshold)
+  }
   if (PROX && mqn) flush_matches(0u, mqn);
   if (PROX) mq_close(a.mq[GEN ? 2 : fat_q ? 1 : 0], mqw, item.query);
 
@@ -876,9 +951,9 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   }
 }
 
-template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false>
+template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false>
 static void launch_pk(const ScanArgs& a, size_t tail, hipStream_t st) {
-  hipLaunchKernelGGL((scan_pk_kernel<PROX, TREE, EXT, NREF, WIDE>), dim3(a.n_items), dim3(WG), sizeof(PkSmem<PROX, TREE, NREF, WIDE>) + tail, st, a);
+  hipLaunchKernelGGL((scan_pk_kernel<PROX, TREE, EXT, NREF, WIDE, SORT>), dim3(a.n_items), dim3(WG), sizeof(PkSmem<PROX, TREE, NREF, WIDE, SORT>) + tail, st, a);
 }
 
 void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen) {
@@ -886,6 +961,13 @@ void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree,
   if (max_terms < 1) max_terms = 1;
   const size_t tail = (size_t)(max_terms - 1) * 256 * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
+  if (a.scand) { // the batch holds sorted queries (they set `ext`): the full instances with the sort
+    if (a.seg.pk_fmask)
+      gen ? launch_pk<true, true, true, MRK_MAX_AND_TERMS, true, true>(a, tail, st) : launch_pk<true, true, true, MAX_PROX_TERMS, true, true>(a, tail, st);
+    else
+      gen ? launch_pk<true, true, true, MRK_MAX_AND_TERMS, false, true>(a, tail, st) : launch_pk<true, true, true, MAX_PROX_TERMS, false, true>(a, tail, st);
+    return;
+  }
   if (a.seg.pk_fmask) { // a segment with 9-32 fields: the same choice among the WIDE instances
     if (gen)
       launch_pk<true, true, true, MRK_MAX_AND_TERMS, true>(a, tail, st);
