@@ -346,8 +346,10 @@ int mrk_batch_stats_get(mrk_batch* b, mrk_batch_stats* out);
 /* device-resident partial top-K of the last submit, for shard merges without a host hop:
    keys[q*MRK_MAX_K + i] = ((weight ^ 0x80000000) << 32) | ~(rowid_base + rowid), sorted
    descending; counts[q]; totals[q].  Valid after mrk_batch_wait.  The keys of a query with mrk_query.sort stand in the
-   sorter's order but are compared by nothing here: merges across shards (mrk_topk_merge*, mrk_shard_exchange) order by
-   (weight, docid) only, so such a query's exchange row leaves with MRK_ROW_DECLINED. */
+   sorter's order; the NARROW rows' merges (mrk_topk_merge*, mrk_topk_merge_rows*, mrk_shard_exchange) order by
+   (weight, docid) only, so such a query's narrow exchange row leaves with MRK_ROW_DECLINED.  The WIDE rows below
+   (MRK_SROW_WORDS, mrk_batch_export_srows, mrk_topk_merge_srows*, mrk_shard_exchange_srows) carry the mapped sort key of every
+   entry and answer a sorted query across segments and shards exactly. */
 int mrk_batch_device_results(mrk_batch* b, const uint64_t** keys, const uint32_t** counts, const uint64_t** totals);
 
 /* copy those three arrays into caller-owned device buffers (e.g. tensors handed to RCCL);
@@ -431,7 +433,41 @@ int mrk_shard_partitioned(mrk_ctx* ctx);
 int mrk_topk_merge_rows_part(mrk_ctx* ctx, const uint64_t* rows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
                              uint32_t k, uint64_t* out_rows);
 
-/* merge n_lists sorted partial top-K lists per query (device pointers):
+/* ------------------------------------------------------------------------------------
+ * Wide exchange rows: sorted queries (mrk_query.sort) across segments and shards.  One row of MRK_SROW_WORDS u64 per query:
+ *   [0 .. MRK_MAX_K-1]         the keys of the narrow row, in the sorter's order
+ *   [MRK_MAX_K] [MRK_MAX_K+1]  count | total_found with MRK_ROW_RERUN / MRK_ROW_DECLINED, as in the narrow row
+ *   [MRK_MAX_K+2 ..]           MRK_MAX_K u32 (two per word, entry 2 j in the low half): entry i = the order-preserving mapped
+ *                              key of keys[i]'s primary attribute; zero past count
+ *   [MRK_SROW_WORDS-1]         the sort spec word: 0 = a relevance query (the u32 plane is zero and ignored); else
+ *                              bit 0 sorted | bit 1 float (else unsigned integer) | bit 2 desc | bits 4-5 then_weight |
+ *                              bits 8-13 bit_count -- all that decides whether two shards' mapped keys and tie rules compare,
+ *                              and nothing of where a segment stores the column
+ * The merge orders a sorted query's entries as the unsharded sorter does: mapped key, then the weight as then_weight says (or not
+ * at all), then GLOBAL docid (rowid_base + rowid) ascending; a relevance query's (spec 0) exactly as mrk_topk_merge_rows does.
+ * Totals add up and the two flag bits are OR-ed through.  Lists of one query whose spec words differ (a sorted row next to a
+ * relevance row included), or a sorted query that some list carries with MRK_ROW_DECLINED, give a merged row with
+ * MRK_ROW_DECLINED and no keys: never a mis-ordered answer.  At most 8 lists.  Relevance queries travel in wide rows too, so a
+ * mixed batch needs one exchange.  Each function is the wide twin of the narrow one above, argument for argument.
+ * A batch has ONE standing destination: mrk_batch_set_srows_dst while a narrow one stands (or the reverse) is MRK_E_INVAL; with
+ * a narrow standing destination a sorted query still leaves with MRK_ROW_DECLINED.  After an overflow rerun (MRK_ROW_RERUN),
+ * mrk_batch_wait + mrk_batch_export_srows hand out the repaired row, mapped keys included.
+ * ---------------------------------------------------------------------------------- */
+#define MRK_SROW_WORDS (MRK_ROW_WORDS + MRK_MAX_K / 2 + 1)
+int mrk_batch_export_srows(mrk_batch* b, uint64_t* srows_dst);
+int mrk_batch_set_srows_dst(mrk_batch* b, uint64_t* srows_dst);
+int mrk_topk_merge_srows(mrk_ctx* ctx, const uint64_t* srows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_srows);
+int mrk_topk_merge_srows_async(mrk_ctx* ctx, const uint64_t* srows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
+                               uint64_t* out_srows, void* wait_event, uint32_t slot);
+int mrk_topk_merge_srows_part(mrk_ctx* ctx, const uint64_t* srows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
+                              uint32_t k, uint64_t* out_srows);
+int mrk_shard_exchange_srows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* srows, uint32_t n_queries, uint32_t k, uint64_t* out_srows,
+                             uint32_t slot);
+/* host only: the raw attribute value (the locator's bits; a float's bit pattern) behind a mapped key of a row with this spec
+   word.  The map folds a float's -0.0 onto +0.0, so -0.0 reads +0.0. */
+uint32_t mrk_sort_unmap_key(uint64_t spec_word, uint32_t mapped);
+
+/* merge n_lists sorted partial top-K lists per query (device pointers; relevance order only):
    in_keys[(l*n_queries + q)*MRK_MAX_K + i], in_counts[l*n_queries + q] -> out_keys[q*MRK_MAX_K + i],
    out_counts[q].  Order: weight desc, global docid asc. Synchronous on the ctx stream. */
 int mrk_topk_merge(mrk_ctx* ctx, const uint64_t* in_keys, const uint32_t* in_counts, uint32_t n_lists,

@@ -157,6 +157,14 @@ SYMBOLS = [
     ("mrk_shard_flags", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("mrk_shard_partitioned", C.c_int, [C.c_void_p]),
     ("mrk_topk_merge_rows_part", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("mrk_batch_export_srows", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("mrk_batch_set_srows_dst", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("mrk_topk_merge_srows", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("mrk_topk_merge_srows_async", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_uint32]),
+    ("mrk_topk_merge_srows_part", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("mrk_shard_exchange_srows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+    ("mrk_sort_unmap_key", C.c_uint32, [C.c_uint64, C.c_uint32]),
     ("mrk_idf", C.c_float, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float]),
     ("mrk_index_from_hits", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("mrk_synth_generate", C.c_int, [C.POINTER(SynthParams), C.POINTER(C.c_void_p)]),

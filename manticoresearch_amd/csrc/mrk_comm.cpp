@@ -166,16 +166,16 @@ int mrk_comm_allreduce_i64_impl(mrk_ctx* ctx, int64_t* values, uint64_t n) {
   return MRK_OK;
 }
 
-// rows (this shard's [n_queries][MRK_ROW_WORDS], device) --all-gather--> rows_all[slot] --merge kernel--> out_rows;
+// rows (this shard's [n_queries][row_words], device; row_words = MRK_ROW_WORDS or MRK_SROW_WORDS) --all-gather--> rows_all[slot] --merge kernel--> out_rows;
 // ordered behind `after` (a hipEvent_t recorded behind the rows' producer; NULL = the rows are ready) without a host wait;
 // completion is the merge slot's (mrk_merge_wait).  *gathered_event_out = the event recorded behind the collective.
-int mrk_comm_exchange_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_queries, hipEvent_t after, uint32_t slot, const uint64_t** rows_all_out,
+int mrk_comm_exchange_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_queries, uint32_t row_words, hipEvent_t after, uint32_t slot, const uint64_t** rows_all_out,
                            hipEvent_t* gathered_event_out) {
   mrk_comm* c = ctx->comm;
   if (!c) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: no communicator (mrk_comm_init)");
   RcclApi* api = rccl();
   HIP_TRY(hipSetDevice(ctx->device));
-  const size_t row_bytes = (size_t)n_queries * MRK_ROW_WORDS * 8, need = row_bytes * (size_t)c->n_ranks;
+  const size_t row_bytes = (size_t)n_queries * row_words * 8, need = row_bytes * (size_t)c->n_ranks;
   if (c->rows_all_bytes[slot] < need) {
     if (c->rows_all[slot]) {
       HIP_TRY(hipStreamSynchronize(c->stream));
@@ -188,7 +188,7 @@ int mrk_comm_exchange_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_querie
   // (a slot that is reused before mrk_merge_wait: its previous merge still reads rows_all[slot])
   if (ctx->merge_used[slot] && ctx->merge_done[slot]) HIP_TRY(hipStreamWaitEvent(c->stream, ctx->merge_done[slot], 0));
   if (after) HIP_TRY(hipStreamWaitEvent(c->stream, after, 0));
-  RCCL_TRY(api, api->AllGather(rows, c->rows_all[slot], (size_t)n_queries * MRK_ROW_WORDS, ncclUint64, c->comm, c->stream));
+  RCCL_TRY(api, api->AllGather(rows, c->rows_all[slot], (size_t)n_queries * row_words, ncclUint64, c->comm, c->stream));
   HIP_TRY(hipEventRecord(c->gathered[slot], c->stream));
   *rows_all_out = (const uint64_t*)c->rows_all[slot];
   *gathered_event_out = c->gathered[slot];
@@ -217,8 +217,8 @@ bool mrk_comm_can_partition(mrk_ctx* ctx) {
   return ctx->comm && api && api->Send && api->Recv && api->GroupStart && api->GroupEnd;
 }
 
-// rows -> (all-to-all of row slices) -> recv [n_ranks][per][MRK_ROW_WORDS] of this rank's queries; ordered behind `after`
-int mrk_comm_exchange_part_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_queries, hipEvent_t after, uint32_t slot, const uint64_t** recv_out,
+// rows -> (all-to-all of row slices) -> recv [n_ranks][per][row_words] of this rank's queries; ordered behind `after`
+int mrk_comm_exchange_part_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_queries, uint32_t row_words, hipEvent_t after, uint32_t slot, const uint64_t** recv_out,
                                 hipEvent_t* gathered_event_out, uint32_t* per_out, uint32_t* first_out, uint32_t* count_out) {
   mrk_comm* c = ctx->comm;
   if (!c) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: no communicator (mrk_comm_init)");
@@ -226,7 +226,7 @@ int mrk_comm_exchange_part_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_q
   HIP_TRY(hipSetDevice(ctx->device));
   uint32_t per, first, count;
   mrk_shard_slice_impl(n_queries, c->n_ranks, c->rank, &per, &first, &count);
-  const size_t need = (size_t)c->n_ranks * per * MRK_ROW_WORDS * 8;
+  const size_t need = (size_t)c->n_ranks * per * row_words * 8;
   if (c->rows_all_bytes[slot] < need) {
     if (c->rows_all[slot]) {
       HIP_TRY(hipStreamSynchronize(c->stream));
@@ -254,8 +254,8 @@ int mrk_comm_exchange_part_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_q
   for (int p = 0; p < c->n_ranks; ++p) {
     uint32_t pf, pc;
     mrk_shard_slice_impl(n_queries, c->n_ranks, p, nullptr, &pf, &pc);
-    if (pc) RCCL_TRY(api, api->Send(rows + (size_t)pf * MRK_ROW_WORDS, (size_t)pc * MRK_ROW_WORDS, ncclUint64, p, c->comm, c->stream));
-    if (count) RCCL_TRY(api, api->Recv(recv + (size_t)p * per * MRK_ROW_WORDS, (size_t)count * MRK_ROW_WORDS, ncclUint64, p, c->comm, c->stream));
+    if (pc) RCCL_TRY(api, api->Send(rows + (size_t)pf * row_words, (size_t)pc * row_words, ncclUint64, p, c->comm, c->stream));
+    if (count) RCCL_TRY(api, api->Recv(recv + (size_t)p * per * row_words, (size_t)count * row_words, ncclUint64, p, c->comm, c->stream));
   }
   RCCL_TRY(api, api->GroupEnd());
   HIP_TRY(hipEventRecord(c->gathered[slot], c->stream));

@@ -403,6 +403,12 @@ struct SortSelArgs {
   uint32_t* out_cnt;
   uint64_t* h_keys;   // pinned host or NULL
   uint32_t* h_cnt;    // pinned host or NULL
+  uint32_t* out_mkeys; // [n_queries][KCAP]: the mapped key (hi >> 32) of out_keys' entries -- what a wide exchange row carries
+  // a standing wide destination (mrk_batch_set_srows_dst): the kernel writes the sorted queries' wide rows itself (the instance
+  // launched without one is compiled without this branch)
+  uint64_t* srows_dst;     // device [n_queries][SROW_WORDS] or NULL
+  const uint64_t* q_total; // [n_queries]   (read with srows_dst only)
+  const uint32_t* q_flags; // [n_queries] QF_*
 };
 void launch_sort_select(const SortSelArgs& a, void* stream);
 
@@ -501,6 +507,26 @@ struct PackRowsArgs {
   uint32_t n;
 };
 void launch_pack_rows(const PackRowsArgs& a, void* stream);
+
+// Wide rows (mrk_sortsel.hip; MRK_SROW_WORDS, include/mrk.h): keys | count | total_found | KCAP mapped keys (u32) | spec word
+constexpr int SROW_WORDS = MRK_SROW_WORDS;
+constexpr int SROW_MKEYS = KCAP + 2, SROW_SPEC = SROW_WORDS - 1; // word offsets of the u32 plane and of the spec word
+struct PackSRowsArgs {
+  const DevQuery* queries; // the sort spec is the query's own (sort_on / sort_flags / sort_tie / sort_bits)
+  const uint64_t* keys;    // [n][KCAP]
+  const uint32_t* mkeys;   // [n][KCAP] or NULL (the batch never held a sorted query)
+  const uint32_t* cnt;
+  const uint64_t* total;
+  uint64_t* rows;          // [n][SROW_WORDS]
+  const uint32_t* flags;   // as PackRowsArgs
+  const uint32_t* declined;
+  uint32_t n;
+  uint32_t skip_sorted;    // != 0: the sorted queries' rows are already written (sort_select_kernel with a standing destination)
+};
+void launch_pack_srows(const PackSRowsArgs& a, void* stream);
+// Merge of <= 8 wide rows per query: MergeRowsArgs with rows of SROW_WORDS.  A sorted query orders by (mapped key, the weight as
+// its tie rule says, ~docid); a relevance query exactly as merge_rows_kernel.
+void launch_merge_srows(const MergeRowsArgs& a, void* stream);
 
 void launch_scan(const ScanArgs& a, void* stream);
 void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen = false); // a.scand: the instances that carry the sort

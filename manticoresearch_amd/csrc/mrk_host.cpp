@@ -112,6 +112,7 @@ constexpr size_t STATE_BYTES = 8 + 8 + 4 + 2 * 4 * mrk::QSTRIDE;
 struct mrk_batch {
   mrk_ctx* ctx = nullptr;
   uint64_t* rows_dst = nullptr; // mrk_batch_set_rows_dst
+  uint64_t* srows_dst = nullptr; // mrk_batch_set_srows_dst (wide rows; excludes rows_dst)
   bool host_copied = true;      // per-query keys / counts / totals of the last submit are in pinned host memory
   hipStream_t stream = nullptr; // every batch runs on its own stream: batches of one context overlap on the device
   uint32_t max_queries = 0;
@@ -148,6 +149,7 @@ struct mrk_batch {
   PinBuf<uint32_t> h_cand_n;
   DevBuf<uint64_t> d_cand;
   DevBuf<uint32_t> d_shist;  // sorted hit-ranked queries: the scan's histogram of queued matches' attribute bins [n][NBINS], then the threshold words [n * QSTRIDE]
+  DevBuf<uint32_t> d_out_mkeys; // [max_queries][KCAP] mapped sort keys of d_out_keys' entries (sorted queries; reserved with d_scand)
   DevBuf<uint64_t> d_scand;  // 16-byte candidates of the sorted queries (two words each); reserved by the first batch that holds one
   PinBuf<uint32_t> h_flags;
   // per query: != 0 when the planner declined it on the last submit's segment; travels in the exchange rows
@@ -862,6 +864,7 @@ static void mrk_batch_destroy_impl(mrk_batch* b) {
   b->h_cand_n.release();
   b->d_cand.release();
   b->d_scand.release();
+  b->d_out_mkeys.release();
   b->d_shist.release();
   b->h_flags.release();
   b->h_decl.release();
@@ -1170,7 +1173,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   if (!extra.empty()) memcpy(b->h_queries.p + n, extra.data(), extra.size() * sizeof(DevQuery));
   if (use_packed && ((rc = b->d_cand.reserve(cand_total + 64)) || (rc = b->d_sel.reserve(2 * (size_t)n + mrk::sel_slice_slots(cand_total, n))))) return rc;
   const bool any_sort = use_packed && plan.sort_total != 0;
-  if (any_sort && (rc = b->d_scand.reserve(2 * plan.sort_total + 64))) return rc;
+  if (any_sort && ((rc = b->d_scand.reserve(2 * plan.sort_total + 64)) || (rc = b->d_out_mkeys.reserve((size_t)b->max_queries * KCAP)))) return rc;
 
   static const bool phase_timing = getenv("MRK_SUBMIT_TIMING") != nullptr;
   auto lap = [&](const char* what) {
@@ -1247,16 +1250,19 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     se.q_flags = b->d_q_flags.p;
     se.h_flags = b->h_flags.p;
     se.h_cand_n = b->h_cand_n.p;
-    if (!b->rows_dst) se.h_keys = b->h_keys.p, se.h_cnt = b->h_cnt.p, se.h_total = b->h_total.p;
-    // a standing rows destination (shard exchange): the sort pass writes the exchange rows itself
+    const bool standing = b->rows_dst || b->srows_dst;
+    if (!standing) se.h_keys = b->h_keys.p, se.h_cnt = b->h_cnt.p, se.h_total = b->h_total.p;
+    // a standing rows destination (shard exchange): the sort pass writes the exchange rows itself (narrow rows; the wide
+    // rows of relevance queries are packed behind the selection, below)
     se.rows_dst = b->rows_dst;
     se.declined = nullptr;
     launch_select(se, st2);
     if (any_sort) { // the sorted queries' own selection, behind the relevance one (which wrote a count of 0 for them)
       mrk::SortSelArgs ss{};
       ss.queries = b->d_queries.p, ss.q_hist = b->d_q_hist.p, ss.q_cand_n = b->d_q_cand_n.p, ss.scand = b->d_scand.p, ss.n_queries = n;
-      ss.out_keys = b->d_out_keys.p, ss.out_cnt = b->d_out_cnt.p;
-      if (!b->rows_dst) ss.h_keys = b->h_keys.p, ss.h_cnt = b->h_cnt.p;
+      ss.out_keys = b->d_out_keys.p, ss.out_cnt = b->d_out_cnt.p, ss.out_mkeys = b->d_out_mkeys.p;
+      if (!standing) ss.h_keys = b->h_keys.p, ss.h_cnt = b->h_cnt.p;
+      ss.srows_dst = b->srows_dst, ss.q_total = b->d_q_total.p, ss.q_flags = b->d_q_flags.p; // a standing wide destination: the sorted queries' rows leave here
       mrk::launch_sort_select(ss, st2);
     }
   } else {
@@ -1276,11 +1282,12 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   HIP_TRY(hipEventRecord(b->ev_merge1, st2));
   {
     bool any = false;
-    // (a sorted query's row is no answer to a merge by (weight, docid): in the exchange it counts as declined)
+    // (a sorted query's NARROW row is no answer to a merge by (weight, docid): in that exchange it counts as declined -- word 2,
+    // which the wide rows, whose merge compares the mapped keys, do not take for a decline)
     for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits);
     b->any_declined = any;
     if (any || b->decl_dirty) {
-      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = (b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits)) ? 1u : 0u;
+      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = b->status[i] != MRK_OK ? 1u : (b->rows_dst && b->sort_loc[i].bits) ? 2u : 0u;
       HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     }
     b->decl_dirty = any;
@@ -1296,6 +1303,16 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     pa.n = n;
     launch_pack_rows(pa, st2);
   }
+  if (b->srows_dst) { // the standing wide export: relevance and declined queries' rows (sort_select_kernel wrote the sorted queries')
+    PackSRowsArgs pa{};
+    pa.queries = b->d_queries.p, pa.keys = b->d_out_keys.p, pa.mkeys = b->d_out_mkeys.p, pa.cnt = b->d_out_cnt.p, pa.total = b->d_q_total.p;
+    pa.rows = b->srows_dst;
+    pa.flags = use_packed ? b->d_q_flags.p : nullptr;
+    pa.declined = b->any_declined ? b->d_decl.p : nullptr;
+    pa.n = n;
+    pa.skip_sorted = use_packed && any_sort ? 1u : 0u;
+    launch_pack_srows(pa, st2);
+  }
   HIP_TRY(hipGetLastError());
   b->packed_run = use_packed;
   b->last_seg = seg;
@@ -1307,7 +1324,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   b->last_sort = any_sort;
   lap("select launched");
   // ---- results to pinned host memory: the packed path's selection wrote them itself; the VLB path copies
-  b->host_copied = b->rows_dst == nullptr;
+  b->host_copied = b->rows_dst == nullptr && b->srows_dst == nullptr;
   if (b->host_copied && !use_packed) {
     HIP_TRY(hipMemcpyAsync(b->h_cnt.p, b->d_out_cnt.p, n * 4, hipMemcpyDeviceToHost, st2));
     HIP_TRY(hipMemcpyAsync(b->h_total.p, b->d_q_total.p, n * 8, hipMemcpyDeviceToHost, st2));
@@ -1368,7 +1385,7 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
       (rc = r->d_items.reserve(n_items + 1)) || (rc = r->d_cand.reserve(cap + 64)) || (rc = r->d_sel.reserve(2 + mrk::sel_slice_slots(cap, 1))))
     return rc;
   const bool sorted = passes[0].sort_on != 0; // (the query's order travels with its passes: sort_* of the DevQuery planned at submit)
-  if (sorted && (rc = r->d_scand.reserve(2 * cap + 64))) return rc;
+  if (sorted && ((rc = r->d_scand.reserve(2 * cap + 64)) || (rc = r->d_out_mkeys.reserve((size_t)r->max_queries * KCAP)))) return rc;
   memcpy(r->h_queries.p, passes.data(), passes.size() * sizeof(DevQuery));
   if (n_items) memcpy(r->h_items.p, items_pk.data(), n_items * sizeof(DevItem));
   HIP_TRY(hipMemcpyAsync(r->d_queries.p, r->h_queries.p, passes.size() * sizeof(DevQuery), hipMemcpyHostToDevice, st));
@@ -1403,7 +1420,7 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   if (sorted) {
     mrk::SortSelArgs ss{};
     ss.queries = r->d_queries.p, ss.q_hist = r->d_q_hist.p, ss.q_cand_n = r->d_q_cand_n.p, ss.scand = r->d_scand.p, ss.n_queries = 1;
-    ss.out_keys = r->d_out_keys.p, ss.out_cnt = r->d_out_cnt.p;
+    ss.out_keys = r->d_out_keys.p, ss.out_cnt = r->d_out_cnt.p, ss.out_mkeys = r->d_out_mkeys.p;
     mrk::launch_sort_select(ss, st);
   }
   HIP_TRY(hipGetLastError());
@@ -1416,6 +1433,7 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   HIP_TRY(hipMemcpyAsync(b->d_out_cnt.p + qi, r->d_out_cnt.p, 4, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_q_total.p + qi, r->d_q_total.p, 8, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_out_keys.p + (size_t)qi * KCAP, r->d_out_keys.p, (size_t)KCAP * 8, hipMemcpyDeviceToDevice, st));
+  if (sorted) HIP_TRY(hipMemcpyAsync(b->d_out_mkeys.p + (size_t)qi * KCAP, r->d_out_mkeys.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st)); // (mrk_batch_export_srows)
   HIP_TRY(hipMemsetAsync(b->d_q_flags.p + qi, 0, 4, st)); // the device-side row is good again
   HIP_TRY(hipStreamSynchronize(st));
   if (flags & QF_ARENA) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the generic evaluator ran out of hit-list memory (ctx tunable gen_spill_mb)", qi);
@@ -1542,7 +1560,15 @@ static int mrk_batch_export_device_impl(mrk_batch* b, uint64_t* keys_dst, uint32
 
 extern "C" int mrk_batch_set_rows_dst(mrk_batch* b, uint64_t* rows_dst) {
   if (!b) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_rows_dst: NULL batch");
+  if (rows_dst && b->srows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_rows_dst: the batch has a standing wide destination (mrk_batch_set_srows_dst)");
   b->rows_dst = rows_dst;
+  return MRK_OK;
+}
+
+extern "C" int mrk_batch_set_srows_dst(mrk_batch* b, uint64_t* srows_dst) {
+  if (!b) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_srows_dst: NULL batch");
+  if (srows_dst && b->rows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_srows_dst: the batch has a standing narrow destination (mrk_batch_set_rows_dst)");
+  b->srows_dst = srows_dst;
   return MRK_OK;
 }
 
@@ -1571,14 +1597,34 @@ static int mrk_batch_export_rows_impl(mrk_batch* b, uint64_t* rows_dst) {
   return MRK_OK;
 }
 
+static int mrk_batch_export_srows_impl(mrk_batch* b, uint64_t* srows_dst) {
+  if (!b || !srows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_srows: NULL argument");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  PackSRowsArgs pa{};
+  pa.queries = b->d_queries.p, pa.keys = b->d_out_keys.p, pa.mkeys = b->d_out_mkeys.p, pa.cnt = b->d_out_cnt.p, pa.total = b->d_q_total.p;
+  pa.rows = srows_dst;
+  pa.flags = b->packed_run ? b->d_q_flags.p : nullptr;
+  pa.declined = b->any_declined ? b->d_decl.p : nullptr;
+  pa.n = b->n_queries;
+  launch_pack_srows(pa, b->stream); // behind the batch's selection kernels
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  b->in_flight = false;
+  return MRK_OK;
+}
+
 // rows of n_lists shards -> merged rows; lists [l][list_stride][ROW_WORDS], queries [0, n_queries) of each, out rows at out_first + q
+// (wide: rows of SROW_WORDS through merge_srows_kernel; the callers keep n_lists <= 8 there)
 static void launch_rows_merge(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t list_stride, uint32_t n_queries, uint32_t k,
-                              uint64_t* out_rows, uint32_t out_first, uint32_t* flags_any) {
+                              uint64_t* out_rows, uint32_t out_first, uint32_t* flags_any, bool wide = false) {
   if (n_lists <= 8) {
     mrk::MergeRowsArgs mr{};
     mr.in_rows = rows_all, mr.n_lists = n_lists, mr.list_stride = list_stride, mr.n_queries = n_queries, mr.k = k;
     mr.out_rows = out_rows, mr.out_first = out_first, mr.flags_any = flags_any;
-    launch_merge_rows(mr, ctx->merge_stream);
+    if (wide)
+      launch_merge_srows(mr, ctx->merge_stream);
+    else
+      launch_merge_rows(mr, ctx->merge_stream);
     return;
   }
   MergeArgs ma{}; // many lists (one GPU serving many segments): the general kernel; same layout only when the stride is the query count
@@ -1591,11 +1637,12 @@ static void launch_rows_merge(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n
 }
 
 static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
-                                   uint64_t* out_rows) {
+                                   uint64_t* out_rows, bool wide = false) {
   if (!ctx || !rows_all || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows: NULL argument");
   if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows: k %u outside 1..%d", k, MRK_MAX_K);
+  if (wide && (n_lists == 0 || n_lists > 8)) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_srows: %u lists (1..8)", n_lists);
   HIP_TRY(hipSetDevice(ctx->device));
-  launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr);
+  launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, wide);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->merge_stream));
   return MRK_OK;
@@ -1604,26 +1651,27 @@ static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint
 // what a rank of the query-partitioned exchange does with its receive buffer: lists [n_lists][list_stride] rows, the rank's
 // `count` queries, merged rows written at out_rows[first + q]
 static int mrk_topk_merge_rows_part_impl(mrk_ctx* ctx, const uint64_t* rows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first,
-                                        uint32_t count, uint32_t k, uint64_t* out_rows) {
+                                        uint32_t count, uint32_t k, uint64_t* out_rows, bool wide = false) {
   if (!ctx || !rows_recv || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: NULL argument");
   if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: k %u outside 1..%d", k, MRK_MAX_K);
   if (n_lists == 0 || n_lists > 8 || count > list_stride) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: %u lists (1..8), %u queries of stride %u", n_lists, count, list_stride);
   HIP_TRY(hipSetDevice(ctx->device));
-  launch_rows_merge(ctx, rows_recv, n_lists, list_stride, count, k, out_rows, first, nullptr);
+  launch_rows_merge(ctx, rows_recv, n_lists, list_stride, count, k, out_rows, first, nullptr, wide);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->merge_stream));
   return MRK_OK;
 }
 
 static int mrk_topk_merge_rows_async_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
-                                         uint64_t* out_rows, void* wait_event, uint32_t slot) {
+                                         uint64_t* out_rows, void* wait_event, uint32_t slot, bool wide = false) {
   if (!ctx || !rows_all || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_async: NULL argument");
+  if (wide && (n_lists == 0 || n_lists > 8)) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_srows_async: %u lists (1..8)", n_lists);
   if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_async: k %u outside 1..%d", k, MRK_MAX_K);
   if (slot >= MRK_MERGE_SLOTS) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_async: slot %u of %d", slot, MRK_MERGE_SLOTS);
   HIP_TRY(hipSetDevice(ctx->device));
   if (!ctx->merge_done[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->merge_done[slot], hipEventDisableTiming));
   if (wait_event) HIP_TRY(hipStreamWaitEvent(ctx->merge_stream, (hipEvent_t)wait_event, 0));
-  launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr);
+  launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, wide);
   HIP_TRY(hipGetLastError());
 
   HIP_TRY(hipEventRecord(ctx->merge_done[slot], ctx->merge_stream));
@@ -1893,6 +1941,21 @@ extern "C" int mrk_topk_merge_rows_part(mrk_ctx* ctx, const uint64_t* rows_recv,
                                         uint32_t k, uint64_t* out_rows) {
   return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, rows_recv, n_lists, list_stride, first, count, k, out_rows); });
 }
+extern "C" int mrk_batch_export_srows(mrk_batch* b, uint64_t* srows_dst) {
+  return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_export_srows_impl(b, srows_dst); });
+}
+extern "C" int mrk_topk_merge_srows(mrk_ctx* ctx, const uint64_t* srows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_srows) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_impl(ctx, srows_all, n_lists, n_queries, k, out_srows, true); });
+}
+extern "C" int mrk_topk_merge_srows_async(mrk_ctx* ctx, const uint64_t* srows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
+                                          uint64_t* out_srows, void* wait_event, uint32_t slot) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_async_impl(ctx, srows_all, n_lists, n_queries, k, out_srows, wait_event, slot, true); });
+}
+extern "C" int mrk_topk_merge_srows_part(mrk_ctx* ctx, const uint64_t* srows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
+                                         uint32_t k, uint64_t* out_srows) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, srows_recv, n_lists, list_stride, first, count, k, out_srows, true); });
+}
+extern "C" uint32_t mrk_sort_unmap_key(uint64_t spec_word, uint32_t mapped) { return mrk::sort_unmap_key(spec_word, mapped); }
 extern "C" int mrk_merge_wait(mrk_ctx* ctx, uint32_t slot) {
   return on_worker(ctx, [&] { return mrk_merge_wait_impl(ctx, slot); });
 }
@@ -1920,8 +1983,10 @@ extern "C" int mrk_comm_allreduce_i64(mrk_ctx* ctx, int64_t* values, uint64_t n)
   if (!ctx || (!values && n)) return mrk_fail(MRK_E_INVAL, "mrk_comm_allreduce_i64: NULL argument");
   return on_worker(ctx, [&] { return mrk_comm_allreduce_i64_impl(ctx, values, n); });
 }
-extern "C" int mrk_shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, uint32_t n_queries, uint32_t k, uint64_t* out_rows,
-                                  uint32_t slot) {
+// one body for narrow rows (MRK_ROW_WORDS) and wide ones (MRK_SROW_WORDS): the row width and the merge kernel are all that differ
+static int shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, uint32_t n_queries, uint32_t k, uint64_t* out_rows, uint32_t slot,
+                          bool wide) {
+  const uint32_t row_words = wide ? MRK_SROW_WORDS : MRK_ROW_WORDS;
   if (!ctx || !rows || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: NULL argument");
   if (slot >= MRK_MERGE_SLOTS) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: slot %u of %d", slot, MRK_MERGE_SLOTS);
   if (batch && batch->ctx != ctx) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: batch and context do not belong together");
@@ -1939,20 +2004,28 @@ extern "C" int mrk_shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t
     if (ctx->exchange_part && mrk_comm_can_partition(ctx) && mrk_comm_ranks(ctx) <= 8) {
       // partitioned by query: this rank receives and merges its slice only (mrk_comm.cpp)
       uint32_t per = 0, first = 0, count = 0;
-      int rc = mrk_comm_exchange_part_impl(ctx, rows, n_queries, after, slot, &rows_all, &gathered, &per, &first, &count);
+      int rc = mrk_comm_exchange_part_impl(ctx, rows, n_queries, row_words, after, slot, &rows_all, &gathered, &per, &first, &count);
       if (rc != MRK_OK) return rc;
       if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: k %u outside 1..%d", k, MRK_MAX_K);
       uint32_t* flags_dev = nullptr;
       HIP_TRY(hipStreamWaitEvent(ctx->merge_stream, gathered, 0));
       if ((rc = mrk_comm_flags_begin(ctx, slot, &flags_dev))) return rc;
-      if (count) launch_rows_merge(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), per, count, k, out_rows, first, flags_dev);
+      if (count) launch_rows_merge(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), per, count, k, out_rows, first, flags_dev, wide);
       HIP_TRY(hipGetLastError());
       return mrk_comm_flags_finish(ctx, slot);
     }
-    int rc = mrk_comm_exchange_impl(ctx, rows, n_queries, after, slot, &rows_all, &gathered);
+    int rc = mrk_comm_exchange_impl(ctx, rows, n_queries, row_words, after, slot, &rows_all, &gathered);
     if (rc != MRK_OK) return rc;
-    return mrk_topk_merge_rows_async_impl(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), n_queries, k, out_rows, (void*)gathered, slot);
+    return mrk_topk_merge_rows_async_impl(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), n_queries, k, out_rows, (void*)gathered, slot, wide);
   });
+}
+extern "C" int mrk_shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, uint32_t n_queries, uint32_t k, uint64_t* out_rows,
+                                  uint32_t slot) {
+  return shard_exchange(ctx, batch, rows, n_queries, k, out_rows, slot, false);
+}
+extern "C" int mrk_shard_exchange_srows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* srows, uint32_t n_queries, uint32_t k, uint64_t* out_srows,
+                                        uint32_t slot) {
+  return shard_exchange(ctx, batch, srows, n_queries, k, out_srows, slot, true);
 }
 extern "C" int mrk_shard_slice(uint32_t n_queries, int n_ranks, int rank, uint32_t* first, uint32_t* count) {
   if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return mrk_fail(MRK_E_INVAL, "mrk_shard_slice: rank %d of %d", rank, n_ranks);

@@ -110,13 +110,13 @@ int mrk_comm_unique_id_impl(uint8_t* id_out);
 int mrk_comm_init_impl(mrk_ctx* ctx, const uint8_t* id_bytes, int n_ranks, int rank);
 void mrk_comm_destroy_impl(mrk_ctx* ctx);
 int mrk_comm_allreduce_i64_impl(mrk_ctx* ctx, int64_t* values, uint64_t n);
-int mrk_comm_exchange_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_queries, hipEvent_t after, uint32_t slot, const uint64_t** rows_all_out,
+int mrk_comm_exchange_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_queries, uint32_t row_words, hipEvent_t after, uint32_t slot, const uint64_t** rows_all_out,
                            hipEvent_t* gathered_event_out);
 int mrk_comm_ranks(const mrk_ctx* ctx);
 int mrk_comm_rank(const mrk_ctx* ctx);
 void mrk_shard_slice_impl(uint32_t n_queries, int n_ranks, int rank, uint32_t* per_out, uint32_t* first_out, uint32_t* count_out);
 bool mrk_comm_can_partition(mrk_ctx* ctx);
-int mrk_comm_exchange_part_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_queries, hipEvent_t after, uint32_t slot, const uint64_t** recv_out,
+int mrk_comm_exchange_part_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_queries, uint32_t row_words, hipEvent_t after, uint32_t slot, const uint64_t** recv_out,
                                 hipEvent_t* gathered_event_out, uint32_t* per_out, uint32_t* first_out, uint32_t* count_out);
 int mrk_comm_flags_begin(mrk_ctx* ctx, uint32_t slot, uint32_t** flags_dev_out);
 int mrk_comm_flags_finish(mrk_ctx* ctx, uint32_t slot);

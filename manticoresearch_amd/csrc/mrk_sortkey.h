@@ -29,6 +29,22 @@ MRK_HD inline uint32_t sort_map_key(uint32_t v, uint32_t flags) {
   return (flags & SORT_DESC) ? m : ~m;
 }
 
+// The sort spec word of a wide exchange row (MRK_SROW_WORDS, include/mrk.h): everything that decides whether two shards' mapped
+// keys and tie rules compare, and nothing of where a segment stores the column.  0 = a relevance query.
+//   bit 0 sorted | bit 1 float | bit 2 desc | bits 4-5 then_weight | bits 8-13 bit_count
+constexpr uint64_t SPEC_SORTED = 1, SPEC_FLOAT = 2, SPEC_DESC = 4;
+MRK_HD inline uint64_t sort_spec_word(uint32_t flags, uint32_t tie, uint32_t bits) {
+  return SPEC_SORTED | ((flags & SORT_FLOAT) ? SPEC_FLOAT : 0u) | ((flags & SORT_DESC) ? SPEC_DESC : 0u) | ((uint64_t)(tie & 3u) << 4) | ((uint64_t)(bits & 63u) << 8);
+}
+MRK_HD inline uint32_t sort_spec_tie(uint64_t spec) { return spec ? (uint32_t)(spec >> 4) & 3u : 1u; } // relevance = weight desc
+
+// the inverse of sort_map_key under a spec word: the attribute's raw value (a float's -0.0 was folded onto +0.0 and reads +0.0)
+MRK_HD inline uint32_t sort_unmap_key(uint64_t spec, uint32_t mapped) {
+  const uint32_t m = (spec & SPEC_DESC) ? mapped : ~mapped;
+  if (!(spec & SPEC_FLOAT)) return m;
+  return (m & 0x80000000u) ? (m ^ 0x80000000u) : ~m;
+}
+
 // pruning bin of a mapped key: monotone non-decreasing in it; lo / shift come from the column's range (mrk_plan.cpp)
 MRK_HD inline uint32_t sort_bin(uint32_t lo, uint32_t shift, uint32_t mapped) {
   if (mapped < lo) return 0u;

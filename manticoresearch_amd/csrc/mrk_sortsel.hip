@@ -8,6 +8,9 @@
 // reaches the threshold bin and the running K-th best in an LDS buffer of 2 K candidates, and sorts that buffer (bitonic, on
 // the full 128 bits) whenever it fills up: exact however many rows share the K-th row's attribute value -- a column with four
 // distinct values puts a quarter of the matches into one bin, and all of them are compared by weight and rowid here.
+//
+// Below it: the WIDE exchange rows that carry a sorted query across segments and shards (pack_srows_kernel) and their merge
+// (merge_srows_kernel).
 #include "mrk_kcommon.h"
 #include "mrk_kprune.h"
 #include "mrk_sortkey.h"
@@ -56,6 +59,8 @@ static __device__ uint32_t sortsel_compact(SortSelSmem& s, uint32_t K) {
   return keep;
 }
 
+// WIDE: the batch has a standing wide destination (a.srows_dst) and the kernel writes the query's wide exchange row itself
+template <bool WIDE>
 __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
   __shared__ SortSelSmem s;
   const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
@@ -103,6 +108,25 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
     const uint64_t key = make_key((int32_t)(uint32_t)l, ~(uint32_t)(l >> 32));
     a.out_keys[(uint64_t)q * KCAP + i] = key;
     if (a.h_keys) a.h_keys[(uint64_t)q * KCAP + i] = key;
+    a.out_mkeys[(uint64_t)q * KCAP + i] = (uint32_t)(s.hi[i] >> 32); // the mapped key travels with the row (wide exchange rows)
+  }
+  if constexpr (WIDE) { // sel_sort_kernel's rule: a query whose candidate list overflowed leaves empty with MRK_ROW_RERUN
+    const bool bad = (a.q_flags[q] & (QF_OVERFLOW | QF_FSM)) != 0;
+    const uint32_t nr = bad ? 0u : m;
+    uint64_t* __restrict__ row = a.srows_dst + (uint64_t)q * SROW_WORDS;
+    for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) {
+      const uint64_t l = s.lo[i];
+      row[i] = i < nr ? make_key((int32_t)(uint32_t)l, ~(uint32_t)(l >> 32)) : 0ull;
+    }
+    for (uint32_t i = tid; i < (uint32_t)KCAP / 2; i += WG) {
+      const uint64_t m0 = 2 * i < nr ? s.hi[2 * i] >> 32 : 0ull, m1 = 2 * i + 1 < nr ? s.hi[2 * i + 1] >> 32 : 0ull;
+      row[SROW_MKEYS + i] = m0 | (m1 << 32);
+    }
+    if (tid == 0) {
+      row[KCAP] = nr;
+      row[KCAP + 1] = bad ? ROW_RERUN : (a.q_total[q] & ~ROW_FLAG_MASK);
+      row[SROW_SPEC] = sort_spec_word(Q->sort_flags, Q->sort_tie, Q->sort_bits);
+    }
   }
   if (tid == 0) {
     a.out_cnt[q] = m;
@@ -112,7 +136,168 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
 
 void launch_sort_select(const SortSelArgs& a, void* stream) {
   if (!a.n_queries) return;
-  hipLaunchKernelGGL(sort_select_kernel, dim3(a.n_queries), dim3(WG), 0, (hipStream_t)stream, a);
+  if (a.srows_dst)
+    hipLaunchKernelGGL(sort_select_kernel<true>, dim3(a.n_queries), dim3(WG), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(sort_select_kernel<false>, dim3(a.n_queries), dim3(WG), 0, (hipStream_t)stream, a);
+}
+
+// ---------------------------------------------------------------------------------------
+// a batch's results as WIDE exchange rows: KCAP keys | count | total_found | KCAP mapped keys (u32) | spec word
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void pack_srows_kernel(PackSRowsArgs a) {
+  const uint32_t q = blockIdx.x, tid = threadIdx.x;
+  if (q >= a.n) return;
+  const DevQuery* __restrict__ Q = a.queries + q;
+  // declined words: 1 = the planner declined the query on this segment; 2 = declined for NARROW rows only (a sorted query
+  // of a batch with a narrow standing destination) -- a wide row answers it
+  const bool declined = a.declined && a.declined[q] == 1u;
+  const bool sorted = Q->sort_on != 0 && !declined;
+  if (a.skip_sorted && sorted) return; // (uniform) sort_select_kernel<true> wrote this row
+  const bool bad = declined || (a.flags && (a.flags[q] & (QF_OVERFLOW | QF_FSM)) != 0);
+  const uint32_t n = bad ? 0u : a.cnt[q] < (uint32_t)KCAP ? a.cnt[q] : (uint32_t)KCAP;
+  uint64_t* __restrict__ row = a.rows + (uint64_t)q * SROW_WORDS;
+  const uint32_t nm = sorted && a.mkeys ? n : 0u; // a relevance row's u32 plane is zero
+  for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) row[i] = i < n ? a.keys[(uint64_t)q * KCAP + i] : 0ull;
+  for (uint32_t i = tid; i < (uint32_t)KCAP / 2; i += WG) {
+    const uint64_t m0 = 2 * i < nm ? a.mkeys[(uint64_t)q * KCAP + 2 * i] : 0u, m1 = 2 * i + 1 < nm ? a.mkeys[(uint64_t)q * KCAP + 2 * i + 1] : 0u;
+    row[SROW_MKEYS + i] = m0 | (m1 << 32);
+  }
+  if (tid == 0) {
+    row[KCAP] = n;
+    row[KCAP + 1] = declined ? ROW_DECLINED : bad ? ROW_RERUN : (a.total[q] & ~ROW_FLAG_MASK);
+    row[SROW_SPEC] = sorted ? sort_spec_word(Q->sort_flags, Q->sort_tie, Q->sort_bits) : 0ull;
+  }
+}
+
+void launch_pack_srows(const PackSRowsArgs& a, void* stream) {
+  if (!a.n) return;
+  hipLaunchKernelGGL(pack_srows_kernel, dim3(a.n), dim3(WG), 0, (hipStream_t)stream, a);
+}
+
+// ---------------------------------------------------------------------------------------
+// merge of <= 8 sorted WIDE rows per query: merge_rows_kernel's pairwise bitonic merges (mrk_select.hip) over entries of
+// 12 bytes -- the u64 key and, in a plane of its own, the u32 mapped key.  The weight and the docid come out of the u64 key,
+// so a sorted query compares (mapped key, the key as the tie rule reads it); a relevance query (spec 0) compares the key alone:
+// exactly merge_rows_kernel's order.  LDS: P lists x KCAP x 12 B = 96 KB for 8 lists (one workgroup per CU on gfx950's 160 KB;
+// 48 KB and three workgroups for up to 4 lists).
+// ---------------------------------------------------------------------------------------
+// the u64 key as tie rule `tie` orders it, larger = better; the zero key is the lists' padding and stays the smallest
+template <uint32_t TIE>
+__device__ __forceinline__ uint64_t tie_key(uint64_t k) {
+  if (TIE == 1u) return k;
+  if (k == 0ull) return 0ull;
+  return TIE == 2u ? k ^ 0xFFFFFFFF00000000ull : k & 0xFFFFFFFFull; // weight ascending / the weight is no part of the order
+}
+
+template <bool SORTED, uint32_t TIE>
+static __device__ void merge_srows_rounds(uint64_t* mk, uint32_t* mm, uint32_t P) {
+  const uint32_t tid = threadIdx.x;
+  auto less = [](uint64_t xk, uint32_t xm, uint64_t yk, uint32_t ym) -> bool {
+    if (SORTED && xm != ym) return xm < ym;
+    return tie_key<TIE>(xk) < tie_key<TIE>(yk);
+  };
+  for (uint32_t step = 1; step < P; step <<= 1) { // this round merges list slot 2 p step with slot (2 p + 1) step
+    const uint32_t pairs = P / (2 * step);
+    for (uint32_t t = tid; t < pairs * KCAP; t += WG) { // top K of A and B as a bitonic sequence, in A's place
+      const uint32_t p = t / KCAP, i = t % KCAP;
+      const size_t ia = (size_t)(2 * p * step) * KCAP + i, ib = (size_t)((2 * p + 1) * step) * KCAP + (KCAP - 1 - i);
+      const uint64_t xk = mk[ia], yk = mk[ib];
+      const uint32_t xm = SORTED ? mm[ia] : 0u, ym = SORTED ? mm[ib] : 0u;
+      if (less(xk, xm, yk, ym)) {
+        mk[ia] = yk;
+        if (SORTED) mm[ia] = ym;
+      }
+    }
+    __syncthreads();
+    for (uint32_t j = KCAP / 2; j > 0; j >>= 1) { // ... sorted descending by half-cleaners
+      for (uint32_t t = tid; t < pairs * (KCAP / 2); t += WG) {
+        const uint32_t p = t / (KCAP / 2), i0 = t % (KCAP / 2);
+        const size_t base = (size_t)(2 * p * step) * KCAP;
+        const size_t i = base + (((i0 & ~(j - 1)) << 1) | (i0 & (j - 1))), ij = i + j;
+        const uint64_t xk = mk[i], yk = mk[ij];
+        const uint32_t xm = SORTED ? mm[i] : 0u, ym = SORTED ? mm[ij] : 0u;
+        if (less(xk, xm, yk, ym)) {
+          mk[i] = yk, mk[ij] = xk;
+          if (SORTED) mm[i] = ym, mm[ij] = xm;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__global__ __launch_bounds__(WG) void merge_srows_kernel(MergeRowsArgs a, uint32_t P) { // P = power of two >= n_lists
+  extern __shared__ uint64_t mk[];                            // [P][KCAP] keys ...
+  uint32_t* mm = reinterpret_cast<uint32_t*>(mk + (size_t)P * KCAP); // ... then [P][KCAP] mapped keys
+  const uint32_t q = blockIdx.x, tid = threadIdx.x;
+  if (q >= a.n_queries) return;
+  const uint64_t spec = a.in_rows[(uint64_t)q * SROW_WORDS + SROW_SPEC]; // list 0's; every list must agree
+  uint64_t total = 0, flags = 0, have = 0;
+  bool mismatch = false;
+  for (uint32_t l = 0; l < P; ++l) {
+    uint32_t cnt = 0;
+    const uint64_t* __restrict__ row = nullptr;
+    if (l < a.n_lists) {
+      row = a.in_rows + ((uint64_t)l * a.list_stride + q) * SROW_WORDS;
+      cnt = (uint32_t)row[KCAP];
+      if (cnt > (uint32_t)KCAP) cnt = KCAP;
+      const uint64_t t = row[KCAP + 1];
+      total += t & ~ROW_FLAG_MASK, flags |= t & ROW_FLAG_MASK, have += cnt;
+      mismatch = mismatch || row[SROW_SPEC] != spec;
+    }
+    for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) mk[l * KCAP + i] = i < cnt ? row[i] : 0ull;
+    if (spec) {
+      const uint32_t* __restrict__ rm = row ? reinterpret_cast<const uint32_t*>(row + SROW_MKEYS) : nullptr;
+      for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) mm[l * KCAP + i] = i < cnt ? rm[i] : 0u;
+    }
+  }
+  __syncthreads();
+  // lists that do not compare (differing spec words: other kind / direction / tie rule / width, or a sorted row next to a relevance
+  // row), and a sorted query some shard declined: the merged row is no answer -- MRK_ROW_DECLINED and no keys
+  const bool none = mismatch || (spec != 0 && (flags & ROW_DECLINED) != 0);
+  if (mismatch) flags |= ROW_DECLINED;
+  if (!none) { // (uniform)
+    const uint32_t tie = sort_spec_tie(spec);
+    if (!spec)
+      merge_srows_rounds<false, 1u>(mk, mm, P);
+    else if (tie == 1u)
+      merge_srows_rounds<true, 1u>(mk, mm, P);
+    else if (tie == 2u)
+      merge_srows_rounds<true, 2u>(mk, mm, P);
+    else
+      merge_srows_rounds<true, 0u>(mk, mm, P);
+  }
+  const uint32_t n = none ? 0u : have < a.k ? (uint32_t)have : a.k;
+  uint64_t* __restrict__ out = a.out_rows + (uint64_t)(a.out_first + q) * SROW_WORDS;
+  for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) out[i] = i < n ? mk[i] : 0ull;
+  const uint32_t nm = spec ? n : 0u;
+  for (uint32_t i = tid; i < (uint32_t)KCAP / 2; i += WG) {
+    const uint64_t m0 = 2 * i < nm ? mm[2 * i] : 0u, m1 = 2 * i + 1 < nm ? mm[2 * i + 1] : 0u;
+    out[SROW_MKEYS + i] = m0 | (m1 << 32);
+  }
+  if (tid == 0) {
+    out[KCAP] = n;
+    out[KCAP + 1] = (total & ~ROW_FLAG_MASK) | flags; // totals add up, the shards' flag bits are OR-ed through (merge_rows_kernel)
+    out[SROW_SPEC] = spec;
+    if (a.flags_any) {
+      if (flags & ROW_RERUN) a.flags_any[0] = 1u;
+      if (flags & ROW_DECLINED) a.flags_any[1] = 1u;
+    }
+  }
+}
+
+void launch_merge_srows(const MergeRowsArgs& a, void* stream) {
+  if (!a.n_queries) return;
+  uint32_t P = 1;
+  while (P < a.n_lists) P <<= 1;
+  const size_t lds = (size_t)P * KCAP * (sizeof(uint64_t) + sizeof(uint32_t));
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)merge_srows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * KCAP * (int)(sizeof(uint64_t) + sizeof(uint32_t)));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(merge_srows_kernel, dim3(a.n_queries), dim3(WG), lds, (hipStream_t)stream, a, P);
 }
 
 } // namespace mrk

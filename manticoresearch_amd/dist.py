@@ -62,6 +62,68 @@ def exchange_partial_topk(keys, counts, totals):
 
 ROW_WORDS = MRK_MAX_K + 2  # MRK_ROW_WORDS: keys | count | total_found
 ROW_RERUN, ROW_DECLINED = 1 << 63, 1 << 62  # MRK_ROW_RERUN / MRK_ROW_DECLINED: flag bits of the total_found word
+# MRK_SROW_WORDS, the wide row that carries a sorted query (mrk_query.sort) across shards:
+#   keys | count | total_found | MRK_MAX_K mapped sort keys (u32, two per word) | sort spec word (0 = a relevance query)
+SROW_WORDS = ROW_WORDS + MRK_MAX_K // 2 + 1
+SROW_MKEYS, SROW_SPEC = MRK_MAX_K + 2, SROW_WORDS - 1  # word offsets of the u32 plane and of the spec word
+SPEC_SORTED, SPEC_FLOAT, SPEC_DESC = 1, 2, 4           # + then_weight << 4 + bit_count << 8 (mrk_sortkey.h, sort_spec_word)
+
+
+def sort_spec_word(kind: int, desc: bool, then_weight: int, bit_count: int) -> int:
+    """The spec word of a sorted query's wide row (kind: SORTKEY_INT 0 / SORTKEY_FLOAT 1)."""
+    return SPEC_SORTED | (SPEC_FLOAT if kind else 0) | (SPEC_DESC if desc else 0) | ((then_weight & 3) << 4) | ((bit_count & 63) << 8)
+
+
+def srow_mkeys(srows: np.ndarray) -> np.ndarray:
+    """[..., MRK_MAX_K] u32 view of wide rows' mapped-key plane (rows: uint64 [..., SROW_WORDS], C-contiguous)."""
+    return np.ascontiguousarray(srows[..., SROW_MKEYS:SROW_SPEC]).view("<u4")
+
+
+def unmap_keys(spec: int, mapped: np.ndarray) -> np.ndarray:
+    """Raw attribute values behind mapped sort keys (mrk_sort_unmap_key per entry; a float's -0.0 reads +0.0)."""
+    f = lib().mrk_sort_unmap_key
+    return np.fromiter((f(spec, int(m)) for m in mapped), dtype=np.uint32, count=len(mapped))
+
+
+def merge_srows_np(srows_all: np.ndarray, k: int) -> np.ndarray:
+    """What merge_srows_kernel computes, in numpy: srows_all uint64 [n_lists, nq, SROW_WORDS] -> [nq, SROW_WORDS].  A sorted query
+    orders by (mapped key, the weight as then_weight says, global docid asc), a relevance query (spec 0) by (weight, docid);
+    totals add up, the two flag bits are OR-ed through; lists whose spec words differ, and a sorted query some list carries
+    with ROW_DECLINED, give ROW_DECLINED and no keys.  The CPU mirror the kernel is tested against; a gloo-only host's merge."""
+    srows_all = np.ascontiguousarray(srows_all, dtype=np.uint64)
+    n_lists, nq, _ = srows_all.shape
+    out = np.zeros((nq, SROW_WORDS), dtype=np.uint64)
+    mask = np.uint64(ROW_RERUN | ROW_DECLINED)
+    for q in range(nq):
+        rows = srows_all[:, q]
+        spec = int(rows[0, SROW_SPEC])
+        cnt = np.minimum(rows[:, MRK_MAX_K], np.uint64(MRK_MAX_K)).astype(np.int64)
+        tf = rows[:, MRK_MAX_K + 1]
+        total = int((tf & ~mask).sum(dtype=np.uint64))
+        flags = int(np.bitwise_or.reduce(tf & mask))
+        mismatch = bool((rows[:, SROW_SPEC] != np.uint64(spec)).any())
+        if mismatch:
+            flags |= ROW_DECLINED
+        out[q, MRK_MAX_K + 1] = np.uint64((total & ~(ROW_RERUN | ROW_DECLINED)) | flags)
+        out[q, SROW_SPEC] = np.uint64(spec)
+        if mismatch or (spec and flags & ROW_DECLINED):
+            continue
+        keys = np.concatenate([rows[l, :cnt[l]] for l in range(n_lists)])
+        mk = np.concatenate([srow_mkeys(rows[l])[:cnt[l]] for l in range(n_lists)]) if spec else np.zeros(len(keys), np.uint32)
+        w = (keys >> np.uint64(32)).astype(np.uint32)  # weight ^ 0x80000000: larger = heavier
+        tie = (spec >> 4) & 3 if spec else 1
+        wpart = w if tie == 1 else ~w if tie == 2 else np.zeros_like(w)
+        nd = keys.astype(np.uint32)                    # ~docid: larger = smaller docid
+        order = np.lexsort((nd, wpart, mk))[::-1]       # descending by (mapped key, weight part, ~docid)
+        n = min(len(keys), k)
+        order = order[:n]
+        out[q, :n] = keys[order]
+        out[q, MRK_MAX_K] = np.uint64(n)
+        if spec:
+            plane = np.zeros(MRK_MAX_K, dtype="<u4")
+            plane[:n] = mk[order]
+            out[q, SROW_MKEYS:SROW_SPEC] = plane.view("<u8")
+    return out
 
 
 def exchange_rows(rows):
@@ -118,7 +180,10 @@ class ShardMerger:
     without blocking; wait(set) blocks until that set's merged rows are in host memory.  merge() is the simple
     synchronous form for one batch."""
 
-    def __init__(self, ctx, batch, n_queries: int, k: int, world: int, device: int, n_batches: int = 1, n_sets: int = 1):
+    def __init__(self, ctx, batch, n_queries: int, k: int, world: int, device: int, n_batches: int = 1, n_sets: int = 1,
+                 sorted_rows: bool = False):
+        """sorted_rows=True: WIDE rows (SROW_WORDS) through the wide entry points -- sorted queries (Query.sort) are merged
+        across the shards in the sorter's order and results() hands back their sort_key; relevance queries travel along."""
         import torch
 
         assert n_sets <= 8  # MRK_MERGE_SLOTS
@@ -131,10 +196,18 @@ class ShardMerger:
         def z(*shape):
             return torch.zeros(shape, dtype=torch.int64, device=dev)
 
-        self.rows = [z(self.nq, ROW_WORDS) for _ in range(n_sets)]
-        self.rows_all = [z(world, self.nq, ROW_WORDS) for _ in range(n_sets)]
-        self.out_rows = [z(self.nq, ROW_WORDS) for _ in range(n_sets)]
-        self.host_rows = [torch.zeros((self.nq, ROW_WORDS), dtype=torch.int64).pin_memory() for _ in range(n_sets)]
+        self.sorted_rows = bool(sorted_rows)
+        self.row_words = rw = SROW_WORDS if sorted_rows else ROW_WORDS
+        L = lib()
+        # the narrow entry points or their wide twins: same arguments
+        self._set_dst = L.mrk_batch_set_srows_dst if sorted_rows else L.mrk_batch_set_rows_dst
+        self._export = L.mrk_batch_export_srows if sorted_rows else L.mrk_batch_export_rows
+        self._exchange = L.mrk_shard_exchange_srows if sorted_rows else L.mrk_shard_exchange
+        self._merge_async = L.mrk_topk_merge_srows_async if sorted_rows else L.mrk_topk_merge_rows_async
+        self.rows = [z(self.nq, rw) for _ in range(n_sets)]
+        self.rows_all = [z(world, self.nq, rw) for _ in range(n_sets)]
+        self.out_rows = [z(self.nq, rw) for _ in range(n_sets)]
+        self.host_rows = [torch.zeros((self.nq, rw), dtype=torch.int64).pin_memory() for _ in range(n_sets)]
         self.gathered = [torch.cuda.Event() for _ in range(n_sets)]
         self.ready = [torch.cuda.Event() for _ in range(n_sets)]
         for ev in self.ready:  # created by their first record; the library re-records them on the batch streams
@@ -152,11 +225,11 @@ class ShardMerger:
         n = self.per_batch
         assert len(batches) * n <= self.nq
         for i, b in enumerate(batches):
-            check(lib().mrk_batch_set_rows_dst(b._h, self.rows[set_index][i * n:].data_ptr()))
+            check(self._set_dst(b._h, self.rows[set_index][i * n:].data_ptr()))
         self.attached[set_index] = list(batches)
 
     def merge(self):
-        check(lib().mrk_batch_export_rows(self.batch._h, self.rows[0].data_ptr()))
+        check(self._export(self.batch._h, self.rows[0].data_ptr()))
         self.merge_attached(1, 0)
         self.wait(0)
         return self.out_rows[0][: self.per_batch]
@@ -187,7 +260,7 @@ class ShardMerger:
                 f, c = C.c_uint32(), C.c_uint32()
                 check(lib().mrk_shard_slice(nq, self.world, self.rank, C.byref(f), C.byref(c)))
                 self.first, self.count = f.value, c.value
-            check(lib().mrk_shard_exchange(self.ctx._h, bh, self.rows[set_index].data_ptr(), nq, self.k,
+            check(self._exchange(self.ctx._h, bh, self.rows[set_index].data_ptr(), nq, self.k,
                                            (self.host_rows if to_host else self.out_rows)[set_index].data_ptr(), set_index))
             self.on_host[set_index] = to_host
             if self.timing is not None:
@@ -205,9 +278,9 @@ class ShardMerger:
         ev = self.gathered[set_index]
         ev.record()  # on torch's current stream, behind the collective's completion
         t1 = time.perf_counter()
-        check(lib().mrk_topk_merge_rows_async(self.ctx._h, rows_all.data_ptr(), self.world, nq, self.k,
-                                              (self.host_rows if to_host else self.out_rows)[set_index].data_ptr(),
-                                              ev.cuda_event, set_index))
+        check(self._merge_async(self.ctx._h, rows_all.data_ptr(), self.world, nq, self.k,
+                                (self.host_rows if to_host else self.out_rows)[set_index].data_ptr(),
+                                ev.cuda_event, set_index))
         self.on_host[set_index] = to_host
         t2 = time.perf_counter()
         if self.timing is not None:
@@ -244,7 +317,7 @@ class ShardMerger:
         n = self.per_batch
         for i, b in enumerate(self.attached[set_index]):
             check(lib().mrk_batch_wait(b._h))  # reruns this shard's overflowed queries, repairs the device-side lists
-            check(lib().mrk_batch_export_rows(b._h, self.rows[set_index][i * n:].data_ptr()))
+            check(self._export(b._h, self.rows[set_index][i * n:].data_ptr()))
         self.merge_attached(len(self.attached[set_index]), set_index, to_host=self.on_host[set_index])
         self.wait(set_index)
         rows = self._merged(set_index)
@@ -268,7 +341,8 @@ class ShardMerger:
 
     def results(self, set_index: int = 0, nq=None, allow_declined: bool = False):
         """Decoded (global docid, weight) lists per query + total_found.  A query some shard declined raises MrkError
-        (allow_declined=True: its entry is None instead)."""
+        (allow_declined=True: its entry is None instead).  With sorted_rows the entries are Matches (rowid = global docid),
+        a sorted query's with sort_key (the attribute's raw value per row), a relevance query's with sort_key None."""
         rows = self.finish(set_index)
         out = []
         if self.partitioned and self.world > 1:
@@ -283,5 +357,11 @@ class ShardMerger:
             k = rows[q, :cnt]
             weight = ((k >> np.uint64(32)).astype(np.uint32) ^ np.uint32(0x80000000)).view(np.int32)
             docid = ~k.astype(np.uint32)
+            if self.sorted_rows:
+                from .api import Matches
+
+                spec = int(rows[q, SROW_SPEC])
+                out.append(Matches(docid, weight, tot, 0, unmap_keys(spec, srow_mkeys(rows[q])[:cnt]) if spec else None))
+                continue
             out.append((docid, weight, tot))
         return out
