@@ -168,13 +168,37 @@ typedef struct {
    attribute rows, a float column that holds a NaN (no strict weak order), cutoff next to a sort, the VLB-direct path.  Locators outside
    the row, bit_count 0 or 33..63, unknown kinds / tie rules: MRK_E_INVAL.  Sorted queries run on the packed block-scan path only. */
 enum { MRK_SORT_RELEVANCE = 0, MRK_SORT_ATTR = 1 };
-enum { MRK_SORTKEY_INT = 0, MRK_SORTKEY_FLOAT = 1 };
+enum { MRK_SORTKEY_INT = 0, MRK_SORTKEY_FLOAT = 1, MRK_SORTKEY_INT64 = 2 /* mrk_order only: signed, as SphAttr_t compares */ };
 typedef struct {
   int32_t kind;                  /* MRK_SORTKEY_* */
   int32_t bit_offset, bit_count; /* CSphAttrLocator of a row attribute: 1..32 bits inside one dword */
   int32_t desc;                  /* 1 = descending */
   int32_t then_weight;           /* 0 = attribute, rowid asc;  1 = attribute, weight DESC, rowid asc;  2 = attribute, weight ASC, rowid asc */
 } mrk_sort;
+
+/* The wider form of the sorter's order (SPH_SORT_EXTENDED; MatchGeneric1_fn .. 3_fn, sphinxsort.cpp:4708-4753): up to
+   MRK_MAX_ORDER_PARTS row attributes, each with its own direction, then the weight as then_weight says (mrk_sort's meaning), rowid
+   ascending last.  Accepted shapes:
+     - ONE part of kind INT64: bit_count 64, dword-aligned, inside the row; compared as a SIGNED 64-bit integer (SPH_KEYPART_INT
+       over a 64-bit locator -- 'ORDER BY id', any bigint column);
+     - ONE or TWO parts of kind INT (1..32 bits inside one dword, unsigned) / FLOAT (32 bits).
+   One part of <= 32 bits answers exactly as the same spec through mrk_query.sort does.  mrk_query.sort and mrk_query.order both set,
+   n_parts outside 1..MRK_MAX_ORDER_PARTS, unknown kinds / tie rules, locators outside the row or straddling a dword, 64 bits that are
+   not dword-aligned, INT64 as one of two parts: MRK_E_INVAL, before a row is read.  Declined per query with MRK_E_UNSUPPORTED: a
+   blob-stored part (bit_offset < 0), a float part whose column holds a NaN, a segment without attribute rows, cutoff next to an
+   order, the VLB-direct path.  A key of more than 32 bits (INT64, two parts) fits no exchange row: such a query leaves in narrow
+   AND wide rows with MRK_ROW_DECLINED and no keys. */
+#define MRK_MAX_ORDER_PARTS 2
+typedef struct {
+  int32_t kind;                  /* MRK_SORTKEY_* */
+  int32_t bit_offset, bit_count; /* CSphAttrLocator of a row attribute */
+  int32_t desc;                  /* 1 = descending */
+} mrk_order_part;
+typedef struct {
+  int32_t n_parts;
+  mrk_order_part parts[MRK_MAX_ORDER_PARTS];
+  int32_t then_weight;           /* as mrk_sort::then_weight, behind the last part */
+} mrk_order;
 
 /* CSphQuery fields that reach the ranker + the query tree */
 typedef struct {
@@ -204,6 +228,7 @@ typedef struct {
   const mrk_filter* weight_filters;
   int32_t n_weight_filters;     /* <= MRK_MAX_FILTERS on the device */
   const mrk_sort* sort;         /* NULL = (weight desc, rowid asc) */
+  const mrk_order* order;       /* NULL = as mrk_query.sort says; not next to a sort */
 } mrk_query;
 
 typedef struct {
@@ -216,6 +241,9 @@ typedef struct {
                                for relevance queries and for mrk_batcher_search (whose rows land in the caller's buffers).  Read from the
                                segment's rows when the result is fetched: no mrk_segment_set_attrs between mrk_batch_submit and mrk_batch_result.  weight is the
                                true weight of every row, also where the weight is no part of the order */
+  const uint64_t* order_key; /* a query with mrk_query.order: per returned row the raw 64-bit value of an INT64 part; else the first part's raw
+                                value in the high dword and the second's (or 0) in the low dword.  Read from the segment's rows like sort_key,
+                                which stays NULL for such a query; NULL for every other query and for mrk_batcher_search */
 } mrk_result;
 
 typedef struct {

@@ -18,11 +18,13 @@
 //
 // Why the sorter matters.  The device returns ONLY the K best matches under ONE order, not the whole match stream.  Feeding those K
 // rows to a queue whose order is another one would silently drop rows the queue wanted, and so would a filter the device did not
-// evaluate (EarlyReject would thin the K rows out).  The device knows two orders (MrkSorterOrder): (weight desc, rowid asc) --
+// evaluate (EarlyReject would thin the K rows out).  The device knows three orders (MrkSorterOrder): (weight desc, rowid asc) --
 // MatchRelevanceLt_fn, sphinxsort.cpp:4541-4547 -- and ONE static row attribute of <= 32 bits first, then optionally the weight, then
 // rowid asc (mrk_query.sort): SPH_SORT_ATTR_DESC / _ASC (MatchAttrLt_fn / MatchAttrGt_fn, :4552-4610) and SPH_SORT_EXTENDED whose
-// comparator state reads [INT|FLOAT attr] [WEIGHT] ROWID asc (MatchGeneric1_fn / 2_fn).  Everything else (strings, expressions and
-// other dynamic or blob locators, 64-bit attributes, weight first of two parts, three and more parts, time segments, group-by,
+// comparator state reads [INT|FLOAT attr] [WEIGHT] ROWID asc (MatchGeneric1_fn / 2_fn); and, as mrk_query.order, SPH_SORT_EXTENDED
+// states that read [INT over a 64-bit locator] [WEIGHT] ROWID asc ('ORDER BY id DESC', a bigint column) or
+// [INT|FLOAT attr] [INT|FLOAT attr] [WEIGHT] ROWID asc (MatchGeneric2_fn / 3_fn, :4723-4753).  Everything else (strings, expressions and
+// other dynamic or blob locators, the weight in front of or between attributes, three and more attributes, time segments, group-by,
 // several sorters, random) keeps the CPU ranker.  The frame replay feeds rows by rowid and the sorter re-reads the attribute through
 // the row pointer, so the replay itself does not change.  MrkEligible therefore admits:
 // one sorter, not group-by, not random, one of those orders, no cutoff next to an attribute order; no packed factors; max_matches and cutoff <= MRK_MAX_K; filters
@@ -66,6 +68,7 @@ struct MrkFlatQuery_t
 	mrk_filter				m_dFilters [ MRK_MAX_FILTERS ];
 	CSphVector<int64_t>		m_dWeightFilterValues [ MRK_MAX_FILTERS ];
 	mrk_sort				m_tSort;				///< the sorter's order when it starts with a row attribute (mrk_query.sort points here)
+	mrk_order				m_tOrder;				///< ... or with a 64-bit attribute / two attributes (mrk_query.order points here)
 	mrk_filter				m_dWeightFilters [ MRK_MAX_FILTERS ];	///< filters on @weight / a weight column (CSphQueryContext::m_pWeightFilter)
 	mrk_query				m_tQuery;
 	CSphVector<CSphString>	m_dDictWords;			///< per node (empty for operators), for tMeta.AddStat
@@ -98,8 +101,51 @@ inline bool MrkSortLocatorOk ( const CSphAttrLocator & tLoc )
 		&& ( tLoc.m_iBitOffset & 31 ) + tLoc.m_iBitCount<=32;
 }
 
-/// Which device order is this sorter?  0 = none (keep the CPU ranker), 1 = relevance, 2 = attribute first (tSort filled).
-inline int MrkSorterOrder ( const CSphQuery & tQuery, const ISphMatchSorter * pSorter, mrk_sort & tSort )
+/// a 64-bit row attribute (the document id, a bigint column): SPH_KEYPART_INT compares it as a signed SphAttr_t
+inline bool MrkSortLocator64Ok ( const CSphAttrLocator & tLoc )
+{
+	return !tLoc.m_bDynamic && !tLoc.IsBlobAttr() && tLoc.m_iBitOffset>=0 && tLoc.m_iBitCount==64 && ( tLoc.m_iBitOffset & 31 )==0;
+}
+
+/// SPH_SORT_EXTENDED states of the shapes mrk_order takes: [INT over a 64-bit locator] | [INT|FLOAT attr] [INT|FLOAT attr], then
+/// [WEIGHT], then ROWID asc (sphParseSortClause ends every clause with an ascending ROWID part).  Anything else -- three attributes,
+/// the weight in front of or between attributes, strings, expressions (dynamic locators) -- is not filled: false.
+inline bool MrkSorterWideOrder ( const CSphMatchComparatorState & tState, mrk_order & tOrder )
+{
+	memset ( &tOrder, 0, sizeof(tOrder) );
+	int i = 0;
+	for ( ; i<CSphMatchComparatorState::MAX_ATTRS && ( tState.m_eKeypart[i]==SPH_KEYPART_INT || tState.m_eKeypart[i]==SPH_KEYPART_FLOAT ); ++i )
+	{
+		if ( i>=MRK_MAX_ORDER_PARTS )
+			return false;
+		const CSphAttrLocator & tLoc = tState.m_tLocator[i];
+		mrk_order_part & tPart = tOrder.parts[i];
+		if ( tState.m_eKeypart[i]==SPH_KEYPART_INT && MrkSortLocator64Ok ( tLoc ) )
+			tPart.kind = MRK_SORTKEY_INT64;
+		else if ( MrkSortLocatorOk ( tLoc ) && ( tState.m_eKeypart[i]==SPH_KEYPART_INT || tLoc.m_iBitCount==32 ) )
+			tPart.kind = tState.m_eKeypart[i]==SPH_KEYPART_FLOAT ? MRK_SORTKEY_FLOAT : MRK_SORTKEY_INT;
+		else
+			return false;
+		tPart.bit_offset = tLoc.m_iBitOffset;
+		tPart.bit_count = tLoc.m_iBitCount;
+		tPart.desc = ( tState.m_uAttrDesc >> i ) & 1;
+	}
+	tOrder.n_parts = i;
+	if ( i<1 || i>=CSphMatchComparatorState::MAX_ATTRS )
+		return false;
+	if ( i==2 && ( tOrder.parts[0].kind==MRK_SORTKEY_INT64 || tOrder.parts[1].kind==MRK_SORTKEY_INT64 ) )
+		return false;	// a 64-bit part stands alone on the device
+	if ( tState.m_eKeypart[i]==SPH_KEYPART_WEIGHT )
+	{
+		tOrder.then_weight = ( ( tState.m_uAttrDesc >> i ) & 1 ) ? 1 : 2;
+		++i;
+	}
+	return i<CSphMatchComparatorState::MAX_ATTRS && tState.m_eKeypart[i]==SPH_KEYPART_ROWID && ( ( tState.m_uAttrDesc >> i ) & 1 )==0;
+}
+
+/// Which device order is this sorter?  0 = none (keep the CPU ranker), 1 = relevance, 2 = one attribute of <= 32 bits first (tSort
+/// filled), 3 = a 64-bit attribute or two attributes first (*pOrder filled; only asked for when pOrder is given).
+inline int MrkSorterOrder ( const CSphQuery & tQuery, const ISphMatchSorter * pSorter, mrk_sort & tSort, mrk_order * pOrder = nullptr )
 {
 	memset ( &tSort, 0, sizeof(tSort) );
 	if ( MrkSorterIsRelevance ( tQuery, pSorter ) )
@@ -108,6 +154,9 @@ inline int MrkSorterOrder ( const CSphQuery & tQuery, const ISphMatchSorter * pS
 		return 0;
 	const CSphMatchComparatorState & tState = pSorter->GetState();
 	const ESphSortKeyPart eKey = tState.m_eKeypart[0];
+	if ( pOrder && tQuery.m_eSort==SPH_SORT_EXTENDED && MrkSorterWideOrder ( tState, *pOrder )
+		&& ( pOrder->n_parts==2 || pOrder->parts[0].kind==MRK_SORTKEY_INT64 ) )
+		return 3;
 	if ( tQuery.m_eSort==SPH_SORT_ATTR_DESC || tQuery.m_eSort==SPH_SORT_ATTR_ASC )
 	{
 		// MatchAttrLt_fn / MatchAttrGt_fn compare SphAttr_t whatever the column's type (a float column by its bits), then weight desc, rowid asc
@@ -144,9 +193,10 @@ inline bool MrkEligible ( const CSphQuery & tQuery, const CSphQueryContext & tCt
 {
 	if ( dSorters.GetLength()!=1 )					{ sWhy = "several sorters"; return false; }
 	mrk_sort tSort;
-	const int iOrder = MrkSorterOrder ( tQuery, dSorters[0], tSort );
-	if ( !iOrder )									{ sWhy = "sorter order is neither (weight desc, rowid asc) nor (row attribute of <= 32 bits [, weight], rowid asc)"; return false; }
-	if ( iOrder==2 && tQuery.m_iCutoff>0 )			{ sWhy = "cutoff next to an attribute order"; return false; }
+	mrk_order tOrder;
+	const int iOrder = MrkSorterOrder ( tQuery, dSorters[0], tSort, &tOrder );
+	if ( !iOrder )									{ sWhy = "sorter order is none of (weight desc, rowid asc), (row attribute of <= 32 bits [, weight], rowid asc), (64-bit row attribute | two row attributes [, weight], rowid asc)"; return false; }
+	if ( iOrder>=2 && tQuery.m_iCutoff>0 )			{ sWhy = "cutoff next to an attribute order"; return false; }
 	if ( tCtx.m_pWeightFilter && tQuery.m_iCutoff>0 )	{ sWhy = "weight filter next to a cutoff"; return false; }	// sphinx.cpp:12223-12267
 	if ( tQuery.m_iCutoff>MRK_MAX_K )				{ sWhy = "cutoff beyond the device top-K"; return false; }	// sphinx.cpp:12261-12267; smaller ones: mrk_query::cutoff
 	if ( uPackedFactorFlags!=SPH_FACTOR_DISABLE )	{ sWhy = "packed factors"; return false; }
@@ -457,8 +507,14 @@ inline bool FlattenXQ ( const XQQuery_t & tXQ, const CSphQuery & tQuery, const C
 	q.total_docs_override = tCtx.m_iTotalDocs;
 	q.local_docs = tCtx.m_pLocalDocs ? tOut.m_dLocalDocs.Begin() : nullptr;
 	// the sorter's order (CSphMatchComparatorState: m_eKeypart, m_tLocator, m_uAttrDesc); relevance leaves q.sort NULL
-	if ( pSorter && MrkSorterOrder ( tQuery, pSorter, tOut.m_tSort )==2 )
-		q.sort = &tOut.m_tSort;
+	if ( pSorter )
+	{
+		const int iOrder = MrkSorterOrder ( tQuery, pSorter, tOut.m_tSort, &tOut.m_tOrder );
+		if ( iOrder==2 )
+			q.sort = &tOut.m_tSort;
+		else if ( iOrder==3 )
+			q.order = &tOut.m_tOrder;	// a 64-bit attribute ('ORDER BY id DESC') or two attributes first
+	}
 	q.cutoff = tQuery.m_iCutoff>0 ? tQuery.m_iCutoff : 0;	// the device hands back the best of the first m_iCutoff matches; MatchExtended's own count then runs out on the last of them
 
 	// filters: every one of them on the device, or the query stays on the CPU (EarlyReject would thin the K rows out).

@@ -56,6 +56,19 @@ class Sort(C.Structure):
     _fields_ = [("kind", C.c_int32), ("bit_offset", C.c_int32), ("bit_count", C.c_int32), ("desc", C.c_int32), ("then_weight", C.c_int32)]
 
 
+MRK_MAX_ORDER_PARTS = 2
+
+
+class OrderPart(C.Structure):
+    """mrk_order_part (include/mrk.h)"""
+    _fields_ = [("kind", C.c_int32), ("bit_offset", C.c_int32), ("bit_count", C.c_int32), ("desc", C.c_int32)]
+
+
+class Order(C.Structure):
+    """mrk_order (include/mrk.h)"""
+    _fields_ = [("n_parts", C.c_int32), ("parts", OrderPart * MRK_MAX_ORDER_PARTS), ("then_weight", C.c_int32)]
+
+
 class Query(C.Structure):
     _fields_ = [("nodes", C.POINTER(Node)), ("n_nodes", C.c_int32), ("children", C.POINTER(C.c_int32)),
                 ("root", C.c_int32), ("ranker", C.c_int32), ("max_matches", C.c_int32),
@@ -63,12 +76,13 @@ class Query(C.Structure):
                 ("plain_idf", C.c_int32), ("normalized_tfidf", C.c_int32), ("total_docs_override", C.c_int64),
                 ("local_docs", C.POINTER(C.c_int64)), ("cutoff", C.c_int32), ("filters", C.POINTER(Filter)),
                 ("n_filters", C.c_int32), ("weight_filters", C.POINTER(Filter)), ("n_weight_filters", C.c_int32),
-                ("sort", C.POINTER(Sort))]
+                ("sort", C.POINTER(Sort)), ("order", C.POINTER(Order))]
 
 
 class Result(C.Structure):
     _fields_ = [("n", C.c_int32), ("total_found", C.c_int64), ("rowid", C.POINTER(C.c_uint32)),
-                ("weight", C.POINTER(C.c_int32)), ("status", C.c_int32), ("sort_key", C.POINTER(C.c_uint32))]
+                ("weight", C.POINTER(C.c_int32)), ("status", C.c_int32), ("sort_key", C.POINTER(C.c_uint32)),
+                ("order_key", C.POINTER(C.c_uint64))]
 
 
 class BatchStats(C.Structure):

@@ -331,7 +331,7 @@ class Filter:
         return d
 
 
-SORTKEY_INT, SORTKEY_FLOAT = 0, 1
+SORTKEY_INT, SORTKEY_FLOAT, SORTKEY_INT64 = 0, 1, 2
 
 
 @dataclass
@@ -344,6 +344,24 @@ class Sort:
     desc: bool = True
     then_weight: int = 1
     kind: int = SORTKEY_INT  # SORTKEY_FLOAT: the dword compares as a float
+
+
+@dataclass
+class OrderPart:
+    """One attribute of an Order (mrk_order_part): SORTKEY_INT = 1..32 bits inside one dword, unsigned; SORTKEY_FLOAT = a 32-bit
+    float; SORTKEY_INT64 = 64 dword-aligned bits compared as a signed integer ('ORDER BY id', a bigint column) -- it stands alone."""
+    bit_offset: int
+    bit_count: int
+    desc: bool = True
+    kind: int = SORTKEY_INT
+
+
+@dataclass
+class Order:
+    """The wider form of the sorter's order (mrk_order, include/mrk.h): one or two attributes, each with its own direction, then
+    the weight as then_weight says (Sort's meaning), rowid ascending last.  One part of <= 32 bits answers exactly as the same Sort."""
+    parts: Sequence[OrderPart]
+    then_weight: int = 1
 
 
 @dataclass
@@ -362,6 +380,7 @@ class Query:
     filters: Optional[Sequence["Filter"]] = None  # CSphQuery::m_dFilters, resolved to attribute locators
     weight_filters: Optional[Sequence["Filter"]] = None  # filters on the match weight (m_pWeightFilter); locator fields unused
     sort: Optional["Sort"] = None             # None = by relevance (weight desc, rowid asc)
+    order: Optional["Order"] = None           # one 64-bit attribute or two attributes first; not next to a sort
 
 
 class _CQueries:
@@ -436,6 +455,13 @@ class _CQueries:
                 cs = _lib.Sort(int(q.sort.kind), int(q.sort.bit_offset), int(q.sort.bit_count), int(bool(q.sort.desc)), int(q.sort.then_weight))
                 c.sort = C.pointer(cs)
                 self.keep.append(cs)
+            if q.order is not None:
+                co = _lib.Order()
+                co.n_parts, co.then_weight = len(q.order.parts), int(q.order.then_weight)
+                for i, p in enumerate(q.order.parts[: _lib.MRK_MAX_ORDER_PARTS]):  # (more parts: n_parts says so and the library refuses)
+                    co.parts[i] = _lib.OrderPart(int(p.kind), int(p.bit_offset), int(p.bit_count), int(bool(p.desc)))
+                c.order = C.pointer(co)
+                self.keep.append(co)
             self.keep += [cn, ch]
 
 
@@ -451,6 +477,8 @@ class Matches:
     total_found: int
     status: int = 0
     sort_key: Optional[np.ndarray] = None  # a sorted query: the primary attribute's raw value per returned row
+    # a query with an Order (uint64): an INT64 part's raw 64 bits; else the first part's raw value << 32 | the second's (or 0)
+    order_key: Optional[np.ndarray] = None
 
 
 # --------------------------------------------------------------------------- device objects
@@ -616,7 +644,8 @@ class Batch:
             rowid = np.ctypeslib.as_array(r.rowid, (max(n, 1),))[:n].copy()
             weight = np.ctypeslib.as_array(r.weight, (max(n, 1),))[:n].copy()
             sk = np.ctypeslib.as_array(r.sort_key, (max(n, 1),))[:n].copy() if r.sort_key else None
-            out.append(Matches(rowid, weight, int(r.total_found), int(r.status), sk))
+            ok = np.ctypeslib.as_array(r.order_key, (max(n, 1),))[:n].copy() if r.order_key else None
+            out.append(Matches(rowid, weight, int(r.total_found), int(r.status), sk, ok))
         return out
 
     def stats(self) -> dict:
@@ -708,5 +737,5 @@ def idf(term_docs: int, total_docs: int, plain: bool = False, normalized: bool =
 __all__ = ["open_rt_ram", "open_rt_segment", "SPH_RANK_PROXIMITY_BM25", "SPH_RANK_BM25", "SPH_RANK_NONE", "SPH_RANK_WORDCOUNT", "SPH_RANK_PROXIMITY",
            "SPH_RANK_MATCHANY", "SPH_RANK_FIELDMASK", "SPH_RANK_SPH04",
            "parse_query", "SPH_QUERY_TERM", "SPH_QUERY_AND", "SPH_QUERY_OR", "SPH_QUERY_MAYBE", "SPH_QUERY_ANDNOT", "SPH_QUERY_PHRASE", "SPH_QUERY_PROXIMITY", "SPH_QUERY_QUORUM", "SPH_QUERY_BEFORE", "SPH_QUERY_NEAR", "SPH_QUERY_NOTNEAR", "SPH_QUERY_SENTENCE", "SPH_QUERY_PARAGRAPH",
-           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "Matches", "ROW_WORDS", "SROW_WORDS", "Context",
+           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "SORTKEY_INT64", "OrderPart", "Order", "Matches", "ROW_WORDS", "SROW_WORDS", "Context",
            "Segment", "Batch", "Batcher", "prepare", "idf", "MrkError", "validate_index", "pair_stats"]

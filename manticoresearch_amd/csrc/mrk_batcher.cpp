@@ -92,6 +92,7 @@ struct mrk_batcher {
     r->res->weight = r->weight;
     r->res->status = res.status;
     r->res->sort_key = nullptr; // (the rows went to the caller's buffers: a sorted query's host reads the attribute by rowid)
+    r->res->order_key = nullptr;
     finish(r, MRK_OK, res.status != MRK_OK ? "the device path declined this query (MRK_E_UNSUPPORTED): keep the CPU ranker" : nullptr);
   }
 

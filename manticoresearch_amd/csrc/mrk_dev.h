@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include "../../include/mrk.h"
+#include "mrk_sortkey.h"
 
 namespace mrk {
 
@@ -279,6 +280,10 @@ struct DevQuery {
   uint32_t sort_cap;   // capacity of the candidate list ...
   uint32_t sort_pad;
   uint64_t sort_off;   // ... and its offset in ScanArgs::scand, in candidates
+  // mrk_query.order of more than 32 key bits (sort_on == SORT_ON_ORDER): sort_item / _shift / _bits / _flags locate the FIRST part,
+  // these the second; the candidates take the 64-bit layouts of mrk_sortkey.h and the bins ord_geom's (bin_lo / bin_shift unused)
+  uint32_t ord_item, ord_shift, ord_bits, ord_flags;
+  OrderGeom ord_geom;
 };
 
 struct DevItem {

@@ -171,9 +171,12 @@ struct mrk_batch {
   std::vector<int32_t> weight;
   std::vector<int32_t> status;
   // sorted queries of the last submit: the locator of the primary attribute (bits 0 = relevance) and the raw values of the returned rows
-  struct SortLoc { uint32_t item = 0, shift = 0, bits = 0; };
+  // (mrk_query.order: `order` = 1 one part of <= 32 bits, planned as a sort; 2 = a 64-bit key, whose second part is p1 and which
+  // leaves in no exchange row; mrk_result.order_key instead of .sort_key)
+  struct SortLoc { uint32_t item = 0, shift = 0, bits = 0, order = 0; mrk::OrderPart p1{0, 0, 0, 0}; };
   std::vector<SortLoc> sort_loc;
   std::vector<uint32_t> sort_key;
+  std::vector<uint64_t> order_key;
   bool last_sort = false;
   bool decoded = false;
   bool packed_run = false;
@@ -917,6 +920,7 @@ static int mrk_batch_create_impl(mrk_ctx* ctx, uint32_t max_queries, mrk_batch**
   b->rowid.resize(nq * KCAP);
   b->weight.resize(nq * KCAP);
   b->sort_key.resize(nq * KCAP);
+  b->order_key.resize(nq * KCAP);
   b->sort_loc.assign(nq, mrk_batch::SortLoc{});
   b->status.assign(nq, MRK_OK);
   *out = b;
@@ -990,7 +994,7 @@ static int cutoff_probe(mrk_batch* b, mrk_segment* seg, const mrk_query* queries
   std::vector<mrk_query> pq;
   std::vector<uint32_t> who;
   for (uint32_t i = 0; i < n; ++i)
-    if (queries[i].cutoff > 0 && queries[i].cutoff <= MRK_MAX_K && queries[i].n_weight_filters == 0 && !queries[i].sort) { // (the others: plan_query says why not)
+    if (queries[i].cutoff > 0 && queries[i].cutoff <= MRK_MAX_K && queries[i].n_weight_filters == 0 && !queries[i].sort && !queries[i].order) { // (the others: plan_query says why not)
       mrk_query q = queries[i];
       q.ranker = MRK_RANK_NONE;
       q.max_matches = q.cutoff;
@@ -1138,7 +1142,10 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     any_ext = any_ext || (b->h_queries.p[i].tree_flags & (mrk::TF_TERMPOS | mrk::TF_ORDER | mrk::TF_PHRASE_LEAF | mrk::TF_NOTNEAR)) != 0 || b->h_queries.p[i].n_filters != 0 || b->h_queries.p[i].n_wfilters != 0 ||
               b->h_queries.p[i].rowid_max != 0xFFFFFFFFu || b->h_queries.p[i].sort_on != 0;
     b->sort_loc[i] = mrk_batch::SortLoc{};
-    if (rc == MRK_OK && b->h_queries.p[i].sort_on) b->sort_loc[i] = mrk_batch::SortLoc{b->h_queries.p[i].sort_item, b->h_queries.p[i].sort_shift, b->h_queries.p[i].sort_bits};
+    if (rc == MRK_OK && b->h_queries.p[i].sort_on) {
+      const DevQuery& hq = b->h_queries.p[i];
+      b->sort_loc[i] = mrk_batch::SortLoc{hq.sort_item, hq.sort_shift, hq.sort_bits, queries[i].order ? hq.sort_on : 0u, mrk::OrderPart{hq.ord_item, hq.ord_shift, hq.ord_bits, hq.ord_flags}};
+    }
     b->h_list_first.p[i] = b->h_queries.p[i].item_first;
     b->h_list_n.p[i] = b->h_queries.p[i].n_items;
     b->h_kq.p[i] = b->h_queries.p[i].k ? b->h_queries.p[i].k : 1;
@@ -1284,10 +1291,11 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     bool any = false;
     // (a sorted query's NARROW row is no answer to a merge by (weight, docid): in that exchange it counts as declined -- word 2,
     // which the wide rows, whose merge compares the mapped keys, do not take for a decline)
-    for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits);
+    // (a query ordered by a 64-bit key, mrk_query.order, fits neither row format: word 1 in every exchange)
+    for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits) || b->sort_loc[i].order == mrk::SORT_ON_ORDER;
     b->any_declined = any;
     if (any || b->decl_dirty) {
-      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = b->status[i] != MRK_OK ? 1u : (b->rows_dst && b->sort_loc[i].bits) ? 2u : 0u;
+      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = (b->status[i] != MRK_OK || b->sort_loc[i].order == mrk::SORT_ON_ORDER) ? 1u : (b->rows_dst && b->sort_loc[i].bits) ? 2u : 0u;
       HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     }
     b->decl_dirty = any;
@@ -1514,8 +1522,14 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
         const mrk_segment* sg = b->last_seg;
         const mrk_batch::SortLoc& sl = b->sort_loc[i];
         for (uint32_t j = 0; j < cnt; ++j) {
-          const uint64_t at = (uint64_t)b->rowid[(size_t)i * KCAP + j] * (sg ? sg->dev.attr_stride : 0) + sl.item;
-          b->sort_key[(size_t)i * KCAP + j] = sg && at < sg->h_attrs.size() ? mrk::sort_extract(sg->h_attrs[at], sl.shift, sl.bits) : 0u;
+          const uint64_t row = (uint64_t)b->rowid[(size_t)i * KCAP + j] * (sg ? sg->dev.attr_stride : 0), at = row + sl.item;
+          const uint32_t v = sg && at < sg->h_attrs.size() ? mrk::sort_extract(sg->h_attrs[at], sl.shift, sl.bits) : 0u;
+          b->sort_key[(size_t)i * KCAP + j] = v;
+          if (sl.order) { // mrk_result.order_key: the first part's raw value | the second's (a 64-bit attribute: its high | low dword)
+            const uint64_t at1 = row + sl.p1.item;
+            const uint32_t v1 = sl.order == mrk::SORT_ON_ORDER && sg && at1 < sg->h_attrs.size() ? mrk::sort_extract(sg->h_attrs[at1], sl.p1.shift, sl.p1.bits) : 0u;
+            b->order_key[(size_t)i * KCAP + j] = ((uint64_t)v << 32) | v1;
+          }
         }
       }
     }
@@ -1526,7 +1540,8 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
   out->total_found = b->status[q] == MRK_OK ? (int64_t)b->h_total.p[q] : 0;
   out->rowid = b->rowid.data() + (size_t)q * KCAP;
   out->weight = b->weight.data() + (size_t)q * KCAP;
-  out->sort_key = b->status[q] == MRK_OK && b->sort_loc[q].bits ? b->sort_key.data() + (size_t)q * KCAP : nullptr;
+  out->sort_key = b->status[q] == MRK_OK && b->sort_loc[q].bits && !b->sort_loc[q].order ? b->sort_key.data() + (size_t)q * KCAP : nullptr;
+  out->order_key = b->status[q] == MRK_OK && b->sort_loc[q].order ? b->order_key.data() + (size_t)q * KCAP : nullptr;
   return MRK_OK;
 }
 

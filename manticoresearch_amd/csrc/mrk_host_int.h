@@ -97,6 +97,7 @@ struct mrk_segment {
     int32_t bit_offset, bit_count, is_float;
     uint32_t lo, hi; // least / largest mapped key of the DESCENDING order (mrk_sortkey.h); lo > hi: no rows
     bool has_nan;
+    uint64_t lo64 = 0, hi64 = 0; // a 64-bit column (is_float == MRK_SORTKEY_INT64, mrk_query.order): the same, of order_map_i64
   };
   // (written by plan_query through a const segment: planning runs on the context's ONE submission thread; with MRK_INLINE_HIP=1 the
   // caller must not submit sorted queries against one segment from two threads at once)

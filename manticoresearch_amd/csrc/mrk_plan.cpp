@@ -718,9 +718,80 @@ void mrk::weight_sum_range(const int32_t* weights, uint32_t nwf, int64_t& rmin, 
   rmax = std::max<int64_t>(1, any_pos ? pos : wmax);
 }
 
-int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
+// The range of a column's mapped keys in the DESCENDING order, once per (segment, locator, kind): the pruning bins' geometry
+static const mrk_segment::SortRange* column_range(const mrk_segment* seg, int32_t bit_offset, int32_t bit_count, int32_t kind) {
+  for (const mrk_segment::SortRange& r : seg->sort_ranges)
+    if (r.bit_offset == bit_offset && r.bit_count == bit_count && r.is_float == kind) return &r;
+  mrk_segment::SortRange r{bit_offset, bit_count, kind, 0xFFFFFFFFu, 0u, false};
+  const uint32_t stride = seg->dev.attr_stride, item = (uint32_t)bit_offset >> 5, shift = (uint32_t)bit_offset & 31u;
+  const uint32_t fl = SORT_DESC | (kind == MRK_SORTKEY_FLOAT ? SORT_FLOAT : 0u);
+  const uint64_t rows = seg->h_attrs.size() / stride;
+  if (kind == MRK_SORTKEY_INT64) {
+    r.lo64 = ~0ull, r.hi64 = 0;
+    for (uint64_t i = 0; i < rows; ++i) {
+      const uint64_t m = order_map_i64((int64_t)(((uint64_t)seg->h_attrs[i * stride + item + 1] << 32) | seg->h_attrs[i * stride + item]), true);
+      r.lo64 = std::min(r.lo64, m), r.hi64 = std::max(r.hi64, m);
+    }
+  } else
+    for (uint64_t i = 0; i < rows; ++i) {
+      const uint32_t v = sort_extract(seg->h_attrs[i * stride + item], shift, (uint32_t)bit_count);
+      if (kind == MRK_SORTKEY_FLOAT && sort_is_nan(v)) r.has_nan = true;
+      const uint32_t m = sort_map_key(v, fl);
+      r.lo = std::min(r.lo, m), r.hi = std::max(r.hi, m);
+    }
+  seg->sort_ranges.push_back(r);
+  return &seg->sort_ranges.back();
+}
+
+int mrk::plan_query(const mrk_segment* seg, const mrk_query& q_in, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
                     BatchPlan& plan, uint32_t rowid_max) {
   memset(&dq, 0, sizeof dq);
+  // mrk_query.order: validated before anything is read.  One part of <= 32 bits IS mrk_query.sort's order and is planned as that (the
+  // same passes, items and bins); a 64-bit key (INT64, two parts) is `ord` from here on.
+  mrk_query q = q_in;
+  mrk_sort sort_of_order;
+  const mrk_order* ord = nullptr;
+  const mrk_segment::SortRange* orange[MRK_MAX_ORDER_PARTS] = {nullptr, nullptr};
+  if (q.order) {
+    const mrk_order& O = *q.order;
+    if (q.sort) return mrk_fail(MRK_E_INVAL, "query %u: mrk_query.sort and mrk_query.order are both set", qi);
+    if (O.n_parts < 1 || O.n_parts > MRK_MAX_ORDER_PARTS) return mrk_fail(MRK_E_INVAL, "query %u: order of %d parts (1..%d)", qi, O.n_parts, MRK_MAX_ORDER_PARTS);
+    if (O.then_weight < 0 || O.then_weight > 2) return mrk_fail(MRK_E_INVAL, "query %u: order tie rule %d", qi, O.then_weight);
+    const uint64_t row_bits = seg->dev.attrs ? (uint64_t)seg->dev.attr_stride * 32 : 0;
+    for (int p = 0; p < O.n_parts; ++p) {
+      const mrk_order_part& P = O.parts[p];
+      if (P.kind != MRK_SORTKEY_INT && P.kind != MRK_SORTKEY_FLOAT && P.kind != MRK_SORTKEY_INT64) return mrk_fail(MRK_E_INVAL, "query %u: order part %d: key kind %d", qi, p, P.kind);
+      if (P.kind == MRK_SORTKEY_INT64 && O.n_parts != 1) return mrk_fail(MRK_E_INVAL, "query %u: a 64-bit order part stands alone (part %d of %d)", qi, p, O.n_parts);
+      if (P.bit_offset < 0) continue; // (a blob-stored part: declined below, once every part's shape has been checked)
+      if (P.kind == MRK_SORTKEY_INT64) {
+        if (P.bit_count != 64 || (P.bit_offset & 31) != 0) return mrk_fail(MRK_E_INVAL, "query %u: order locator %d/%d is not 64 dword-aligned bits", qi, P.bit_offset, P.bit_count);
+      } else {
+        if (P.bit_count < 1 || P.bit_count > 32 || (P.bit_offset & 31) + P.bit_count > 32)
+          return mrk_fail(MRK_E_INVAL, "query %u: order locator %d/%d is not 1..32 bits inside one dword", qi, P.bit_offset, P.bit_count);
+        if (P.kind == MRK_SORTKEY_FLOAT && P.bit_count != 32) return mrk_fail(MRK_E_INVAL, "query %u: a float order part needs a 32-bit attribute", qi);
+      }
+      if (row_bits && (uint64_t)P.bit_offset + (uint64_t)P.bit_count > row_bits)
+        return mrk_fail(MRK_E_INVAL, "query %u: order locator %d/%d outside the %u-dword row", qi, P.bit_offset, P.bit_count, seg->dev.attr_stride);
+    }
+    if (O.n_parts == 1 && O.parts[0].kind != MRK_SORTKEY_INT64) {
+      sort_of_order = mrk_sort{O.parts[0].kind, O.parts[0].bit_offset, O.parts[0].bit_count, O.parts[0].desc, O.then_weight};
+      q.sort = &sort_of_order;
+    } else {
+      for (int p = 0; p < O.n_parts; ++p)
+        if (O.parts[p].bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: order by a blob-stored or computed attribute (part %d has no row locator)", qi, p);
+      if (!seg->dev.attrs || seg->h_attrs.empty())
+        return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ordering by attributes needs the segment's attribute rows (mrk_segment_set_attrs)", qi);
+      if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ordered queries run on the packed path only", qi);
+      if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to an order (which rows count depends on the scan order)", qi);
+      for (int p = 0; p < O.n_parts; ++p) {
+        orange[p] = column_range(seg, O.parts[p].bit_offset, O.parts[p].bit_count, O.parts[p].kind);
+        if (orange[p]->has_nan) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the float column of order part %d holds a NaN (no strict weak order)", qi, p);
+      }
+      if (O.n_parts == 2) orange[0] = column_range(seg, O.parts[0].bit_offset, O.parts[0].bit_count, O.parts[0].kind); // (the second lookup may have moved the first)
+      ord = &O;
+    }
+    q.order = nullptr;
+  }
   dq.item_first = (uint32_t)plan.items.size();
   dq.out_q = qi;
   if (!q.nodes || q.n_nodes <= 0 || q.root < 0 || q.root >= q.n_nodes) return mrk_fail(MRK_E_INVAL, "query %u: bad tree", qi);
@@ -754,27 +825,12 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
       return mrk_fail(MRK_E_INVAL, "query %u: sort locator %d/%d outside the %u-dword row", qi, S.bit_offset, S.bit_count, seg->dev.attr_stride);
     if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sorted queries run on the packed path only", qi);
     if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to a sort (which rows count depends on the scan order)", qi);
-    // the column's range of mapped keys, once per (segment, locator): the pruning bins' geometry; a NaN ends the query here
-    for (const mrk_segment::SortRange& r : seg->sort_ranges)
-      if (r.bit_offset == S.bit_offset && r.bit_count == S.bit_count && r.is_float == S.kind) srange = &r;
-    if (!srange) {
-      mrk_segment::SortRange r{S.bit_offset, S.bit_count, S.kind, 0xFFFFFFFFu, 0u, false};
-      const uint32_t stride = seg->dev.attr_stride, item = (uint32_t)S.bit_offset >> 5, shift = (uint32_t)S.bit_offset & 31u;
-      const uint32_t fl = SORT_DESC | (S.kind == MRK_SORTKEY_FLOAT ? SORT_FLOAT : 0u);
-      const uint64_t rows = seg->h_attrs.size() / stride;
-      for (uint64_t i = 0; i < rows; ++i) {
-        const uint32_t v = sort_extract(seg->h_attrs[i * stride + item], shift, (uint32_t)S.bit_count);
-        if (S.kind == MRK_SORTKEY_FLOAT && sort_is_nan(v)) r.has_nan = true;
-        const uint32_t m = sort_map_key(v, fl);
-        r.lo = std::min(r.lo, m), r.hi = std::max(r.hi, m);
-      }
-      seg->sort_ranges.push_back(r);
-      srange = &seg->sort_ranges.back();
-    }
+    // the column's range of mapped keys: the pruning bins' geometry; a NaN ends the query here
+    srange = column_range(seg, S.bit_offset, S.bit_count, S.kind);
     if (srange->has_nan) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the float sort column holds a NaN (no strict weak order)", qi);
   }
   // (a sorted query reads attribute rows like a filtered one: the packed block scan's EXT instances only)
-  const bool filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || q.sort != nullptr;
+  const bool filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || q.sort != nullptr || ord != nullptr;
 
   // The specialised paths first; a shape they decline goes to the generic per-doc evaluator (mrk_keval.h) when the segment
   // has what it reads (packed doclists + hit references), else the decline stands.
@@ -1166,11 +1222,46 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
     dq.bin_lo = (int32_t)lo;
     dq.bin_shift = sh;
   }
+  if (ord) { // a 64-bit key: two dwords of the row, the compressed bins of mrk_sortkey.h
+    const mrk_order_part &A = ord->parts[0], &B = ord->parts[ord->n_parts - 1];
+    const bool i64 = A.kind == MRK_SORTKEY_INT64;
+    auto flags_of = [](const mrk_order_part& P) { return (P.kind == MRK_SORTKEY_FLOAT ? SORT_FLOAT : 0u) | (P.desc ? SORT_DESC : 0u); };
+    dq.sort_on = SORT_ON_ORDER;
+    dq.sort_tie = (uint32_t)ord->then_weight;
+    uint32_t a_lo, a_hi, b_lo, b_hi;
+    auto directed = [](uint32_t& lo, uint32_t& hi, bool desc) { // ascending: the keys are complemented
+      if (lo > hi) lo = hi = 0;
+      if (!desc) {
+        const uint32_t l = ~hi, h = ~lo;
+        lo = l, hi = h;
+      }
+    };
+    if (i64) { // high dword signed, low dword unsigned, one direction
+      dq.sort_item = ((uint32_t)A.bit_offset >> 5) + 1, dq.sort_shift = 0, dq.sort_bits = 32, dq.sort_flags = flags_of(A) | SORT_SIGNED;
+      dq.ord_item = (uint32_t)A.bit_offset >> 5, dq.ord_shift = 0, dq.ord_bits = 32, dq.ord_flags = flags_of(A);
+      uint64_t lo = orange[0]->lo64, hi = orange[0]->hi64;
+      if (lo > hi) lo = hi = 0;
+      if (!A.desc) {
+        const uint64_t l = ~hi, h = ~lo;
+        lo = l, hi = h;
+      }
+      a_lo = (uint32_t)(lo >> 32), b_lo = (uint32_t)lo, a_hi = (uint32_t)(hi >> 32), b_hi = (uint32_t)hi;
+    } else {
+      dq.sort_item = (uint32_t)A.bit_offset >> 5, dq.sort_shift = (uint32_t)A.bit_offset & 31u, dq.sort_bits = (uint32_t)A.bit_count, dq.sort_flags = flags_of(A);
+      dq.ord_item = (uint32_t)B.bit_offset >> 5, dq.ord_shift = (uint32_t)B.bit_offset & 31u, dq.ord_bits = (uint32_t)B.bit_count, dq.ord_flags = flags_of(B);
+      a_lo = orange[0]->lo, a_hi = orange[0]->hi, b_lo = orange[1]->lo, b_hi = orange[1]->hi;
+      directed(a_lo, a_hi, A.desc != 0), directed(b_lo, b_hi, B.desc != 0);
+    }
+    dq.ord_geom = order_geom(a_lo, a_hi, b_lo, b_hi, i64);
+    dq.sort_flags |= SORT_WIDE;
+    dq.bin_mode = BIN_WEIGHT;
+    dq.bin_lo = 0, dq.bin_shift = 0;
+  }
   {
     uint64_t cap = 0;
     for (int k : cover) cap += (uint64_t)T.kws[k].docs;
     cap = std::min<uint64_t>(std::max<uint64_t>(cap, 1), (uint64_t)1 << 20);
-    if (q.sort) { // 16-byte candidates in the arena of the sorted queries; the relevance selection sees an empty list
+    if (q.sort || ord) { // 16-byte candidates in the arena of the sorted queries; the relevance selection sees an empty list
       dq.cand_cap = 0;
       dq.cand_off = plan.cand_total;
       dq.sort_cap = (uint32_t)cap;

@@ -70,6 +70,9 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   // a sorted query (uniform per logical query): its 16-byte candidates go to their own arena, binned by the mapped attribute key
   bool sorted = false;
   uint32_t so_item = 0, so_shift = 0, so_bits = 32, so_flags = 0, so_tie = 0;
+  bool wide_ord = false; // mrk_query.order's 64-bit key (see scan_pk_kernel)
+  OrderPart op1{0u, 0u, 32u, 0u};
+  OrderGeom og{0u, 0u, 0u, 0u};
   uint64_t* scand = nullptr;
   uint32_t *ghist = nullptr, *gcount = nullptr, *gtaubin = nullptr;
 
@@ -95,7 +98,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
         if constexpr (SORT) {
           if (sorted) {
             if (fits) *reinterpret_cast<ulonglong2*>(scand + 2 * (uint64_t)(basep + i)) = make_ulonglong2(key, L.cbuf2[i]);
-            atomicAdd(&s.hist[sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))], 1u);
+            atomicAdd(&s.hist[wide_ord ? order_bin(og, key) : sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))], 1u);
             continue;
           }
         }
@@ -240,6 +243,11 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
           sorted = son_ != 0;
           so_item = si_, so_shift = ss_, so_bits = sb_, so_flags = sf_, so_tie = st_;
           if (sorted) cand_cap = sc_, scand = a.scand + 2 * so_;
+          wide_ord = son_ == SORT_ON_ORDER;
+          if (wide_ord) { // (uniform; rare: the second part and the bins' geometry are read only here)
+            op1 = OrderPart{U(Q->ord_item), U(Q->ord_shift), U(Q->ord_bits), U(Q->ord_flags)};
+            og = OrderGeom{U(Q->ord_geom.a_lo), U(Q->ord_geom.b_lo), U(Q->ord_geom.nb), U(Q->ord_geom.shift)};
+          }
         }
         ghist = a.q_hist + (uint64_t)oq * NBINS;
         gcount = a.q_cand_n + (size_t)oq * QSTRIDE;
@@ -364,7 +372,11 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
     if (is_live) {
       ++total;
       const uint32_t grow = a.seg.rowid_base + rowid;
-      if (SORT && sorted) { // the order starts with the row's attribute; the weight, final here, only breaks ties
+      if (SORT && wide_ord) {
+        key = order_row_key(a.seg.attrs + (uint64_t)rowid * a.seg.attr_stride, OrderPart{so_item, so_shift, so_bits, so_flags}, op1);
+        key2 = order_lo(so_tie, (int32_t)weight, grow);
+        push = order_bin(og, key) >= tau_bin;
+      } else if (SORT && sorted) { // the order starts with the row's attribute; the weight, final here, only breaks ties
         const uint32_t mk = sort_map_key(sort_extract(a.seg.attrs[(uint64_t)rowid * a.seg.attr_stride + so_item], so_shift, so_bits), so_flags);
         key = ((uint64_t)mk << 32) | sort_weight_part(so_tie, (int32_t)weight);
         key2 = ((uint64_t)(~grow) << 32) | weight;

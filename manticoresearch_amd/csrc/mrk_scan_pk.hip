@@ -149,6 +149,10 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   const bool sorted = SORT && Q->sort_on != 0;
   const uint32_t so_item = SORT ? Q->sort_item : 0u, so_shift = SORT ? Q->sort_shift : 0u, so_bits = SORT ? Q->sort_bits : 32u,
                  so_flags = SORT ? Q->sort_flags : 0u, so_tie = SORT ? Q->sort_tie : 0u;
+  // (uniform) the order is mrk_query.order's 64-bit key: two dwords of the row, the 64-bit candidate layouts and bins of mrk_sortkey.h
+  const bool wide_ord = SORT && (so_flags & SORT_WIDE) != 0;
+  // (the second part and the bins' geometry are read from the descriptor where they are used: scalar loads on a rare branch)
+  auto ord_key = [&](uint32_t row) { return order_row_key(a.seg.attrs + (uint64_t)row * a.seg.attr_stride, OrderPart{so_item, so_shift, so_bits, so_flags}, OrderPart{Q->ord_item, Q->ord_shift, Q->ord_bits, Q->ord_flags}); };
   uint64_t* __restrict__ scand = sorted ? a.scand + 2 * Q->sort_off : nullptr;
   const uint32_t cand_cap = sorted ? Q->sort_cap : Q->cand_cap;
   uint64_t* __restrict__ cand = a.cand + Q->cand_off;
@@ -207,7 +211,7 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
         if constexpr (SORT) {
           if (sorted) {
             if (fits) *reinterpret_cast<ulonglong2*>(scand + 2 * (uint64_t)(basep + i)) = make_ulonglong2(key, L.cbuf2[i]);
-            atomicAdd(&L.hist[sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))], 1u);
+            atomicAdd(&L.hist[wide_ord ? order_bin(Q->ord_geom, key) : sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))], 1u);
             continue;
           }
         }
@@ -262,7 +266,12 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
       ++total;
       const uint32_t grow = rowid_base + rowid;
       uint32_t bin;
-      if (SORT && sorted) { // the sorter reads the row's attribute (the order's first part); the weight only breaks ties
+      if (SORT && wide_ord) { // two dwords of the row make the key; the weight and the rowid share the low word
+        key = ord_key(rowid);
+        bin = order_bin(Q->ord_geom, key);
+        key2 = order_lo(so_tie, (int32_t)weight, grow);
+        push = bin >= tau_bin;
+      } else if (SORT && sorted) { // the sorter reads the row's attribute (the order's first part); the weight only breaks ties
         const uint32_t mk = sort_map_key(sort_extract(a.seg.attrs[(uint64_t)rowid * a.seg.attr_stride + so_item], so_shift, so_bits), so_flags);
         bin = sort_bin((uint32_t)bin_lo, bin_shift, mk);
         key = ((uint64_t)mk << 32) | sort_weight_part(so_tie, (int32_t)weight);
@@ -896,8 +905,9 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
             for (int r = 0; r < 2; ++r) {
               uint32_t bin = 0;
               if (live[r])
-                bin = sort_bin((uint32_t)bin_lo, bin_shift,
-                               sort_map_key(sort_extract(a.seg.attrs[(uint64_t)row[r] * a.seg.attr_stride + so_item], so_shift, so_bits), so_flags));
+                bin = wide_ord ? order_bin(Q->ord_geom, ord_key(row[r]))
+                               : sort_bin((uint32_t)bin_lo, bin_shift,
+                                          sort_map_key(sort_extract(a.seg.attrs[(uint64_t)row[r] * a.seg.attr_stride + so_item], so_shift, so_bits), so_flags));
               const bool keep = live[r] && bin >= tau_pre;
               if (live[r] && !keep) ++total; // a match all the same: it just cannot reach the top K
               if (keep) atomicAdd(shist + bin, 1u); // (attribute bins scatter: a lane-wise add beats one atomic per distinct bin)

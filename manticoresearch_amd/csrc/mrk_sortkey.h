@@ -60,5 +60,78 @@ MRK_HD inline uint32_t sort_weight_part(uint32_t tie, int32_t weight) {
   return tie == 1u ? w : tie == 2u ? ~w : 0u;
 }
 
+// ---------------------------------------------------------------------------------------
+// The wider order (mrk_query.order): ONE signed 64-bit attribute, or TWO attributes of <= 32 bits.  Both are two dwords to the
+// device: a 64-bit attribute is its high dword compared as a signed integer, then its low dword as an unsigned one, both in the
+// attribute's direction.  The mapped key is 64 bits, larger = better: map32(first) << 32 | map32(second).
+//   hi = the 64-bit mapped key
+//   lo = weight as the tie rule orders it << 32 | ~global rowid      then_weight 1 / 2 (the true weight comes back out of the part)
+//   lo = ~global rowid << 32 | the true weight                       then_weight 0
+// ---------------------------------------------------------------------------------------
+constexpr uint32_t SORT_SIGNED = 4;                // a part's flags: the dword is a signed integer (the high dword of an int64)
+constexpr uint32_t SORT_WIDE = 8;                  // DevQuery::sort_flags of a query with sort_on == SORT_ON_ORDER (the kernels test this bit of a word they hold anyway)
+constexpr uint32_t SORT_ON_ATTR = 1, SORT_ON_ORDER = 2; // DevQuery::sort_on
+
+MRK_HD inline uint32_t order_map_part(uint32_t v, uint32_t flags) { return sort_map_key((flags & SORT_SIGNED) ? v ^ 0x80000000u : v, flags); }
+// the part's raw value (a float's -0.0 reads +0.0)
+MRK_HD inline uint32_t order_unmap_part(uint32_t mapped, uint32_t flags) {
+  const uint32_t v = sort_unmap_key(((flags & SORT_FLOAT) ? SPEC_FLOAT : 0u) | ((flags & SORT_DESC) ? SPEC_DESC : 0u), mapped);
+  return (flags & SORT_SIGNED) ? v ^ 0x80000000u : v;
+}
+MRK_HD inline uint64_t order_key(uint32_t a, uint32_t b) { return ((uint64_t)a << 32) | b; }
+// where a part lives in the row and how it compares: dword, bit offset inside it, width, SORT_FLOAT | SORT_DESC | SORT_SIGNED
+struct OrderPart {
+  uint32_t item, shift, bits, flags;
+};
+// the 64-bit mapped key of an attribute row
+MRK_HD inline uint64_t order_row_key(const uint32_t* row, const OrderPart& p0, const OrderPart& p1) {
+  return order_key(order_map_part(sort_extract(row[p0.item], p0.shift, p0.bits), p0.flags), order_map_part(sort_extract(row[p1.item], p1.shift, p1.bits), p1.flags));
+}
+// a signed 64-bit attribute as one mapped key, and back (== order_key over its dwords: high SORT_SIGNED, low plain)
+MRK_HD inline uint64_t order_map_i64(int64_t v, bool desc) {
+  const uint64_t m = (uint64_t)v ^ 0x8000000000000000ull;
+  return desc ? m : ~m;
+}
+MRK_HD inline int64_t order_unmap_i64(uint64_t mapped, bool desc) { return (int64_t)((desc ? mapped : ~mapped) ^ 0x8000000000000000ull); }
+
+MRK_HD inline uint32_t order_unweight_part(uint32_t tie, uint32_t part) { return (tie == 2u ? ~part : part) ^ 0x80000000u; }
+MRK_HD inline uint64_t order_lo(uint32_t tie, int32_t weight, uint32_t grow) {
+  return tie ? ((uint64_t)sort_weight_part(tie, weight) << 32) | (uint32_t)~grow : ((uint64_t)(uint32_t)~grow << 32) | (uint32_t)weight;
+}
+MRK_HD inline int32_t order_lo_weight(uint32_t tie, uint64_t lo) { return (int32_t)(tie ? order_unweight_part(tie, (uint32_t)(lo >> 32)) : (uint32_t)lo); }
+MRK_HD inline uint32_t order_lo_rowid(uint32_t tie, uint64_t lo) { return ~(tie ? (uint32_t)lo : (uint32_t)(lo >> 32)); }
+
+// Pruning bin of a 64-bit mapped key.  Uniform bins over the raw 64 bits would put every row of one first value into one bin (the
+// second part's 2^32 span per first value dwarfs its real range), so the key is compressed first: with the parts' least mapped keys
+// a_lo / b_lo in the column and nb = the bits of the second part's range,
+//   c = (a - a_lo) << nb  +  (b - b_lo)        bin = c >> shift, clamped to 1023
+// monotone non-decreasing in the key as long as b stays inside its range.  A 64-bit attribute takes nb = 32 and a_lo : b_lo = the
+// least key of the column: the sum, in wrapping 64-bit arithmetic, is then exactly key - least key.  Keys below the range (no row of
+// the column the planner saw holds one) land in bin 0.
+struct OrderGeom {
+  uint32_t a_lo, b_lo, nb, shift;
+};
+MRK_HD inline uint32_t order_bin(const OrderGeom& g, uint64_t key) {
+  const uint32_t a = (uint32_t)(key >> 32), b = (uint32_t)key;
+  if (a < g.a_lo || (a == g.a_lo && b < g.b_lo)) return 0u;
+  const uint64_t c = (((uint64_t)(a - g.a_lo) << g.nb) + (uint64_t)b - (uint64_t)g.b_lo) >> g.shift;
+  return c < 1023u ? (uint32_t)c : 1023u;
+}
+// the geometry from the parts' ranges of mapped keys (in the query's directions); a 64-bit attribute: a = high, b = low dwords of
+// its least / largest key and i64 = true
+MRK_HD inline OrderGeom order_geom(uint32_t a_lo, uint32_t a_hi, uint32_t b_lo, uint32_t b_hi, bool i64) {
+  OrderGeom g{a_lo, b_lo, 32u, 0u};
+  uint64_t top; // the largest compressed key
+  if (i64)
+    top = order_key(a_hi, b_hi) - order_key(a_lo, b_lo);
+  else {
+    g.nb = 0;
+    while (g.nb < 32u && ((uint64_t)(b_hi - b_lo) >> g.nb) != 0u) ++g.nb;
+    top = ((uint64_t)(a_hi - a_lo) << g.nb) + (b_hi - b_lo);
+  }
+  while (g.shift < 63u && (top >> g.shift) >= 1024u) ++g.shift;
+  return g;
+}
+
 #undef MRK_HD
 } // namespace mrk

@@ -71,6 +71,10 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
   uint32_t n = a.q_cand_n[(size_t)q * QSTRIDE];
   if (n > Q->sort_cap) n = Q->sort_cap;
   const uint32_t lo = (uint32_t)Q->bin_lo, shift = Q->bin_shift;
+  // (uniform) mrk_query.order's 64-bit key: the bin of the whole high word, weight and rowid out of the low word by the tie layout
+  const bool wide_ord = Q->sort_on == SORT_ON_ORDER;
+  const OrderGeom og = Q->ord_geom;
+  const uint32_t tie = Q->sort_tie;
   const ulonglong2* __restrict__ src = reinterpret_cast<const ulonglong2*>(a.scand) + Q->sort_off;
   if (tid < 64) {
     const uint32_t tb = threshold_bin(a.q_hist + (uint64_t)q * NBINS, K);
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
     ulonglong2 c = make_ulonglong2(0, 0);
     if (f < n) {
       c = src[f];
-      push = sort_bin(lo, shift, (uint32_t)(c.x >> 32)) >= tau_bin && (!have_tau || sortkey_gt(c.x, c.y, th, tl));
+      push = (wide_ord ? order_bin(og, c.x) : sort_bin(lo, shift, (uint32_t)(c.x >> 32))) >= tau_bin && (!have_tau || sortkey_gt(c.x, c.y, th, tl));
     }
     const uint64_t bal = __ballot(push);
     if (bal) {
@@ -105,12 +109,13 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
   // the rows leave in the relevance format: make_key(true weight, global rowid)
   for (uint32_t i = tid; i < m; i += WG) {
     const uint64_t l = s.lo[i];
-    const uint64_t key = make_key((int32_t)(uint32_t)l, ~(uint32_t)(l >> 32));
+    const uint64_t key = wide_ord ? make_key(order_lo_weight(tie, l), order_lo_rowid(tie, l)) : make_key((int32_t)(uint32_t)l, ~(uint32_t)(l >> 32));
     a.out_keys[(uint64_t)q * KCAP + i] = key;
     if (a.h_keys) a.h_keys[(uint64_t)q * KCAP + i] = key;
     a.out_mkeys[(uint64_t)q * KCAP + i] = (uint32_t)(s.hi[i] >> 32); // the mapped key travels with the row (wide exchange rows)
   }
-  if constexpr (WIDE) { // sel_sort_kernel's rule: a query whose candidate list overflowed leaves empty with MRK_ROW_RERUN
+  // (a 64-bit key does not fit a wide row: pack_srows_kernel marks that query's row MRK_ROW_DECLINED)
+  if (WIDE && !wide_ord) { // sel_sort_kernel's rule: a query whose candidate list overflowed leaves empty with MRK_ROW_RERUN
     const bool bad = (a.q_flags[q] & (QF_OVERFLOW | QF_FSM)) != 0;
     const uint32_t nr = bad ? 0u : m;
     uint64_t* __restrict__ row = a.srows_dst + (uint64_t)q * SROW_WORDS;

@@ -2,7 +2,9 @@
 """tools/sort_time.py [--docs D] [--queries N] [--reps R] [--out FILE] -- what ordering by an attribute costs next to the relevance
 order: the bench corpus, N 2-way ANDs of common keywords per launch, every leg on the block-scan kernel's EXT instances (the
 relevance legs are forced there by a pass-all RANGE filter).  Legs: BM25 by relevance; BM25 ORDER BY ts DESC; PROXIMITY_BM25 by
-relevance with prox_prune = 0; PROXIMITY_BM25 ORDER BY ts DESC.  Per leg: warm-up launches, then R launches timed one by one
+relevance with prox_prune = 0; PROXIMITY_BM25 ORDER BY ts DESC; and, where the checkout has Query.order, BM25 ORDER BY cat DESC, ts DESC
+(a 4-valued category first) and BM25 ORDER BY big DESC (a signed 64-bit column), on rows of their own set behind the other legs, which
+keep the one-dword rows they always ran on.  Per leg: warm-up launches, then R launches timed one by one
 (submit -> wait, wall clock) -> median, min, max in ms, plus the scan's HIP-event time and n_cands / total_found.  Run on a checkout
 without Query.sort it times the relevance legs only (the figures of the commit before)."""
 import argparse
@@ -42,12 +44,14 @@ has_sort = hasattr(m, "Sort")
 pass_all = [m.Filter(0, 32, min=0, max=0xFFFFFFFF)]
 
 
-def leg(name, ranker, sort):
+def leg(name, ranker, sort, order=None):
     qs = []
     for i in range(N):
         a, b = common[i]
         q = m.Query(m.XQNode.AND(kw(a, 1), kw(b, 2)), ranker=ranker, max_matches=1000)
-        if sort:
+        if order is not None:
+            q.order = order
+        elif sort:
             q.sort = m.Sort(0, 32, desc=True, then_weight=1)
         else:
             q.filters = pass_all
@@ -83,6 +87,16 @@ ctx.set("prox_prune", 0)
 result["legs"]["proximity_bm25 relevance"] = leg("PROXIMITY_BM25 by relevance, prox_prune = 0", m.SPH_RANK_PROXIMITY_BM25, False)
 if has_sort:
     result["legs"]["proximity_bm25 order by ts desc"] = leg("PROXIMITY_BM25 ORDER BY ts DESC", m.SPH_RANK_PROXIMITY_BM25, True)
+if hasattr(m, "Order"):  # rows: ts | a 4-valued category | a bigint of both signs (low, high dword)
+    wide = np.zeros((args.docs, 4), np.uint32)
+    wide[:, 0] = rows[:, 0]
+    wide[:, 1] = rng.integers(0, 4, args.docs).astype(np.uint32)
+    wide[:, 2:4] = rng.integers(-(1 << 40), 1 << 40, args.docs).astype(np.int64).view(np.uint32).reshape(args.docs, 2)
+    seg.set_attrs(wide)
+    result["legs"]["bm25 order by cat desc, ts desc"] = leg("BM25 ORDER BY cat DESC, ts DESC", m.SPH_RANK_BM25, True,
+                                                            m.Order([m.OrderPart(32, 2, desc=True), m.OrderPart(0, 32, desc=True)], then_weight=1))
+    result["legs"]["bm25 order by big desc"] = leg("BM25 ORDER BY big DESC", m.SPH_RANK_BM25, True,
+                                                   m.Order([m.OrderPart(64, 64, desc=True, kind=m.SORTKEY_INT64)], then_weight=1))
 if args.out:
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
