@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <optional>
 
 using namespace mrk;
 
@@ -718,10 +719,13 @@ void mrk::weight_sum_range(const int32_t* weights, uint32_t nwf, int64_t& rmin, 
   rmax = std::max<int64_t>(1, any_pos ? pos : wmax);
 }
 
-// The range of a column's mapped keys in the DESCENDING order, once per (segment, locator, kind): the pruning bins' geometry
-static const mrk_segment::SortRange* column_range(const mrk_segment* seg, int32_t bit_offset, int32_t bit_count, int32_t kind) {
-  for (const mrk_segment::SortRange& r : seg->sort_ranges)
-    if (r.bit_offset == bit_offset && r.bit_count == bit_count && r.is_float == kind) return &r;
+// The range of a column's mapped keys in the DESCENDING order, once per (segment, locator, kind): the pruning bins' geometry.
+// Answers the entry's place in seg->sort_ranges (a later call may move the entries: take pointers once every column was looked up)
+static size_t column_range(const mrk_segment* seg, int32_t bit_offset, int32_t bit_count, int32_t kind) {
+  for (size_t i = 0; i < seg->sort_ranges.size(); ++i) {
+    const mrk_segment::SortRange& r = seg->sort_ranges[i];
+    if (r.bit_offset == bit_offset && r.bit_count == bit_count && r.is_float == kind) return i;
+  }
   mrk_segment::SortRange r{bit_offset, bit_count, kind, 0xFFFFFFFFu, 0u, false};
   const uint32_t stride = seg->dev.attr_stride, item = (uint32_t)bit_offset >> 5, shift = (uint32_t)bit_offset & 31u;
   const uint32_t fl = SORT_DESC | (kind == MRK_SORTKEY_FLOAT ? SORT_FLOAT : 0u);
@@ -740,24 +744,70 @@ static const mrk_segment::SortRange* column_range(const mrk_segment* seg, int32_
       r.lo = std::min(r.lo, m), r.hi = std::max(r.hi, m);
     }
   seg->sort_ranges.push_back(r);
-  return &seg->sort_ranges.back();
+  return seg->sort_ranges.size() - 1;
 }
 
-int mrk::plan_query(const mrk_segment* seg, const mrk_query& q_in, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
-                    BatchPlan& plan, uint32_t rowid_max) {
-  memset(&dq, 0, sizeof dq);
+// ---- plan_query's stages: member functions of one PlanState per query, called top to bottom by plan_query.  A stage that can
+// decline the query answers MRK_OK or the code (message set).
+
+// The sorter's order as the stages after resolve_order / resolve_sort read it, whether it came as mrk_query.sort or mrk_query.order:
+// no part = relevance; one part of <= 32 bits = the narrow key (DevQuery::sort_on 1); a 64-bit key (one INT64 part, or two parts) = wide
+struct KeyPart {
+  int32_t kind, bit_offset, bit_count;
+  bool desc;
+  const mrk_segment::SortRange* range; // the column's mapped keys (DESCENDING order)
+  uint32_t flags() const { return (kind == MRK_SORTKEY_FLOAT ? SORT_FLOAT : 0u) | (desc ? SORT_DESC : 0u); }
+  uint32_t item() const { return (uint32_t)bit_offset >> 5; }
+};
+struct KeySpec {
+  int n_parts = 0;
+  KeyPart part[MRK_MAX_ORDER_PARTS];
+  int32_t tie = 0; // mrk_sort::then_weight
+  bool wide = false;
+};
+
+struct PlanState {
+  // what plan_query was handed
+  const mrk_segment* const seg;
+  const mrk_query& q;
+  const bool use_packed;
+  const uint32_t qi;
+  // what the stages work out, in their order
+  KeySpec order;
+  bool filtered = false; // the query reads attribute rows: the packed block scan's EXT instances only
+  PlanTree T;
+  std::optional<GenBuild> gen_build; // (built only for the shapes that go to the generic evaluator: 0.8 KB to clear)
+  int root = -1, n = 0; // the tree's root node, its keywords
+  uint32_t ranker = 0;
+  bool single_word = false, pure_and = false, prox = false;
+  IntVec words; // distinct words in GetQwords traversal order
+  bool got_dupes = false;
+  IntVec cover; // driver keywords: one pass each
+  uint32_t req = 0;
+  bool empty = false;
+  uint64_t bytes = 0, pbytes = 0;
+
+  // a key of <= 32 bits: 1..32 bits inside one dword, a float takes all 32.  `noun` / `key` name the spec in the messages
+  static int check_key_locator(uint32_t qi, const char* noun, const char* key, int32_t kind, int32_t bit_offset, int32_t bit_count) {
+    if (bit_count < 1 || bit_count > 32 || (bit_offset & 31) + bit_count > 32)
+      return mrk_fail(MRK_E_INVAL, "query %u: %s locator %d/%d is not 1..32 bits inside one dword", qi, noun, bit_offset, bit_count);
+    if (kind == MRK_SORTKEY_FLOAT && bit_count != 32) return mrk_fail(MRK_E_INVAL, "query %u: a float %s needs a 32-bit attribute", qi, key);
+    return MRK_OK;
+  }
+  static int check_key_in_row(const mrk_segment* seg, uint32_t qi, const char* noun, int32_t bit_offset, int32_t bit_count) {
+    if ((uint64_t)bit_offset + (uint64_t)bit_count > (uint64_t)seg->dev.attr_stride * 32)
+      return mrk_fail(MRK_E_INVAL, "query %u: %s locator %d/%d outside the %u-dword row", qi, noun, bit_offset, bit_count, seg->dev.attr_stride);
+    return MRK_OK;
+  }
+
   // mrk_query.order: validated before anything is read.  One part of <= 32 bits IS mrk_query.sort's order and is planned as that (the
-  // same passes, items and bins); a 64-bit key (INT64, two parts) is `ord` from here on.
-  mrk_query q = q_in;
-  mrk_sort sort_of_order;
-  const mrk_order* ord = nullptr;
-  const mrk_segment::SortRange* orange[MRK_MAX_ORDER_PARTS] = {nullptr, nullptr};
-  if (q.order) {
+  // same passes, items and bins; resolve_sort finishes it); a 64-bit key (INT64, two parts) is resolved here, its columns' ranges included.
+  int resolve_order() {
+    if (!q.order) return MRK_OK;
     const mrk_order& O = *q.order;
     if (q.sort) return mrk_fail(MRK_E_INVAL, "query %u: mrk_query.sort and mrk_query.order are both set", qi);
     if (O.n_parts < 1 || O.n_parts > MRK_MAX_ORDER_PARTS) return mrk_fail(MRK_E_INVAL, "query %u: order of %d parts (1..%d)", qi, O.n_parts, MRK_MAX_ORDER_PARTS);
     if (O.then_weight < 0 || O.then_weight > 2) return mrk_fail(MRK_E_INVAL, "query %u: order tie rule %d", qi, O.then_weight);
-    const uint64_t row_bits = seg->dev.attrs ? (uint64_t)seg->dev.attr_stride * 32 : 0;
     for (int p = 0; p < O.n_parts; ++p) {
       const mrk_order_part& P = O.parts[p];
       if (P.kind != MRK_SORTKEY_INT && P.kind != MRK_SORTKEY_FLOAT && P.kind != MRK_SORTKEY_INT64) return mrk_fail(MRK_E_INVAL, "query %u: order part %d: key kind %d", qi, p, P.kind);
@@ -765,98 +815,103 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q_in, int64_t item_
       if (P.bit_offset < 0) continue; // (a blob-stored part: declined below, once every part's shape has been checked)
       if (P.kind == MRK_SORTKEY_INT64) {
         if (P.bit_count != 64 || (P.bit_offset & 31) != 0) return mrk_fail(MRK_E_INVAL, "query %u: order locator %d/%d is not 64 dword-aligned bits", qi, P.bit_offset, P.bit_count);
-      } else {
-        if (P.bit_count < 1 || P.bit_count > 32 || (P.bit_offset & 31) + P.bit_count > 32)
-          return mrk_fail(MRK_E_INVAL, "query %u: order locator %d/%d is not 1..32 bits inside one dword", qi, P.bit_offset, P.bit_count);
-        if (P.kind == MRK_SORTKEY_FLOAT && P.bit_count != 32) return mrk_fail(MRK_E_INVAL, "query %u: a float order part needs a 32-bit attribute", qi);
-      }
-      if (row_bits && (uint64_t)P.bit_offset + (uint64_t)P.bit_count > row_bits)
-        return mrk_fail(MRK_E_INVAL, "query %u: order locator %d/%d outside the %u-dword row", qi, P.bit_offset, P.bit_count, seg->dev.attr_stride);
+      } else if (int rc = check_key_locator(qi, "order", "order part", P.kind, P.bit_offset, P.bit_count))
+        return rc;
+      if (seg->dev.attrs && seg->dev.attr_stride)
+        if (int rc = check_key_in_row(seg, qi, "order", P.bit_offset, P.bit_count)) return rc;
     }
-    if (O.n_parts == 1 && O.parts[0].kind != MRK_SORTKEY_INT64) {
-      sort_of_order = mrk_sort{O.parts[0].kind, O.parts[0].bit_offset, O.parts[0].bit_count, O.parts[0].desc, O.then_weight};
-      q.sort = &sort_of_order;
-    } else {
-      for (int p = 0; p < O.n_parts; ++p)
-        if (O.parts[p].bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: order by a blob-stored or computed attribute (part %d has no row locator)", qi, p);
-      if (!seg->dev.attrs || seg->h_attrs.empty())
-        return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ordering by attributes needs the segment's attribute rows (mrk_segment_set_attrs)", qi);
-      if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ordered queries run on the packed path only", qi);
-      if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to an order (which rows count depends on the scan order)", qi);
-      for (int p = 0; p < O.n_parts; ++p) {
-        orange[p] = column_range(seg, O.parts[p].bit_offset, O.parts[p].bit_count, O.parts[p].kind);
-        if (orange[p]->has_nan) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the float column of order part %d holds a NaN (no strict weak order)", qi, p);
-      }
-      if (O.n_parts == 2) orange[0] = column_range(seg, O.parts[0].bit_offset, O.parts[0].bit_count, O.parts[0].kind); // (the second lookup may have moved the first)
-      ord = &O;
+    order.n_parts = O.n_parts;
+    order.tie = O.then_weight;
+    for (int p = 0; p < O.n_parts; ++p) order.part[p] = KeyPart{O.parts[p].kind, O.parts[p].bit_offset, O.parts[p].bit_count, O.parts[p].desc != 0, nullptr};
+    if (O.n_parts == 1 && O.parts[0].kind != MRK_SORTKEY_INT64) return MRK_OK; // (resolve_sort checks it as the mrk_sort it is)
+    order.wide = true;
+    for (int p = 0; p < O.n_parts; ++p)
+      if (O.parts[p].bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: order by a blob-stored or computed attribute (part %d has no row locator)", qi, p);
+    if (!seg->dev.attrs || seg->h_attrs.empty())
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ordering by attributes needs the segment's attribute rows (mrk_segment_set_attrs)", qi);
+    if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ordered queries run on the packed path only", qi);
+    if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to an order (which rows count depends on the scan order)", qi);
+    size_t at[MRK_MAX_ORDER_PARTS];
+    for (int p = 0; p < O.n_parts; ++p) {
+      at[p] = column_range(seg, O.parts[p].bit_offset, O.parts[p].bit_count, O.parts[p].kind);
+      if (seg->sort_ranges[at[p]].has_nan) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the float column of order part %d holds a NaN (no strict weak order)", qi, p);
     }
-    q.order = nullptr;
+    for (int p = 0; p < O.n_parts; ++p) order.part[p].range = &seg->sort_ranges[at[p]];
+    return MRK_OK;
   }
-  dq.item_first = (uint32_t)plan.items.size();
-  dq.out_q = qi;
-  if (!q.nodes || q.n_nodes <= 0 || q.root < 0 || q.root >= q.n_nodes) return mrk_fail(MRK_E_INVAL, "query %u: bad tree", qi);
-  for (int i = 0; i < q.n_nodes; ++i) // (ExtHit_t::m_uQuerypos is a WORD, sphinxint.h:733; the arithmetic on positions below assumes as much)
-    if (q.nodes[i].op == MRK_OP_TERM && (q.nodes[i].atom_pos < 0 || q.nodes[i].atom_pos > 0xFFFF))
-      return mrk_fail(MRK_E_INVAL, "query %u: query position %d of node %d", qi, q.nodes[i].atom_pos, i);
-  if (q.max_matches <= 0 || q.max_matches > MRK_MAX_K)
-    return mrk_fail(MRK_E_UNSUPPORTED, "query %u: max_matches %d outside 1..%d", qi, q.max_matches, MRK_MAX_K);
-  // cutoff (MatchExtended, sphinx.cpp:12197-12199, 12261-12267): the sorter's Push() never says no (sphinxsort.cpp:722-759), so the
-  // scan stops after the first `cutoff` rows that got as far as the sorter -- the caller found the last of them with a probe
-  // launch (cutoff_probe, mrk_host.cpp) and hands it down as rowid_max: rows past it never reach the ranker
-  if (q.cutoff > 0 && !use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff runs on the packed path only", qi);
-  if (q.cutoff > MRK_MAX_K) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff %d (device path: <= %d)", qi, q.cutoff, MRK_MAX_K);
-  if (q.cutoff > 0 && q.n_weight_filters > 0)
-    return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to a weight filter (which rows count depends on their weights)", qi);
-  // The sorter's order (mrk_query.sort).  Checked before anything is read: a hostile locator ends here.
-  const mrk_segment::SortRange* srange = nullptr;
-  if (q.sort) {
-    const mrk_sort& S = *q.sort;
-    if (S.kind != MRK_SORTKEY_INT && S.kind != MRK_SORTKEY_FLOAT) return mrk_fail(MRK_E_INVAL, "query %u: sort key kind %d", qi, S.kind);
-    if (S.then_weight < 0 || S.then_weight > 2) return mrk_fail(MRK_E_INVAL, "query %u: sort tie rule %d", qi, S.then_weight);
-    if (S.bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sort by a blob-stored or computed attribute (no row locator)", qi);
-    if (S.bit_count == 64 && (S.bit_offset & 31) == 0 && seg->dev.attrs && (uint64_t)S.bit_offset + 64 <= (uint64_t)seg->dev.attr_stride * 32)
+
+  // The narrow key: mrk_query.sort, or the mrk_query.order that is one.  Checked before anything is read: a hostile locator ends here.
+  int resolve_sort() {
+    if (q.sort) {
+      const mrk_sort& Q = *q.sort;
+      order.n_parts = 1;
+      order.tie = Q.then_weight;
+      order.part[0] = KeyPart{Q.kind, Q.bit_offset, Q.bit_count, Q.desc != 0, nullptr};
+    } else if (order.n_parts != 1 || order.wide)
+      return MRK_OK;
+    KeyPart& P = order.part[0];
+    if (P.kind != MRK_SORTKEY_INT && P.kind != MRK_SORTKEY_FLOAT) return mrk_fail(MRK_E_INVAL, "query %u: sort key kind %d", qi, P.kind);
+    if (order.tie < 0 || order.tie > 2) return mrk_fail(MRK_E_INVAL, "query %u: sort tie rule %d", qi, order.tie);
+    if (P.bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sort by a blob-stored or computed attribute (no row locator)", qi);
+    if (P.bit_count == 64 && (P.bit_offset & 31) == 0 && seg->dev.attrs && (uint64_t)P.bit_offset + 64 <= (uint64_t)seg->dev.attr_stride * 32)
       return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sort by a 64-bit attribute (device path: <= 32 bits)", qi);
-    if (S.bit_count < 1 || S.bit_count > 32 || (S.bit_offset & 31) + S.bit_count > 32)
-      return mrk_fail(MRK_E_INVAL, "query %u: sort locator %d/%d is not 1..32 bits inside one dword", qi, S.bit_offset, S.bit_count);
-    if (S.kind == MRK_SORTKEY_FLOAT && S.bit_count != 32) return mrk_fail(MRK_E_INVAL, "query %u: a float sort key needs a 32-bit attribute", qi);
+    if (int rc = check_key_locator(qi, "sort", "sort key", P.kind, P.bit_offset, P.bit_count)) return rc;
     if (!seg->dev.attrs || seg->h_attrs.empty())
       return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sorting by an attribute needs the segment's attribute rows (mrk_segment_set_attrs)", qi);
-    if ((uint64_t)S.bit_offset + (uint64_t)S.bit_count > (uint64_t)seg->dev.attr_stride * 32)
-      return mrk_fail(MRK_E_INVAL, "query %u: sort locator %d/%d outside the %u-dword row", qi, S.bit_offset, S.bit_count, seg->dev.attr_stride);
+    if (int rc = check_key_in_row(seg, qi, "sort", P.bit_offset, P.bit_count)) return rc;
     if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: sorted queries run on the packed path only", qi);
     if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to a sort (which rows count depends on the scan order)", qi);
     // the column's range of mapped keys: the pruning bins' geometry; a NaN ends the query here
-    srange = column_range(seg, S.bit_offset, S.bit_count, S.kind);
-    if (srange->has_nan) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the float sort column holds a NaN (no strict weak order)", qi);
+    P.range = &seg->sort_ranges[column_range(seg, P.bit_offset, P.bit_count, P.kind)];
+    if (P.range->has_nan) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the float sort column holds a NaN (no strict weak order)", qi);
+    return MRK_OK;
   }
-  // (a sorted query reads attribute rows like a filtered one: the packed block scan's EXT instances only)
-  const bool filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || q.sort != nullptr || ord != nullptr;
 
-  // The specialised paths first; a shape they decline goes to the generic per-doc evaluator (mrk_keval.h) when the segment
-  // has what it reads (packed doclists + hit references), else the decline stands.
-  PlanTree T;
-  GenBuild* Gp = nullptr; // (built only for the shapes that go to the generic evaluator: 0.8 KB to clear)
-  struct GenHolder {
-    alignas(GenBuild) unsigned char raw[sizeof(GenBuild)];
-    bool live = false;
-    ~GenHolder() {
-      if (live) reinterpret_cast<GenBuild*>(raw)->~GenBuild();
+  // what plan_query checks of the query itself before the tree is walked
+  int check_query() const {
+    if (!q.nodes || q.n_nodes <= 0 || q.root < 0 || q.root >= q.n_nodes) return mrk_fail(MRK_E_INVAL, "query %u: bad tree", qi);
+    for (int i = 0; i < q.n_nodes; ++i) // (ExtHit_t::m_uQuerypos is a WORD, sphinxint.h:733; the arithmetic on positions below assumes as much)
+      if (q.nodes[i].op == MRK_OP_TERM && (q.nodes[i].atom_pos < 0 || q.nodes[i].atom_pos > 0xFFFF))
+        return mrk_fail(MRK_E_INVAL, "query %u: query position %d of node %d", qi, q.nodes[i].atom_pos, i);
+    if (q.max_matches <= 0 || q.max_matches > MRK_MAX_K)
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: max_matches %d outside 1..%d", qi, q.max_matches, MRK_MAX_K);
+    // cutoff (MatchExtended, sphinx.cpp:12197-12199, 12261-12267): the sorter's Push() never says no (sphinxsort.cpp:722-759), so the
+    // scan stops after the first `cutoff` rows that got as far as the sorter -- the caller found the last of them with a probe
+    // launch (cutoff_probe, mrk_host.cpp) and hands it down as rowid_max: rows past it never reach the ranker
+    if (q.cutoff > 0 && !use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff runs on the packed path only", qi);
+    if (q.cutoff > MRK_MAX_K) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff %d (device path: <= %d)", qi, q.cutoff, MRK_MAX_K);
+    if (q.cutoff > 0 && q.n_weight_filters > 0)
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to a weight filter (which rows count depends on their weights)", qi);
+    return MRK_OK;
+  }
+
+  // values on the tree program's register stack at its deepest
+  static int stack_depth(const PlanTree& T) {
+    int sp = 0, deep = 0;
+    for (const PlanNode& pn : T.nodes) {
+      sp += (pn.op == PN_TERM || pn.op == PN_QUORUM) ? 1 : (pn.op == PN_PHRASEFIX || pn.op == PN_ORDERFIX) ? 0 : -1;
+      deep = std::max(deep, sp);
     }
-  } gen_holder;
-  int root = -1;
-  bool single_word = false, pure_and = false, prox = false;
-  uint32_t ranker = 0;
-  int n = 0;
-  bool T_used = false;
-  auto shape = [&](bool gen) -> int {
-    if (T_used) T = PlanTree(); // (the first call finds it fresh)
-    T_used = true;
+    return deep;
+  }
+
+  // What reads hit streams runs on the packed path of a segment with hit references (`what`: "NOTNEAR runs" ...) and packs a rowid
+  // into 31 bits (`path`: the kernel family the message names)
+  int needs_hit_refs(const char* what) const {
+    if (!use_packed || !seg->dev.pk_hit) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %s on the packed path only", qi, what);
+    return MRK_OK;
+  }
+  int needs_rowids_31(const char* path) const {
+    if (seg->total_docs >= (1ull << 31)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %s path needs < 2^31 docs per segment", qi, path);
+    return MRK_OK;
+  }
+
+  // The evaluation tree, what it needs of the segment, the ranker: for the specialised paths (gen = false) or the generic evaluator
+  int shape(bool gen) {
+    if (gen) T = PlanTree(); // (the generic evaluator's turn comes second: the specialised paths found it fresh)
     int tree_err = MRK_OK;
     if (gen) {
-      if (gen_holder.live) reinterpret_cast<GenBuild*>(gen_holder.raw)->~GenBuild();
-      Gp = new (gen_holder.raw) GenBuild();
-      gen_holder.live = true;
-      GenBuild& G = *Gp;
+      GenBuild& G = gen_build.emplace();
       root = build_gen(seg, q, q.root, T, G, qi, 0, tree_err);
       if (root >= 0 && G.overflow) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: tree too large for the device path", qi);
       if (root >= 0) {
@@ -877,14 +932,8 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q_in, int64_t item_
     if (pure_and && (q.nodes[q.root].op == MRK_OP_AND || q.nodes[q.root].op == MRK_OP_PHRASE || q.nodes[q.root].op == MRK_OP_PROXIMITY || q.nodes[q.root].op == MRK_OP_NEAR))
       for (int i = 0; i < q.nodes[q.root].n_children; ++i) pure_and &= q.nodes[q.children[q.nodes[q.root].first_child + i]].op == MRK_OP_TERM;
     if (!pure_and && !use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: boolean trees run on the packed path only", qi);
-    if (!pure_and) { // the device evaluates the program on a TREE_STACK-deep register stack
-      int sp = 0, deep = 0;
-      for (const PlanNode& pn : T.nodes) {
-        sp += (pn.op == PN_TERM || pn.op == PN_QUORUM) ? 1 : (pn.op == PN_PHRASEFIX || pn.op == PN_ORDERFIX) ? 0 : -1;
-        deep = std::max(deep, sp);
-      }
-      if (deep > TREE_STACK) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: tree nests deeper than the device path evaluates", qi);
-    }
+    // the device evaluates the program on a TREE_STACK-deep register stack
+    if (!pure_and && stack_depth(T) > TREE_STACK) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: tree nests deeper than the device path evaluates", qi);
 
     prox = false; // a state ranker reads the hit streams
     if (gen && T.gen_nearn) {
@@ -901,64 +950,59 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q_in, int64_t item_
     if (T.ph_leaf && n > MAX_PROX_TERMS)
       return mrk_fail(MRK_E_UNSUPPORTED, "query %u: PHRASE in a tree of %d keywords (device path: <= %d)", qi, n, MAX_PROX_TERMS);
     if (T.notnear) { // decided over the two keywords' hits: the hit-reading kernel, <= 4 hit streams
-      if (!use_packed || !seg->dev.pk_hit) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: NOTNEAR runs on the packed path only", qi);
+      if (int rc = needs_hit_refs("NOTNEAR runs")) return rc;
       if (n > MAX_PROX_TERMS) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: NOTNEAR in a query of %d keywords (device path: <= %d)", qi, n, MAX_PROX_TERMS);
       if (T.termpos || T.quorum) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: NOTNEAR next to position modifiers / a quorum node", qi);
-      if (seg->total_docs >= (1ull << 31)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: hit path needs < 2^31 docs per segment", qi);
+      if (int rc = needs_rowids_31("hit")) return rc;
     }
     if (T.termpos) { // whether a keyword holds a doc is decided over its hits: the hit-reading kernel, <= 4 hit streams
-      if (!use_packed || !seg->dev.pk_hit) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: position modifiers run on the packed path only", qi);
+      if (int rc = needs_hit_refs("position modifiers run")) return rc;
       if (n > MAX_PROX_TERMS) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: position modifiers in a query of %d keywords (device path: <= %d)", qi, n, MAX_PROX_TERMS);
-      if (seg->total_docs >= (1ull << 31)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: hit path needs < 2^31 docs per segment", qi);
+      if (int rc = needs_rowids_31("hit")) return rc;
       for (const PlanKw& k : T.kws)
         if (k.tp_kind < 0 || k.tp_kind > MRK_TERMPOS_LIMIT || (k.tp_kind == MRK_TERMPOS_LIMIT && k.tp_max <= 0))
           return mrk_fail(MRK_E_INVAL, "query %u: bad position modifier", qi);
     }
     if (T.phrase || T.ph_leaf) {
-      if (!use_packed || !seg->dev.pk_hit) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: PHRASE runs on the packed path only", qi);
-      if (seg->total_docs >= (1ull << 31)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: hit path needs < 2^31 docs per segment", qi);
+      if (int rc = needs_hit_refs("PHRASE runs")) return rc;
+      if (int rc = needs_rowids_31("hit")) return rc;
     }
+    const bool weight_sum = (q.ranker == MRK_RANK_PROXIMITY_BM25 || q.ranker == MRK_RANK_PROXIMITY) && single_word;
     switch (q.ranker) {
-      case MRK_RANK_NONE: ranker = MRK_RANK_NONE; break;
-      case MRK_RANK_BM25: ranker = MRK_RANK_BM25; break;
+      case MRK_RANK_NONE:
+      case MRK_RANK_BM25: ranker = (uint32_t)q.ranker; break;
       case MRK_RANK_PROXIMITY_BM25:
       case MRK_RANK_PROXIMITY:
-        // a single keyword is ranked by ExtRanker_WeightSum_c (sphinxsearch.cpp:4195-4196, 4216-4217)
-        if (single_word) {
-          ranker = q.ranker == MRK_RANK_PROXIMITY_BM25 ? MRK_RANK_BM25 : MRK_RANK_PROXIMITY;
-          if (ranker == MRK_RANK_PROXIMITY && !use_packed)
-            return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ranker=proximity runs on the packed path only", qi);
-        } else {
-          if (!use_packed || !seg->dev.pk_hit)
-            return mrk_fail(MRK_E_UNSUPPORTED, "query %u: proximity rankers run on the packed path only", qi);
-          if (n > MAX_PROX_TERMS && !gen)
-            return mrk_fail(MRK_E_UNSUPPORTED, "query %u: proximity over %d keywords (device path: <= %d)", qi, n, MAX_PROX_TERMS);
-          if (seg->total_docs >= (1ull << 31)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: proximity path needs < 2^31 docs per segment", qi);
-          if (T.multiand3_inner && !gen) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: 3-keyword AND below another operator with a hit ranker", qi);
-          ranker = (uint32_t)q.ranker;
-          prox = true;
-        }
-        break;
       case MRK_RANK_WORDCOUNT:
       case MRK_RANK_MATCHANY:
       case MRK_RANK_FIELDMASK:
-      case MRK_RANK_SPH04:
-        // always ExtRanker_State_T over the hit stream, single keyword or not (sphinxsearch.cpp:4214-4236)
-        if (!use_packed || !seg->dev.pk_hit)
-          return mrk_fail(MRK_E_UNSUPPORTED, "query %u: hit rankers run on the packed path only", qi);
+      case MRK_RANK_SPH04: {
+        // a single keyword under a proximity ranker is ranked by ExtRanker_WeightSum_c (sphinxsearch.cpp:4195-4196, 4216-4217)
+        if (weight_sum) {
+          ranker = q.ranker == MRK_RANK_PROXIMITY_BM25 ? MRK_RANK_BM25 : MRK_RANK_PROXIMITY;
+          if (ranker == MRK_RANK_PROXIMITY && !use_packed)
+            return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ranker=proximity runs on the packed path only", qi);
+          break;
+        }
+        // the others are always ExtRanker_State_T over the hit stream, single keyword or not (sphinxsearch.cpp:4214-4236)
+        const bool proximity = q.ranker == MRK_RANK_PROXIMITY_BM25 || q.ranker == MRK_RANK_PROXIMITY;
+        if (int rc = needs_hit_refs(proximity ? "proximity rankers run" : "hit rankers run")) return rc;
         if (n > MAX_PROX_TERMS && !gen)
-          return mrk_fail(MRK_E_UNSUPPORTED, "query %u: hit ranker over %d keywords (device path: <= %d)", qi, n, MAX_PROX_TERMS);
-        if (seg->total_docs >= (1ull << 31)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: hit path needs < 2^31 docs per segment", qi);
+          return mrk_fail(MRK_E_UNSUPPORTED, proximity ? "query %u: proximity over %d keywords (device path: <= %d)" : "query %u: hit ranker over %d keywords (device path: <= %d)", qi, n, MAX_PROX_TERMS);
+        if (int rc = needs_rowids_31(proximity ? "proximity" : "hit")) return rc;
         if (T.multiand3_inner && !gen) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: 3-keyword AND below another operator with a hit ranker", qi);
         ranker = (uint32_t)q.ranker;
         prox = true;
         break;
+      }
       default: return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ranker %d not on the device path", qi, q.ranker);
     }
-
     return MRK_OK;
-  };
-  {
+  }
+
+  // The specialised paths first; a shape they decline goes to the generic per-doc evaluator (mrk_keval.h) when the segment
+  // has what it reads (packed doclists + hit references), else the decline stands.
+  int shape_query() {
     int rc = shape(false);
     if (rc == MRK_E_UNSUPPORTED && use_packed && seg->dev.pk_hit) {
       char fast_msg[256];
@@ -970,119 +1014,75 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q_in, int64_t item_
         return mrk_fail(MRK_E_UNSUPPORTED, "%s; generic evaluator: %s", fast_msg, gen_msg);
       }
     }
-    if (rc != MRK_OK) return rc;
+    return rc;
   }
 
-  // attribute filters (EarlyReject): resolved locators over the segment's .spa rows
-  dq.n_filters = 0;
-  dq.rowid_max = rowid_max;
-  if (q.n_filters < 0 || (q.n_filters > 0 && !q.filters)) return mrk_fail(MRK_E_INVAL, "query %u: bad filter list", qi);
-  if (q.n_filters > 0) {
-    if (!seg->dev.attrs) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: filters need the segment's attribute rows (mrk_segment_set_attrs)", qi);
-    if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: filters run on the packed path only", qi);
-    if (q.n_filters > MRK_MAX_FILTERS) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %d filters (device path: <= %d)", qi, q.n_filters, MRK_MAX_FILTERS);
-    for (int i = 0; i < q.n_filters; ++i) {
-      const mrk_filter& f = q.filters[i];
-      DevFilter& d = dq.filters[i];
-      memset(&d, 0, sizeof d);
+  // One mrk_filter as the kernels read it: a row attribute, a multi-value attribute in the blob pool, or (on_weight) the match weight,
+  // whose locator fields are ignored
+  int translate_filter(const mrk_filter& f, bool on_weight, DevFilter& d) const {
+    memset(&d, 0, sizeof d);
+    if (on_weight) {
+      if (f.kind != MRK_FILTER_VALUES && f.kind != MRK_FILTER_RANGE) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: weight filter kind %d", qi, f.kind);
+    } else {
       if (f.kind != MRK_FILTER_VALUES && f.kind != MRK_FILTER_RANGE && f.kind != MRK_FILTER_FLOATRANGE)
         return mrk_fail(MRK_E_UNSUPPORTED, "query %u: filter kind %d not on the device path", qi, f.kind);
       if (f.kind == MRK_FILTER_FLOATRANGE && f.bit_count != 32) return mrk_fail(MRK_E_INVAL, "query %u: a float filter needs a 32-bit attribute", qi);
-      if (f.mva_bits) { // a multi-value attribute in the blob pool
-        if (f.mva_bits != 32 && f.mva_bits != 64) return mrk_fail(MRK_E_INVAL, "query %u: MVA width %d", qi, f.mva_bits);
-        if (f.kind == MRK_FILTER_FLOATRANGE) return mrk_fail(MRK_E_INVAL, "query %u: a float range over an MVA", qi);
-        if (!seg->dev.blobs) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: MVA filters need the segment's blob pool (mrk_segment_set_blobs)", qi);
-        if (f.n_blob_attrs < 1 || f.n_blob_attrs > 255 || f.blob_attr_id < 0 || f.blob_attr_id >= f.n_blob_attrs || (uint32_t)f.n_blob_attrs != seg->n_blob_attrs)
-          return mrk_fail(MRK_E_INVAL, "query %u: blob attribute %d of %d (the segment's rows hold %u)", qi, f.blob_attr_id, f.n_blob_attrs, seg->n_blob_attrs);
-        if (seg->dev.attr_stride < 4) return mrk_fail(MRK_E_INVAL, "query %u: rows of %u dwords hold no blob locator", qi, seg->dev.attr_stride);
-        d.kind = (uint32_t)f.kind | (f.exclude ? 1u << 8 : 0) | (f.has_equal_min ? 1u << 9 : 0) | (f.has_equal_max ? 1u << 10 : 0);
-        d.mva = (uint32_t)f.mva_bits | (f.mva_all ? 1u << 8 : 0) | ((uint32_t)f.blob_attr_id << 16) | ((uint32_t)f.n_blob_attrs << 24);
-        d.lo = f.min_value, d.hi = f.max_value;
-        if (f.kind == MRK_FILTER_VALUES) {
-          if (f.n_values < 1 || !f.values) return mrk_fail(MRK_E_INVAL, "query %u: values filter without values", qi);
-          if (f.n_values > MRK_MAX_FILTER_VALUES) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %d filter values (device path: <= %d)", qi, f.n_values, MRK_MAX_FILTER_VALUES);
-          d.n_values = (uint32_t)f.n_values;
-          for (int k = 0; k < f.n_values; ++k) d.values[k] = f.values[k];
-        }
-        continue;
-      }
+    }
+    const bool in_row = !on_weight && !f.mva_bits;
+    if (!on_weight && f.mva_bits) { // a multi-value attribute in the blob pool
+      if (f.mva_bits != 32 && f.mva_bits != 64) return mrk_fail(MRK_E_INVAL, "query %u: MVA width %d", qi, f.mva_bits);
+      if (f.kind == MRK_FILTER_FLOATRANGE) return mrk_fail(MRK_E_INVAL, "query %u: a float range over an MVA", qi);
+      if (!seg->dev.blobs) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: MVA filters need the segment's blob pool (mrk_segment_set_blobs)", qi);
+      if (f.n_blob_attrs < 1 || f.n_blob_attrs > 255 || f.blob_attr_id < 0 || f.blob_attr_id >= f.n_blob_attrs || (uint32_t)f.n_blob_attrs != seg->n_blob_attrs)
+        return mrk_fail(MRK_E_INVAL, "query %u: blob attribute %d of %d (the segment's rows hold %u)", qi, f.blob_attr_id, f.n_blob_attrs, seg->n_blob_attrs);
+      if (seg->dev.attr_stride < 4) return mrk_fail(MRK_E_INVAL, "query %u: rows of %u dwords hold no blob locator", qi, seg->dev.attr_stride);
+      d.mva = (uint32_t)f.mva_bits | (f.mva_all ? 1u << 8 : 0) | ((uint32_t)f.blob_attr_id << 16) | ((uint32_t)f.n_blob_attrs << 24);
+    } else if (in_row) {
       const bool wide = f.bit_count == 64;
       if (f.bit_offset < 0 || f.bit_count < 1 || (!wide && (f.bit_count > 32 || (f.bit_offset & 31) + f.bit_count > 32)) || (wide && (f.bit_offset & 31)) ||
-          (uint64_t)(f.bit_offset + f.bit_count) > (uint64_t)seg->dev.attr_stride * 32)
+          (uint64_t)f.bit_offset + (uint64_t)f.bit_count > (uint64_t)seg->dev.attr_stride * 32)
         return mrk_fail(MRK_E_INVAL, "query %u: filter locator %d/%d outside the %u-dword row", qi, f.bit_offset, f.bit_count, seg->dev.attr_stride);
-      d.kind = (uint32_t)f.kind | (f.exclude ? 1u << 8 : 0) | (f.has_equal_min ? 1u << 9 : 0) | (f.has_equal_max ? 1u << 10 : 0) |
-               (f.open_left ? 1u << 11 : 0) | (f.open_right ? 1u << 12 : 0);
       d.item = (uint32_t)f.bit_offset >> 5;
       d.shift = (uint32_t)f.bit_offset & 31u;
       d.bits = (uint32_t)f.bit_count;
-      d.lo = f.min_value, d.hi = f.max_value;
-      if (f.kind == MRK_FILTER_FLOATRANGE) { // the bounds travel as their bit patterns
-        uint32_t lo_bits, hi_bits;
-        memcpy(&lo_bits, &f.fmin, 4), memcpy(&hi_bits, &f.fmax, 4);
-        d.lo = lo_bits, d.hi = hi_bits;
-      }
-      if (f.kind == MRK_FILTER_VALUES) {
-        if (f.n_values < 1 || !f.values) return mrk_fail(MRK_E_INVAL, "query %u: values filter without values", qi);
-        if (f.n_values > MRK_MAX_FILTER_VALUES) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %d filter values (device path: <= %d)", qi, f.n_values, MRK_MAX_FILTER_VALUES);
-        d.n_values = (uint32_t)f.n_values;
-        for (int k = 0; k < f.n_values; ++k) d.values[k] = f.values[k];
-      }
     }
-    dq.n_filters = (uint32_t)q.n_filters;
-  }
-  // filters on the match weight (m_pWeightFilter): evaluated where a match's weight is final
-  dq.n_wfilters = 0;
-  if (q.n_weight_filters < 0 || (q.n_weight_filters > 0 && !q.weight_filters)) return mrk_fail(MRK_E_INVAL, "query %u: bad weight filter list", qi);
-  if (q.n_weight_filters > 0) {
-    if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: weight filters run on the packed path only", qi);
-    if (q.n_weight_filters > MRK_MAX_FILTERS) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %d weight filters (device path: <= %d)", qi, q.n_weight_filters, MRK_MAX_FILTERS);
-    for (int i = 0; i < q.n_weight_filters; ++i) {
-      const mrk_filter& f = q.weight_filters[i];
-      DevFilter& d = dq.wfilters[i];
-      memset(&d, 0, sizeof d);
-      if (f.kind != MRK_FILTER_VALUES && f.kind != MRK_FILTER_RANGE) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: weight filter kind %d", qi, f.kind);
-      d.kind = (uint32_t)f.kind | (f.exclude ? 1u << 8 : 0) | (f.has_equal_min ? 1u << 9 : 0) | (f.has_equal_max ? 1u << 10 : 0);
-      d.lo = f.min_value, d.hi = f.max_value;
-      if (f.kind == MRK_FILTER_VALUES) {
-        if (f.n_values < 1 || !f.values) return mrk_fail(MRK_E_INVAL, "query %u: values filter without values", qi);
-        if (f.n_values > MRK_MAX_FILTER_VALUES) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %d filter values (device path: <= %d)", qi, f.n_values, MRK_MAX_FILTER_VALUES);
-        d.n_values = (uint32_t)f.n_values;
-        for (int k = 0; k < f.n_values; ++k) d.values[k] = f.values[k];
-      }
+    d.kind = (uint32_t)f.kind | (f.exclude ? 1u << 8 : 0) | (f.has_equal_min ? 1u << 9 : 0) | (f.has_equal_max ? 1u << 10 : 0);
+    if (in_row) d.kind |= (f.open_left ? 1u << 11 : 0) | (f.open_right ? 1u << 12 : 0);
+    d.lo = f.min_value, d.hi = f.max_value;
+    if (in_row && f.kind == MRK_FILTER_FLOATRANGE) { // the bounds travel as their bit patterns
+      uint32_t lo_bits, hi_bits;
+      memcpy(&lo_bits, &f.fmin, 4), memcpy(&hi_bits, &f.fmax, 4);
+      d.lo = lo_bits, d.hi = hi_bits;
     }
-    dq.n_wfilters = (uint32_t)q.n_weight_filters;
+    if (f.kind == MRK_FILTER_VALUES) {
+      if (f.n_values < 1 || !f.values) return mrk_fail(MRK_E_INVAL, "query %u: values filter without values", qi);
+      if (f.n_values > MRK_MAX_FILTER_VALUES) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %d filter values (device path: <= %d)", qi, f.n_values, MRK_MAX_FILTER_VALUES);
+      d.n_values = (uint32_t)f.n_values;
+      for (int k = 0; k < f.n_values; ++k) d.values[k] = f.values[k];
+    }
+    return MRK_OK;
   }
 
-  // IDFs: distinct words in GetQwords traversal order (searchnode.cpp:2029-2055, 3276-3286)
-  IntVec words;
-  for (int i = 0; i < n; ++i) {
-    if (T.kws[i].hidden) { // read for its hits only
-      T.kws[i].weighted_first = false;
-      continue;
-    }
-    bool seen = false;
-    for (int w : words) seen |= T.kws[i].term_id >= 0 && T.kws[w].term_id == T.kws[i].term_id; // words missing from the dictionary are distinct words
-    T.kws[i].weighted_first = !seen;
-    if (!seen) words.push_back(i);
-  }
-  int n_visible = 0;
-  for (const PlanKw& k : T.kws) n_visible += k.hidden ? 0 : 1;
-  const bool got_dupes = (int)words.size() != n_visible; // HasQwordDupes: proximity rankers switch to their HANDLE_DUPES update
-  const int64_t total_docs = q.total_docs_override > 0 ? q.total_docs_override : (int64_t)seg->total_docs;
-  for (int w : words) {
-    PlanKw& t = T.kws[w];
-    int64_t term_docs = t.docs;
-    if (q.local_docs && q.local_docs[t.node] >= 0) term_docs = q.local_docs[t.node];
-    t.idf = mrk_idf(term_docs, total_docs, q.plain_idf, q.normalized_tfidf, (int)words.size(), t.boost);
+  // A filter list of the query: attribute filters (EarlyReject: resolved locators over the segment's .spa rows), or filters on the
+  // match weight (m_pWeightFilter: evaluated where a match's weight is final)
+  int translate_filters(const char* noun, const mrk_filter* list, int32_t count, bool on_weight, DevFilter* out, uint32_t& n_out) const {
+    n_out = 0;
+    if (count < 0 || (count > 0 && !list)) return mrk_fail(MRK_E_INVAL, "query %u: bad %s list", qi, noun);
+    if (count == 0) return MRK_OK;
+    if (!on_weight && !seg->dev.attrs) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: filters need the segment's attribute rows (mrk_segment_set_attrs)", qi);
+    if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %ss run on the packed path only", qi, noun);
+    if (count > MRK_MAX_FILTERS) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %d %ss (device path: <= %d)", qi, count, noun, MRK_MAX_FILTERS);
+    for (int i = 0; i < count; ++i)
+      if (int rc = translate_filter(list[i], on_weight, out[i])) return rc;
+    n_out = (uint32_t)count;
+    return MRK_OK;
   }
 
-  dq.ranker = ranker;
-  dq.n_qwords = (uint32_t)words.size(); // ExtRanker_c::m_iQwords (sphinxsearch.cpp:730-731)
-  dq.max_qpos = 0;                      // ... m_iMaxQpos = GetQwords() (:4294-4296, 4372)
-  {
-    // ... over the keywords the query does not EXCLUDE: TagExcluded (sphinx.cpp:15107-15129) marks the words on the right of an
-    // ANDNOT, toggling with every nesting, and an excluded word's GetQwords() answers -1 (searchnode.cpp:2039, 2053).  (The tree
-    // was walked by build_tree / build_gen above: it is a tree of at most PLAN_CAP nodes.)
+  // ExtRanker_c::m_iMaxQpos = GetQwords() (sphinxsearch.cpp:4294-4296, 4372)
+  // ... over the keywords the query does not EXCLUDE: TagExcluded (sphinx.cpp:15107-15129) marks the words on the right of an
+  // ANDNOT, toggling with every nesting, and an excluded word's GetQwords() answers -1 (searchnode.cpp:2039, 2053).  (The tree
+  // was walked by build_tree / build_gen before: it is a tree of at most PLAN_CAP nodes.)
+  static uint32_t max_query_pos(const mrk_query& q, const PlanTree& T) {
     std::vector<uint8_t> ex((size_t)q.n_nodes, 0);
     struct Walk {
       const mrk_query& q;
@@ -1099,56 +1099,88 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q_in, int64_t item_
       }
     } walk{q, ex};
     walk.go(q.root, false, 0);
+    uint32_t max_qpos = 0;
     for (const PlanKw& k : T.kws)
-      if (!k.hidden && !(k.node >= 0 && k.node < q.n_nodes && ex[(size_t)k.node])) dq.max_qpos = std::max<uint32_t>(dq.max_qpos, (uint32_t)std::max(k.atom_pos, 0));
+      if (!k.hidden && !(k.node >= 0 && k.node < q.n_nodes && ex[(size_t)k.node])) max_qpos = std::max<uint32_t>(max_qpos, (uint32_t)std::max(k.atom_pos, 0));
+    return max_qpos;
   }
-  dq.k = (uint32_t)q.max_matches;
-  dq.n_weights = seg->n_fields;
-  dq.index_weight = (uint32_t)(q.index_weight ? q.index_weight : 1);
-  for (uint32_t f = 0; f < 32; ++f)
-    dq.weights[f] = (q.field_weights && (int)f < q.n_weights) ? q.field_weights[f] : 1; // BindWeights default
 
-  // ---- passes: one per driver keyword of the tree's candidate cover
-  IntVec cover;
-  if (pure_and)
-    cover.push_back(0); // kws are already in ExtMultiAnd_T node order: the rarest keyword drives
-  else
-    cover_of(T, root, cover);
-  {
-    IntVec uniq;
-    for (int k : cover)
-      if (std::find(uniq.begin(), uniq.end(), k) == uniq.end()) uniq.push_back(k);
-    cover = uniq;
-  }
-  if ((int)cover.size() > MAX_PASSES)
-    return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %zu driver keywords (device path: <= %d)", qi, cover.size(), MAX_PASSES);
-  const uint32_t req = pure_and ? (n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u) : required_of(T, root);
-  bool empty = false;
-  for (int k = 0; k < n; ++k)
-    if ((req >> k & 1u) && !T.kws[k].docs) empty = true; // a required keyword without postings (searchnode.cpp:2922)
-
-  uint64_t bytes = 0, pbytes = 0;
-  for (int k = 0; k < n; ++k)
-    if (T.kws[k].docs) {
-      bytes += seg->terms[T.kws[k].term_id].doclist_len;
-      pbytes += seg->terms[T.kws[k].term_id].packed_bytes;
+  // IDFs: distinct words in GetQwords traversal order (searchnode.cpp:2029-2055, 3276-3286); then what the ranker reads of the query
+  void weigh_words(DevQuery& dq) {
+    for (int i = 0; i < n; ++i) {
+      if (T.kws[i].hidden) { // read for its hits only
+        T.kws[i].weighted_first = false;
+        continue;
+      }
+      bool seen = false;
+      for (int w : words) seen |= T.kws[i].term_id >= 0 && T.kws[w].term_id == T.kws[i].term_id; // words missing from the dictionary are distinct words
+      T.kws[i].weighted_first = !seen;
+      if (!seen) words.push_back(i);
     }
+    int n_visible = 0;
+    for (const PlanKw& k : T.kws) n_visible += k.hidden ? 0 : 1;
+    got_dupes = (int)words.size() != n_visible; // HasQwordDupes: proximity rankers switch to their HANDLE_DUPES update
+    const int64_t total_docs = q.total_docs_override > 0 ? q.total_docs_override : (int64_t)seg->total_docs;
+    for (int w : words) {
+      PlanKw& t = T.kws[w];
+      int64_t term_docs = t.docs;
+      if (q.local_docs && q.local_docs[t.node] >= 0) term_docs = q.local_docs[t.node];
+      t.idf = mrk_idf(term_docs, total_docs, q.plain_idf, q.normalized_tfidf, (int)words.size(), t.boost);
+    }
+    dq.ranker = ranker;
+    dq.n_qwords = (uint32_t)words.size(); // ExtRanker_c::m_iQwords (sphinxsearch.cpp:730-731)
+    dq.max_qpos = max_query_pos(q, T);
+    dq.k = (uint32_t)q.max_matches;
+    dq.n_weights = seg->n_fields;
+    dq.index_weight = (uint32_t)(q.index_weight ? q.index_weight : 1);
+    for (uint32_t f = 0; f < 32; ++f)
+      dq.weights[f] = (q.field_weights && (int)f < q.n_weights) ? q.field_weights[f] : 1; // BindWeights default
+  }
 
-  // pruning histogram geometry (packed path): bins must be monotone in the sorter's order
-  dq.bin_mode = BIN_WEIGHT;
-  dq.bin_lo = INT32_MIN;
-  dq.bin_shift = 31; // fallback: (almost) no pruning, always correct
-  if (ranker == MRK_RANK_NONE) {
-    // all weights equal: order is rowid ascending => bin on the (global) rowid
+  // The passes' drivers (one per keyword of the tree's candidate cover), the keywords no match goes without, what the scan reads
+  int choose_cover() {
+    IntVec all;
+    if (pure_and)
+      all.push_back(0); // kws are already in ExtMultiAnd_T node order: the rarest keyword drives
+    else
+      cover_of(T, root, all);
+    for (int k : all)
+      if (std::find(cover.begin(), cover.end(), k) == cover.end()) cover.push_back(k);
+    if ((int)cover.size() > MAX_PASSES)
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: %zu driver keywords (device path: <= %d)", qi, cover.size(), MAX_PASSES);
+    req = pure_and ? (n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u) : required_of(T, root);
+    for (int k = 0; k < n; ++k)
+      if ((req >> k & 1u) && !T.kws[k].docs) empty = true; // a required keyword without postings (searchnode.cpp:2922)
+    for (int k = 0; k < n; ++k)
+      if (T.kws[k].docs) {
+        bytes += seg->terms[T.kws[k].term_id].doclist_len;
+        pbytes += seg->terms[T.kws[k].term_id].packed_bytes;
+      }
+    return MRK_OK;
+  }
+
+  // ---- pruning histogram geometry (packed path): bins must be monotone in the sorter's order
+
+  // the least shift that brings `span` under NBINS bins
+  static uint32_t bin_shift_for(uint64_t span) {
+    uint32_t sh = 0;
+    while (sh < 31 && (span >> sh) >= (uint64_t)NBINS) ++sh;
+    return sh;
+  }
+
+  // all weights equal: order is rowid ascending => bin on the (global) rowid
+  static void bins_by_rowid(const mrk_segment* seg, DevQuery& dq) {
     dq.bin_mode = BIN_ROWID;
     const uint64_t max_row = (uint64_t)seg->dev.rowid_base + (seg->total_docs ? seg->total_docs : 1);
-    uint32_t sh = 0;
-    while (sh < 31 && (max_row >> sh) >= (uint64_t)NBINS) ++sh;
-    if (max_row > 0xFFFFFFFFull) sh = 22;
-    dq.bin_shift = sh;
+    dq.bin_shift = max_row > 0xFFFFFFFFull ? 22 : bin_shift_for(max_row);
     dq.bin_lo = 0;
-  } else {
-    // weight = ((int)((sum tfidf + 0.5f) * 1000) + rank * 1000) * index_weight; any keyword may be absent
+  }
+
+  // weight = ((int)((sum tfidf + 0.5f) * 1000) + rank * 1000) * index_weight; any keyword may be absent
+  void bins_by_weight(DevQuery& dq) const {
+    dq.bin_mode = BIN_WEIGHT;
+    dq.bin_lo = INT32_MIN;
+    dq.bin_shift = 31; // fallback: (almost) no pruning, always correct
     double lo = 0.0, hi = 0.0;
     for (int i = 0; i < n; ++i) {
       const double idf = T.kws[i].weighted_first ? T.kws[i].idf : 0.0;
@@ -1197,318 +1229,338 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q_in, int64_t item_
                            ((__int128)b1 + (__int128)rmax * sc) * iw};
     const __int128 wlo = *std::min_element(c, c + 4), whi = *std::max_element(c, c + 4);
     if (wlo > INT32_MIN && whi < INT32_MAX && std::llabs(rmin) < INT32_MAX / 1000 && std::llabs(rmax) < INT32_MAX / 1000) {
-      const uint64_t span = (uint64_t)(whi - wlo) + 1;
-      uint32_t sh = 0;
-      while (sh < 31 && ((span - 1) >> sh) >= (uint64_t)NBINS) ++sh;
       dq.bin_lo = (int32_t)wlo;
-      dq.bin_shift = sh;
+      dq.bin_shift = bin_shift_for((uint64_t)(whi - wlo));
     }
   }
-  if (q.sort) { // the order starts with the attribute: the bins span the column's range of mapped keys (bin_lo read as unsigned)
-    const mrk_sort& S = *q.sort;
-    dq.sort_on = 1;
-    dq.sort_item = (uint32_t)S.bit_offset >> 5, dq.sort_shift = (uint32_t)S.bit_offset & 31u, dq.sort_bits = (uint32_t)S.bit_count;
-    dq.sort_flags = (S.kind == MRK_SORTKEY_FLOAT ? SORT_FLOAT : 0u) | (S.desc ? SORT_DESC : 0u);
-    dq.sort_tie = (uint32_t)S.then_weight;
-    uint32_t lo = srange->lo, hi = srange->hi;
+
+  // a column's range of mapped keys in the query's direction: no rows = 0..0; ascending: the keys are complemented
+  template <typename U>
+  static void directed(U& lo, U& hi, bool desc) {
     if (lo > hi) lo = hi = 0;
-    if (!S.desc) { // ascending: the keys are complemented
-      const uint32_t l = ~hi, h = ~lo;
+    if (!desc) {
+      const U l = ~hi, h = ~lo;
       lo = l, hi = h;
     }
-    uint32_t sh = 0;
-    while (sh < 31 && ((hi - lo) >> sh) >= (uint32_t)NBINS) ++sh;
-    dq.bin_mode = BIN_WEIGHT;
-    dq.bin_lo = (int32_t)lo;
-    dq.bin_shift = sh;
   }
-  if (ord) { // a 64-bit key: two dwords of the row, the compressed bins of mrk_sortkey.h
-    const mrk_order_part &A = ord->parts[0], &B = ord->parts[ord->n_parts - 1];
+
+  // the order starts with an attribute: where the key lies in the row, and the bins over the column's range of mapped keys
+  static void bins_by_key(const KeySpec& O, DevQuery& dq) {
+    const KeyPart &A = O.part[0], &B = O.part[O.n_parts - 1];
+    dq.sort_tie = (uint32_t)O.tie;
+    dq.bin_mode = BIN_WEIGHT;
+    dq.sort_item = A.item(), dq.sort_shift = (uint32_t)A.bit_offset & 31u, dq.sort_bits = (uint32_t)A.bit_count, dq.sort_flags = A.flags();
+    if (!O.wide) { // (bin_lo read as unsigned)
+      dq.sort_on = SORT_ON_ATTR;
+      uint32_t lo = A.range->lo, hi = A.range->hi;
+      directed(lo, hi, A.desc);
+      dq.bin_lo = (int32_t)lo;
+      dq.bin_shift = bin_shift_for(hi - lo);
+      return;
+    }
+    // a 64-bit key: two dwords of the row, the compressed bins of mrk_sortkey.h
     const bool i64 = A.kind == MRK_SORTKEY_INT64;
-    auto flags_of = [](const mrk_order_part& P) { return (P.kind == MRK_SORTKEY_FLOAT ? SORT_FLOAT : 0u) | (P.desc ? SORT_DESC : 0u); };
     dq.sort_on = SORT_ON_ORDER;
-    dq.sort_tie = (uint32_t)ord->then_weight;
     uint32_t a_lo, a_hi, b_lo, b_hi;
-    auto directed = [](uint32_t& lo, uint32_t& hi, bool desc) { // ascending: the keys are complemented
-      if (lo > hi) lo = hi = 0;
-      if (!desc) {
-        const uint32_t l = ~hi, h = ~lo;
-        lo = l, hi = h;
-      }
-    };
     if (i64) { // high dword signed, low dword unsigned, one direction
-      dq.sort_item = ((uint32_t)A.bit_offset >> 5) + 1, dq.sort_shift = 0, dq.sort_bits = 32, dq.sort_flags = flags_of(A) | SORT_SIGNED;
-      dq.ord_item = (uint32_t)A.bit_offset >> 5, dq.ord_shift = 0, dq.ord_bits = 32, dq.ord_flags = flags_of(A);
-      uint64_t lo = orange[0]->lo64, hi = orange[0]->hi64;
-      if (lo > hi) lo = hi = 0;
-      if (!A.desc) {
-        const uint64_t l = ~hi, h = ~lo;
-        lo = l, hi = h;
-      }
+      dq.sort_item = A.item() + 1, dq.sort_shift = 0, dq.sort_bits = 32, dq.sort_flags = A.flags() | SORT_SIGNED;
+      dq.ord_item = A.item(), dq.ord_shift = 0, dq.ord_bits = 32, dq.ord_flags = A.flags();
+      uint64_t lo = A.range->lo64, hi = A.range->hi64;
+      directed(lo, hi, A.desc);
       a_lo = (uint32_t)(lo >> 32), b_lo = (uint32_t)lo, a_hi = (uint32_t)(hi >> 32), b_hi = (uint32_t)hi;
     } else {
-      dq.sort_item = (uint32_t)A.bit_offset >> 5, dq.sort_shift = (uint32_t)A.bit_offset & 31u, dq.sort_bits = (uint32_t)A.bit_count, dq.sort_flags = flags_of(A);
-      dq.ord_item = (uint32_t)B.bit_offset >> 5, dq.ord_shift = (uint32_t)B.bit_offset & 31u, dq.ord_bits = (uint32_t)B.bit_count, dq.ord_flags = flags_of(B);
-      a_lo = orange[0]->lo, a_hi = orange[0]->hi, b_lo = orange[1]->lo, b_hi = orange[1]->hi;
-      directed(a_lo, a_hi, A.desc != 0), directed(b_lo, b_hi, B.desc != 0);
+      dq.ord_item = B.item(), dq.ord_shift = (uint32_t)B.bit_offset & 31u, dq.ord_bits = (uint32_t)B.bit_count, dq.ord_flags = B.flags();
+      a_lo = A.range->lo, a_hi = A.range->hi, b_lo = B.range->lo, b_hi = B.range->hi;
+      directed(a_lo, a_hi, A.desc), directed(b_lo, b_hi, B.desc);
     }
     dq.ord_geom = order_geom(a_lo, a_hi, b_lo, b_hi, i64);
     dq.sort_flags |= SORT_WIDE;
-    dq.bin_mode = BIN_WEIGHT;
     dq.bin_lo = 0, dq.bin_shift = 0;
   }
-  {
+
+  // the query's candidate list: a slot range of the batch's arena (16-byte candidates in the arena of the sorted queries; the
+  // relevance selection sees an empty list)
+  void reserve_candidates(DevQuery& dq, BatchPlan& plan) const {
     uint64_t cap = 0;
     for (int k : cover) cap += (uint64_t)T.kws[k].docs;
     cap = std::min<uint64_t>(std::max<uint64_t>(cap, 1), (uint64_t)1 << 20);
-    if (q.sort || ord) { // 16-byte candidates in the arena of the sorted queries; the relevance selection sees an empty list
+    dq.cand_off = plan.cand_total;
+    if (order.n_parts) {
       dq.cand_cap = 0;
-      dq.cand_off = plan.cand_total;
       dq.sort_cap = (uint32_t)cap;
       dq.sort_off = plan.sort_total;
       plan.sort_total += cap;
     } else {
       dq.cand_cap = (uint32_t)cap;
-      dq.cand_off = plan.cand_total;
       plan.cand_total += cap;
     }
   }
-  if (empty) {
-    dq.n_terms = (uint32_t)n;
-    dq.n_items = 0;
-    return MRK_OK;
+
+  // ---- the bitmap-driven kernels: whole window ranges instead of block ranges
+
+  // the tree program: op | left node << 8 | right node << 16 | keyword << 24 (slot: the pass's keyword order; none = the tree's)
+  static void pack_prog(const PlanTree& T, const IntVec* slot, DevQuery& P) {
+    P.n_nodes = (uint32_t)T.nodes.size();
+    for (size_t i = 0; i < T.nodes.size(); ++i) {
+      const PlanNode& pn = T.nodes[i];
+      const int kw = pn.kw < 0 ? 0 : slot ? (*slot)[pn.kw] : pn.kw;
+      P.prog[i] = pn.op | ((uint32_t)(pn.l < 0 ? 0 : pn.l) << 8) | ((uint32_t)(pn.r < 0 ? 0 : pn.r) << 16) | ((uint32_t)kw << 24);
+    }
   }
-  plan.algo_bytes += bytes;
-  plan.dev_bytes += use_packed ? pbytes : bytes;
-  plan.any_prox = plan.any_prox || prox || T.phrase || T.ph_leaf || T.termpos || T.notnear || T.gen; // (every generic-path candidate goes through the queue)
-  plan.any_tree = plan.any_tree || !pure_and;
+
+  // One entry for the pass's whole window range; layout_batch cuts it once the batch's total is known (a wave's fixed costs --
+  // tables, final publish, atomics on the query's counters -- want long runs of windows).  dev_bytes: what the kernel reads instead
+  // of the packed blocks counted before
+  void emit_window_item(DevQuery& P, uint32_t pass_index, uint32_t kind, uint64_t dev_bytes, BatchPlan& plan) const {
+    P.item_first = (uint32_t)plan.items_bm.size();
+    plan.dev_bytes += dev_bytes - pbytes;
+    DevItem it{};
+    it.query = pass_index;
+    it.blk_begin = 0;
+    it.blk_end = (uint32_t)seg->dev.n_windows;
+    it.kind = kind;
+    plan.items_bm.push_back(it);
+    P.n_items = 1;
+  }
+
+  // what the three kernels share: the packed path of a segment with doc-set bitmaps, nothing that reads attribute rows or weights
+  bool bitmaps_usable() const {
+    return use_packed && seg->dev.bm && !seg->wide && seg->ctx->bitmap_inv > 0 && !filtered && q.n_weight_filters == 0;
+  }
+  bool is_dense(int k) const { return T.kws[k].docs && seg->terms[T.kws[k].term_id].bm_off != ~0ull; }
+
+  // ... and the tree kernel's two uses (mrk_scan_bt.hip): a plain tree whose cover is common enough (cover_inv: 1 / the least share of
+  // the docs), every keyword unrestricted in fields (a bitmap bit is then "the keyword holds the doc"), one of them dense (sparse
+  // keywords are fine, their window words are assembled from a block cursor)
+  bool tree_kernel_usable(int cover_inv) const {
+    if (!bitmaps_usable() || seg->ctx->bt_cover_inv <= 0 || T.gen || T.ph_leaf || T.quorum || T.order || T.termpos || T.notnear || n > MAX_PROX_TERMS ||
+        seg->total_docs >= (1ull << 32) || T.nodes.size() > 16)
+      return false;
+    uint64_t cover_docs = 0;
+    for (int k : cover) cover_docs += (uint64_t)T.kws[k].docs;
+    if (cover_docs * (uint64_t)cover_inv < seg->total_docs) return false;
+    const uint32_t all_fields = seg->n_fields >= 32 ? 0xFFFFFFFFu : (1u << seg->n_fields) - 1u;
+    int n_dense = 0;
+    for (int k = 0; k < n; ++k) {
+      if ((T.kws[k].queried32 & all_fields) != all_fields) return false;
+      n_dense += is_dense(k);
+    }
+    return n_dense > 0 && stack_depth(T) <= TREE_STACK;
+  }
+  // bitmaps of the dense keywords + packed blocks of the sparse ones + every keyword's tf / field words
+  uint64_t tree_kernel_bytes() const {
+    uint64_t b = 0;
+    for (int k = 0; k < n; ++k)
+      if (T.kws[k].docs) {
+        const HostTerm& h = seg->terms[T.kws[k].term_id];
+        b += h.bm_off != ~0ull ? (uint64_t)seg->dev.n_windows * 256 + (uint64_t)h.nblocks * 256 : h.packed_bytes;
+      }
+    return b;
+  }
 
   // two dense keywords: the bitmap kernel (mrk_scan_bm.hip) walks 2048-rowid windows instead of blocks
-  if (use_packed && pure_and && !T.phrase && n == 2 && !filtered && q.n_weight_filters == 0 && (ranker == MRK_RANK_NONE || ranker == MRK_RANK_BM25) && seg->dev.bm && !seg->wide &&
-      seg->ctx->bitmap_inv > 0 && seg->terms[T.kws[0].term_id].bm_off != ~0ull && seg->terms[T.kws[1].term_id].bm_off != ~0ull) {
+  bool pair_on_bitmaps(DevQuery& dq, BatchPlan& plan) const {
+    if (!bitmaps_usable() || !pure_and || T.phrase || n != 2 || (ranker != MRK_RANK_NONE && ranker != MRK_RANK_BM25) || !is_dense(0) || !is_dense(1)) return false;
     dq.n_terms = 2;
     for (int i = 0; i < 2; ++i) fill_term(seg, T.kws[i], dq.t[i]);
     dq.tree_flags = TF_MULTIAND | TF_BITMAP;
-    dq.item_first = (uint32_t)plan.items_bm.size();
-    const uint64_t nwin = seg->dev.n_windows;
     // bitmaps + tf / field bytes of the docs (one byte each where the segment has the nibble plane, else the attr words)
-    const uint64_t bm_bytes = 2 * nwin * 256 + ((uint64_t)dq.t[0].nblocks + dq.t[1].nblocks) * (seg->dev.pk_attr1 ? 128 : 256);
-    plan.dev_bytes += bm_bytes - pbytes; // (pbytes was added above)
-    // one entry for the whole window range; mrk_batch_submit cuts it once the batch's total is known (a wave's
-    // fixed costs -- tables, final publish, atomics on the query's counters -- want long runs of windows)
-    DevItem it{};
-    it.query = qi;
-    it.blk_begin = 0;
-    it.blk_end = (uint32_t)nwin;
-    plan.items_bm.push_back(it);
-    dq.n_items = 1;
-    return MRK_OK;
+    const uint64_t bm_bytes = 2 * (uint64_t)seg->dev.n_windows * 256 + ((uint64_t)dq.t[0].nblocks + dq.t[1].nblocks) * (seg->dev.pk_attr1 ? 128 : 256);
+    emit_window_item(dq, qi, 0, bm_bytes, plan);
+    return true;
   }
 
   // A tree whose candidate cover is a common keyword: evaluate it on bitmap words, 2048 rowids per step, instead of
-  // walking the cover's docs block by block (mrk_scan_bt.hip).  Needs every keyword unrestricted in fields (a bitmap bit
-  // is then "the keyword holds the doc"); sparse keywords are fine, their window words are assembled from a block cursor.
-  {
-    const uint32_t all_fields = seg->n_fields >= 32 ? 0xFFFFFFFFu : (1u << seg->n_fields) - 1u;
-    bool ok = use_packed && seg->dev.bm && !seg->wide && seg->ctx->bitmap_inv > 0 && seg->ctx->bt_cover_inv > 0 && !T.gen && !T.phrase && !T.ph_leaf && !T.quorum && !T.order &&
-              !T.termpos && !T.notnear && !filtered && q.n_weight_filters == 0 && n <= MAX_PROX_TERMS && seg->total_docs < (1ull << 32) && T.nodes.size() <= 16;
-    uint64_t cover_docs = 0;
-    for (int k : cover) cover_docs += (uint64_t)T.kws[k].docs;
-    // (a pure AND keeps the old bar of 1/32: below it the block walk behind a selective driver -- skiplist seeks, a probe per doc --
-    // beats streaming every keyword's bitmap; with 1/1024 the headline's selective x common stratum went from 0.36 to 0.54 ms)
-    ok = ok && cover_docs * (uint64_t)(pure_and ? std::min(seg->ctx->bt_cover_inv, 32) : seg->ctx->bt_cover_inv) >= seg->total_docs;
-    int n_dense = 0;
-    for (int k = 0; ok && k < n; ++k) {
-      ok = (T.kws[k].queried32 & all_fields) == all_fields;
-      if (T.kws[k].docs && seg->terms[T.kws[k].term_id].bm_off != ~0ull) ++n_dense;
-    }
-    if (ok && pure_and) { // (the tree program of a pure AND is its left-deep chain: at most two values on the stack)
-      int sp = 0, deep = 0;
-      for (const PlanNode& pn : T.nodes) sp += pn.op == PN_TERM ? 1 : -1, deep = std::max(deep, sp);
-      ok = deep <= TREE_STACK;
-    }
-    if (ok && n_dense > 0) {
-      dq.n_terms = (uint32_t)n;
-      for (int i = 0; i < n; ++i) fill_term(seg, T.kws[i], dq.t[i]);
-      dq.tree_flags = (pure_and ? TF_MULTIAND : 0) | (got_dupes ? TF_DUPES : 0) | TF_BTREE | (seg->ctx->prox_bound_keywords ? TF_LCS_BY_KEYWORDS : 0);
-      dq.n_nodes = (uint32_t)T.nodes.size();
-      for (size_t i = 0; i < T.nodes.size(); ++i) {
-        const PlanNode& pn = T.nodes[i];
-        dq.prog[i] = pn.op | ((uint32_t)(pn.l < 0 ? 0 : pn.l) << 8) | ((uint32_t)(pn.r < 0 ? 0 : pn.r) << 16) | ((uint32_t)(pn.kw < 0 ? 0 : pn.kw) << 24);
-      }
-      dq.item_first = (uint32_t)plan.items_bm.size();
-      const uint64_t nwin = seg->dev.n_windows;
-      uint64_t bt_bytes = 0; // bitmaps of the dense keywords + packed blocks of the sparse ones + every keyword's tf / field words
-      for (int k = 0; k < n; ++k)
-        if (T.kws[k].docs) {
-          const HostTerm& h = seg->terms[T.kws[k].term_id];
-          bt_bytes += h.bm_off != ~0ull ? nwin * 256 + (uint64_t)h.nblocks * 256 : h.packed_bytes;
-        }
-      plan.dev_bytes += bt_bytes - pbytes; // (pbytes was added above)
-      DevItem it{};
-      it.query = qi;
-      it.blk_begin = 0;
-      it.blk_end = (uint32_t)nwin;
-      it.kind = 1;
-      plan.items_bm.push_back(it);
-      dq.n_items = 1;
-      return MRK_OK;
-    }
+  // walking the cover's docs block by block (mrk_scan_bt.hip).
+  // (a pure AND keeps the old bar of 1/32: below it the block walk behind a selective driver -- skiplist seeks, a probe per doc --
+  // beats streaming every keyword's bitmap; with 1/1024 the headline's selective x common stratum went from 0.36 to 0.54 ms)
+  bool tree_on_bitmaps(DevQuery& dq, BatchPlan& plan) const {
+    const int bt_cover_inv = seg->ctx->bt_cover_inv;
+    if (T.phrase || !tree_kernel_usable(pure_and ? std::min(bt_cover_inv, 32) : bt_cover_inv)) return false;
+    dq.n_terms = (uint32_t)n;
+    for (int i = 0; i < n; ++i) fill_term(seg, T.kws[i], dq.t[i]);
+    dq.tree_flags = (pure_and ? TF_MULTIAND : 0) | (got_dupes ? TF_DUPES : 0) | TF_BTREE | (seg->ctx->prox_bound_keywords ? TF_LCS_BY_KEYWORDS : 0);
+    pack_prog(T, nullptr, dq);
+    emit_window_item(dq, qi, 1, tree_kernel_bytes(), plan);
+    return true;
   }
 
-  DevQuery base_copy; // (1.3 KB: only copied when the query runs as several passes)
-  if (cover.size() > 1) base_copy = dq;
-  const DevQuery& base = base_copy;
-  for (size_t p = 0; p < cover.size(); ++p) {
-    DevQuery* P = &dq;
-    uint32_t pass_index = qi;
-    if (p > 0) {
-      plan.extra.push_back(base);
-      P = &plan.extra.back();
-      pass_index = n_queries + (uint32_t)plan.extra.size() - 1;
-      P->item_first = (uint32_t)plan.items.size();
-    }
-    if (T.gen) P->item_first = (uint32_t)plan.items_bm.size(), P->n_items = 0;
-    // keyword order of this pass: driver, then required keywords by ascending docs, then the rest
-    IntVec order;
-    const int drv = cover[p];
-    order.push_back(drv);
-    if (pure_and)
-      for (int k = 1; k < n; ++k) order.push_back(k);
-    else {
-      IntVec rq, rest;
-      for (int k = 0; k < n; ++k)
-        if (k != drv) ((req >> k & 1u) ? rq : rest).push_back(k);
-      auto by_docs = [&](int a, int b) { return T.kws[a].docs < T.kws[b].docs; };
-      std::stable_sort(rq.begin(), rq.end(), by_docs);
-      std::stable_sort(rest.begin(), rest.end(), by_docs);
-      order.append(rq.begin(), rq.end());
-      order.append(rest.begin(), rest.end());
-    }
-    IntVec slot(n);
-    for (int i = 0; i < n; ++i) slot[order[i]] = i;
-    P->n_terms = (uint32_t)n;
-    for (int i = 0; i < n; ++i) fill_term(seg, T.kws[order[i]], P->t[i]);
-    P->req_mask = P->excl_mask = 0;
-    P->tree_flags = (T.phrase ? TF_PHRASE : pure_and ? TF_MULTIAND : T.ph_leaf ? TF_PHRASE_LEAF : 0) | (got_dupes ? TF_DUPES : 0) | (T.termpos ? TF_TERMPOS : 0) | (T.order ? TF_ORDER : 0) | (T.notnear ? TF_NOTNEAR : 0) | (T.gen ? TF_GEN : 0) | (T.gen_nearn ? TF_GEN_NEARN : 0);
-    if (T.gen) { // the evaluator's program, keyword slots as this pass orders them
-      GenProg gp = Gp->prog;
-      for (uint32_t i = 0; i < gp.n_nodes; ++i) {
-        GenNode& g = gp.nodes[i];
-        if (g.kind == GN_TERM) g.kid[0] = (uint8_t)slot[g.kid[0]];
-        if (g.kind == GN_MULTIAND || g.kind == GN_QUORUM)
-          for (int k = 0; k < g.n_kids; ++k) g.kid[k] = (uint8_t)slot[g.kid[k]];
-        if (g.kind == GN_PHRASE || g.kind == GN_PROX)
-          for (int k = 0; k < g.n_words; ++k) g.aux[k] = (uint8_t)slot[g.aux[k]];
-        if (g.kind == GN_UNIT && g.aux[0] != 0xFF) g.aux[0] = (uint8_t)slot[g.aux[0]];
+  // A root PHRASE / PROXIMITY whose words are common: the AND of its words -- the candidates the word state machine has to look
+  // at -- comes off the doc-set bitmaps, 8192 rowids per step (scan_bt_kernel), instead of the rarest word's blocks one by one
+  // with a probe per doc and word; the candidates travel through the same queue to the same hit pass (rank_kernel<1>).
+  // Config 5's phrase fifth spent 20 of its 36 ms per launch in the block walk.
+  bool phrase_on_bitmaps(DevQuery& P, uint32_t pass_index, BatchPlan& plan) const {
+    if (!T.phrase || cover.size() != 1 || !seg->ctx->bt_phrase || !pure_and || got_dupes || n < 2 || !tree_kernel_usable(seg->ctx->bt_cover_inv)) return false;
+    P.tree_flags |= TF_BTREE | TF_MULTIAND;
+    emit_window_item(P, pass_index, 1, tree_kernel_bytes(), plan);
+    return true;
+  }
+
+  // ---- the block scan's passes
+
+  // ExtQuorum_c's m_dChildren over time: query-position order; a keyword leaves (RemoveFast: the last one takes its place) once the
+  // doc it sits on was its last -- keywords without docs right at the warmup (searchnode.cpp:4468-4483, 4517-4537)
+  void quorum_schedule(const IntVec& slot, DevQuery& P) const {
+    P.qr_thr = (uint32_t)T.q_thr;
+    if (T.quorum_root && prox) P.tree_flags |= TF_QUORUM_HITS;
+    int list[QUORUM_EVENTS], ln = T.q_n;
+    for (int i = 0; i < ln; ++i) list[i] = T.q_kw0 + i, P.qr_mask |= 1u << slot[T.q_kw0 + i];
+    auto pack_order = [&]() {
+      uint32_t o = 0xFFFFFFFFu;
+      for (int i = ln - 1; i >= 0; --i) o = (o << 4) | (uint32_t)slot[list[i]];
+      return o;
+    };
+    auto last_of = [&](int k) -> int64_t { return T.kws[k].docs ? (int64_t)seg->terms[T.kws[k].term_id].last_rowid : -1; };
+    for (int i = 0; i < ln; ++i) // warmup: keywords that hold no doc at all
+      if (last_of(list[i]) < 0) {
+        list[i] = list[--ln];
+        --i;
       }
-      P->gen_prog = (uint32_t)plan.gen_progs.size();
-      plan.gen_progs.push_back(gp);
-    }
-    P->nn_a = T.notnear ? (uint32_t)slot[T.nn_a] : 0u, P->nn_b = T.notnear ? (uint32_t)slot[T.nn_b] : 0u, P->nn_dist = (uint32_t)T.nn_dist;
-    P->px_dist = (uint32_t)T.px_dist;
-    P->qr_mask = P->qr_thr = P->qr_n = 0;
-    if (T.quorum) {
-      // m_dChildren over time: query-position order; a keyword leaves (RemoveFast: the last one takes its place) once the
-      // doc it sits on was its last -- keywords without docs right at the warmup (searchnode.cpp:4468-4483, 4517-4537)
-      P->qr_thr = (uint32_t)T.q_thr;
-      if (T.quorum_root && prox) P->tree_flags |= TF_QUORUM_HITS;
-      int list[QUORUM_EVENTS], ln = T.q_n;
-      for (int i = 0; i < ln; ++i) list[i] = T.q_kw0 + i, P->qr_mask |= 1u << slot[T.q_kw0 + i];
-      auto pack_order = [&]() {
-        uint32_t o = 0xFFFFFFFFu;
-        for (int i = ln - 1; i >= 0; --i) o = (o << 4) | (uint32_t)slot[list[i]];
-        return o;
-      };
-      auto last_of = [&](int k) -> int64_t { return T.kws[k].docs ? (int64_t)seg->terms[T.kws[k].term_id].last_rowid : -1; };
-      for (int i = 0; i < ln; ++i) // warmup: keywords that hold no doc at all
-        if (last_of(list[i]) < 0) {
+    P.qr_ord[0] = pack_order();
+    while (ln > 0 && P.qr_n < (uint32_t)QUORUM_EVENTS) {
+      int64_t r = INT64_MAX;
+      for (int i = 0; i < ln; ++i) r = std::min(r, last_of(list[i]));
+      for (int i = 0; i < ln; ++i)
+        if (last_of(list[i]) == r) {
           list[i] = list[--ln];
           --i;
         }
-      P->qr_ord[0] = pack_order();
-      while (ln > 0 && P->qr_n < (uint32_t)QUORUM_EVENTS) {
-        int64_t r = INT64_MAX;
-        for (int i = 0; i < ln; ++i) r = std::min(r, last_of(list[i]));
-        for (int i = 0; i < ln; ++i)
-          if (last_of(list[i]) == r) {
-            list[i] = list[--ln];
-            --i;
-          }
-        P->qr_row[P->qr_n] = (uint32_t)r;
-        P->qr_ord[++P->qr_n] = pack_order();
-      }
+      P.qr_row[P.qr_n] = (uint32_t)r;
+      P.qr_ord[++P.qr_n] = pack_order();
     }
-    P->ph_mask = 0;
-    for (int k = 0; k < T.ph_n; ++k) P->ph_mask |= 1u << slot[T.ph_kw0 + k];
-    for (size_t i = 0; i < T.atoms.size(); ++i) P->ph_atoms[i] = (uint32_t)T.atoms[i];
-    {
+  }
+
+  // the evaluator's program, keyword slots as the pass orders them
+  static void remap_gen_prog(GenProg& gp, const IntVec& slot) {
+    for (uint32_t i = 0; i < gp.n_nodes; ++i) {
+      GenNode& g = gp.nodes[i];
+      if (g.kind == GN_TERM) g.kid[0] = (uint8_t)slot[g.kid[0]];
+      if (g.kind == GN_MULTIAND || g.kind == GN_QUORUM)
+        for (int k = 0; k < g.n_kids; ++k) g.kid[k] = (uint8_t)slot[g.kid[k]];
+      if (g.kind == GN_PHRASE || g.kind == GN_PROX)
+        for (int k = 0; k < g.n_words; ++k) g.aux[k] = (uint8_t)slot[g.aux[k]];
+      if (g.kind == GN_UNIT && g.aux[0] != 0xFF) g.aux[0] = (uint8_t)slot[g.aux[0]];
+    }
+  }
+
+  // One pass per driver keyword of the cover: dq is the first, the others are copies of it in plan.extra
+  void emit_passes(DevQuery& dq, int64_t item_bytes, uint32_t n_queries, BatchPlan& plan) const {
+    DevQuery base_copy; // (1.3 KB: only copied when the query runs as several passes)
+    if (cover.size() > 1) base_copy = dq;
+    const DevQuery& base = base_copy;
+    for (size_t p = 0; p < cover.size(); ++p) {
+      DevQuery* P = &dq;
+      uint32_t pass_index = qi;
+      if (p > 0) {
+        plan.extra.push_back(base);
+        P = &plan.extra.back();
+        pass_index = n_queries + (uint32_t)plan.extra.size() - 1;
+        P->item_first = (uint32_t)plan.items.size();
+      }
+      if (T.gen) P->item_first = (uint32_t)plan.items_bm.size(), P->n_items = 0;
+      // keyword order of this pass: driver, then required keywords by ascending docs, then the rest
+      IntVec order;
+      const int drv = cover[p];
+      order.push_back(drv);
+      if (pure_and)
+        for (int k = 1; k < n; ++k) order.push_back(k);
+      else {
+        IntVec rq, rest;
+        for (int k = 0; k < n; ++k)
+          if (k != drv) ((req >> k & 1u) ? rq : rest).push_back(k);
+        auto by_docs = [&](int a, int b) { return T.kws[a].docs < T.kws[b].docs; };
+        std::stable_sort(rq.begin(), rq.end(), by_docs);
+        std::stable_sort(rest.begin(), rest.end(), by_docs);
+        order.append(rq.begin(), rq.end());
+        order.append(rest.begin(), rest.end());
+      }
+      IntVec slot(n);
+      for (int i = 0; i < n; ++i) slot[order[i]] = i;
+      P->n_terms = (uint32_t)n;
+      for (int i = 0; i < n; ++i) fill_term(seg, T.kws[order[i]], P->t[i]);
+      P->req_mask = P->excl_mask = 0;
+      P->tree_flags = (T.phrase ? TF_PHRASE : pure_and ? TF_MULTIAND : T.ph_leaf ? TF_PHRASE_LEAF : 0) | (got_dupes ? TF_DUPES : 0) | (T.termpos ? TF_TERMPOS : 0) | (T.order ? TF_ORDER : 0) | (T.notnear ? TF_NOTNEAR : 0) | (T.gen ? TF_GEN : 0) | (T.gen_nearn ? TF_GEN_NEARN : 0);
+      if (T.gen) {
+        P->gen_prog = (uint32_t)plan.gen_progs.size();
+        plan.gen_progs.push_back(gen_build->prog);
+        remap_gen_prog(plan.gen_progs.back(), slot);
+      }
+      P->nn_a = T.notnear ? (uint32_t)slot[T.nn_a] : 0u, P->nn_b = T.notnear ? (uint32_t)slot[T.nn_b] : 0u, P->nn_dist = (uint32_t)T.nn_dist;
+      P->px_dist = (uint32_t)T.px_dist;
+      P->qr_mask = P->qr_thr = P->qr_n = 0;
+      if (T.quorum) quorum_schedule(slot, *P);
+      P->ph_mask = 0;
+      for (int k = 0; k < T.ph_n; ++k) P->ph_mask |= 1u << slot[T.ph_kw0 + k];
+      for (size_t i = 0; i < T.atoms.size(); ++i) P->ph_atoms[i] = (uint32_t)T.atoms[i];
       for (int k = 0; k < n; ++k)
         if (req >> k & 1u) P->req_mask |= 1u << slot[k];
       for (size_t e = 0; e < p; ++e) P->excl_mask |= 1u << slot[cover[e]];
-      P->n_nodes = (uint32_t)T.nodes.size();
-      for (size_t i = 0; i < T.nodes.size(); ++i) {
-        const PlanNode& pn = T.nodes[i];
-        P->prog[i] = pn.op | ((uint32_t)(pn.l < 0 ? 0 : pn.l) << 8) | ((uint32_t)(pn.r < 0 ? 0 : pn.r) << 16) |
-                     ((uint32_t)(pn.kw < 0 ? 0 : slot[pn.kw]) << 24);
-      }
-    }
-    // A root PHRASE / PROXIMITY whose words are common: the AND of its words -- the candidates the word state machine has to look
-    // at -- comes off the doc-set bitmaps, 8192 rowids per step (scan_bt_kernel), instead of the rarest word's blocks one by one
-    // with a probe per doc and word; the candidates travel through the same queue to the same hit pass (rank_kernel<1>).
-    // Config 5's phrase fifth spent 20 of its 36 ms per launch in the block walk.
-    if (T.phrase && p == 0 && cover.size() == 1 && use_packed && seg->dev.bm && !seg->wide && seg->ctx->bitmap_inv > 0 && seg->ctx->bt_cover_inv > 0 && seg->ctx->bt_phrase &&
-        pure_and && !got_dupes && !T.gen && !T.termpos && !T.notnear && !T.order && !T.quorum && !filtered && q.n_weight_filters == 0 && n >= 2 && n <= MAX_PROX_TERMS &&
-        seg->total_docs < (1ull << 32) && T.nodes.size() <= 16 && (uint64_t)T.kws[cover[0]].docs * (uint64_t)seg->ctx->bt_cover_inv >= seg->total_docs) {
-      const uint32_t all_fields = seg->n_fields >= 32 ? 0xFFFFFFFFu : (1u << seg->n_fields) - 1u;
-      bool ok = true;
-      int n_dense = 0, sp = 0, deep = 0;
-      for (int k = 0; k < n; ++k) {
-        ok = ok && T.kws[k].docs && (T.kws[k].queried32 & all_fields) == all_fields;
-        if (T.kws[k].docs && seg->terms[T.kws[k].term_id].bm_off != ~0ull) ++n_dense;
-      }
-      for (const PlanNode& pn : T.nodes) sp += pn.op == PN_TERM ? 1 : -1, deep = std::max(deep, sp);
-      if (ok && n_dense > 0 && deep <= TREE_STACK) {
-        P->tree_flags |= TF_BTREE | TF_MULTIAND;
-        P->item_first = (uint32_t)plan.items_bm.size();
-        const uint64_t nwin = seg->dev.n_windows;
-        uint64_t bt_bytes = 0;
-        for (int k = 0; k < n; ++k) {
-          const HostTerm& h = seg->terms[T.kws[k].term_id];
-          bt_bytes += h.bm_off != ~0ull ? nwin * 256 + (uint64_t)h.nblocks * 256 : h.packed_bytes;
+      pack_prog(T, &slot, *P);
+      if (phrase_on_bitmaps(*P, pass_index, plan)) continue;
+      // work items: contiguous ranges of driver-term blocks, ~item_bytes of doclist each
+      const uint32_t nb0 = P->t[0].nblocks;
+      if (nb0) {
+        const double per_block = (double)(use_packed ? pbytes : bytes) / (double)nb0 / (double)cover.size();
+        uint64_t bpi = (uint64_t)((double)item_bytes / std::max(per_block, 1.0));
+        bpi = std::max<uint64_t>(T0_BLOCKS, (bpi / T0_BLOCKS) * T0_BLOCKS);
+        for (uint64_t b = 0; b < nb0; b += bpi) {
+          DevItem it{};
+          it.query = pass_index;
+          it.blk_begin = (uint32_t)b;
+          it.blk_end = (uint32_t)std::min<uint64_t>(nb0, b + bpi);
+          if (T.gen) { // its own launch (the scan instance that hands over a reference per keyword), behind the block items
+            it.kind = 2;
+            plan.items_bm.push_back(it);
+            ++P->n_items;
+          } else
+            plan.items.push_back(it);
         }
-        plan.dev_bytes += bt_bytes - pbytes; // (pbytes was added above)
-        DevItem it{};
-        it.query = pass_index;
-        it.blk_begin = 0;
-        it.blk_end = (uint32_t)nwin;
-        it.kind = 1;
-        plan.items_bm.push_back(it);
-        P->n_items = 1;
-        continue;
       }
+      if (!T.gen) P->n_items = (uint32_t)plan.items.size() - P->item_first;
     }
-    // work items: contiguous ranges of driver-term blocks, ~item_bytes of doclist each
-    const uint32_t nb0 = P->t[0].nblocks;
-    if (nb0) {
-      const double per_block = (double)(use_packed ? pbytes : bytes) / (double)nb0 / (double)cover.size();
-      uint64_t bpi = (uint64_t)((double)item_bytes / std::max(per_block, 1.0));
-      bpi = std::max<uint64_t>(T0_BLOCKS, (bpi / T0_BLOCKS) * T0_BLOCKS);
-      for (uint64_t b = 0; b < nb0; b += bpi) {
-        DevItem it{};
-        it.query = pass_index;
-        it.blk_begin = (uint32_t)b;
-        it.blk_end = (uint32_t)std::min<uint64_t>(nb0, b + bpi);
-        if (T.gen) { // its own launch (the scan instance that hands over a reference per keyword), behind the block items
-          it.kind = 2;
-          plan.items_bm.push_back(it);
-          ++P->n_items;
-        } else
-          plan.items.push_back(it);
-      }
-    }
-    if (!T.gen) P->n_items = (uint32_t)plan.items.size() - P->item_first;
   }
+};
+
+int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
+                    BatchPlan& plan, uint32_t rowid_max) {
+  memset(&dq, 0, sizeof dq);
+  PlanState S{seg, q, use_packed, qi};
+  // validate: hostile order / sort specs are MRK_E_INVAL before a row is read
+  if (int rc = S.resolve_order()) return rc;
+  dq.item_first = (uint32_t)plan.items.size();
+  dq.out_q = qi;
+  if (int rc = S.check_query()) return rc;
+  if (int rc = S.resolve_sort()) return rc;
+  // (a sorted query reads attribute rows like a filtered one: the packed block scan's EXT instances only)
+  S.filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || S.order.n_parts > 0;
+  // the evaluation tree and who evaluates it
+  if (int rc = S.shape_query()) return rc;
+  dq.rowid_max = rowid_max;
+  if (int rc = S.translate_filters("filter", q.filters, q.n_filters, false, dq.filters, dq.n_filters)) return rc;
+  if (int rc = S.translate_filters("weight filter", q.weight_filters, q.n_weight_filters, true, dq.wfilters, dq.n_wfilters)) return rc;
+  S.weigh_words(dq);
+  if (int rc = S.choose_cover()) return rc;
+  // pruning bins and the candidate list
+  if (S.order.n_parts)
+    PlanState::bins_by_key(S.order, dq);
+  else if (S.ranker == MRK_RANK_NONE)
+    PlanState::bins_by_rowid(seg, dq);
+  else
+    S.bins_by_weight(dq);
+  S.reserve_candidates(dq, plan);
+  if (S.empty) {
+    dq.n_terms = (uint32_t)S.n;
+    dq.n_items = 0;
+    return MRK_OK;
+  }
+  const PlanTree& T = S.T;
+  plan.algo_bytes += S.bytes;
+  plan.dev_bytes += use_packed ? S.pbytes : S.bytes;
+  plan.any_prox = plan.any_prox || S.prox || T.phrase || T.ph_leaf || T.termpos || T.notnear || T.gen; // (every generic-path candidate goes through the queue)
+  plan.any_tree = plan.any_tree || !S.pure_and;
+  // passes and work items: a bitmap-driven kernel where one applies, else the block scan, one pass per driver keyword
+  if (S.pair_on_bitmaps(dq, plan) || S.tree_on_bitmaps(dq, plan)) return MRK_OK;
+  S.emit_passes(dq, item_bytes, n_queries, plan);
   return MRK_OK;
 }
 
