@@ -377,7 +377,8 @@ int mrk_batch_stats_get(mrk_batch* b, mrk_batch_stats* out);
    sorter's order; the NARROW rows' merges (mrk_topk_merge*, mrk_topk_merge_rows*, mrk_shard_exchange) order by
    (weight, docid) only, so such a query's narrow exchange row leaves with MRK_ROW_DECLINED.  The WIDE rows below
    (MRK_SROW_WORDS, mrk_batch_export_srows, mrk_topk_merge_srows*, mrk_shard_exchange_srows) carry the mapped sort key of every
-   entry and answer a sorted query across segments and shards exactly. */
+   entry and answer a sorted query across segments and shards exactly; the ORDER rows further below (MRK_OROW_WORDS) do the
+   same for a query ordered by a 64-bit key (mrk_query.order), which narrow and wide rows decline. */
 int mrk_batch_device_results(mrk_batch* b, const uint64_t** keys, const uint32_t** counts, const uint64_t** totals);
 
 /* copy those three arrays into caller-owned device buffers (e.g. tensors handed to RCCL);
@@ -494,6 +495,47 @@ int mrk_shard_exchange_srows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* sro
 /* host only: the raw attribute value (the locator's bits; a float's bit pattern) behind a mapped key of a row with this spec
    word.  The map folds a float's -0.0 onto +0.0, so -0.0 reads +0.0. */
 uint32_t mrk_sort_unmap_key(uint64_t spec_word, uint32_t mapped);
+
+/* ------------------------------------------------------------------------------------
+ * Order rows: queries ordered by a 64-bit key (mrk_query.order: one INT64 attribute, or two attributes of <= 32 bits) across
+ * segments and shards.  Narrow and wide rows decline such a query (its mapped key has 64 bits); an order row carries it.  One row
+ * of MRK_OROW_WORDS u64 per query:
+ *   [0 .. MRK_MAX_K-1]         the keys of the narrow row, in the sorter's order
+ *   [MRK_MAX_K] [MRK_MAX_K+1]  count | total_found with MRK_ROW_RERUN / MRK_ROW_DECLINED, as in the narrow row
+ *   [MRK_MAX_K+2 ..]           MRK_MAX_K u64: entry i = the 64-bit order-preserving mapped key of keys[i] (larger = better:
+ *                              map32(first part) << 32 | map32(second part)); zero past count
+ *   [MRK_OROW_WORDS-1]         the order spec word: 0 = a relevance query (the plane is zero and ignored); else
+ *                              bit 0 ordered | bit 1 wide (a 64-bit key) | bit 2 INT64 | bits 4-5 then_weight |
+ *                              part p in the 16 bits from bit 8 + 16 p: bit 0 float | bit 1 desc | bit 2 signed (the high dword
+ *                              of an INT64) | bits 4-9 bit_count -- all that decides whether two shards' mapped keys and tie
+ *                              rules compare and how a mapped key turns back into a raw value, nothing of where a segment
+ *                              stores the columns
+ * A mrk_query.sort query travels in order rows too, and so does a one-part order of <= 32 bits (which is that sort): its 32-bit
+ * mapped key stands in the high dword over a zero low dword and its spec has the wide bit clear.  Relevance queries travel with
+ * spec 0 and a zero plane, so a mixed batch needs one exchange.  The merge orders an ordered query's entries as the unsharded
+ * sorter does: mapped key, then the weight as then_weight says (or not at all), then GLOBAL docid ascending; a relevance query's
+ * exactly as mrk_topk_merge_rows does (words 0 .. MRK_MAX_K+1 of its merged row equal that merge's).  Totals add up and the two
+ * flag bits are OR-ed through.  A shard whose planner declined the query (e.g. a NaN in that shard's float part) sends it with
+ * MRK_ROW_DECLINED, no keys and spec word 0; such a list's spec word is not compared.  The lists that answer the query must agree
+ * in every bit of their spec words.  If they do not, or if the query is ordered and some list carries it with MRK_ROW_DECLINED,
+ * the merged row has MRK_ROW_DECLINED, no keys and the answering lists' spec word (that of the first one, if they differ; the same
+ * row whichever list declined): never a mis-ordered answer.  At most 8 lists.  Each function is the twin of the wide one above, argument for argument.  A batch has ONE
+ * standing destination of the three kinds: setting a second kind while one stands is MRK_E_INVAL.  After an overflow rerun
+ * (MRK_ROW_RERUN), mrk_batch_wait + mrk_batch_export_orows hand out the repaired row, mapped keys included.
+ * ---------------------------------------------------------------------------------- */
+#define MRK_OROW_WORDS (MRK_ROW_WORDS + MRK_MAX_K + 1)
+int mrk_batch_export_orows(mrk_batch* b, uint64_t* orows_dst);
+int mrk_batch_set_orows_dst(mrk_batch* b, uint64_t* orows_dst);
+int mrk_topk_merge_orows(mrk_ctx* ctx, const uint64_t* orows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_orows);
+int mrk_topk_merge_orows_async(mrk_ctx* ctx, const uint64_t* orows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
+                               uint64_t* out_orows, void* wait_event, uint32_t slot);
+int mrk_topk_merge_orows_part(mrk_ctx* ctx, const uint64_t* orows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
+                              uint32_t k, uint64_t* out_orows);
+int mrk_shard_exchange_orows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* orows, uint32_t n_queries, uint32_t k, uint64_t* out_orows,
+                             uint32_t slot);
+/* host only: the value behind a 64-bit mapped key of a row with this order spec word, in mrk_result.order_key's format: the raw
+   int64, or raw0 << 32 | raw1 (a sort spec: raw0 << 32).  A float's -0.0 reads +0.0. */
+uint64_t mrk_order_unmap_key(uint64_t spec_word, uint64_t mapped);
 
 /* merge n_lists sorted partial top-K lists per query (device pointers; relevance order only):
    in_keys[(l*n_queries + q)*MRK_MAX_K + i], in_counts[l*n_queries + q] -> out_keys[q*MRK_MAX_K + i],

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("MRK_LIB_PATH") or os.path.join(CSRC, "libmrk.so")  # 
 
 MRK_OK, MRK_E_INVAL, MRK_E_UNSUPPORTED, MRK_E_HIP, MRK_E_NOMEM, MRK_E_FORMAT = 0, -1, -2, -3, -4, -5
 MRK_MAX_K = 1024
+OROW_WORDS = MRK_MAX_K + 2 + MRK_MAX_K + 1  # MRK_OROW_WORDS: keys | count | total_found | MRK_MAX_K mapped keys (u64) | order spec word
 MRK_MAX_AND_TERMS = 8
 
 
@@ -179,6 +180,14 @@ SYMBOLS = [
     ("mrk_topk_merge_srows_part", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("mrk_shard_exchange_srows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     ("mrk_sort_unmap_key", C.c_uint32, [C.c_uint64, C.c_uint32]),
+    ("mrk_batch_export_orows", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("mrk_batch_set_orows_dst", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("mrk_topk_merge_orows", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("mrk_topk_merge_orows_async", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_uint32]),
+    ("mrk_topk_merge_orows_part", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("mrk_shard_exchange_orows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+    ("mrk_order_unmap_key", C.c_uint64, [C.c_uint64, C.c_uint64]),
     ("mrk_idf", C.c_float, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float]),
     ("mrk_index_from_hits", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("mrk_synth_generate", C.c_int, [C.POINTER(SynthParams), C.POINTER(C.c_void_p)]),

@@ -467,6 +467,7 @@ class _CQueries:
 
 ROW_WORDS = _lib.MRK_MAX_K + 2                     # MRK_ROW_WORDS: keys | count | total_found
 SROW_WORDS = ROW_WORDS + _lib.MRK_MAX_K // 2 + 1   # MRK_SROW_WORDS: ... | MRK_MAX_K mapped sort keys (u32) | sort spec word
+OROW_WORDS = _lib.OROW_WORDS                       # MRK_OROW_WORDS: ... | MRK_MAX_K mapped order keys (u64) | order spec word
 
 
 @dataclass
@@ -667,6 +668,12 @@ class Batch:
         [n_queries][SROW_WORDS] of u64, given by its address: sorted queries leave with their mapped sort keys and spec word."""
         check(lib().mrk_batch_export_srows(self._h, srows_dst))
 
+    def export_orows(self, orows_dst: int) -> None:
+        """The last submit's results as ORDER rows (mrk_batch_export_orows) into a caller-owned device buffer [n_queries][OROW_WORDS]
+        of u64, given by its address: queries ordered by a 64-bit key (Query.order) and sorted queries leave with their 64-bit
+        mapped keys and order spec word, relevance queries with a zero plane and spec 0."""
+        check(lib().mrk_batch_export_orows(self._h, orows_dst))
+
     def search(self, seg: Segment, queries: Sequence[Query]) -> List[Matches]:
         self.submit(seg, queries)
         self.wait()
@@ -737,5 +744,5 @@ def idf(term_docs: int, total_docs: int, plain: bool = False, normalized: bool =
 __all__ = ["open_rt_ram", "open_rt_segment", "SPH_RANK_PROXIMITY_BM25", "SPH_RANK_BM25", "SPH_RANK_NONE", "SPH_RANK_WORDCOUNT", "SPH_RANK_PROXIMITY",
            "SPH_RANK_MATCHANY", "SPH_RANK_FIELDMASK", "SPH_RANK_SPH04",
            "parse_query", "SPH_QUERY_TERM", "SPH_QUERY_AND", "SPH_QUERY_OR", "SPH_QUERY_MAYBE", "SPH_QUERY_ANDNOT", "SPH_QUERY_PHRASE", "SPH_QUERY_PROXIMITY", "SPH_QUERY_QUORUM", "SPH_QUERY_BEFORE", "SPH_QUERY_NEAR", "SPH_QUERY_NOTNEAR", "SPH_QUERY_SENTENCE", "SPH_QUERY_PARAGRAPH",
-           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "SORTKEY_INT64", "OrderPart", "Order", "Matches", "ROW_WORDS", "SROW_WORDS", "Context",
+           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "SORTKEY_INT64", "OrderPart", "Order", "Matches", "ROW_WORDS", "SROW_WORDS", "OROW_WORDS", "Context",
            "Segment", "Batch", "Batcher", "prepare", "idf", "MrkError", "validate_index", "pair_stats"]

@@ -166,7 +166,7 @@ int mrk_comm_allreduce_i64_impl(mrk_ctx* ctx, int64_t* values, uint64_t n) {
   return MRK_OK;
 }
 
-// rows (this shard's [n_queries][row_words], device; row_words = MRK_ROW_WORDS or MRK_SROW_WORDS) --all-gather--> rows_all[slot] --merge kernel--> out_rows;
+// rows (this shard's [n_queries][row_words], device; row_words = MRK_ROW_WORDS, MRK_SROW_WORDS or MRK_OROW_WORDS) --all-gather--> rows_all[slot] --merge kernel--> out_rows;
 // ordered behind `after` (a hipEvent_t recorded behind the rows' producer; NULL = the rows are ready) without a host wait;
 // completion is the merge slot's (mrk_merge_wait).  *gathered_event_out = the event recorded behind the collective.
 int mrk_comm_exchange_impl(mrk_ctx* ctx, const uint64_t* rows, uint32_t n_queries, uint32_t row_words, hipEvent_t after, uint32_t slot, const uint64_t** rows_all_out,

@@ -412,8 +412,12 @@ struct SortSelArgs {
   // a standing wide destination (mrk_batch_set_srows_dst): the kernel writes the sorted queries' wide rows itself (the instance
   // launched without one is compiled without this branch)
   uint64_t* srows_dst;     // device [n_queries][SROW_WORDS] or NULL
-  const uint64_t* q_total; // [n_queries]   (read with srows_dst only)
+  const uint64_t* q_total; // [n_queries]   (read with a standing destination only)
   const uint32_t* q_flags; // [n_queries] QF_*
+  // order rows (MRK_OROW_WORDS): the whole 64-bit mapped key of out_keys' entries (a sort's 32-bit key in the high dword); NULL = the
+  // batch never held a query ordered by a 64-bit key and has no standing order-row destination
+  uint64_t* out_mkeys64;   // [n_queries][KCAP] or NULL
+  uint64_t* orows_dst;     // a standing order-row destination (mrk_batch_set_orows_dst): device [n_queries][OROW_WORDS] or NULL (excludes srows_dst)
 };
 void launch_sort_select(const SortSelArgs& a, void* stream);
 
@@ -532,6 +536,27 @@ void launch_pack_srows(const PackSRowsArgs& a, void* stream);
 // Merge of <= 8 wide rows per query: MergeRowsArgs with rows of SROW_WORDS.  A sorted query orders by (mapped key, the weight as
 // its tie rule says, ~docid); a relevance query exactly as merge_rows_kernel.
 void launch_merge_srows(const MergeRowsArgs& a, void* stream);
+
+// Order rows (mrk_sortsel.hip; MRK_OROW_WORDS, include/mrk.h): keys | count | total_found | KCAP mapped keys (u64) | order spec word
+constexpr int OROW_WORDS = MRK_OROW_WORDS;
+constexpr int OROW_MKEYS = KCAP + 2, OROW_SPEC = OROW_WORDS - 1; // word offsets of the u64 plane and of the spec word
+struct PackORowsArgs {
+  const DevQuery* queries;  // the order spec is the query's own (order_spec_word over sort_* / ord_*)
+  const uint64_t* keys;     // [n][KCAP]
+  const uint64_t* mkeys64;  // [n][KCAP] or NULL: then no query of the batch has a 64-bit key and ...
+  const uint32_t* mkeys;    // ... [n][KCAP] (or NULL: no sorted query either) holds the sorts' 32-bit mapped keys
+  const uint32_t* cnt;
+  const uint64_t* total;
+  uint64_t* rows;           // [n][OROW_WORDS]
+  const uint32_t* flags;    // as PackRowsArgs
+  const uint32_t* declined; // [n] == 1: the planner declined the query on this segment
+  uint32_t n;
+  uint32_t skip_sorted;     // != 0: the sorted and ordered queries' rows are already written (sort_select_kernel with a standing destination)
+};
+void launch_pack_orows(const PackORowsArgs& a, void* stream);
+// Merge of <= 8 order rows per query: MergeRowsArgs with rows of OROW_WORDS.  An ordered query orders by (64-bit mapped key, the
+// weight as its tie rule says, ~docid); a relevance query exactly as merge_rows_kernel.
+void launch_merge_orows(const MergeRowsArgs& a, void* stream);
 
 void launch_scan(const ScanArgs& a, void* stream);
 void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen = false); // a.scand: the instances that carry the sort

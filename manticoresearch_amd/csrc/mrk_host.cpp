@@ -113,6 +113,7 @@ struct mrk_batch {
   mrk_ctx* ctx = nullptr;
   uint64_t* rows_dst = nullptr; // mrk_batch_set_rows_dst
   uint64_t* srows_dst = nullptr; // mrk_batch_set_srows_dst (wide rows; excludes rows_dst)
+  uint64_t* orows_dst = nullptr; // mrk_batch_set_orows_dst (order rows; excludes the other two)
   bool host_copied = true;      // per-query keys / counts / totals of the last submit are in pinned host memory
   hipStream_t stream = nullptr; // every batch runs on its own stream: batches of one context overlap on the device
   uint32_t max_queries = 0;
@@ -150,11 +151,15 @@ struct mrk_batch {
   DevBuf<uint64_t> d_cand;
   DevBuf<uint32_t> d_shist;  // sorted hit-ranked queries: the scan's histogram of queued matches' attribute bins [n][NBINS], then the threshold words [n * QSTRIDE]
   DevBuf<uint32_t> d_out_mkeys; // [max_queries][KCAP] mapped sort keys of d_out_keys' entries (sorted queries; reserved with d_scand)
+  DevBuf<uint64_t> d_out_mkeys64; // [max_queries][KCAP] the whole 64-bit mapped keys (order rows): reserved with d_scand by the first batch that holds a 64-bit order or has a standing order-row destination
   DevBuf<uint64_t> d_scand;  // 16-byte candidates of the sorted queries (two words each); reserved by the first batch that holds one
   PinBuf<uint32_t> h_flags;
   // per query: != 0 when the planner declined it on the last submit's segment; travels in the exchange rows
+  // ([max_queries, 2 max_queries): the words as ORDER rows read them -- a 64-bit order is no decline there; uploaded when the
+  // submit holds one: decl_order)
   PinBuf<uint32_t> h_decl;
   DevBuf<uint32_t> d_decl;
+  bool decl_order = false;
   bool decl_dirty = false; // d_decl holds non-zero words of an earlier submit
   bool any_declined = false;
   // HBM match queues of the hit-ranked queries (scan kernels -> rank_kernel): [0] plain trees, [1] PHRASE & co
@@ -172,7 +177,7 @@ struct mrk_batch {
   std::vector<int32_t> status;
   // sorted queries of the last submit: the locator of the primary attribute (bits 0 = relevance) and the raw values of the returned rows
   // (mrk_query.order: `order` = 1 one part of <= 32 bits, planned as a sort; 2 = a 64-bit key, whose second part is p1 and which
-  // leaves in no exchange row; mrk_result.order_key instead of .sort_key)
+  // leaves in ORDER rows only (MRK_OROW_WORDS); mrk_result.order_key instead of .sort_key)
   struct SortLoc { uint32_t item = 0, shift = 0, bits = 0, order = 0; mrk::OrderPart p1{0, 0, 0, 0}; };
   std::vector<SortLoc> sort_loc;
   std::vector<uint32_t> sort_key;
@@ -868,6 +873,7 @@ static void mrk_batch_destroy_impl(mrk_batch* b) {
   b->d_cand.release();
   b->d_scand.release();
   b->d_out_mkeys.release();
+  b->d_out_mkeys64.release();
   b->d_shist.release();
   b->h_flags.release();
   b->h_decl.release();
@@ -898,7 +904,7 @@ static int mrk_batch_create_impl(mrk_ctx* ctx, uint32_t max_queries, mrk_batch**
       (rc = b->h_total.reserve(nq)) || (rc = b->d_queries.reserve(nq)) ||
       (rc = b->d_state.reserve(nq * (STATE_BYTES + (size_t)NBINS * 4))) || (rc = b->d_list_first.reserve(nq)) || (rc = b->d_list_n.reserve(nq)) ||
       (rc = b->d_kq.reserve(nq)) || (rc = b->d_out_keys.reserve(nq * KCAP)) || (rc = b->d_out_cnt.reserve(nq)) ||
-      (rc = b->h_flags.reserve(nq)) || (rc = b->h_cand_n.reserve(nq)) || (rc = b->h_decl.reserve(nq)) || (rc = b->d_decl.reserve(nq)) || (rc = b->d_mq_count.reserve(3 * mrk::MQ_SHARDS))) {
+      (rc = b->h_flags.reserve(nq)) || (rc = b->h_cand_n.reserve(nq)) || (rc = b->h_decl.reserve(2 * (size_t)nq)) || (rc = b->d_decl.reserve(2 * (size_t)nq)) || (rc = b->d_mq_count.reserve(3 * mrk::MQ_SHARDS))) {
     mrk_batch_destroy_impl(b);
     return rc;
   }
@@ -1094,6 +1100,14 @@ static void bind_select(const mrk_batch* b, const mrk_segment* seg, uint32_t n_q
   se.rowid_hi = (uint32_t)(seg->dev.rowid_base + docs - 1);
 }
 
+// what pack_orows_kernel reads of the batch's last submit (the caller sets rows, flags, n, skip_sorted)
+static void bind_pack_orows(mrk_batch* b, mrk::PackORowsArgs& pa) {
+  pa.queries = b->d_queries.p, pa.keys = b->d_out_keys.p, pa.mkeys64 = b->d_out_mkeys64.p, pa.mkeys = b->d_out_mkeys.p;
+  pa.cnt = b->d_out_cnt.p, pa.total = b->d_q_total.p;
+  // (a 64-bit order is word 1 -- declined -- for narrow and wide rows: the submit that held one uploaded the order rows' own words)
+  pa.declined = !b->any_declined ? nullptr : b->decl_order ? b->d_decl.p + b->max_queries : b->d_decl.p;
+}
+
 static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n) {
   if (!b || !seg || (!queries && n)) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: NULL argument");
   if (n > b->max_queries) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: %u queries > batch capacity %u", n, b->max_queries);
@@ -1181,6 +1195,9 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   if (use_packed && ((rc = b->d_cand.reserve(cand_total + 64)) || (rc = b->d_sel.reserve(2 * (size_t)n + mrk::sel_slice_slots(cand_total, n))))) return rc;
   const bool any_sort = use_packed && plan.sort_total != 0;
   if (any_sort && ((rc = b->d_scand.reserve(2 * plan.sort_total + 64)) || (rc = b->d_out_mkeys.reserve((size_t)b->max_queries * KCAP)))) return rc;
+  bool any_order = false; // a 64-bit key: the order rows' plane, from here on
+  for (uint32_t i = 0; i < n && any_sort; ++i) any_order = any_order || b->sort_loc[i].order == mrk::SORT_ON_ORDER;
+  if (any_sort && (any_order || b->orows_dst) && (rc = b->d_out_mkeys64.reserve((size_t)b->max_queries * KCAP))) return rc;
 
   static const bool phase_timing = getenv("MRK_SUBMIT_TIMING") != nullptr;
   auto lap = [&](const char* what) {
@@ -1257,7 +1274,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     se.q_flags = b->d_q_flags.p;
     se.h_flags = b->h_flags.p;
     se.h_cand_n = b->h_cand_n.p;
-    const bool standing = b->rows_dst || b->srows_dst;
+    const bool standing = b->rows_dst || b->srows_dst || b->orows_dst;
     if (!standing) se.h_keys = b->h_keys.p, se.h_cnt = b->h_cnt.p, se.h_total = b->h_total.p;
     // a standing rows destination (shard exchange): the sort pass writes the exchange rows itself (narrow rows; the wide
     // rows of relevance queries are packed behind the selection, below)
@@ -1270,6 +1287,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
       ss.out_keys = b->d_out_keys.p, ss.out_cnt = b->d_out_cnt.p, ss.out_mkeys = b->d_out_mkeys.p;
       if (!standing) ss.h_keys = b->h_keys.p, ss.h_cnt = b->h_cnt.p;
       ss.srows_dst = b->srows_dst, ss.q_total = b->d_q_total.p, ss.q_flags = b->d_q_flags.p; // a standing wide destination: the sorted queries' rows leave here
+      ss.out_mkeys64 = b->d_out_mkeys64.p, ss.orows_dst = b->orows_dst;
       mrk::launch_sort_select(ss, st2);
     }
   } else {
@@ -1291,12 +1309,18 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     bool any = false;
     // (a sorted query's NARROW row is no answer to a merge by (weight, docid): in that exchange it counts as declined -- word 2,
     // which the wide rows, whose merge compares the mapped keys, do not take for a decline)
-    // (a query ordered by a 64-bit key, mrk_query.order, fits neither row format: word 1 in every exchange)
+    // (a query ordered by a 64-bit key, mrk_query.order, fits neither of these two row formats: word 1; ORDER rows read words of their own, below)
     for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits) || b->sort_loc[i].order == mrk::SORT_ON_ORDER;
     b->any_declined = any;
     if (any || b->decl_dirty) {
       for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = (b->status[i] != MRK_OK || b->sort_loc[i].order == mrk::SORT_ON_ORDER) ? 1u : (b->rows_dst && b->sort_loc[i].bits) ? 2u : 0u;
       HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
+    }
+    b->decl_order = any_order;
+    if (any_order) { // the same words for ORDER rows, which carry a 64-bit key
+      uint32_t* ho = b->h_decl.p + b->max_queries;
+      for (uint32_t i = 0; i < n; ++i) ho[i] = b->status[i] != MRK_OK ? 1u : 0u;
+      HIP_TRY(hipMemcpyAsync(b->d_decl.p + b->max_queries, ho, n * 4, hipMemcpyHostToDevice, st2));
     }
     b->decl_dirty = any;
   }
@@ -1321,6 +1345,15 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     pa.skip_sorted = use_packed && any_sort ? 1u : 0u;
     launch_pack_srows(pa, st2);
   }
+  if (b->orows_dst) { // the standing order-row export: relevance and declined queries' rows (sort_select_kernel wrote the others')
+    mrk::PackORowsArgs pa{};
+    bind_pack_orows(b, pa);
+    pa.rows = b->orows_dst;
+    pa.flags = use_packed ? b->d_q_flags.p : nullptr;
+    pa.n = n;
+    pa.skip_sorted = use_packed && any_sort ? 1u : 0u;
+    mrk::launch_pack_orows(pa, st2);
+  }
   HIP_TRY(hipGetLastError());
   b->packed_run = use_packed;
   b->last_seg = seg;
@@ -1332,7 +1365,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   b->last_sort = any_sort;
   lap("select launched");
   // ---- results to pinned host memory: the packed path's selection wrote them itself; the VLB path copies
-  b->host_copied = b->rows_dst == nullptr && b->srows_dst == nullptr;
+  b->host_copied = b->rows_dst == nullptr && b->srows_dst == nullptr && b->orows_dst == nullptr;
   if (b->host_copied && !use_packed) {
     HIP_TRY(hipMemcpyAsync(b->h_cnt.p, b->d_out_cnt.p, n * 4, hipMemcpyDeviceToHost, st2));
     HIP_TRY(hipMemcpyAsync(b->h_total.p, b->d_q_total.p, n * 8, hipMemcpyDeviceToHost, st2));
@@ -1394,6 +1427,8 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
     return rc;
   const bool sorted = passes[0].sort_on != 0; // (the query's order travels with its passes: sort_* of the DevQuery planned at submit)
   if (sorted && ((rc = r->d_scand.reserve(2 * cap + 64)) || (rc = r->d_out_mkeys.reserve((size_t)r->max_queries * KCAP)))) return rc;
+  const bool keys64 = sorted && b->d_out_mkeys64.p != nullptr; // the batch keeps the 64-bit mapped keys (order rows)
+  if (keys64 && (rc = r->d_out_mkeys64.reserve((size_t)r->max_queries * KCAP))) return rc;
   memcpy(r->h_queries.p, passes.data(), passes.size() * sizeof(DevQuery));
   if (n_items) memcpy(r->h_items.p, items_pk.data(), n_items * sizeof(DevItem));
   HIP_TRY(hipMemcpyAsync(r->d_queries.p, r->h_queries.p, passes.size() * sizeof(DevQuery), hipMemcpyHostToDevice, st));
@@ -1429,6 +1464,7 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
     mrk::SortSelArgs ss{};
     ss.queries = r->d_queries.p, ss.q_hist = r->d_q_hist.p, ss.q_cand_n = r->d_q_cand_n.p, ss.scand = r->d_scand.p, ss.n_queries = 1;
     ss.out_keys = r->d_out_keys.p, ss.out_cnt = r->d_out_cnt.p, ss.out_mkeys = r->d_out_mkeys.p;
+    ss.out_mkeys64 = keys64 ? r->d_out_mkeys64.p : nullptr;
     mrk::launch_sort_select(ss, st);
   }
   HIP_TRY(hipGetLastError());
@@ -1442,6 +1478,7 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   HIP_TRY(hipMemcpyAsync(b->d_q_total.p + qi, r->d_q_total.p, 8, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipMemcpyAsync(b->d_out_keys.p + (size_t)qi * KCAP, r->d_out_keys.p, (size_t)KCAP * 8, hipMemcpyDeviceToDevice, st));
   if (sorted) HIP_TRY(hipMemcpyAsync(b->d_out_mkeys.p + (size_t)qi * KCAP, r->d_out_mkeys.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st)); // (mrk_batch_export_srows)
+  if (keys64) HIP_TRY(hipMemcpyAsync(b->d_out_mkeys64.p + (size_t)qi * KCAP, r->d_out_mkeys64.p, (size_t)KCAP * 8, hipMemcpyDeviceToDevice, st)); // (mrk_batch_export_orows)
   HIP_TRY(hipMemsetAsync(b->d_q_flags.p + qi, 0, 4, st)); // the device-side row is good again
   HIP_TRY(hipStreamSynchronize(st));
   if (flags & QF_ARENA) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the generic evaluator ran out of hit-list memory (ctx tunable gen_spill_mb)", qi);
@@ -1576,6 +1613,7 @@ static int mrk_batch_export_device_impl(mrk_batch* b, uint64_t* keys_dst, uint32
 extern "C" int mrk_batch_set_rows_dst(mrk_batch* b, uint64_t* rows_dst) {
   if (!b) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_rows_dst: NULL batch");
   if (rows_dst && b->srows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_rows_dst: the batch has a standing wide destination (mrk_batch_set_srows_dst)");
+  if (rows_dst && b->orows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_rows_dst: the batch has a standing order-row destination (mrk_batch_set_orows_dst)");
   b->rows_dst = rows_dst;
   return MRK_OK;
 }
@@ -1583,7 +1621,16 @@ extern "C" int mrk_batch_set_rows_dst(mrk_batch* b, uint64_t* rows_dst) {
 extern "C" int mrk_batch_set_srows_dst(mrk_batch* b, uint64_t* srows_dst) {
   if (!b) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_srows_dst: NULL batch");
   if (srows_dst && b->rows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_srows_dst: the batch has a standing narrow destination (mrk_batch_set_rows_dst)");
+  if (srows_dst && b->orows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_srows_dst: the batch has a standing order-row destination (mrk_batch_set_orows_dst)");
   b->srows_dst = srows_dst;
+  return MRK_OK;
+}
+
+extern "C" int mrk_batch_set_orows_dst(mrk_batch* b, uint64_t* orows_dst) {
+  if (!b) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_orows_dst: NULL batch");
+  if (orows_dst && b->rows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_orows_dst: the batch has a standing narrow destination (mrk_batch_set_rows_dst)");
+  if (orows_dst && b->srows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_orows_dst: the batch has a standing wide destination (mrk_batch_set_srows_dst)");
+  b->orows_dst = orows_dst;
   return MRK_OK;
 }
 
@@ -1628,15 +1675,36 @@ static int mrk_batch_export_srows_impl(mrk_batch* b, uint64_t* srows_dst) {
   return MRK_OK;
 }
 
+static int mrk_batch_export_orows_impl(mrk_batch* b, uint64_t* orows_dst) {
+  if (!b || !orows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_orows: NULL argument");
+  HIP_TRY(hipSetDevice(b->ctx->device));
+  mrk::PackORowsArgs pa{};
+  bind_pack_orows(b, pa);
+  pa.rows = orows_dst;
+  pa.flags = b->packed_run ? b->d_q_flags.p : nullptr;
+  pa.n = b->n_queries;
+  mrk::launch_pack_orows(pa, b->stream); // behind the batch's selection kernels
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  b->in_flight = false;
+  return MRK_OK;
+}
+
+// the three exchange-row formats: the row width and the merge kernel are all that differ between their entry points
+enum RowKind { ROWS_NARROW, ROWS_WIDE, ROWS_ORDER };
+
 // rows of n_lists shards -> merged rows; lists [l][list_stride][ROW_WORDS], queries [0, n_queries) of each, out rows at out_first + q
-// (wide: rows of SROW_WORDS through merge_srows_kernel; the callers keep n_lists <= 8 there)
+// (wide: rows of SROW_WORDS through merge_srows_kernel, order rows of OROW_WORDS through merge_orows_kernel; the callers keep
+// n_lists <= 8 there)
 static void launch_rows_merge(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t list_stride, uint32_t n_queries, uint32_t k,
-                              uint64_t* out_rows, uint32_t out_first, uint32_t* flags_any, bool wide = false) {
+                              uint64_t* out_rows, uint32_t out_first, uint32_t* flags_any, RowKind kind = ROWS_NARROW) {
   if (n_lists <= 8) {
     mrk::MergeRowsArgs mr{};
     mr.in_rows = rows_all, mr.n_lists = n_lists, mr.list_stride = list_stride, mr.n_queries = n_queries, mr.k = k;
     mr.out_rows = out_rows, mr.out_first = out_first, mr.flags_any = flags_any;
-    if (wide)
+    if (kind == ROWS_ORDER)
+      launch_merge_orows(mr, ctx->merge_stream);
+    else if (kind == ROWS_WIDE)
       launch_merge_srows(mr, ctx->merge_stream);
     else
       launch_merge_rows(mr, ctx->merge_stream);
@@ -1652,12 +1720,12 @@ static void launch_rows_merge(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n
 }
 
 static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
-                                   uint64_t* out_rows, bool wide = false) {
+                                   uint64_t* out_rows, RowKind kind = ROWS_NARROW) {
   if (!ctx || !rows_all || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows: NULL argument");
   if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows: k %u outside 1..%d", k, MRK_MAX_K);
-  if (wide && (n_lists == 0 || n_lists > 8)) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_srows: %u lists (1..8)", n_lists);
+  if (kind != ROWS_NARROW && (n_lists == 0 || n_lists > 8)) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_%s: %u lists (1..8)", kind == ROWS_ORDER ? "orows" : "srows", n_lists);
   HIP_TRY(hipSetDevice(ctx->device));
-  launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, wide);
+  launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, kind);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->merge_stream));
   return MRK_OK;
@@ -1666,27 +1734,27 @@ static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint
 // what a rank of the query-partitioned exchange does with its receive buffer: lists [n_lists][list_stride] rows, the rank's
 // `count` queries, merged rows written at out_rows[first + q]
 static int mrk_topk_merge_rows_part_impl(mrk_ctx* ctx, const uint64_t* rows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first,
-                                        uint32_t count, uint32_t k, uint64_t* out_rows, bool wide = false) {
+                                        uint32_t count, uint32_t k, uint64_t* out_rows, RowKind kind = ROWS_NARROW) {
   if (!ctx || !rows_recv || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: NULL argument");
   if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: k %u outside 1..%d", k, MRK_MAX_K);
   if (n_lists == 0 || n_lists > 8 || count > list_stride) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: %u lists (1..8), %u queries of stride %u", n_lists, count, list_stride);
   HIP_TRY(hipSetDevice(ctx->device));
-  launch_rows_merge(ctx, rows_recv, n_lists, list_stride, count, k, out_rows, first, nullptr, wide);
+  launch_rows_merge(ctx, rows_recv, n_lists, list_stride, count, k, out_rows, first, nullptr, kind);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->merge_stream));
   return MRK_OK;
 }
 
 static int mrk_topk_merge_rows_async_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
-                                         uint64_t* out_rows, void* wait_event, uint32_t slot, bool wide = false) {
+                                         uint64_t* out_rows, void* wait_event, uint32_t slot, RowKind kind = ROWS_NARROW) {
   if (!ctx || !rows_all || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_async: NULL argument");
-  if (wide && (n_lists == 0 || n_lists > 8)) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_srows_async: %u lists (1..8)", n_lists);
+  if (kind != ROWS_NARROW && (n_lists == 0 || n_lists > 8)) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_%s_async: %u lists (1..8)", kind == ROWS_ORDER ? "orows" : "srows", n_lists);
   if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_async: k %u outside 1..%d", k, MRK_MAX_K);
   if (slot >= MRK_MERGE_SLOTS) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_async: slot %u of %d", slot, MRK_MERGE_SLOTS);
   HIP_TRY(hipSetDevice(ctx->device));
   if (!ctx->merge_done[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->merge_done[slot], hipEventDisableTiming));
   if (wait_event) HIP_TRY(hipStreamWaitEvent(ctx->merge_stream, (hipEvent_t)wait_event, 0));
-  launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, wide);
+  launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, kind);
   HIP_TRY(hipGetLastError());
 
   HIP_TRY(hipEventRecord(ctx->merge_done[slot], ctx->merge_stream));
@@ -1960,16 +2028,31 @@ extern "C" int mrk_batch_export_srows(mrk_batch* b, uint64_t* srows_dst) {
   return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_export_srows_impl(b, srows_dst); });
 }
 extern "C" int mrk_topk_merge_srows(mrk_ctx* ctx, const uint64_t* srows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_srows) {
-  return on_worker(ctx, [&] { return mrk_topk_merge_rows_impl(ctx, srows_all, n_lists, n_queries, k, out_srows, true); });
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_impl(ctx, srows_all, n_lists, n_queries, k, out_srows, ROWS_WIDE); });
 }
 extern "C" int mrk_topk_merge_srows_async(mrk_ctx* ctx, const uint64_t* srows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
                                           uint64_t* out_srows, void* wait_event, uint32_t slot) {
-  return on_worker(ctx, [&] { return mrk_topk_merge_rows_async_impl(ctx, srows_all, n_lists, n_queries, k, out_srows, wait_event, slot, true); });
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_async_impl(ctx, srows_all, n_lists, n_queries, k, out_srows, wait_event, slot, ROWS_WIDE); });
 }
 extern "C" int mrk_topk_merge_srows_part(mrk_ctx* ctx, const uint64_t* srows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
                                          uint32_t k, uint64_t* out_srows) {
-  return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, srows_recv, n_lists, list_stride, first, count, k, out_srows, true); });
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, srows_recv, n_lists, list_stride, first, count, k, out_srows, ROWS_WIDE); });
 }
+extern "C" int mrk_batch_export_orows(mrk_batch* b, uint64_t* orows_dst) {
+  return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_export_orows_impl(b, orows_dst); });
+}
+extern "C" int mrk_topk_merge_orows(mrk_ctx* ctx, const uint64_t* orows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_orows) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_impl(ctx, orows_all, n_lists, n_queries, k, out_orows, ROWS_ORDER); });
+}
+extern "C" int mrk_topk_merge_orows_async(mrk_ctx* ctx, const uint64_t* orows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
+                                          uint64_t* out_orows, void* wait_event, uint32_t slot) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_async_impl(ctx, orows_all, n_lists, n_queries, k, out_orows, wait_event, slot, ROWS_ORDER); });
+}
+extern "C" int mrk_topk_merge_orows_part(mrk_ctx* ctx, const uint64_t* orows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
+                                         uint32_t k, uint64_t* out_orows) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, orows_recv, n_lists, list_stride, first, count, k, out_orows, ROWS_ORDER); });
+}
+extern "C" uint64_t mrk_order_unmap_key(uint64_t spec_word, uint64_t mapped) { return mrk::order_unmap_key(spec_word, mapped); }
 extern "C" uint32_t mrk_sort_unmap_key(uint64_t spec_word, uint32_t mapped) { return mrk::sort_unmap_key(spec_word, mapped); }
 extern "C" int mrk_merge_wait(mrk_ctx* ctx, uint32_t slot) {
   return on_worker(ctx, [&] { return mrk_merge_wait_impl(ctx, slot); });
@@ -1998,10 +2081,11 @@ extern "C" int mrk_comm_allreduce_i64(mrk_ctx* ctx, int64_t* values, uint64_t n)
   if (!ctx || (!values && n)) return mrk_fail(MRK_E_INVAL, "mrk_comm_allreduce_i64: NULL argument");
   return on_worker(ctx, [&] { return mrk_comm_allreduce_i64_impl(ctx, values, n); });
 }
-// one body for narrow rows (MRK_ROW_WORDS) and wide ones (MRK_SROW_WORDS): the row width and the merge kernel are all that differ
+// one body for narrow rows (MRK_ROW_WORDS), wide ones (MRK_SROW_WORDS) and order rows (MRK_OROW_WORDS): the row width and the merge
+// kernel are all that differ
 static int shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, uint32_t n_queries, uint32_t k, uint64_t* out_rows, uint32_t slot,
-                          bool wide) {
-  const uint32_t row_words = wide ? MRK_SROW_WORDS : MRK_ROW_WORDS;
+                          RowKind kind) {
+  const uint32_t row_words = kind == ROWS_ORDER ? MRK_OROW_WORDS : kind == ROWS_WIDE ? MRK_SROW_WORDS : MRK_ROW_WORDS;
   if (!ctx || !rows || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: NULL argument");
   if (slot >= MRK_MERGE_SLOTS) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: slot %u of %d", slot, MRK_MERGE_SLOTS);
   if (batch && batch->ctx != ctx) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: batch and context do not belong together");
@@ -2025,22 +2109,26 @@ static int shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, 
       uint32_t* flags_dev = nullptr;
       HIP_TRY(hipStreamWaitEvent(ctx->merge_stream, gathered, 0));
       if ((rc = mrk_comm_flags_begin(ctx, slot, &flags_dev))) return rc;
-      if (count) launch_rows_merge(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), per, count, k, out_rows, first, flags_dev, wide);
+      if (count) launch_rows_merge(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), per, count, k, out_rows, first, flags_dev, kind);
       HIP_TRY(hipGetLastError());
       return mrk_comm_flags_finish(ctx, slot);
     }
     int rc = mrk_comm_exchange_impl(ctx, rows, n_queries, row_words, after, slot, &rows_all, &gathered);
     if (rc != MRK_OK) return rc;
-    return mrk_topk_merge_rows_async_impl(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), n_queries, k, out_rows, (void*)gathered, slot, wide);
+    return mrk_topk_merge_rows_async_impl(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), n_queries, k, out_rows, (void*)gathered, slot, kind);
   });
 }
 extern "C" int mrk_shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, uint32_t n_queries, uint32_t k, uint64_t* out_rows,
                                   uint32_t slot) {
-  return shard_exchange(ctx, batch, rows, n_queries, k, out_rows, slot, false);
+  return shard_exchange(ctx, batch, rows, n_queries, k, out_rows, slot, ROWS_NARROW);
 }
 extern "C" int mrk_shard_exchange_srows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* srows, uint32_t n_queries, uint32_t k, uint64_t* out_srows,
                                         uint32_t slot) {
-  return shard_exchange(ctx, batch, srows, n_queries, k, out_srows, slot, true);
+  return shard_exchange(ctx, batch, srows, n_queries, k, out_srows, slot, ROWS_WIDE);
+}
+extern "C" int mrk_shard_exchange_orows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* orows, uint32_t n_queries, uint32_t k, uint64_t* out_orows,
+                                        uint32_t slot) {
+  return shard_exchange(ctx, batch, orows, n_queries, k, out_orows, slot, ROWS_ORDER);
 }
 extern "C" int mrk_shard_slice(uint32_t n_queries, int n_ranks, int rank, uint32_t* first, uint32_t* count) {
   if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return mrk_fail(MRK_E_INVAL, "mrk_shard_slice: rank %d of %d", rank, n_ranks);

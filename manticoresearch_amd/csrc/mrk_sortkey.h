@@ -133,5 +133,41 @@ MRK_HD inline OrderGeom order_geom(uint32_t a_lo, uint32_t a_hi, uint32_t b_lo, 
   return g;
 }
 
+// ---------------------------------------------------------------------------------------
+// The order spec word of an ORDER row (MRK_OROW_WORDS, include/mrk.h), whose entries carry a 64-bit mapped key: everything that
+// decides whether two shards' mapped keys and tie rules compare and how a mapped key turns back into a raw value, and nothing of
+// where a segment stores the columns.  0 = a relevance query.
+//   bit 0 ordered | bit 1 wide (a 64-bit key; clear = a sort: the 32-bit mapped key in the high dword, the low dword zero) |
+//   bit 2 INT64 (one signed 64-bit attribute) | bits 4-5 then_weight | part p in the 16 bits from bit 8 + 16 p:
+//   bit 0 float | bit 1 desc | bit 2 signed (the high dword of an INT64) | bits 4-9 bit_count
+// ---------------------------------------------------------------------------------------
+constexpr uint64_t OSPEC_ORDERED = 1, OSPEC_WIDE = 2, OSPEC_INT64 = 4;
+constexpr uint32_t OSPEC_PART_FLOAT = 1, OSPEC_PART_DESC = 2, OSPEC_PART_SIGNED = 4;
+MRK_HD inline uint64_t order_spec_part(uint32_t flags, uint32_t bits) {
+  return ((flags & SORT_FLOAT) ? OSPEC_PART_FLOAT : 0u) | ((flags & SORT_DESC) ? OSPEC_PART_DESC : 0u) | ((flags & SORT_SIGNED) ? OSPEC_PART_SIGNED : 0u) | ((uint64_t)(bits & 63u) << 4);
+}
+// from a DevQuery's own words: sort_on (SORT_ON_ATTR / SORT_ON_ORDER), the first part's sort_flags / sort_bits, the second's ord_flags /
+// ord_bits (read for SORT_ON_ORDER only), sort_tie
+MRK_HD inline uint64_t order_spec_word(uint32_t sort_on, uint32_t flags0, uint32_t bits0, uint32_t flags1, uint32_t bits1, uint32_t tie) {
+  if (!sort_on) return 0ull;
+  uint64_t w = OSPEC_ORDERED | ((uint64_t)(tie & 3u) << 4) | (order_spec_part(flags0, bits0) << 8);
+  if (sort_on == SORT_ON_ORDER) w |= OSPEC_WIDE | ((flags0 & SORT_SIGNED) ? OSPEC_INT64 : 0u) | (order_spec_part(flags1, bits1) << 24);
+  return w;
+}
+MRK_HD inline uint32_t order_spec_tie(uint64_t spec) { return spec ? (uint32_t)(spec >> 4) & 3u : 1u; } // relevance = weight desc
+// part p's SORT_FLOAT | SORT_DESC | SORT_SIGNED out of a spec word
+MRK_HD inline uint32_t order_spec_flags(uint64_t spec, uint32_t p) {
+  const uint32_t f = (uint32_t)(spec >> (8u + 16u * p));
+  return ((f & OSPEC_PART_FLOAT) ? SORT_FLOAT : 0u) | ((f & OSPEC_PART_DESC) ? SORT_DESC : 0u) | ((f & OSPEC_PART_SIGNED) ? SORT_SIGNED : 0u);
+}
+// the inverse of the 64-bit map under a spec word, in mrk_result.order_key's format: the raw int64, or raw0 << 32 | raw1 (a sort
+// spec: raw0 << 32); a float's -0.0 reads +0.0
+MRK_HD inline uint64_t order_unmap_key(uint64_t spec, uint64_t mapped) {
+  if (!spec) return 0ull;
+  const uint32_t r0 = order_unmap_part((uint32_t)(mapped >> 32), order_spec_flags(spec, 0));
+  if (!(spec & OSPEC_WIDE)) return (uint64_t)r0 << 32;
+  return ((uint64_t)r0 << 32) | order_unmap_part((uint32_t)mapped, order_spec_flags(spec, 1));
+}
+
 #undef MRK_HD
 } // namespace mrk

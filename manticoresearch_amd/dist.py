@@ -126,8 +126,104 @@ def merge_srows_np(srows_all: np.ndarray, k: int) -> np.ndarray:
     return out
 
 
+# MRK_OROW_WORDS, the order row that carries a query ordered by a 64-bit key (mrk_query.order) across shards:
+#   keys | count | total_found | MRK_MAX_K mapped keys (u64) | order spec word (0 = a relevance query)
+OROW_WORDS = _lib.OROW_WORDS
+OROW_MKEYS, OROW_SPEC = MRK_MAX_K + 2, OROW_WORDS - 1  # word offsets of the u64 plane and of the spec word
+OSPEC_ORDERED, OSPEC_WIDE, OSPEC_INT64 = 1, 2, 4       # + then_weight << 4 + part p << (8 + 16 p) (mrk_sortkey.h, order_spec_word)
+OSPEC_PART_FLOAT, OSPEC_PART_DESC, OSPEC_PART_SIGNED = 1, 2, 4  # + bit_count << 4
+
+
+def order_spec_word(parts, then_weight: int) -> int:
+    """The spec word of an ordered query's order row.  parts: one or two objects with kind / desc / bit_count (api.OrderPart;
+    an api.Sort is one part).  One part of <= 32 bits is a sort (wide bit clear); kind SORTKEY_INT64 stands alone."""
+    def part(kind, desc, bits, signed=False):
+        return (OSPEC_PART_FLOAT if kind == 1 else 0) | (OSPEC_PART_DESC if desc else 0) | (OSPEC_PART_SIGNED if signed else 0) | ((bits & 63) << 4)
+
+    parts = list(parts)
+    assert 1 <= len(parts) <= 2
+    w = OSPEC_ORDERED | ((then_weight & 3) << 4)
+    p0 = parts[0]
+    if int(p0.kind) == 2:  # high dword signed, low dword plain, one direction
+        assert len(parts) == 1
+        return w | OSPEC_WIDE | OSPEC_INT64 | (part(0, p0.desc, 32, True) << 8) | (part(0, p0.desc, 32) << 24)
+    w |= part(int(p0.kind), p0.desc, int(p0.bit_count)) << 8
+    if len(parts) == 2:
+        w |= OSPEC_WIDE | (part(int(parts[1].kind), parts[1].desc, int(parts[1].bit_count)) << 24)
+    return w
+
+
+def orow_mkeys(orows: np.ndarray) -> np.ndarray:
+    """[..., MRK_MAX_K] u64 view of order rows' mapped-key plane (rows: uint64 [..., OROW_WORDS])."""
+    return orows[..., OROW_MKEYS:OROW_SPEC]
+
+
+def _unmap_part(m: np.ndarray, f: int) -> np.ndarray:
+    m = m.astype(np.uint32)
+    if not f & OSPEC_PART_DESC:
+        m = ~m
+    if f & OSPEC_PART_FLOAT:
+        m = np.where(m & np.uint32(0x80000000), m ^ np.uint32(0x80000000), ~m).astype(np.uint32)
+    return m ^ np.uint32(0x80000000) if f & OSPEC_PART_SIGNED else m
+
+
+def unmap_order_keys(spec: int, mapped: np.ndarray) -> np.ndarray:
+    """The values behind 64-bit mapped keys of a row with this order spec word (mrk_order_unmap_key per entry, in numpy), in
+    Matches.order_key's format: the raw int64 as u64, or raw0 << 32 | raw1; a sort spec: raw0 << 32.  A float's -0.0 reads +0.0."""
+    mapped = np.asarray(mapped, dtype=np.uint64)
+    if not spec:
+        return np.zeros(len(mapped), np.uint64)
+    r0 = _unmap_part(mapped >> np.uint64(32), (spec >> 8) & 0xFFFF).astype(np.uint64) << np.uint64(32)
+    if not spec & OSPEC_WIDE:
+        return r0
+    return r0 | _unmap_part(mapped & np.uint64(0xFFFFFFFF), (spec >> 24) & 0xFFFF).astype(np.uint64)
+
+
+def merge_orows_np(orows_all: np.ndarray, k: int) -> np.ndarray:
+    """What merge_orows_kernel computes, in numpy: orows_all uint64 [n_lists, nq, OROW_WORDS] -> [nq, OROW_WORDS].  An ordered query
+    orders by (64-bit mapped key, the weight as then_weight says, global docid asc), a relevance query (spec 0) by (weight, docid);
+    totals add up, the two flag bits are OR-ed through; answering lists whose spec words differ in any bit, and an ordered query some
+    list carries with ROW_DECLINED (its spec word, 0 from a shard whose planner declined, is not compared), give ROW_DECLINED and no
+    keys under the answering lists' spec word.  The CPU mirror the kernel is tested against; a gloo-only host's merge."""
+    orows_all = np.ascontiguousarray(orows_all, dtype=np.uint64)
+    n_lists, nq, _ = orows_all.shape
+    out = np.zeros((nq, OROW_WORDS), dtype=np.uint64)
+    mask = np.uint64(ROW_RERUN | ROW_DECLINED)
+    for q in range(nq):
+        rows = orows_all[:, q]
+        cnt = np.minimum(rows[:, MRK_MAX_K], np.uint64(MRK_MAX_K)).astype(np.int64)
+        tf = rows[:, MRK_MAX_K + 1]
+        total = int((tf & ~mask).sum(dtype=np.uint64))
+        flags = int(np.bitwise_or.reduce(tf & mask))
+        # the spec word is that of the lists which answer the query (a declining shard sends spec 0 and has no say): they must agree
+        specs = rows[(tf & np.uint64(ROW_DECLINED)) == 0, OROW_SPEC]
+        spec = int(specs[0]) if len(specs) else 0
+        mismatch = bool((specs != np.uint64(spec)).any())
+        if mismatch:
+            flags |= ROW_DECLINED
+        out[q, MRK_MAX_K + 1] = np.uint64((total & ~(ROW_RERUN | ROW_DECLINED)) | flags)
+        out[q, OROW_SPEC] = np.uint64(spec)
+        if mismatch or (spec and flags & ROW_DECLINED):
+            continue
+        keys = np.concatenate([rows[l, :cnt[l]] for l in range(n_lists)])
+        mk = np.concatenate([rows[l, OROW_MKEYS:OROW_MKEYS + cnt[l]] for l in range(n_lists)]) if spec else np.zeros(len(keys), np.uint64)
+        w = (keys >> np.uint64(32)).astype(np.uint32)  # weight ^ 0x80000000: larger = heavier
+        tie = (spec >> 4) & 3 if spec else 1
+        wpart = w if tie == 1 else ~w if tie == 2 else np.zeros_like(w)
+        nd = keys.astype(np.uint32)                    # ~docid: larger = smaller docid
+        order = np.lexsort((nd, wpart, mk))[::-1]       # descending by (mapped key as u64, weight part, ~docid)
+        n = min(len(keys), k)
+        order = order[:n]
+        out[q, :n] = keys[order]
+        out[q, MRK_MAX_K] = np.uint64(n)
+        if spec:
+            out[q, OROW_MKEYS:OROW_MKEYS + n] = mk[order]
+    return out
+
+
 def exchange_rows(rows):
-    """ONE all-gather of [nq, ROW_WORDS] result rows -> [world, nq, ROW_WORDS] (gloo on CPU tensors, RCCL on device)."""
+    """ONE all-gather of [nq, W] result rows -> [world, nq, W] (gloo on CPU tensors, RCCL on device); W = ROW_WORDS, SROW_WORDS or
+    OROW_WORDS: the row width is the tensor's."""
     import torch
     import torch.distributed as dist
 
@@ -147,7 +243,8 @@ def shard_slice(n_queries: int, world: int, rank: int):
 
 def exchange_rows_partitioned(rows):
     """The exchange partitioned by QUERY over torch.distributed (gloo on CPU tensors, RCCL on device tensors): every rank sends each
-    owner its rows of the owner's queries and receives every shard's rows of its own -> (recv [world, per, ROW_WORDS], first, count).
+    owner its rows of the owner's queries and receives every shard's rows of its own -> (recv [world, per, W], first, count), W the
+    rows' own width (narrow, wide or order rows).
     The same all-to-all of row slices mrk_shard_exchange issues through the library's communicator (grouped ncclSend / ncclRecv)."""
     import torch
     import torch.distributed as dist
@@ -181,8 +278,11 @@ class ShardMerger:
     synchronous form for one batch."""
 
     def __init__(self, ctx, batch, n_queries: int, k: int, world: int, device: int, n_batches: int = 1, n_sets: int = 1,
-                 sorted_rows: bool = False):
-        """sorted_rows=True: WIDE rows (SROW_WORDS) through the wide entry points -- sorted queries (Query.sort) are merged
+                 sorted_rows: bool = False, order_rows: bool = False):
+        """order_rows=True (excludes sorted_rows): ORDER rows (OROW_WORDS) through the order-row entry points -- queries ordered by
+        a 64-bit key (Query.order) and sorted queries are merged across the shards in the sorter's order; results() hands back
+        order_key for the former and sort_key for the latter, decoded from the spec word alone; relevance queries travel along.
+        sorted_rows=True: WIDE rows (SROW_WORDS) through the wide entry points -- sorted queries (Query.sort) are merged
         across the shards in the sorter's order and results() hands back their sort_key; relevance queries travel along."""
         import torch
 
@@ -196,14 +296,17 @@ class ShardMerger:
         def z(*shape):
             return torch.zeros(shape, dtype=torch.int64, device=dev)
 
-        self.sorted_rows = bool(sorted_rows)
-        self.row_words = rw = SROW_WORDS if sorted_rows else ROW_WORDS
+        if sorted_rows and order_rows:
+            raise ValueError("ShardMerger: sorted_rows and order_rows are mutually exclusive (a batch has one standing destination)")
+        self.sorted_rows, self.order_rows = bool(sorted_rows), bool(order_rows)
+        self.row_words = rw = OROW_WORDS if order_rows else SROW_WORDS if sorted_rows else ROW_WORDS
         L = lib()
-        # the narrow entry points or their wide twins: same arguments
-        self._set_dst = L.mrk_batch_set_srows_dst if sorted_rows else L.mrk_batch_set_rows_dst
-        self._export = L.mrk_batch_export_srows if sorted_rows else L.mrk_batch_export_rows
-        self._exchange = L.mrk_shard_exchange_srows if sorted_rows else L.mrk_shard_exchange
-        self._merge_async = L.mrk_topk_merge_srows_async if sorted_rows else L.mrk_topk_merge_rows_async
+        # the narrow entry points or their wide / order-row twins: same arguments
+        kind = "orows" if order_rows else "srows" if sorted_rows else "rows"
+        self._set_dst = getattr(L, f"mrk_batch_set_{kind}_dst")
+        self._export = getattr(L, f"mrk_batch_export_{kind}")
+        self._exchange = getattr(L, f"mrk_shard_exchange_{kind}") if kind != "rows" else L.mrk_shard_exchange
+        self._merge_async = getattr(L, f"mrk_topk_merge_{kind}_async")
         self.rows = [z(self.nq, rw) for _ in range(n_sets)]
         self.rows_all = [z(world, self.nq, rw) for _ in range(n_sets)]
         self.out_rows = [z(self.nq, rw) for _ in range(n_sets)]
@@ -342,7 +445,8 @@ class ShardMerger:
     def results(self, set_index: int = 0, nq=None, allow_declined: bool = False):
         """Decoded (global docid, weight) lists per query + total_found.  A query some shard declined raises MrkError
         (allow_declined=True: its entry is None instead).  With sorted_rows the entries are Matches (rowid = global docid),
-        a sorted query's with sort_key (the attribute's raw value per row), a relevance query's with sort_key None."""
+        a sorted query's with sort_key (the attribute's raw value per row), a relevance query's with sort_key None.  With
+        order_rows: a 64-bit order's entry carries order_key (Matches.order_key's format), a sort's sort_key."""
         rows = self.finish(set_index)
         out = []
         if self.partitioned and self.world > 1:
@@ -357,6 +461,16 @@ class ShardMerger:
             k = rows[q, :cnt]
             weight = ((k >> np.uint64(32)).astype(np.uint32) ^ np.uint32(0x80000000)).view(np.int32)
             docid = ~k.astype(np.uint32)
+            if self.order_rows:
+                from .api import Matches
+
+                spec = int(rows[q, OROW_SPEC])
+                vals = unmap_order_keys(spec, orow_mkeys(rows[q])[:cnt]) if spec else None
+                if spec & OSPEC_WIDE:
+                    out.append(Matches(docid, weight, tot, 0, None, vals))
+                else:
+                    out.append(Matches(docid, weight, tot, 0, (vals >> np.uint64(32)).astype(np.uint32) if spec else None))
+                continue
             if self.sorted_rows:
                 from .api import Matches
 
