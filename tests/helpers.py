@@ -15,16 +15,20 @@ import numpy as np
 _TOKEN = re.compile(r"[a-z0-9_а-я]+|[㐀-龿]")
 
 
-def tokenize(text: str, min_word_len: int = 1) -> List[Tuple[str, int]]:
-    """-> [(token, position)], positions 1-based; overshort ASCII words keep their slot."""
+def tokenize(text: str, min_word_len: int = 1, boundary: str = "", boundary_step: int = 0) -> List[Tuple[str, int]]:
+    """-> [(token, position)], positions 1-based; overshort ASCII words keep their slot.  boundary / boundary_step = the index's
+    phrase_boundary characters and phrase_boundary_step: such a character right behind a word and in front of a separator (or the
+    end) moves the next word boundary_step positions further on."""
     out = []
     pos = 0
-    for m in _TOKEN.finditer(text.lower()):
+    low = text.lower()
+    for m in _TOKEN.finditer(low):
         t = m.group(0)
         pos += 1
-        if len(t) < min_word_len and t.isascii():
-            continue
-        out.append((t, pos))
+        if len(t) >= min_word_len or not t.isascii():
+            out.append((t, pos))
+        if boundary and low[m.end():m.end() + 1] in tuple(boundary) and not _TOKEN.match(low, m.end() + 1):
+            pos += boundary_step
     return out
 
 
@@ -82,7 +86,7 @@ def tokenize_sp(text: str, min_word_len: int = 1) -> List[Tuple[str, int]]:
     return out
 
 
-def make_hits(docs: Sequence[Sequence[str]], min_word_len: int = 1, index_sp: bool = False):
+def make_hits(docs: Sequence[Sequence[str]], min_word_len: int = 1, index_sp: bool = False, boundary: str = "", boundary_step: int = 0):
     """docs[rowid] = [field0 text, field1 text, ...] -> (wordid, rowid, hitpos) arrays sorted
     by (wordid, rowid, hitpos), plus the vocabulary {token: term_id} (wordid = term_id + 1).
     The field-end marker goes on every hit at the field's last position (sphinx.cpp:22533-22548)."""
@@ -90,7 +94,7 @@ def make_hits(docs: Sequence[Sequence[str]], min_word_len: int = 1, index_sp: bo
     raw = []
     for rowid, fields in enumerate(docs):
         for f, text in enumerate(fields):
-            toks = tokenize_sp(text, min_word_len) if index_sp else tokenize(text, min_word_len)
+            toks = tokenize_sp(text, min_word_len) if index_sp else tokenize(text, min_word_len, boundary, boundary_step)
             last = toks[-1][1] if toks else 0
             for i, (t, pos) in enumerate(toks):
                 raw.append((t, rowid, f, pos, pos == last))

@@ -2,7 +2,7 @@
 the oracle.  As in test_gpu_sort.py the expected answer is the oracle's result for the same query with max_matches = number of docs
 (every match with its weight), ordered on the host by numpy -- lexsort over (first part, second part, weight per the tie rule,
 rowid) with the parts as numpy reads the raw rows (int64 view for a 64-bit attribute, float32 compare for floats, unsigned for
-integers) -- and cut to K.  Every comparison is exact: rowids, weights, order_key and total_found."""
+integers) -- and cut to K (sorted_expect.expected_order).  Every comparison is exact: rowids, weights, order_key and total_found."""
 import ctypes as C
 import dataclasses
 import json
@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 from helpers import synth_postings
+from sorted_expect import expected_order as expected  # (shared with test_gpu_sort.py and the recorded-result tests)
+from sorted_expect import part_key, raw_of  # noqa: F401
 from test_gpu_parity import kw, orc_index_of, to_orc
 from test_gpu_sort import AUX, BITS, FLT, TS
 from test_gpu_sort import check as check_sort
@@ -59,37 +61,6 @@ def make_rows(rng, n_docs, const_second=False):
 
 def part_specs(m):
     return sorts(m)  # name -> (bit_offset, bit_count, kind): ts, bits5, bool, cat, float
-
-
-def raw_of(rows, rowid, off, cnt):
-    dw = rows[rowid, off >> 5]
-    return dw if cnt == 32 else (dw >> np.uint32(off & 31)) & np.uint32((1 << cnt) - 1)
-
-
-def part_key(raw, kind, desc):
-    """what np.lexsort orders ascending, best first"""
-    key = raw.view(np.float32).astype(np.float64) + 0.0 if kind == 1 else raw.astype(np.float64)  # (exact: 32-bit values; -0.0 == +0.0)
-    return -key if desc else key
-
-
-def expected(orc, oi, q, rows, n_docs):
-    full = to_orc(orc, dataclasses.replace(q, sort=None, order=None, max_matches=max(n_docs, 1))).run(oi)
-    assert len(full.rowid) == full.total_found
-    o = q.order
-    w = full.weight.astype(np.int64)
-    kw_ = -w if o.then_weight == 1 else w if o.then_weight == 2 else np.zeros_like(w)
-    p0 = o.parts[0]
-    if p0.kind == 2:
-        item = p0.bit_offset >> 5
-        v = np.ascontiguousarray(rows[full.rowid, item:item + 2]).view(np.int64).reshape(-1)
-        keys = [~v if p0.desc else v]  # (~v = -v - 1: descending without overflowing at INT64_MIN)
-        okey = v.view(np.uint64)
-    else:
-        raws = [raw_of(rows, full.rowid, p.bit_offset, p.bit_count) for p in o.parts]
-        keys = [part_key(r, p.kind, p.desc) for r, p in zip(raws, o.parts)]
-        okey = (raws[0].astype(np.uint64) << np.uint64(32)) | (raws[1].astype(np.uint64) if len(raws) > 1 else np.uint64(0))
-    order = np.lexsort(tuple([full.rowid, kw_] + keys[::-1]))[: q.max_matches]
-    return full.rowid[order], full.weight[order], okey[order], int(full.total_found)
 
 
 def check(orc, oi, rows, n_docs, queries, got, what=""):

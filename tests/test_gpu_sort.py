@@ -1,6 +1,7 @@
 """GPU: queries ordered by a row attribute (Query.sort: ORDER BY attr [, weight()]) against the oracle.  The oracle ranks with any
 max_matches, so the expected answer is its result for the same query with max_matches = number of docs (every match with its
-weight), ordered on the host by numpy -- lexsort over (attribute as numpy reads it, weight per the tie rule, rowid) -- cut to K.
+weight), ordered on the host by numpy -- lexsort over (attribute as numpy reads it, weight per the tie rule, rowid) -- cut to K
+(sorted_expect.expected_sort, itself pinned on the reference's recorded results by test_sorted_golden_cpu.py).
 The attribute key is computed by numpy from the raw rows (unsigned compare for integers, float32 compare for floats), not by the
 library's map.  Every comparison is exact."""
 import dataclasses
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 from helpers import synth_postings
+from sorted_expect import expected_sort as expected  # (shared with test_gpu_order.py and the recorded-result tests)
 from test_gpu_parity import kw, orc_index_of, to_orc
 
 pytestmark = pytest.mark.gpu
@@ -48,20 +50,6 @@ def make_rows(rng, n_docs):
 def sorts(m):
     return {"ts": (TS * 32, 32, m.SORTKEY_INT), "bits5": (BITS * 32 + 3, 5, m.SORTKEY_INT), "bool": (BITS * 32 + 31, 1, m.SORTKEY_INT),
             "cat": (BITS * 32 + 10, 2, m.SORTKEY_INT), "float": (FLT * 32, 32, m.SORTKEY_FLOAT)}
-
-
-def expected(orc, oi, q, rows, n_docs):
-    full = to_orc(orc, dataclasses.replace(q, sort=None, max_matches=max(n_docs, 1))).run(oi)
-    assert len(full.rowid) == full.total_found
-    s = q.sort
-    dw = rows[full.rowid, s.bit_offset >> 5]
-    raw = dw if s.bit_count == 32 else (dw >> np.uint32(s.bit_offset & 31)) & np.uint32((1 << s.bit_count) - 1)
-    key = raw.view(np.float32).astype(np.float64) if s.kind == 1 else raw.astype(np.float64)  # (exact: 32-bit values)
-    w = full.weight.astype(np.int64)
-    k1 = -key if s.desc else key
-    k2 = -w if s.then_weight == 1 else w if s.then_weight == 2 else np.zeros_like(w)
-    order = np.lexsort((full.rowid, k2, k1 + 0.0))[: q.max_matches]  # (+ 0.0: -0.0 == +0.0 either way; spelled out)
-    return full.rowid[order], full.weight[order], raw[order], int(full.total_found)
 
 
 def check(orc, oi, rows, n_docs, queries, got, what=""):
