@@ -187,7 +187,15 @@ typedef struct {
    not dword-aligned, INT64 as one of two parts: MRK_E_INVAL, before a row is read.  Declined per query with MRK_E_UNSUPPORTED: a
    blob-stored part (bit_offset < 0), a float part whose column holds a NaN, a segment without attribute rows, cutoff next to an
    order, the VLB-direct path.  A key of more than 32 bits (INT64, two parts) fits no exchange row: such a query leaves in narrow
-   AND wide rows with MRK_ROW_DECLINED and no keys. */
+   AND wide rows with MRK_ROW_DECLINED and no keys.
+   The weight in FRONT of the parts (SPH_KEYPART_WEIGHT as key part 0 of MatchGeneric2_fn / 3_fn: 'ORDER BY weight() DESC, attr'):
+   then_weight = MRK_ORDER_WEIGHT_FIRST_DESC / _ASC -- the weight, then the parts in their order and directions, rowid ascending last.
+   mrk_order keeps its size and layout (callers built against it stay valid): then_weight says where the weight stands, behind the
+   parts (0 / 1 / 2) or in front of them, so "in front and behind" cannot be said.  The same shapes of parts; _ASC also takes
+   n_parts 0 ('ORDER BY weight() ASC': it reads no attribute row and needs none); _DESC without parts is relevance (leave order NULL)
+   and MRK_E_INVAL, like every other value of then_weight.  No exchange row carries the weight's position yet: a weight-first query
+   leaves in narrow, wide and order rows with MRK_ROW_DECLINED, no keys and spec word 0.  mrk_result.order_key holds the raw parts as
+   for every order (NULL without parts). */
 #define MRK_MAX_ORDER_PARTS 2
 typedef struct {
   int32_t kind;                  /* MRK_SORTKEY_* */
@@ -197,8 +205,11 @@ typedef struct {
 typedef struct {
   int32_t n_parts;
   mrk_order_part parts[MRK_MAX_ORDER_PARTS];
-  int32_t then_weight;           /* as mrk_sort::then_weight, behind the last part */
+  int32_t then_weight;           /* as mrk_sort::then_weight, behind the last part; or MRK_ORDER_WEIGHT_FIRST_*: in front of the first */
 } mrk_order;
+#define MRK_ORDER_WEIGHT_FIRST 0x100 /* then_weight = this | 1 (weight DESC) or | 2 (weight ASC): the weight leads the order */
+#define MRK_ORDER_WEIGHT_FIRST_DESC ( MRK_ORDER_WEIGHT_FIRST | 1 )
+#define MRK_ORDER_WEIGHT_FIRST_ASC ( MRK_ORDER_WEIGHT_FIRST | 2 )
 
 /* CSphQuery fields that reach the ranker + the query tree */
 typedef struct {

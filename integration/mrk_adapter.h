@@ -109,7 +109,7 @@ inline bool MrkSortLocator64Ok ( const CSphAttrLocator & tLoc )
 
 /// SPH_SORT_EXTENDED states of the shapes mrk_order takes: [INT over a 64-bit locator] | [INT|FLOAT attr] [INT|FLOAT attr], then
 /// [WEIGHT], then ROWID asc (sphParseSortClause ends every clause with an ascending ROWID part).  Anything else -- three attributes,
-/// the weight in front of or between attributes, strings, expressions (dynamic locators) -- is not filled: false.
+/// the weight between attributes (in front of them: MrkSorterWeightFirst), strings, expressions (dynamic locators) -- is not filled: false.
 inline bool MrkSorterWideOrder ( const CSphMatchComparatorState & tState, mrk_order & tOrder )
 {
 	memset ( &tOrder, 0, sizeof(tOrder) );
@@ -143,8 +143,46 @@ inline bool MrkSorterWideOrder ( const CSphMatchComparatorState & tState, mrk_or
 	return i<CSphMatchComparatorState::MAX_ATTRS && tState.m_eKeypart[i]==SPH_KEYPART_ROWID && ( ( tState.m_uAttrDesc >> i ) & 1 )==0;
 }
 
+/// SPH_SORT_EXTENDED states whose key part 0 is the WEIGHT (MatchGeneric2_fn / 3_fn with SPH_KEYPART_WEIGHT first: 'ORDER BY weight()
+/// DESC, attr', '@weight DESC, date_added DESC'), followed by [INT over a 64-bit locator] | [INT|FLOAT attr] [INT|FLOAT attr] | nothing
+/// with the weight ASCENDING ('ORDER BY weight() ASC'; weight descending alone is relevance), then ROWID asc: mrk_order with
+/// then_weight = MRK_ORDER_WEIGHT_FIRST_DESC / _ASC from m_uAttrDesc bit 0.  Anything else -- a third attribute, strings, ROWID descending, the weight twice -- false.
+inline bool MrkSorterWeightFirst ( const CSphMatchComparatorState & tState, mrk_order & tOrder )
+{
+	memset ( &tOrder, 0, sizeof(tOrder) );
+	if ( tState.m_eKeypart[0]!=SPH_KEYPART_WEIGHT )
+		return false;
+	tOrder.then_weight = ( tState.m_uAttrDesc & 1 ) ? MRK_ORDER_WEIGHT_FIRST_DESC : MRK_ORDER_WEIGHT_FIRST_ASC;
+	int i = 1;
+	for ( ; i<CSphMatchComparatorState::MAX_ATTRS && ( tState.m_eKeypart[i]==SPH_KEYPART_INT || tState.m_eKeypart[i]==SPH_KEYPART_FLOAT ); ++i )
+	{
+		if ( i>MRK_MAX_ORDER_PARTS )
+			return false;
+		const CSphAttrLocator & tLoc = tState.m_tLocator[i];
+		mrk_order_part & tPart = tOrder.parts[i-1];
+		if ( tState.m_eKeypart[i]==SPH_KEYPART_INT && MrkSortLocator64Ok ( tLoc ) )
+			tPart.kind = MRK_SORTKEY_INT64;
+		else if ( MrkSortLocatorOk ( tLoc ) && ( tState.m_eKeypart[i]==SPH_KEYPART_INT || tLoc.m_iBitCount==32 ) )
+			tPart.kind = tState.m_eKeypart[i]==SPH_KEYPART_FLOAT ? MRK_SORTKEY_FLOAT : MRK_SORTKEY_INT;
+		else
+			return false;
+		tPart.bit_offset = tLoc.m_iBitOffset;
+		tPart.bit_count = tLoc.m_iBitCount;
+		tPart.desc = ( tState.m_uAttrDesc >> i ) & 1;
+	}
+	tOrder.n_parts = i-1;
+	if ( i>=CSphMatchComparatorState::MAX_ATTRS )
+		return false;
+	if ( tOrder.n_parts==0 && tOrder.then_weight==MRK_ORDER_WEIGHT_FIRST_DESC )
+		return false;	// (weight desc, rowid asc) is relevance: MrkSorterIsRelevance answers it
+	if ( tOrder.n_parts==2 && ( tOrder.parts[0].kind==MRK_SORTKEY_INT64 || tOrder.parts[1].kind==MRK_SORTKEY_INT64 ) )
+		return false;	// a 64-bit part stands alone on the device
+	return tState.m_eKeypart[i]==SPH_KEYPART_ROWID && ( ( tState.m_uAttrDesc >> i ) & 1 )==0;
+}
+
 /// Which device order is this sorter?  0 = none (keep the CPU ranker), 1 = relevance, 2 = one attribute of <= 32 bits first (tSort
-/// filled), 3 = a 64-bit attribute or two attributes first (*pOrder filled; only asked for when pOrder is given).
+/// filled), 3 = a 64-bit attribute or two attributes first, or the weight first with attributes (or nothing, ascending) behind it
+/// (*pOrder filled; only asked for when pOrder is given).
 inline int MrkSorterOrder ( const CSphQuery & tQuery, const ISphMatchSorter * pSorter, mrk_sort & tSort, mrk_order * pOrder = nullptr )
 {
 	memset ( &tSort, 0, sizeof(tSort) );
@@ -156,6 +194,8 @@ inline int MrkSorterOrder ( const CSphQuery & tQuery, const ISphMatchSorter * pS
 	const ESphSortKeyPart eKey = tState.m_eKeypart[0];
 	if ( pOrder && tQuery.m_eSort==SPH_SORT_EXTENDED && MrkSorterWideOrder ( tState, *pOrder )
 		&& ( pOrder->n_parts==2 || pOrder->parts[0].kind==MRK_SORTKEY_INT64 ) )
+		return 3;
+	if ( pOrder && tQuery.m_eSort==SPH_SORT_EXTENDED && MrkSorterWeightFirst ( tState, *pOrder ) )
 		return 3;
 	if ( tQuery.m_eSort==SPH_SORT_ATTR_DESC || tQuery.m_eSort==SPH_SORT_ATTR_ASC )
 	{
@@ -195,7 +235,7 @@ inline bool MrkEligible ( const CSphQuery & tQuery, const CSphQueryContext & tCt
 	mrk_sort tSort;
 	mrk_order tOrder;
 	const int iOrder = MrkSorterOrder ( tQuery, dSorters[0], tSort, &tOrder );
-	if ( !iOrder )									{ sWhy = "sorter order is none of (weight desc, rowid asc), (row attribute of <= 32 bits [, weight], rowid asc), (64-bit row attribute | two row attributes [, weight], rowid asc)"; return false; }
+	if ( !iOrder )									{ sWhy = "sorter order is none of (weight desc, rowid asc), (row attribute of <= 32 bits [, weight], rowid asc), (64-bit row attribute | two row attributes [, weight], rowid asc), (weight, up to two row attributes | a 64-bit one, rowid asc)"; return false; }
 	if ( iOrder>=2 && tQuery.m_iCutoff>0 )			{ sWhy = "cutoff next to an attribute order"; return false; }
 	if ( tCtx.m_pWeightFilter && tQuery.m_iCutoff>0 )	{ sWhy = "weight filter next to a cutoff"; return false; }	// sphinx.cpp:12223-12267
 	if ( tQuery.m_iCutoff>MRK_MAX_K )				{ sWhy = "cutoff beyond the device top-K"; return false; }	// sphinx.cpp:12261-12267; smaller ones: mrk_query::cutoff

@@ -57,6 +57,7 @@ class Sort(C.Structure):
     _fields_ = [("kind", C.c_int32), ("bit_offset", C.c_int32), ("bit_count", C.c_int32), ("desc", C.c_int32), ("then_weight", C.c_int32)]
 
 
+ORDER_WEIGHT_FIRST = 0x100  # MRK_ORDER_WEIGHT_FIRST: then_weight = this | 1 (weight DESC) / | 2 (weight ASC), the weight leads the order
 MRK_MAX_ORDER_PARTS = 2
 
 

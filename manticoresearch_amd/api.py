@@ -359,9 +359,17 @@ class OrderPart:
 @dataclass
 class Order:
     """The wider form of the sorter's order (mrk_order, include/mrk.h): one or two attributes, each with its own direction, then
-    the weight as then_weight says (Sort's meaning), rowid ascending last.  One part of <= 32 bits answers exactly as the same Sort."""
+    the weight as then_weight says (Sort's meaning), rowid ascending last.  One part of <= 32 bits answers exactly as the same Sort.
+    weight_first puts the weight in FRONT of the parts instead ('ORDER BY weight() DESC, attr'): 1 = weight DESC, 2 = weight ASC, then
+    the parts, rowid ascending last; Order(parts=[], weight_first=2) is 'ORDER BY weight() ASC'.  then_weight left alone is 1, or 0
+    next to weight_first; both together are refused (mrk_order says where the weight stands in ONE word: MRK_ORDER_WEIGHT_FIRST_*)."""
     parts: Sequence[OrderPart]
-    then_weight: int = 1
+    then_weight: Optional[int] = None
+    weight_first: int = 0
+
+    def __post_init__(self):
+        if self.then_weight is None:
+            self.then_weight = 0 if self.weight_first else 1
 
 
 @dataclass
@@ -457,7 +465,12 @@ class _CQueries:
                 self.keep.append(cs)
             if q.order is not None:
                 co = _lib.Order()
-                co.n_parts, co.then_weight = len(q.order.parts), int(q.order.then_weight)
+                wf = int(q.order.weight_first)
+                if wf not in (0, 1, 2):
+                    raise ValueError(f"query {qi}: Order.weight_first {wf} (0 = behind the parts as then_weight says, 1 = weight DESC first, 2 = weight ASC first)")
+                if wf and int(q.order.then_weight):
+                    raise ValueError(f"query {qi}: Order with the weight in front (weight_first {wf}) and behind (then_weight {q.order.then_weight})")
+                co.n_parts, co.then_weight = len(q.order.parts), (_lib.ORDER_WEIGHT_FIRST | wf) if wf else int(q.order.then_weight)
                 for i, p in enumerate(q.order.parts[: _lib.MRK_MAX_ORDER_PARTS]):  # (more parts: n_parts says so and the library refuses)
                     co.parts[i] = _lib.OrderPart(int(p.kind), int(p.bit_offset), int(p.bit_count), int(bool(p.desc)))
                 c.order = C.pointer(co)

@@ -284,6 +284,10 @@ struct DevQuery {
   // these the second; the candidates take the 64-bit layouts of mrk_sortkey.h and the bins ord_geom's (bin_lo / bin_shift unused)
   uint32_t ord_item, ord_shift, ord_bits, ord_flags;
   OrderGeom ord_geom;
+  // MRK_ORDER_WEIGHT_FIRST_* (sort_on == SORT_ON_WEIGHT, SORT_WFIRST in sort_flags): the weight leads, sort_tie = its direction (1 DESC /
+  // 2 ASC), bin_lo / bin_shift = the relevance bins of the weight; wf_parts = 0..2 dwords of the row behind it, located by sort_* / ord_*
+  uint32_t wf_parts;
+  uint32_t wf_pad;
 };
 
 struct DevItem {

@@ -178,7 +178,14 @@ struct mrk_batch {
   // sorted queries of the last submit: the locator of the primary attribute (bits 0 = relevance) and the raw values of the returned rows
   // (mrk_query.order: `order` = 1 one part of <= 32 bits, planned as a sort; 2 = a 64-bit key, whose second part is p1 and which
   // leaves in ORDER rows only (MRK_OROW_WORDS); mrk_result.order_key instead of .sort_key)
-  struct SortLoc { uint32_t item = 0, shift = 0, bits = 0, order = 0; mrk::OrderPart p1{0, 0, 0, 0}; };
+  struct SortLoc {
+    uint32_t item = 0, shift = 0, bits = 0, order = 0;
+    mrk::OrderPart p1{0, 0, 0, 0};
+    // the query fits no NARROW or WIDE exchange row: a 64-bit key, or the weight in front of the parts (MRK_ORDER_WEIGHT_FIRST_*) ...
+    bool no_row() const { return order == mrk::SORT_ON_ORDER || order == mrk::SORT_ON_WEIGHT; }
+    // ... and the latter no ORDER row either (the order spec word does not carry the weight's position yet)
+    bool no_orow() const { return order == mrk::SORT_ON_WEIGHT; }
+  };
   std::vector<SortLoc> sort_loc;
   std::vector<uint32_t> sort_key;
   std::vector<uint64_t> order_key;
@@ -1310,16 +1317,16 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     // (a sorted query's NARROW row is no answer to a merge by (weight, docid): in that exchange it counts as declined -- word 2,
     // which the wide rows, whose merge compares the mapped keys, do not take for a decline)
     // (a query ordered by a 64-bit key, mrk_query.order, fits neither of these two row formats: word 1; ORDER rows read words of their own, below)
-    for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits) || b->sort_loc[i].order == mrk::SORT_ON_ORDER;
+    for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits) || b->sort_loc[i].no_row();
     b->any_declined = any;
     if (any || b->decl_dirty) {
-      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = (b->status[i] != MRK_OK || b->sort_loc[i].order == mrk::SORT_ON_ORDER) ? 1u : (b->rows_dst && b->sort_loc[i].bits) ? 2u : 0u;
+      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = (b->status[i] != MRK_OK || b->sort_loc[i].no_row()) ? 1u : (b->rows_dst && b->sort_loc[i].bits) ? 2u : 0u;
       HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     }
     b->decl_order = any_order;
     if (any_order) { // the same words for ORDER rows, which carry a 64-bit key
       uint32_t* ho = b->h_decl.p + b->max_queries;
-      for (uint32_t i = 0; i < n; ++i) ho[i] = b->status[i] != MRK_OK ? 1u : 0u;
+      for (uint32_t i = 0; i < n; ++i) ho[i] = (b->status[i] != MRK_OK || b->sort_loc[i].no_orow()) ? 1u : 0u;
       HIP_TRY(hipMemcpyAsync(b->d_decl.p + b->max_queries, ho, n * 4, hipMemcpyHostToDevice, st2));
     }
     b->decl_dirty = any;
@@ -1564,7 +1571,8 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
           b->sort_key[(size_t)i * KCAP + j] = v;
           if (sl.order) { // mrk_result.order_key: the first part's raw value | the second's (a 64-bit attribute: its high | low dword)
             const uint64_t at1 = row + sl.p1.item;
-            const uint32_t v1 = sl.order == mrk::SORT_ON_ORDER && sg && at1 < sg->h_attrs.size() ? mrk::sort_extract(sg->h_attrs[at1], sl.p1.shift, sl.p1.bits) : 0u;
+            // (a weight-first order: its parts alone, as for every order; a second part that is not there has p1.bits == 0)
+            const uint32_t v1 = (sl.order == mrk::SORT_ON_ORDER || (sl.order == mrk::SORT_ON_WEIGHT && sl.p1.bits)) && sg && at1 < sg->h_attrs.size() ? mrk::sort_extract(sg->h_attrs[at1], sl.p1.shift, sl.p1.bits) : 0u;
             b->order_key[(size_t)i * KCAP + j] = ((uint64_t)v << 32) | v1;
           }
         }
@@ -1578,7 +1586,7 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
   out->rowid = b->rowid.data() + (size_t)q * KCAP;
   out->weight = b->weight.data() + (size_t)q * KCAP;
   out->sort_key = b->status[q] == MRK_OK && b->sort_loc[q].bits && !b->sort_loc[q].order ? b->sort_key.data() + (size_t)q * KCAP : nullptr;
-  out->order_key = b->status[q] == MRK_OK && b->sort_loc[q].order ? b->order_key.data() + (size_t)q * KCAP : nullptr;
+  out->order_key = b->status[q] == MRK_OK && b->sort_loc[q].order && b->sort_loc[q].bits ? b->order_key.data() + (size_t)q * KCAP : nullptr;
   return MRK_OK;
 }
 

@@ -8,11 +8,8 @@ namespace mrk {
 // Pruning bin of a match: monotone non-decreasing in the sorter's order (weight, then lower
 // rowid), so "K matches already sit in higher bins" proves a match cannot reach the top K.
 __device__ __forceinline__ uint32_t bin_of(uint32_t mode, int32_t lo, uint32_t shift, int32_t weight, uint32_t grow) {
-  if (mode == BIN_WEIGHT) {
-    if (weight < lo) return 0u;
-    const uint32_t b = (uint32_t)(weight - lo) >> shift;
-    return b < (uint32_t)NBINS ? b : (uint32_t)NBINS - 1u;
-  }
+  static_assert(NBINS == 1024, "weight_bin (mrk_sortkey.h) holds the bin count");
+  if (mode == BIN_WEIGHT) return weight_bin(lo, shift, weight); // (one definition for host and device)
   const uint32_t b = grow >> shift;
   return (uint32_t)NBINS - 1u - (b < (uint32_t)NBINS ? b : (uint32_t)NBINS - 1u);
 }

@@ -764,6 +764,8 @@ struct KeySpec {
   KeyPart part[MRK_MAX_ORDER_PARTS];
   int32_t tie = 0; // mrk_sort::then_weight
   bool wide = false;
+  int32_t wfirst = 0; // mrk_order::then_weight = MRK_ORDER_WEIGHT_FIRST_*: the weight leads (1 DESC / 2 ASC), n_parts may be 0
+  bool sorted() const { return n_parts > 0 || wfirst != 0; }
 };
 
 struct PlanState {
@@ -806,8 +808,11 @@ struct PlanState {
     if (!q.order) return MRK_OK;
     const mrk_order& O = *q.order;
     if (q.sort) return mrk_fail(MRK_E_INVAL, "query %u: mrk_query.sort and mrk_query.order are both set", qi);
-    if (O.n_parts < 1 || O.n_parts > MRK_MAX_ORDER_PARTS) return mrk_fail(MRK_E_INVAL, "query %u: order of %d parts (1..%d)", qi, O.n_parts, MRK_MAX_ORDER_PARTS);
-    if (O.then_weight < 0 || O.then_weight > 2) return mrk_fail(MRK_E_INVAL, "query %u: order tie rule %d", qi, O.then_weight);
+    // then_weight says where the weight stands: behind the parts (0 / 1 / 2) or, MRK_ORDER_WEIGHT_FIRST_DESC / _ASC, in front of them
+    const int32_t wfirst = (O.then_weight == MRK_ORDER_WEIGHT_FIRST_DESC || O.then_weight == MRK_ORDER_WEIGHT_FIRST_ASC) ? O.then_weight & 3 : 0;
+    if ((O.n_parts < 1 && !(wfirst == 2 && O.n_parts == 0)) || O.n_parts > MRK_MAX_ORDER_PARTS)
+      return mrk_fail(MRK_E_INVAL, "query %u: order of %d parts (1..%d)", qi, O.n_parts, MRK_MAX_ORDER_PARTS);
+    if (!wfirst && (O.then_weight < 0 || O.then_weight > 2)) return mrk_fail(MRK_E_INVAL, "query %u: order tie rule %d", qi, O.then_weight);
     for (int p = 0; p < O.n_parts; ++p) {
       const mrk_order_part& P = O.parts[p];
       if (P.kind != MRK_SORTKEY_INT && P.kind != MRK_SORTKEY_FLOAT && P.kind != MRK_SORTKEY_INT64) return mrk_fail(MRK_E_INVAL, "query %u: order part %d: key kind %d", qi, p, P.kind);
@@ -821,13 +826,15 @@ struct PlanState {
         if (int rc = check_key_in_row(seg, qi, "order", P.bit_offset, P.bit_count)) return rc;
     }
     order.n_parts = O.n_parts;
-    order.tie = O.then_weight;
+    order.tie = wfirst ? 0 : O.then_weight;
+    order.wfirst = wfirst;
     for (int p = 0; p < O.n_parts; ++p) order.part[p] = KeyPart{O.parts[p].kind, O.parts[p].bit_offset, O.parts[p].bit_count, O.parts[p].desc != 0, nullptr};
-    if (O.n_parts == 1 && O.parts[0].kind != MRK_SORTKEY_INT64) return MRK_OK; // (resolve_sort checks it as the mrk_sort it is)
-    order.wide = true;
+    // (a weight-first order is resolved here whatever its parts: one candidate layout for all of them, none of it mrk_query.sort's)
+    if (O.n_parts == 1 && O.parts[0].kind != MRK_SORTKEY_INT64 && !wfirst) return MRK_OK; // (resolve_sort checks it as the mrk_sort it is)
+    order.wide = O.n_parts == 2 || (O.n_parts == 1 && O.parts[0].kind == MRK_SORTKEY_INT64);
     for (int p = 0; p < O.n_parts; ++p)
       if (O.parts[p].bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: order by a blob-stored or computed attribute (part %d has no row locator)", qi, p);
-    if (!seg->dev.attrs || seg->h_attrs.empty())
+    if (O.n_parts && (!seg->dev.attrs || seg->h_attrs.empty()))
       return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ordering by attributes needs the segment's attribute rows (mrk_segment_set_attrs)", qi);
     if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: ordered queries run on the packed path only", qi);
     if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to an order (which rows count depends on the scan order)", qi);
@@ -847,7 +854,7 @@ struct PlanState {
       order.n_parts = 1;
       order.tie = Q.then_weight;
       order.part[0] = KeyPart{Q.kind, Q.bit_offset, Q.bit_count, Q.desc != 0, nullptr};
-    } else if (order.n_parts != 1 || order.wide)
+    } else if (order.n_parts != 1 || order.wide || order.wfirst)
       return MRK_OK;
     KeyPart& P = order.part[0];
     if (P.kind != MRK_SORTKEY_INT && P.kind != MRK_SORTKEY_FLOAT) return mrk_fail(MRK_E_INVAL, "query %u: sort key kind %d", qi, P.kind);
@@ -1278,6 +1285,29 @@ struct PlanState {
     dq.bin_lo = 0, dq.bin_shift = 0;
   }
 
+  // the weight leads the order (MRK_ORDER_WEIGHT_FIRST_*): the relevance bins of the weight -- the kernels complement the bin for weight
+  // ASC --, and behind it where the parts lie in the row: 0..2 dwords (a 64-bit attribute: high, low), no geometry of theirs.  A ranker
+  // whose weights are all equal (NONE) fills one bin: correct, through the list overflow and the rerun, and not fast
+  void bins_by_weight_first(DevQuery& dq) const {
+    const KeySpec& O = order;
+    bins_by_weight(dq);
+    dq.sort_on = SORT_ON_WEIGHT;
+    dq.sort_tie = (uint32_t)O.wfirst;
+    dq.sort_flags = SORT_WFIRST;
+    if (O.n_parts) {
+      const KeyPart &A = O.part[0], &B = O.part[O.n_parts - 1];
+      if (A.kind == MRK_SORTKEY_INT64) {
+        dq.sort_item = A.item() + 1, dq.sort_shift = 0, dq.sort_bits = 32, dq.sort_flags |= A.flags() | SORT_SIGNED;
+        dq.ord_item = A.item(), dq.ord_shift = 0, dq.ord_bits = 32, dq.ord_flags = A.flags();
+        dq.wf_parts = 2;
+      } else {
+        dq.sort_item = A.item(), dq.sort_shift = (uint32_t)A.bit_offset & 31u, dq.sort_bits = (uint32_t)A.bit_count, dq.sort_flags |= A.flags();
+        if (O.n_parts == 2) dq.ord_item = B.item(), dq.ord_shift = (uint32_t)B.bit_offset & 31u, dq.ord_bits = (uint32_t)B.bit_count, dq.ord_flags = B.flags();
+        dq.wf_parts = (uint32_t)O.n_parts;
+      }
+    }
+  }
+
   // the query's candidate list: a slot range of the batch's arena (16-byte candidates in the arena of the sorted queries; the
   // relevance selection sees an empty list)
   void reserve_candidates(DevQuery& dq, BatchPlan& plan) const {
@@ -1285,7 +1315,7 @@ struct PlanState {
     for (int k : cover) cap += (uint64_t)T.kws[k].docs;
     cap = std::min<uint64_t>(std::max<uint64_t>(cap, 1), (uint64_t)1 << 20);
     dq.cand_off = plan.cand_total;
-    if (order.n_parts) {
+    if (order.sorted()) {
       dq.cand_cap = 0;
       dq.sort_cap = (uint32_t)cap;
       dq.sort_off = plan.sort_total;
@@ -1532,7 +1562,7 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
   if (int rc = S.check_query()) return rc;
   if (int rc = S.resolve_sort()) return rc;
   // (a sorted query reads attribute rows like a filtered one: the packed block scan's EXT instances only)
-  S.filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || S.order.n_parts > 0;
+  S.filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || S.order.sorted();
   // the evaluation tree and who evaluates it
   if (int rc = S.shape_query()) return rc;
   dq.rowid_max = rowid_max;
@@ -1541,7 +1571,9 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
   S.weigh_words(dq);
   if (int rc = S.choose_cover()) return rc;
   // pruning bins and the candidate list
-  if (S.order.n_parts)
+  if (S.order.wfirst)
+    S.bins_by_weight_first(dq);
+  else if (S.order.n_parts)
     PlanState::bins_by_key(S.order, dq);
   else if (S.ranker == MRK_RANK_NONE)
     PlanState::bins_by_rowid(seg, dq);

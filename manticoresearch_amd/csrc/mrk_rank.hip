@@ -71,6 +71,8 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   bool sorted = false;
   uint32_t so_item = 0, so_shift = 0, so_bits = 32, so_flags = 0, so_tie = 0;
   bool wide_ord = false; // mrk_query.order's 64-bit key (see scan_pk_kernel)
+  bool wfirst = false;   // MRK_ORDER_WEIGHT_FIRST_*: the weight leads and takes the bin (see scan_pk_kernel)
+  uint32_t wf_parts = 0;
   OrderPart op1{0u, 0u, 32u, 0u};
   OrderGeom og{0u, 0u, 0u, 0u};
   uint64_t* scand = nullptr;
@@ -98,7 +100,10 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
         if constexpr (SORT) {
           if (sorted) {
             if (fits) *reinterpret_cast<ulonglong2*>(scand + 2 * (uint64_t)(basep + i)) = make_ulonglong2(key, L.cbuf2[i]);
-            atomicAdd(&s.hist[wide_ord ? order_bin(og, key) : sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))], 1u);
+            atomicAdd(&s.hist[wfirst     ? wfirst_bin(so_tie, bin_lo, bin_shift, wfirst_weight(so_tie, key))
+                              : wide_ord ? order_bin(og, key)
+                                         : sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))],
+                      1u);
             continue;
           }
         }
@@ -248,6 +253,11 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
             op1 = OrderPart{U(Q->ord_item), U(Q->ord_shift), U(Q->ord_bits), U(Q->ord_flags)};
             og = OrderGeom{U(Q->ord_geom.a_lo), U(Q->ord_geom.b_lo), U(Q->ord_geom.nb), U(Q->ord_geom.shift)};
           }
+          wfirst = son_ == SORT_ON_WEIGHT;
+          if (wfirst) { // (uniform; the parts behind the weight)
+            op1 = OrderPart{U(Q->ord_item), U(Q->ord_shift), U(Q->ord_bits), U(Q->ord_flags)};
+            wf_parts = U(Q->wf_parts);
+          }
         }
         ghist = a.q_hist + (uint64_t)oq * NBINS;
         gcount = a.q_cand_n + (size_t)oq * QSTRIDE;
@@ -372,7 +382,12 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
     if (is_live) {
       ++total;
       const uint32_t grow = a.seg.rowid_base + rowid;
-      if (SORT && wide_ord) {
+      if (SORT && wfirst) { // the weight, final here, leads and takes the bin; the row's parts only break its ties
+        const uint64_t pk = wfirst_row_key(a.seg.attrs + (uint64_t)rowid * a.seg.attr_stride, wf_parts, OrderPart{so_item, so_shift, so_bits, so_flags}, op1);
+        key = wfirst_hi(so_tie, (int32_t)weight, pk);
+        key2 = wfirst_lo(pk, grow);
+        push = wfirst_bin(so_tie, bin_lo, bin_shift, (int32_t)weight) >= tau_bin;
+      } else if (SORT && wide_ord) {
         key = order_row_key(a.seg.attrs + (uint64_t)rowid * a.seg.attr_stride, OrderPart{so_item, so_shift, so_bits, so_flags}, op1);
         key2 = order_lo(so_tie, (int32_t)weight, grow);
         push = order_bin(og, key) >= tau_bin;

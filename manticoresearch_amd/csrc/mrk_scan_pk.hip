@@ -151,6 +151,8 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
                  so_flags = SORT ? Q->sort_flags : 0u, so_tie = SORT ? Q->sort_tie : 0u;
   // (uniform) the order is mrk_query.order's 64-bit key: two dwords of the row, the 64-bit candidate layouts and bins of mrk_sortkey.h
   const bool wide_ord = SORT && (so_flags & SORT_WIDE) != 0;
+  // (uniform) the weight leads the order (MRK_ORDER_WEIGHT_FIRST_*): the weight-first layout of mrk_sortkey.h, binned by the weight
+  const bool wfirst = SORT && (so_flags & SORT_WFIRST) != 0;
   // (the second part and the bins' geometry are read from the descriptor where they are used: scalar loads on a rare branch)
   auto ord_key = [&](uint32_t row) { return order_row_key(a.seg.attrs + (uint64_t)row * a.seg.attr_stride, OrderPart{so_item, so_shift, so_bits, so_flags}, OrderPart{Q->ord_item, Q->ord_shift, Q->ord_bits, Q->ord_flags}); };
   uint64_t* __restrict__ scand = sorted ? a.scand + 2 * Q->sort_off : nullptr;
@@ -211,7 +213,10 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
         if constexpr (SORT) {
           if (sorted) {
             if (fits) *reinterpret_cast<ulonglong2*>(scand + 2 * (uint64_t)(basep + i)) = make_ulonglong2(key, L.cbuf2[i]);
-            atomicAdd(&L.hist[wide_ord ? order_bin(Q->ord_geom, key) : sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))], 1u);
+            atomicAdd(&L.hist[wfirst     ? wfirst_bin(so_tie, bin_lo, bin_shift, wfirst_weight(so_tie, key))
+                              : wide_ord ? order_bin(Q->ord_geom, key)
+                                         : sort_bin((uint32_t)bin_lo, bin_shift, (uint32_t)(key >> 32))],
+                      1u);
             continue;
           }
         }
@@ -266,7 +271,14 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
       ++total;
       const uint32_t grow = rowid_base + rowid;
       uint32_t bin;
-      if (SORT && wide_ord) { // two dwords of the row make the key; the weight and the rowid share the low word
+      if (SORT && wfirst) { // the weight leads and takes the bin; the row's parts (0..2 dwords) only break its ties
+        const uint64_t pk = wfirst_row_key(a.seg.attrs + (uint64_t)rowid * a.seg.attr_stride, Q->wf_parts, OrderPart{so_item, so_shift, so_bits, so_flags},
+                                           OrderPart{Q->ord_item, Q->ord_shift, Q->ord_bits, Q->ord_flags});
+        bin = wfirst_bin(so_tie, bin_lo, bin_shift, (int32_t)weight);
+        key = wfirst_hi(so_tie, (int32_t)weight, pk);
+        key2 = wfirst_lo(pk, grow);
+        push = bin >= tau_bin;
+      } else if (SORT && wide_ord) { // two dwords of the row make the key; the weight and the rowid share the low word
         key = ord_key(rowid);
         bin = order_bin(Q->ord_geom, key);
         key2 = order_lo(so_tie, (int32_t)weight, grow);
@@ -366,7 +378,9 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   // attribute bin test runs HERE, in front of the match queue -- it needs no hits.  The scan keeps its own histogram of the matches'
   // attribute bins (a.s_hist; the rank kernel's candidates go to q_hist later and must not be counted twice): K matches at or above bin
   // T prove that a match below T cannot reach the top K; it is counted (total_found) and its hits are never read.
-  const bool pre_prune = SORT && PROX && sorted && need_hits && !phrase && !GEN && Q->n_wfilters == 0 && a.s_hist != nullptr;
+  // (not for a weight-first order: its bin is the weight's, which a hit-ranked match has behind the hit pass only; where the weight is
+  // final at scan time -- NONE / BM25 -- the match goes straight to emit_match and its test)
+  const bool pre_prune = SORT && PROX && sorted && !wfirst && need_hits && !phrase && !GEN && Q->n_wfilters == 0 && a.s_hist != nullptr;
   uint32_t* __restrict__ shist = pre_prune ? a.s_hist + (uint64_t)oq * NBINS : nullptr;
   uint32_t* __restrict__ stau = pre_prune ? a.s_tau + (size_t)oq * QSTRIDE : nullptr;
   uint32_t tau_pre = pre_prune ? __hip_atomic_load(stau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;

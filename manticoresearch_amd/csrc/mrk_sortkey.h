@@ -52,6 +52,14 @@ MRK_HD inline uint32_t sort_bin(uint32_t lo, uint32_t shift, uint32_t mapped) {
   return b < 1023u ? b : 1023u;
 }
 
+// pruning bin of a weight (the relevance order's BIN_WEIGHT bins: bin_of of mrk_kprune.h calls this): monotone non-decreasing in it,
+// 1024 bins; lo / shift = DevQuery::bin_lo / bin_shift as bins_by_weight (mrk_plan.cpp) sets them
+MRK_HD inline uint32_t weight_bin(int32_t lo, uint32_t shift, int32_t weight) {
+  if (weight < lo) return 0u;
+  const uint32_t b = ((uint32_t)weight - (uint32_t)lo) >> shift; // (== (uint32_t)(weight - lo), without the signed overflow)
+  return b < 1024u ? b : 1023u;
+}
+
 // A candidate of a sorted query is 128 bits, compared as (hi, lo), larger = better:
 //   hi = mapped key << 32 | the weight as the tie rule orders it (0 where the weight is no part of the order)
 //   lo = ~global rowid << 32 | the true weight
@@ -131,6 +139,34 @@ MRK_HD inline OrderGeom order_geom(uint32_t a_lo, uint32_t a_hi, uint32_t b_lo, 
   }
   while (g.shift < 63u && (top >> g.shift) >= 1024u) ++g.shift;
   return g;
+}
+
+// ---------------------------------------------------------------------------------------
+// The weight in FRONT of the parts (MRK_ORDER_WEIGHT_FIRST_*; SPH_KEYPART_WEIGHT as key part 0 of MatchGeneric2_fn / 3_fn): one
+// layout for every shape of parts, wf = 1 weight DESC / 2 weight ASC (sort_weight_part's tie values; DevQuery::sort_tie holds it),
+//   hi = the weight as wf orders it << 32 | d1
+//   lo = d2 << 32 | ~global rowid
+// d1 : d2 = the parts' 64-bit mapped key exactly as above -- map32(first) : map32(second), the second 0 for a single part of <= 32
+// bits, both 0 without parts (weight ASC alone), the high : low dwords of an INT64's mapped key.  The true weight comes back out of
+// the weight part through order_unweight_part.  The pruning bin is the WEIGHT's: the relevance bins (weight_bin above, which
+// bin_of(BIN_WEIGHT, ..) of mrk_kprune.h is) for weight DESC, 1023 - that bin for weight ASC.
+// ---------------------------------------------------------------------------------------
+constexpr uint32_t SORT_WFIRST = 16;  // DevQuery::sort_flags of a query with sort_on == SORT_ON_WEIGHT (scan_pk_kernel tests this bit, as it does SORT_WIDE)
+constexpr uint32_t SORT_ON_WEIGHT = 3; // DevQuery::sort_on
+MRK_HD inline uint64_t wfirst_hi(uint32_t wf, int32_t weight, uint64_t parts_key) { return ((uint64_t)sort_weight_part(wf, weight) << 32) | (uint32_t)(parts_key >> 32); }
+MRK_HD inline uint64_t wfirst_lo(uint64_t parts_key, uint32_t grow) { return (parts_key << 32) | (uint32_t)~grow; }
+MRK_HD inline int32_t wfirst_weight(uint32_t wf, uint64_t hi) { return (int32_t)order_unweight_part(wf, (uint32_t)(hi >> 32)); }
+MRK_HD inline uint32_t wfirst_rowid(uint64_t lo) { return ~(uint32_t)lo; }
+MRK_HD inline uint64_t wfirst_parts_key(uint64_t hi, uint64_t lo) { return (hi << 32) | (lo >> 32); } // d1 : d2
+// d1 : d2 of an attribute row; n_parts 0..2 (an INT64 counts as its two dwords).  Without parts the row is not read (it may not exist)
+MRK_HD inline uint64_t wfirst_row_key(const uint32_t* row, uint32_t n_parts, const OrderPart& p0, const OrderPart& p1) {
+  if (!n_parts) return 0ull;
+  return order_key(order_map_part(sort_extract(row[p0.item], p0.shift, p0.bits), p0.flags), n_parts > 1u ? order_map_part(sort_extract(row[p1.item], p1.shift, p1.bits), p1.flags) : 0u);
+}
+// lo / shift: DevQuery::bin_lo / bin_shift as bins_by_weight (mrk_plan.cpp) sets them for the relevance order
+MRK_HD inline uint32_t wfirst_bin(uint32_t wf, int32_t lo, uint32_t shift, int32_t weight) {
+  const uint32_t b = weight_bin(lo, shift, weight);
+  return wf == 2u ? 1023u - b : b;
 }
 
 // ---------------------------------------------------------------------------------------

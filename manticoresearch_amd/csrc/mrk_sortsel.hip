@@ -8,6 +8,8 @@
 // reaches the threshold bin and the running K-th best in an LDS buffer of 2 K candidates, and sorts that buffer (bitonic, on
 // the full 128 bits) whenever it fills up: exact however many rows share the K-th row's attribute value -- a column with four
 // distinct values puts a quarter of the matches into one bin, and all of them are compared by weight and rowid here.
+// A weight-first order (MRK_ORDER_WEIGHT_FIRST_*) takes the same walk with the weight-first layout: the bin is the weight's, out of
+// hi's high dword, and the parts' mapped key -- hi's low dword : lo's high dword -- decides inside a weight class.
 //
 // Below it: the WIDE exchange rows that carry a sorted query across segments and shards (pack_srows_kernel) and their merge
 // (merge_srows_kernel), then the ORDER rows that carry a 64-bit mapped key per entry (pack_orows_kernel, merge_orows_kernel).
@@ -79,6 +81,9 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
   const bool wide_ord = Q->sort_on == SORT_ON_ORDER;
   const OrderGeom og = Q->ord_geom;
   const uint32_t tie = Q->sort_tie;
+  // (uniform) MRK_ORDER_WEIGHT_FIRST_*: the weight, in hi's high dword, takes the bin; the parts' mapped key is hi's low : lo's high dword
+  const bool wfirst = Q->sort_on == SORT_ON_WEIGHT;
+  const int32_t wlo = Q->bin_lo;
   const ulonglong2* __restrict__ src = reinterpret_cast<const ulonglong2*>(a.scand) + Q->sort_off;
   if (tid < 64) {
     const uint32_t tb = threshold_bin(a.q_hist + (uint64_t)q * NBINS, K);
@@ -95,7 +100,8 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
     ulonglong2 c = make_ulonglong2(0, 0);
     if (f < n) {
       c = src[f];
-      push = (wide_ord ? order_bin(og, c.x) : sort_bin(lo, shift, (uint32_t)(c.x >> 32))) >= tau_bin && (!have_tau || sortkey_gt(c.x, c.y, th, tl));
+      const uint32_t bin = wfirst ? wfirst_bin(tie, wlo, shift, wfirst_weight(tie, c.x)) : wide_ord ? order_bin(og, c.x) : sort_bin(lo, shift, (uint32_t)(c.x >> 32));
+      push = bin >= tau_bin && (!have_tau || sortkey_gt(c.x, c.y, th, tl));
     }
     const uint64_t bal = __ballot(push);
     if (bal) {
@@ -112,15 +118,19 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
   const uint32_t m = sortsel_compact(s, K); // sorted best first
   // the rows leave in the relevance format: make_key(true weight, global rowid)
   for (uint32_t i = tid; i < m; i += WG) {
-    const uint64_t l = s.lo[i];
-    const uint64_t key = wide_ord ? make_key(order_lo_weight(tie, l), order_lo_rowid(tie, l)) : make_key((int32_t)(uint32_t)l, ~(uint32_t)(l >> 32));
+    const uint64_t h = s.hi[i], l = s.lo[i];
+    const uint64_t key = wfirst     ? make_key(wfirst_weight(tie, h), wfirst_rowid(l))
+                         : wide_ord ? make_key(order_lo_weight(tie, l), order_lo_rowid(tie, l))
+                                    : make_key((int32_t)(uint32_t)l, ~(uint32_t)(l >> 32));
+    const uint64_t mk = wfirst ? wfirst_parts_key(h, l) : wide_ord ? h : h & 0xFFFFFFFF00000000ull; // (weight-first: the parts' key d1 : d2)
     a.out_keys[(uint64_t)q * KCAP + i] = key;
     if (a.h_keys) a.h_keys[(uint64_t)q * KCAP + i] = key;
-    a.out_mkeys[(uint64_t)q * KCAP + i] = (uint32_t)(s.hi[i] >> 32); // the mapped key travels with the row (wide exchange rows)
-    if (a.out_mkeys64) a.out_mkeys64[(uint64_t)q * KCAP + i] = wide_ord ? s.hi[i] : s.hi[i] & 0xFFFFFFFF00000000ull; // ... all of it (order rows)
+    a.out_mkeys[(uint64_t)q * KCAP + i] = (uint32_t)(mk >> 32); // the mapped key travels with the row (wide exchange rows)
+    if (a.out_mkeys64) a.out_mkeys64[(uint64_t)q * KCAP + i] = mk; // ... all of it (order rows)
   }
-  // (a 64-bit key does not fit a wide row: pack_srows_kernel marks that query's row MRK_ROW_DECLINED)
-  if (DST == DST_WIDE && !wide_ord) { // sel_sort_kernel's rule: a query whose candidate list overflowed leaves empty with MRK_ROW_RERUN
+  // (a 64-bit key does not fit a wide row: pack_srows_kernel marks that query's row MRK_ROW_DECLINED; no exchange row carries the
+  // weight's position yet: pack_srows_kernel / pack_orows_kernel mark a weight-first query's row the same way)
+  if (DST == DST_WIDE && !wide_ord && !wfirst) { // sel_sort_kernel's rule: a query whose candidate list overflowed leaves empty with MRK_ROW_RERUN
     const bool bad = (a.q_flags[q] & (QF_OVERFLOW | QF_FSM)) != 0;
     const uint32_t nr = bad ? 0u : m;
     uint64_t* __restrict__ row = a.srows_dst + (uint64_t)q * SROW_WORDS;
@@ -138,7 +148,7 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
       row[SROW_SPEC] = sort_spec_word(Q->sort_flags, Q->sort_tie, Q->sort_bits);
     }
   }
-  if (DST == DST_ORDER) { // the same rule; sorts and 64-bit orders alike
+  if (DST == DST_ORDER && !wfirst) { // the same rule; sorts and 64-bit orders alike
     const bool bad = (a.q_flags[q] & (QF_OVERFLOW | QF_FSM)) != 0;
     const uint32_t nr = bad ? 0u : m;
     uint64_t* __restrict__ row = a.orows_dst + (uint64_t)q * OROW_WORDS;

@@ -4,7 +4,8 @@ order: the bench corpus, N 2-way ANDs of common keywords per launch, every leg o
 relevance legs are forced there by a pass-all RANGE filter).  Legs: BM25 by relevance; BM25 ORDER BY ts DESC; PROXIMITY_BM25 by
 relevance with prox_prune = 0; PROXIMITY_BM25 ORDER BY ts DESC; and, where the checkout has Query.order, BM25 ORDER BY cat DESC, ts DESC
 (a 4-valued category first) and BM25 ORDER BY big DESC (a signed 64-bit column), on rows of their own set behind the other legs, which
-keep the one-dword rows they always ran on.  Per leg: warm-up launches, then R launches timed one by one
+keep the one-dword rows they always ran on; and, where Order has weight_first, BM25 and PROXIMITY_BM25 ORDER BY weight() DESC, ts DESC
+(relevance first, the timestamp as the tie-break: to be read against the relevance legs).  Per leg: warm-up launches, then R launches timed one by one
 (submit -> wait, wall clock) -> median, min, max in ms, plus the scan's HIP-event time and n_cands / total_found.  Run on a checkout
 without Query.sort it times the relevance legs only (the figures of the commit before)."""
 import argparse
@@ -97,6 +98,10 @@ if hasattr(m, "Order"):  # rows: ts | a 4-valued category | a bigint of both sig
                                                             m.Order([m.OrderPart(32, 2, desc=True), m.OrderPart(0, 32, desc=True)], then_weight=1))
     result["legs"]["bm25 order by big desc"] = leg("BM25 ORDER BY big DESC", m.SPH_RANK_BM25, True,
                                                    m.Order([m.OrderPart(64, 64, desc=True, kind=m.SORTKEY_INT64)], then_weight=1))
+if hasattr(m, "Order") and "weight_first" in getattr(m.Order, "__dataclass_fields__", {}):  # relevance first, the timestamp as the tie-break
+    wf = m.Order([m.OrderPart(0, 32, desc=True)], weight_first=1)
+    result["legs"]["bm25 order by weight desc, ts desc"] = leg("BM25 ORDER BY weight() DESC, ts DESC", m.SPH_RANK_BM25, True, wf)
+    result["legs"]["proximity_bm25 order by weight desc, ts desc"] = leg("PROXIMITY_BM25 ORDER BY weight() DESC, ts DESC", m.SPH_RANK_PROXIMITY_BM25, True, wf)
 if args.out:
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
