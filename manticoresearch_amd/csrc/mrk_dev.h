@@ -314,13 +314,6 @@ struct BmGroup {
 };
 static_assert(sizeof(BmGroup) % sizeof(DevItem) == 0, "groups ride behind the work items in the items buffer");
 
-// candidate key: bigger = better under MatchRelevanceLt_fn (weight desc, rowid asc)
-__host__ __device__ inline uint64_t make_key(int32_t weight, uint32_t rowid) {
-  return ((uint64_t)((uint32_t)weight ^ 0x80000000u) << 32) | (uint32_t)(~rowid);
-}
-__host__ __device__ inline int32_t key_weight(uint64_t k) { return (int32_t)((uint32_t)(k >> 32) ^ 0x80000000u); }
-__host__ __device__ inline uint32_t key_rowid(uint64_t k) { return ~(uint32_t)k; }
-
 // Matched docs of hit-ranked queries travel from the scan kernels to rank_kernel through an HBM queue of 64-entry chunks
 // (structure of arrays: per chunk MQ_PLANES rows of 64 dwords -- rowid, tfidf sum, fields | contributing keywords << 8,
 // one packed-array reference per keyword -- each written and read as one coalesced 256-B row)
@@ -413,8 +406,8 @@ struct SortSelArgs {
   uint64_t* h_keys;   // pinned host or NULL
   uint32_t* h_cnt;    // pinned host or NULL
   uint32_t* out_mkeys; // [n_queries][KCAP]: the mapped key (hi >> 32) of out_keys' entries -- what a wide exchange row carries
-  // a standing wide destination (mrk_batch_set_srows_dst): the kernel writes the sorted queries' wide rows itself (the instance
-  // launched without one is compiled without this branch)
+  // a standing wide destination (mrk_batch_set_srows_dst): the kernel writes the sorted queries' wide rows itself, through the row
+  // writer of mrk_krows.h (the instance launched without a destination is compiled without this branch)
   uint64_t* srows_dst;     // device [n_queries][SROW_WORDS] or NULL
   const uint64_t* q_total; // [n_queries]   (read with a standing destination only)
   const uint32_t* q_flags; // [n_queries] QF_*
@@ -461,7 +454,7 @@ struct SelectArgs {
   uint32_t* h_flags;       // pinned host [n_queries] or NULL
   uint32_t* h_cand_n;      // pinned host [n_queries] or NULL
   uint64_t* rows_dst;      // device [n_queries][ROW_WORDS] or NULL: the exchange rows (keys zero-padded | count | total_found or MRK_ROW_RERUN)
-  const uint32_t* declined; // unused by the kernel (declined queries' rows are rewritten by pack_rows_kernel)
+  const uint32_t* declined; // unused by the kernel (declined queries' rows are rewritten by pack_xrows_kernel)
 };
 
 // One launch instead of two copies and a memset in front of every scan: query and work-item descriptors are read from the
@@ -493,74 +486,50 @@ struct MergeArgs {
   const uint64_t* in_rows;
   uint64_t* out_rows;
 };
-// Merge of the shards' result rows, up to 8 lists per query (mrk_select.hip): every list arrives sorted, so the lists are merged
-// pairwise by bitonic MERGES in LDS (top-K of two sorted K-lists = elementwise max of one against the other reversed, then ten
-// half-cleaner stages) -- three rounds for eight shards instead of sorting 8 K keys from scratch.
+// The three exchange-row formats (include/mrk.h; the kernels' view of them: mrk_krows.h).  Every row starts KCAP keys | count |
+// total_found; a WIDE row (MRK_SROW_WORDS) goes on with KCAP mapped keys (u32) | sort spec word, an ORDER row (MRK_OROW_WORDS) with
+// KCAP mapped keys (u64) | order spec word.
+enum RowKind { ROWS_NARROW, ROWS_WIDE, ROWS_ORDER };
+constexpr int ROW_WORDS = MRK_ROW_WORDS;
+constexpr uint64_t ROW_RERUN = MRK_ROW_RERUN, ROW_DECLINED = MRK_ROW_DECLINED, ROW_FLAG_MASK = MRK_ROW_RERUN | MRK_ROW_DECLINED;
+constexpr int SROW_WORDS = MRK_SROW_WORDS;
+constexpr int SROW_MKEYS = KCAP + 2, SROW_SPEC = SROW_WORDS - 1; // word offsets of the u32 plane and of the spec word
+constexpr int OROW_WORDS = MRK_OROW_WORDS;
+constexpr int OROW_MKEYS = KCAP + 2, OROW_SPEC = OROW_WORDS - 1; // word offsets of the u64 plane and of the spec word
+
+// Merge of the shards' result rows, up to 8 lists per query (merge_xrows_kernel, mrk_sortsel.hip): every list arrives sorted, so the
+// lists are merged pairwise by bitonic MERGES in LDS (top-K of two sorted K-lists = elementwise max of one against the other reversed,
+// then ten half-cleaner stages) -- three rounds for eight shards instead of sorting 8 K keys from scratch.  A sorted or ordered query
+// (wide and order rows) orders by (mapped key, the weight as its tie rule says, ~docid); a relevance query, and every query of narrow
+// rows, by the key alone.
 struct MergeRowsArgs {
-  const uint64_t* in_rows; // list l of query q: in_rows[(l * list_stride + q) * ROW_WORDS]
+  const uint64_t* in_rows; // list l of query q: in_rows[(l * list_stride + q) * the format's row words]
   uint32_t n_lists;        // <= 8
   uint32_t list_stride;    // rows between consecutive lists (>= n_queries: a rank's receive buffer is sized for the largest slice)
   uint32_t n_queries;
   uint32_t k;
-  uint64_t* out_rows;      // merged row of query q -> out_rows[(out_first + q) * ROW_WORDS] (device or pinned host memory)
+  uint64_t* out_rows;      // merged row of query q -> out_rows[(out_first + q) * row words] (device or pinned host memory)
   uint32_t out_first;
   uint32_t* flags_any;     // device dword pair or NULL: [0] = 1 if any merged row carries MRK_ROW_RERUN, [1] = ... MRK_ROW_DECLINED
 };
-void launch_merge_rows(const MergeRowsArgs& a, void* stream);
-constexpr int ROW_WORDS = MRK_ROW_WORDS;
-constexpr uint64_t ROW_RERUN = MRK_ROW_RERUN, ROW_DECLINED = MRK_ROW_DECLINED, ROW_FLAG_MASK = MRK_ROW_RERUN | MRK_ROW_DECLINED;
+void launch_merge_xrows(RowKind kind, const MergeRowsArgs& a, void* stream);
 
-struct PackRowsArgs {
-  const uint64_t* keys;   // [n][KCAP]
-  const uint32_t* cnt;    // [n]
-  const uint64_t* total;  // [n]
-  uint64_t* rows;         // [n][ROW_WORDS]
-  const uint32_t* flags;  // [n] QF_* of the scan (NULL = none): a flagged query's row is poisoned, not trusted
-  const uint32_t* declined; // [n] != 0: the planner declined the query on this segment (NULL = none declined)
-  uint32_t n;
-};
-void launch_pack_rows(const PackRowsArgs& a, void* stream);
-
-// Wide rows (mrk_sortsel.hip; MRK_SROW_WORDS, include/mrk.h): keys | count | total_found | KCAP mapped keys (u32) | spec word
-constexpr int SROW_WORDS = MRK_SROW_WORDS;
-constexpr int SROW_MKEYS = KCAP + 2, SROW_SPEC = SROW_WORDS - 1; // word offsets of the u32 plane and of the spec word
-struct PackSRowsArgs {
-  const DevQuery* queries; // the sort spec is the query's own (sort_on / sort_flags / sort_tie / sort_bits)
-  const uint64_t* keys;    // [n][KCAP]
-  const uint32_t* mkeys;   // [n][KCAP] or NULL (the batch never held a sorted query)
-  const uint32_t* cnt;
-  const uint64_t* total;
-  uint64_t* rows;          // [n][SROW_WORDS]
-  const uint32_t* flags;   // as PackRowsArgs
-  const uint32_t* declined;
-  uint32_t n;
-  uint32_t skip_sorted;    // != 0: the sorted queries' rows are already written (sort_select_kernel with a standing destination)
-};
-void launch_pack_srows(const PackSRowsArgs& a, void* stream);
-// Merge of <= 8 wide rows per query: MergeRowsArgs with rows of SROW_WORDS.  A sorted query orders by (mapped key, the weight as
-// its tie rule says, ~docid); a relevance query exactly as merge_rows_kernel.
-void launch_merge_srows(const MergeRowsArgs& a, void* stream);
-
-// Order rows (mrk_sortsel.hip; MRK_OROW_WORDS, include/mrk.h): keys | count | total_found | KCAP mapped keys (u64) | order spec word
-constexpr int OROW_WORDS = MRK_OROW_WORDS;
-constexpr int OROW_MKEYS = KCAP + 2, OROW_SPEC = OROW_WORDS - 1; // word offsets of the u64 plane and of the spec word
-struct PackORowsArgs {
-  const DevQuery* queries;  // the order spec is the query's own (order_spec_word over sort_* / ord_*)
+// A batch's results as exchange rows of one format (pack_xrows_kernel, mrk_sortsel.hip)
+struct PackXRowsArgs {
+  const DevQuery* queries;  // the spec word is the query's own (sort_* / ord_*); NULL for narrow rows, which carry none
   const uint64_t* keys;     // [n][KCAP]
-  const uint64_t* mkeys64;  // [n][KCAP] or NULL: then no query of the batch has a 64-bit key and ...
-  const uint32_t* mkeys;    // ... [n][KCAP] (or NULL: no sorted query either) holds the sorts' 32-bit mapped keys
-  const uint32_t* cnt;
-  const uint64_t* total;
-  uint64_t* rows;           // [n][OROW_WORDS]
-  const uint32_t* flags;    // as PackRowsArgs
-  const uint32_t* declined; // [n] == 1: the planner declined the query on this segment
+  const uint64_t* mkeys64;  // order rows: [n][KCAP] or NULL: then no query of the batch has a 64-bit key and ...
+  const uint32_t* mkeys;    // ... [n][KCAP] (or NULL: no sorted query either) holds the sorts' 32-bit mapped keys: all a wide row carries
+  const uint32_t* cnt;      // [n]
+  const uint64_t* total;    // [n]
+  uint64_t* rows;           // [n][the format's row words]
+  const uint32_t* flags;    // [n] QF_* of the scan (NULL = none): a flagged query's row is poisoned, not trusted
+  const uint32_t* declined; // [n] (NULL = none declined) 1: the planner declined the query on this segment; 2: declined for NARROW rows only
+                            // (a sorted query of a batch with a narrow standing destination) -- a wide row answers it
   uint32_t n;
   uint32_t skip_sorted;     // != 0: the sorted and ordered queries' rows are already written (sort_select_kernel with a standing destination)
 };
-void launch_pack_orows(const PackORowsArgs& a, void* stream);
-// Merge of <= 8 order rows per query: MergeRowsArgs with rows of OROW_WORDS.  An ordered query orders by (64-bit mapped key, the
-// weight as its tie rule says, ~docid); a relevance query exactly as merge_rows_kernel.
-void launch_merge_orows(const MergeRowsArgs& a, void* stream);
+void launch_pack_xrows(RowKind kind, const PackXRowsArgs& a, void* stream);
 
 void launch_scan(const ScanArgs& a, void* stream);
 void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen = false); // a.scand: the instances that carry the sort

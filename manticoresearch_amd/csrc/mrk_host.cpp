@@ -1107,12 +1107,13 @@ static void bind_select(const mrk_batch* b, const mrk_segment* seg, uint32_t n_q
   se.rowid_hi = (uint32_t)(seg->dev.rowid_base + docs - 1);
 }
 
-// what pack_orows_kernel reads of the batch's last submit (the caller sets rows, flags, n, skip_sorted)
-static void bind_pack_orows(mrk_batch* b, mrk::PackORowsArgs& pa) {
-  pa.queries = b->d_queries.p, pa.keys = b->d_out_keys.p, pa.mkeys64 = b->d_out_mkeys64.p, pa.mkeys = b->d_out_mkeys.p;
-  pa.cnt = b->d_out_cnt.p, pa.total = b->d_q_total.p;
+// what pack_xrows_kernel reads of the batch's last submit for rows of `kind` (the caller sets rows, flags, n, skip_sorted)
+static void bind_pack_rows(mrk_batch* b, PackXRowsArgs& pa, RowKind kind) {
+  pa.keys = b->d_out_keys.p, pa.cnt = b->d_out_cnt.p, pa.total = b->d_q_total.p;
+  if (kind != ROWS_NARROW) pa.queries = b->d_queries.p, pa.mkeys = b->d_out_mkeys.p;
+  if (kind == ROWS_ORDER) pa.mkeys64 = b->d_out_mkeys64.p;
   // (a 64-bit order is word 1 -- declined -- for narrow and wide rows: the submit that held one uploaded the order rows' own words)
-  pa.declined = !b->any_declined ? nullptr : b->decl_order ? b->d_decl.p + b->max_queries : b->d_decl.p;
+  pa.declined = !b->any_declined ? nullptr : kind == ROWS_ORDER && b->decl_order ? b->d_decl.p + b->max_queries : b->d_decl.p;
 }
 
 static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n) {
@@ -1331,35 +1332,18 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     }
     b->decl_dirty = any;
   }
-  if (b->rows_dst && (!use_packed || b->any_declined)) { // standing export for the shard exchange (the packed path's sort pass wrote the rows already, unless a query was declined: those rows are marked here)
-    PackRowsArgs pa{};
-    pa.keys = b->d_out_keys.p;
-    pa.cnt = b->d_out_cnt.p;
-    pa.total = b->d_q_total.p;
-    pa.rows = b->rows_dst;
-    pa.flags = use_packed ? b->d_q_flags.p : nullptr;
-    pa.declined = b->any_declined ? b->d_decl.p : nullptr;
-    pa.n = n;
-    launch_pack_rows(pa, st2);
-  }
-  if (b->srows_dst) { // the standing wide export: relevance and declined queries' rows (sort_select_kernel wrote the sorted queries')
-    PackSRowsArgs pa{};
-    pa.queries = b->d_queries.p, pa.keys = b->d_out_keys.p, pa.mkeys = b->d_out_mkeys.p, pa.cnt = b->d_out_cnt.p, pa.total = b->d_q_total.p;
-    pa.rows = b->srows_dst;
-    pa.flags = use_packed ? b->d_q_flags.p : nullptr;
-    pa.declined = b->any_declined ? b->d_decl.p : nullptr;
-    pa.n = n;
-    pa.skip_sorted = use_packed && any_sort ? 1u : 0u;
-    launch_pack_srows(pa, st2);
-  }
-  if (b->orows_dst) { // the standing order-row export: relevance and declined queries' rows (sort_select_kernel wrote the others')
-    mrk::PackORowsArgs pa{};
-    bind_pack_orows(b, pa);
-    pa.rows = b->orows_dst;
+  // The standing export.  Narrow rows: the packed path's sort pass wrote them already, unless a query was declined -- those rows are
+  // marked here.  Wide and order rows: relevance and declined queries' rows (sort_select_kernel wrote the others').
+  const RowKind dst_kind = b->orows_dst ? ROWS_ORDER : b->srows_dst ? ROWS_WIDE : ROWS_NARROW;
+  uint64_t* const dst = b->orows_dst ? b->orows_dst : b->srows_dst ? b->srows_dst : b->rows_dst;
+  if (dst && (dst_kind != ROWS_NARROW || !use_packed || b->any_declined)) {
+    PackXRowsArgs pa{};
+    bind_pack_rows(b, pa, dst_kind);
+    pa.rows = dst;
     pa.flags = use_packed ? b->d_q_flags.p : nullptr;
     pa.n = n;
-    pa.skip_sorted = use_packed && any_sort ? 1u : 0u;
-    mrk::launch_pack_orows(pa, st2);
+    pa.skip_sorted = dst_kind != ROWS_NARROW && use_packed && any_sort ? 1u : 0u;
+    launch_pack_xrows(dst_kind, pa, st2);
   }
   HIP_TRY(hipGetLastError());
   b->packed_run = use_packed;
@@ -1618,29 +1602,20 @@ static int mrk_batch_export_device_impl(mrk_batch* b, uint64_t* keys_dst, uint32
   return MRK_OK;
 }
 
-extern "C" int mrk_batch_set_rows_dst(mrk_batch* b, uint64_t* rows_dst) {
-  if (!b) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_rows_dst: NULL batch");
-  if (rows_dst && b->srows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_rows_dst: the batch has a standing wide destination (mrk_batch_set_srows_dst)");
-  if (rows_dst && b->orows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_rows_dst: the batch has a standing order-row destination (mrk_batch_set_orows_dst)");
-  b->rows_dst = rows_dst;
+// a batch has ONE standing destination
+static int batch_set_dst(mrk_batch* b, uint64_t* dst, RowKind kind) {
+  static const char* const fn[] = {"mrk_batch_set_rows_dst", "mrk_batch_set_srows_dst", "mrk_batch_set_orows_dst"};
+  static const char* const what[] = {"narrow", "wide", "order-row"};
+  if (!b) return mrk_fail(MRK_E_INVAL, "%s: NULL batch", fn[kind]);
+  uint64_t** const slot[] = {&b->rows_dst, &b->srows_dst, &b->orows_dst};
+  for (int o = 0; o < 3; ++o)
+    if (dst && o != kind && *slot[o]) return mrk_fail(MRK_E_INVAL, "%s: the batch has a standing %s destination (%s)", fn[kind], what[o], fn[o]);
+  *slot[kind] = dst;
   return MRK_OK;
 }
-
-extern "C" int mrk_batch_set_srows_dst(mrk_batch* b, uint64_t* srows_dst) {
-  if (!b) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_srows_dst: NULL batch");
-  if (srows_dst && b->rows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_srows_dst: the batch has a standing narrow destination (mrk_batch_set_rows_dst)");
-  if (srows_dst && b->orows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_srows_dst: the batch has a standing order-row destination (mrk_batch_set_orows_dst)");
-  b->srows_dst = srows_dst;
-  return MRK_OK;
-}
-
-extern "C" int mrk_batch_set_orows_dst(mrk_batch* b, uint64_t* orows_dst) {
-  if (!b) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_orows_dst: NULL batch");
-  if (orows_dst && b->rows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_orows_dst: the batch has a standing narrow destination (mrk_batch_set_rows_dst)");
-  if (orows_dst && b->srows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_set_orows_dst: the batch has a standing wide destination (mrk_batch_set_srows_dst)");
-  b->orows_dst = orows_dst;
-  return MRK_OK;
-}
+extern "C" int mrk_batch_set_rows_dst(mrk_batch* b, uint64_t* rows_dst) { return batch_set_dst(b, rows_dst, ROWS_NARROW); }
+extern "C" int mrk_batch_set_srows_dst(mrk_batch* b, uint64_t* srows_dst) { return batch_set_dst(b, srows_dst, ROWS_WIDE); }
+extern "C" int mrk_batch_set_orows_dst(mrk_batch* b, uint64_t* orows_dst) { return batch_set_dst(b, orows_dst, ROWS_ORDER); }
 
 static int mrk_batch_record_event_impl(mrk_batch* b, void* hip_event) {
   if (!b || !hip_event) return mrk_fail(MRK_E_INVAL, "mrk_batch_record_event: NULL argument");
@@ -1649,73 +1624,30 @@ static int mrk_batch_record_event_impl(mrk_batch* b, void* hip_event) {
   return MRK_OK;
 }
 
-static int mrk_batch_export_rows_impl(mrk_batch* b, uint64_t* rows_dst) {
-  if (!b || !rows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_rows: NULL argument");
+static int batch_export_rows(mrk_batch* b, uint64_t* dst, RowKind kind) {
+  if (!b || !dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_%s: NULL argument", kind == ROWS_ORDER ? "orows" : kind == ROWS_WIDE ? "srows" : "rows");
   HIP_TRY(hipSetDevice(b->ctx->device));
-  PackRowsArgs pa{};
-  pa.keys = b->d_out_keys.p;
-  pa.cnt = b->d_out_cnt.p;
-  pa.total = b->d_q_total.p;
-  pa.rows = rows_dst;
+  PackXRowsArgs pa{};
+  bind_pack_rows(b, pa, kind);
+  pa.rows = dst;
   pa.flags = b->packed_run ? b->d_q_flags.p : nullptr;
-  pa.declined = b->any_declined ? b->d_decl.p : nullptr;
   pa.n = b->n_queries;
-  launch_pack_rows(pa, b->stream); // behind the batch's selection kernel
+  launch_pack_xrows(kind, pa, b->stream); // behind the batch's selection kernels
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(b->stream));
   b->in_flight = false;
   return MRK_OK;
 }
 
-static int mrk_batch_export_srows_impl(mrk_batch* b, uint64_t* srows_dst) {
-  if (!b || !srows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_srows: NULL argument");
-  HIP_TRY(hipSetDevice(b->ctx->device));
-  PackSRowsArgs pa{};
-  pa.queries = b->d_queries.p, pa.keys = b->d_out_keys.p, pa.mkeys = b->d_out_mkeys.p, pa.cnt = b->d_out_cnt.p, pa.total = b->d_q_total.p;
-  pa.rows = srows_dst;
-  pa.flags = b->packed_run ? b->d_q_flags.p : nullptr;
-  pa.declined = b->any_declined ? b->d_decl.p : nullptr;
-  pa.n = b->n_queries;
-  launch_pack_srows(pa, b->stream); // behind the batch's selection kernels
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  b->in_flight = false;
-  return MRK_OK;
-}
-
-static int mrk_batch_export_orows_impl(mrk_batch* b, uint64_t* orows_dst) {
-  if (!b || !orows_dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_orows: NULL argument");
-  HIP_TRY(hipSetDevice(b->ctx->device));
-  mrk::PackORowsArgs pa{};
-  bind_pack_orows(b, pa);
-  pa.rows = orows_dst;
-  pa.flags = b->packed_run ? b->d_q_flags.p : nullptr;
-  pa.n = b->n_queries;
-  mrk::launch_pack_orows(pa, b->stream); // behind the batch's selection kernels
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(b->stream));
-  b->in_flight = false;
-  return MRK_OK;
-}
-
-// the three exchange-row formats: the row width and the merge kernel are all that differ between their entry points
-enum RowKind { ROWS_NARROW, ROWS_WIDE, ROWS_ORDER };
-
-// rows of n_lists shards -> merged rows; lists [l][list_stride][ROW_WORDS], queries [0, n_queries) of each, out rows at out_first + q
-// (wide: rows of SROW_WORDS through merge_srows_kernel, order rows of OROW_WORDS through merge_orows_kernel; the callers keep
-// n_lists <= 8 there)
+// rows of n_lists shards -> merged rows; lists [l][list_stride][row words of `kind`], queries [0, n_queries) of each, out rows at
+// out_first + q (the callers keep n_lists <= 8 for wide and order rows)
 static void launch_rows_merge(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t list_stride, uint32_t n_queries, uint32_t k,
                               uint64_t* out_rows, uint32_t out_first, uint32_t* flags_any, RowKind kind = ROWS_NARROW) {
   if (n_lists <= 8) {
     mrk::MergeRowsArgs mr{};
     mr.in_rows = rows_all, mr.n_lists = n_lists, mr.list_stride = list_stride, mr.n_queries = n_queries, mr.k = k;
     mr.out_rows = out_rows, mr.out_first = out_first, mr.flags_any = flags_any;
-    if (kind == ROWS_ORDER)
-      launch_merge_orows(mr, ctx->merge_stream);
-    else if (kind == ROWS_WIDE)
-      launch_merge_srows(mr, ctx->merge_stream);
-    else
-      launch_merge_rows(mr, ctx->merge_stream);
+    launch_merge_xrows(kind, mr, ctx->merge_stream);
     return;
   }
   MergeArgs ma{}; // many lists (one GPU serving many segments): the general kernel; same layout only when the stride is the query count
@@ -2019,7 +1951,7 @@ extern "C" int mrk_batch_record_event(mrk_batch* b, void* hip_event) {
   return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_record_event_impl(b, hip_event); });
 }
 extern "C" int mrk_batch_export_rows(mrk_batch* b, uint64_t* rows_dst) {
-  return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_export_rows_impl(b, rows_dst); });
+  return on_worker(b ? b->ctx : nullptr, [&] { return batch_export_rows(b, rows_dst, ROWS_NARROW); });
 }
 extern "C" int mrk_topk_merge_rows(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_rows) {
   return on_worker(ctx, [&] { return mrk_topk_merge_rows_impl(ctx, rows_all, n_lists, n_queries, k, out_rows); });
@@ -2033,7 +1965,7 @@ extern "C" int mrk_topk_merge_rows_part(mrk_ctx* ctx, const uint64_t* rows_recv,
   return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, rows_recv, n_lists, list_stride, first, count, k, out_rows); });
 }
 extern "C" int mrk_batch_export_srows(mrk_batch* b, uint64_t* srows_dst) {
-  return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_export_srows_impl(b, srows_dst); });
+  return on_worker(b ? b->ctx : nullptr, [&] { return batch_export_rows(b, srows_dst, ROWS_WIDE); });
 }
 extern "C" int mrk_topk_merge_srows(mrk_ctx* ctx, const uint64_t* srows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_srows) {
   return on_worker(ctx, [&] { return mrk_topk_merge_rows_impl(ctx, srows_all, n_lists, n_queries, k, out_srows, ROWS_WIDE); });
@@ -2047,7 +1979,7 @@ extern "C" int mrk_topk_merge_srows_part(mrk_ctx* ctx, const uint64_t* srows_rec
   return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, srows_recv, n_lists, list_stride, first, count, k, out_srows, ROWS_WIDE); });
 }
 extern "C" int mrk_batch_export_orows(mrk_batch* b, uint64_t* orows_dst) {
-  return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_export_orows_impl(b, orows_dst); });
+  return on_worker(b ? b->ctx : nullptr, [&] { return batch_export_rows(b, orows_dst, ROWS_ORDER); });
 }
 extern "C" int mrk_topk_merge_orows(mrk_ctx* ctx, const uint64_t* orows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_orows) {
   return on_worker(ctx, [&] { return mrk_topk_merge_rows_impl(ctx, orows_all, n_lists, n_queries, k, out_orows, ROWS_ORDER); });

@@ -583,29 +583,6 @@ __global__ __launch_bounds__(WG) void merge_kernel(MergeArgs a) {
   if (tid == 0) a.out_cnt[q] = n;
 }
 
-// a batch's results as exchange rows: KCAP keys | count | total_found
-__global__ __launch_bounds__(WG) void pack_rows_kernel(PackRowsArgs a) {
-  const uint32_t q = blockIdx.x;
-  if (q >= a.n) return;
-  uint64_t* __restrict__ row = a.rows + (uint64_t)q * ROW_WORDS;
-  // a query whose candidate list overflowed has no trustworthy list on the device until the host reran it: its row goes
-  // out empty with ROW_RERUN set in the total_found word; a query this shard declined (MRK_E_UNSUPPORTED) goes out empty
-  // with ROW_DECLINED.  The merge ORs both bits through: the receiver reruns / fails the query, never a partial answer.
-  const bool declined = a.declined && a.declined[q] != 0;
-  const bool bad = declined || (a.flags && (a.flags[q] & (QF_OVERFLOW | QF_FSM)) != 0);
-  const uint32_t n = bad ? 0u : a.cnt[q] < (uint32_t)KCAP ? a.cnt[q] : (uint32_t)KCAP;
-  for (uint32_t i = threadIdx.x; i < (uint32_t)KCAP; i += WG) row[i] = i < n ? a.keys[(uint64_t)q * KCAP + i] : 0ull;
-  if (threadIdx.x == 0) {
-    row[KCAP] = n;
-    row[KCAP + 1] = declined ? ROW_DECLINED : bad ? ROW_RERUN : (a.total[q] & ~ROW_FLAG_MASK);
-  }
-}
-
-void launch_pack_rows(const PackRowsArgs& a, void* stream) {
-  if (!a.n) return;
-  hipLaunchKernelGGL(pack_rows_kernel, dim3(a.n), dim3(WG), 0, (hipStream_t)stream, a);
-}
-
 void launch_scan(const ScanArgs& a, void* stream) {
   if (!a.n_items) return;
   hipLaunchKernelGGL(scan_kernel, dim3(a.n_items), dim3(WG), 0, (hipStream_t)stream, a);

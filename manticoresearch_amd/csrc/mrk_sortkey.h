@@ -13,6 +13,12 @@
 
 namespace mrk {
 
+// candidate key of the relevance order, and the format every result row leaves in: bigger = better under MatchRelevanceLt_fn
+// (weight desc, rowid asc)
+MRK_HD inline uint64_t make_key(int32_t weight, uint32_t rowid) { return ((uint64_t)((uint32_t)weight ^ 0x80000000u) << 32) | (uint32_t)(~rowid); }
+MRK_HD inline int32_t key_weight(uint64_t k) { return (int32_t)((uint32_t)(k >> 32) ^ 0x80000000u); }
+MRK_HD inline uint32_t key_rowid(uint64_t k) { return ~(uint32_t)k; }
+
 constexpr uint32_t SORT_FLOAT = 1, SORT_DESC = 2; // DevQuery::sort_flags
 
 // the attribute's bits out of its dword (sphGetRowAttr, sphinx.h:993-1014, for locators of <= 32 bits)
@@ -167,6 +173,24 @@ MRK_HD inline uint64_t wfirst_row_key(const uint32_t* row, uint32_t n_parts, con
 MRK_HD inline uint32_t wfirst_bin(uint32_t wf, int32_t lo, uint32_t shift, int32_t weight) {
   const uint32_t b = weight_bin(lo, shift, weight);
   return wf == 2u ? 1023u - b : b;
+}
+
+// ---------------------------------------------------------------------------------------
+// A candidate (hi, lo) under whichever of the three layouts above DevQuery::sort_on names (SORT_ON_ATTR: the sort's; SORT_ON_ORDER:
+// the 64-bit order's; SORT_ON_WEIGHT: weight-first), tie = DevQuery::sort_tie: its pruning bin (lo / shift = DevQuery::bin_lo /
+// bin_shift, g = ord_geom), the key it leaves the device with -- make_key(true weight, global rowid) -- and its 64-bit mapped key (a
+// sort's 32 bits in the high dword; weight-first: the parts' key d1 : d2)
+// ---------------------------------------------------------------------------------------
+MRK_HD inline uint32_t cand_bin(uint32_t sort_on, uint32_t tie, int32_t lo, uint32_t shift, const OrderGeom& g, uint64_t hi) {
+  return sort_on == SORT_ON_WEIGHT ? wfirst_bin(tie, lo, shift, wfirst_weight(tie, hi)) : sort_on == SORT_ON_ORDER ? order_bin(g, hi) : sort_bin((uint32_t)lo, shift, (uint32_t)(hi >> 32));
+}
+MRK_HD inline uint64_t cand_out_key(uint32_t sort_on, uint32_t tie, uint64_t hi, uint64_t lo) {
+  return sort_on == SORT_ON_WEIGHT  ? make_key(wfirst_weight(tie, hi), wfirst_rowid(lo))
+         : sort_on == SORT_ON_ORDER ? make_key(order_lo_weight(tie, lo), order_lo_rowid(tie, lo))
+                                    : make_key((int32_t)(uint32_t)lo, ~(uint32_t)(lo >> 32));
+}
+MRK_HD inline uint64_t cand_mkey(uint32_t sort_on, uint64_t hi, uint64_t lo) {
+  return sort_on == SORT_ON_WEIGHT ? wfirst_parts_key(hi, lo) : sort_on == SORT_ON_ORDER ? hi : hi & 0xFFFFFFFF00000000ull;
 }
 
 // ---------------------------------------------------------------------------------------

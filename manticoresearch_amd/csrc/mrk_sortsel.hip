@@ -11,13 +11,15 @@
 // A weight-first order (MRK_ORDER_WEIGHT_FIRST_*) takes the same walk with the weight-first layout: the bin is the weight's, out of
 // hi's high dword, and the parts' mapped key -- hi's low dword : lo's high dword -- decides inside a weight class.
 //
-// Below it: the WIDE exchange rows that carry a sorted query across segments and shards (pack_srows_kernel) and their merge
-// (merge_srows_kernel), then the ORDER rows that carry a 64-bit mapped key per entry (pack_orows_kernel, merge_orows_kernel).
+// Below it: the exchange rows that carry a batch's results across segments and shards, in their three formats (mrk_krows.h) -- one
+// pack kernel (pack_xrows_kernel) and one merge of <= 8 lists per query (merge_xrows_kernel), each instantiated per format.
 #include "mrk_kcommon.h"
 #include "mrk_kprune.h"
+#include "mrk_krows.h"
 #include "mrk_sortkey.h"
 
 #include <atomic>
+#include <type_traits>
 
 namespace mrk {
 
@@ -76,14 +78,10 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
   const uint32_t K = Q->k ? (Q->k < (uint32_t)KCAP ? Q->k : (uint32_t)KCAP) : 1u;
   uint32_t n = a.q_cand_n[(size_t)q * QSTRIDE];
   if (n > Q->sort_cap) n = Q->sort_cap;
-  const uint32_t lo = (uint32_t)Q->bin_lo, shift = Q->bin_shift;
-  // (uniform) mrk_query.order's 64-bit key: the bin of the whole high word, weight and rowid out of the low word by the tie layout
-  const bool wide_ord = Q->sort_on == SORT_ON_ORDER;
+  // (uniform) which of mrk_sortkey.h's three candidate layouts the list holds, and what its bins are taken from
+  const uint32_t sort_on = Q->sort_on, tie = Q->sort_tie, shift = Q->bin_shift;
+  const int32_t blo = Q->bin_lo;
   const OrderGeom og = Q->ord_geom;
-  const uint32_t tie = Q->sort_tie;
-  // (uniform) MRK_ORDER_WEIGHT_FIRST_*: the weight, in hi's high dword, takes the bin; the parts' mapped key is hi's low : lo's high dword
-  const bool wfirst = Q->sort_on == SORT_ON_WEIGHT;
-  const int32_t wlo = Q->bin_lo;
   const ulonglong2* __restrict__ src = reinterpret_cast<const ulonglong2*>(a.scand) + Q->sort_off;
   if (tid < 64) {
     const uint32_t tb = threshold_bin(a.q_hist + (uint64_t)q * NBINS, K);
@@ -100,8 +98,7 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
     ulonglong2 c = make_ulonglong2(0, 0);
     if (f < n) {
       c = src[f];
-      const uint32_t bin = wfirst ? wfirst_bin(tie, wlo, shift, wfirst_weight(tie, c.x)) : wide_ord ? order_bin(og, c.x) : sort_bin(lo, shift, (uint32_t)(c.x >> 32));
-      push = bin >= tau_bin && (!have_tau || sortkey_gt(c.x, c.y, th, tl));
+      push = cand_bin(sort_on, tie, blo, shift, og, c.x) >= tau_bin && (!have_tau || sortkey_gt(c.x, c.y, th, tl));
     }
     const uint64_t bal = __ballot(push);
     if (bal) {
@@ -117,51 +114,27 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
   }
   const uint32_t m = sortsel_compact(s, K); // sorted best first
   // the rows leave in the relevance format: make_key(true weight, global rowid)
+  auto key_at = [&](uint32_t i) { return cand_out_key(sort_on, tie, s.hi[i], s.lo[i]); };
+  auto mkey_at = [&](uint32_t i) { return cand_mkey(sort_on, s.hi[i], s.lo[i]); };
   for (uint32_t i = tid; i < m; i += WG) {
-    const uint64_t h = s.hi[i], l = s.lo[i];
-    const uint64_t key = wfirst     ? make_key(wfirst_weight(tie, h), wfirst_rowid(l))
-                         : wide_ord ? make_key(order_lo_weight(tie, l), order_lo_rowid(tie, l))
-                                    : make_key((int32_t)(uint32_t)l, ~(uint32_t)(l >> 32));
-    const uint64_t mk = wfirst ? wfirst_parts_key(h, l) : wide_ord ? h : h & 0xFFFFFFFF00000000ull; // (weight-first: the parts' key d1 : d2)
+    const uint64_t key = key_at(i), mk = mkey_at(i);
     a.out_keys[(uint64_t)q * KCAP + i] = key;
     if (a.h_keys) a.h_keys[(uint64_t)q * KCAP + i] = key;
     a.out_mkeys[(uint64_t)q * KCAP + i] = (uint32_t)(mk >> 32); // the mapped key travels with the row (wide exchange rows)
     if (a.out_mkeys64) a.out_mkeys64[(uint64_t)q * KCAP + i] = mk; // ... all of it (order rows)
   }
-  // (a 64-bit key does not fit a wide row: pack_srows_kernel marks that query's row MRK_ROW_DECLINED; no exchange row carries the
-  // weight's position yet: pack_srows_kernel / pack_orows_kernel mark a weight-first query's row the same way)
-  if (DST == DST_WIDE && !wide_ord && !wfirst) { // sel_sort_kernel's rule: a query whose candidate list overflowed leaves empty with MRK_ROW_RERUN
-    const bool bad = (a.q_flags[q] & (QF_OVERFLOW | QF_FSM)) != 0;
-    const uint32_t nr = bad ? 0u : m;
-    uint64_t* __restrict__ row = a.srows_dst + (uint64_t)q * SROW_WORDS;
-    for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) {
-      const uint64_t l = s.lo[i];
-      row[i] = i < nr ? make_key((int32_t)(uint32_t)l, ~(uint32_t)(l >> 32)) : 0ull;
-    }
-    for (uint32_t i = tid; i < (uint32_t)KCAP / 2; i += WG) {
-      const uint64_t m0 = 2 * i < nr ? s.hi[2 * i] >> 32 : 0ull, m1 = 2 * i + 1 < nr ? s.hi[2 * i + 1] >> 32 : 0ull;
-      row[SROW_MKEYS + i] = m0 | (m1 << 32);
-    }
-    if (tid == 0) {
-      row[KCAP] = nr;
-      row[KCAP + 1] = bad ? ROW_RERUN : (a.q_total[q] & ~ROW_FLAG_MASK);
-      row[SROW_SPEC] = sort_spec_word(Q->sort_flags, Q->sort_tie, Q->sort_bits);
-    }
-  }
-  if (DST == DST_ORDER && !wfirst) { // the same rule; sorts and 64-bit orders alike
-    const bool bad = (a.q_flags[q] & (QF_OVERFLOW | QF_FSM)) != 0;
-    const uint32_t nr = bad ? 0u : m;
-    uint64_t* __restrict__ row = a.orows_dst + (uint64_t)q * OROW_WORDS;
-    for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) {
-      const uint64_t h = s.hi[i], l = s.lo[i];
-      const uint64_t key = wide_ord ? make_key(order_lo_weight(tie, l), order_lo_rowid(tie, l)) : make_key((int32_t)(uint32_t)l, ~(uint32_t)(l >> 32));
-      row[i] = i < nr ? key : 0ull;
-      row[OROW_MKEYS + i] = i < nr ? (wide_ord ? h : h & 0xFFFFFFFF00000000ull) : 0ull;
-    }
-    if (tid == 0) {
-      row[KCAP] = nr;
-      row[KCAP + 1] = bad ? ROW_RERUN : (a.q_total[q] & ~ROW_FLAG_MASK);
-      row[OROW_SPEC] = order_spec_word(Q->sort_on, Q->sort_flags, Q->sort_bits, Q->ord_flags, Q->ord_bits, Q->sort_tie);
+  // The standing destination's row.  A 64-bit key does not fit a wide row, and no exchange row carries the weight's position yet: no
+  // row is written then, and pack_xrows_kernel marks that query's row MRK_ROW_DECLINED.  sel_sort_kernel's rule: a query whose
+  // candidate list overflowed leaves empty with MRK_ROW_RERUN.
+  if constexpr (DST != DST_NONE) {
+    using Fmt = std::conditional_t<DST == DST_WIDE, WideFmt, OrderFmt>;
+    if (sort_on != SORT_ON_WEIGHT && (Fmt::WIDE_KEYS || sort_on != SORT_ON_ORDER)) { // (uniform)
+      const bool bad = (a.q_flags[q] & (QF_OVERFLOW | QF_FSM)) != 0;
+      const uint32_t nr = bad ? 0u : m;
+      uint64_t* __restrict__ row = (DST == DST_WIDE ? a.srows_dst : a.orows_dst) + (uint64_t)q * Fmt::WORDS;
+      write_row_keys(row, nr, key_at);
+      Fmt::store_plane(row, nr, [&](uint32_t i) { return Fmt::mkey_of(mkey_at(i)); });
+      if (tid == 0) write_row_header<Fmt>(row, nr, row_total_word(false, bad, a.q_total[q]), Fmt::spec_of(*Q));
     }
   }
   if (tid == 0) {
@@ -181,44 +154,42 @@ void launch_sort_select(const SortSelArgs& a, void* stream) {
 }
 
 // ---------------------------------------------------------------------------------------
-// a batch's results as WIDE exchange rows: KCAP keys | count | total_found | KCAP mapped keys (u32) | spec word
+// a batch's results as exchange rows of one format.  Sorts and 64-bit orders leave with their mapped keys where the format has a
+// plane for them; relevance queries with spec 0 and a zero plane.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void pack_srows_kernel(PackSRowsArgs a) {
-  const uint32_t q = blockIdx.x, tid = threadIdx.x;
+template <class Fmt>
+__global__ __launch_bounds__(WG) void pack_xrows_kernel(PackXRowsArgs a) {
+  constexpr bool PLANE = Fmt::MK_BYTES != 0;
+  const uint32_t q = blockIdx.x;
   if (q >= a.n) return;
-  const DevQuery* __restrict__ Q = a.queries + q;
-  // declined words: 1 = the planner declined the query on this segment; 2 = declined for NARROW rows only (a sorted query
-  // of a batch with a narrow standing destination) -- a wide row answers it
-  const bool declined = a.declined && a.declined[q] == 1u;
-  const bool sorted = Q->sort_on != 0 && !declined;
-  if (a.skip_sorted && sorted) return; // (uniform) sort_select_kernel<DST_WIDE> wrote this row
+  const uint32_t dw = a.declined ? a.declined[q] : 0u; // (2 = declined for narrow rows only)
+  const bool declined = PLANE ? dw == 1u : dw != 0u;
+  const uint32_t sort_on = PLANE ? a.queries[q].sort_on : 0u; // (narrow rows: a sorted query is a declined one)
+  const bool sorted = sort_on != 0 && !declined;
+  if (a.skip_sorted && sorted) return; // (uniform) sort_select_kernel wrote this row
   const bool bad = declined || (a.flags && (a.flags[q] & (QF_OVERFLOW | QF_FSM)) != 0);
   const uint32_t n = bad ? 0u : a.cnt[q] < (uint32_t)KCAP ? a.cnt[q] : (uint32_t)KCAP;
-  uint64_t* __restrict__ row = a.rows + (uint64_t)q * SROW_WORDS;
-  const uint32_t nm = sorted && a.mkeys ? n : 0u; // a relevance row's u32 plane is zero
-  for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) row[i] = i < n ? a.keys[(uint64_t)q * KCAP + i] : 0ull;
-  for (uint32_t i = tid; i < (uint32_t)KCAP / 2; i += WG) {
-    const uint64_t m0 = 2 * i < nm ? a.mkeys[(uint64_t)q * KCAP + 2 * i] : 0u, m1 = 2 * i + 1 < nm ? a.mkeys[(uint64_t)q * KCAP + 2 * i + 1] : 0u;
-    row[SROW_MKEYS + i] = m0 | (m1 << 32);
-  }
-  if (tid == 0) {
-    row[KCAP] = n;
-    row[KCAP + 1] = declined ? ROW_DECLINED : bad ? ROW_RERUN : (a.total[q] & ~ROW_FLAG_MASK);
-    row[SROW_SPEC] = sorted ? sort_spec_word(Q->sort_flags, Q->sort_tie, Q->sort_bits) : 0ull;
-  }
+  uint64_t* __restrict__ row = a.rows + (uint64_t)q * Fmt::WORDS;
+  // a 64-bit key needs the 64-bit plane; a sort's key is whole in the u32 plane too (a batch that never saw a 64-bit key has no other)
+  const uint32_t nm = sorted && (a.mkeys64 || (a.mkeys && (!Fmt::WIDE_KEYS || sort_on != SORT_ON_ORDER))) ? n : 0u;
+  write_row_keys(row, n, [&](uint32_t i) { return a.keys[(uint64_t)q * KCAP + i]; });
+  Fmt::store_plane(row, nm, [&](uint32_t i) { return Fmt::mkey_of(a.mkeys64 ? a.mkeys64[(uint64_t)q * KCAP + i] : (uint64_t)a.mkeys[(uint64_t)q * KCAP + i] << 32); });
+  if (threadIdx.x == 0) write_row_header<Fmt>(row, n, row_total_word(declined, bad, a.total[q]), sorted ? Fmt::spec_of(a.queries[q]) : 0ull);
 }
 
-void launch_pack_srows(const PackSRowsArgs& a, void* stream) {
+void launch_pack_xrows(RowKind kind, const PackXRowsArgs& a, void* stream) {
   if (!a.n) return;
-  hipLaunchKernelGGL(pack_srows_kernel, dim3(a.n), dim3(WG), 0, (hipStream_t)stream, a);
+  auto* kernel = kind == ROWS_ORDER ? pack_xrows_kernel<OrderFmt> : kind == ROWS_WIDE ? pack_xrows_kernel<WideFmt> : pack_xrows_kernel<NarrowFmt>;
+  hipLaunchKernelGGL(kernel, dim3(a.n), dim3(WG), 0, (hipStream_t)stream, a);
 }
 
 // ---------------------------------------------------------------------------------------
-// merge of <= 8 sorted WIDE rows per query: merge_rows_kernel's pairwise bitonic merges (mrk_select.hip) over entries of
-// 12 bytes -- the u64 key and, in a plane of its own, the u32 mapped key.  The weight and the docid come out of the u64 key,
-// so a sorted query compares (mapped key, the key as the tie rule reads it); a relevance query (spec 0) compares the key alone:
-// exactly merge_rows_kernel's order.  LDS: P lists x KCAP x 12 B = 96 KB for 8 lists (one workgroup per CU on gfx950's 160 KB;
-// 48 KB and three workgroups for up to 4 lists).
+// merge of <= 8 sorted rows per query (the shard exchange's merge step; CSphMatchQueue::MoveTo across chunks, sphinxsort.cpp:681-710):
+// one workgroup per query, all lists in LDS, merged pairwise by bitonic merges over entries of 8 + Fmt::MK_BYTES bytes -- the u64 key
+// and, in a plane of its own, the mapped key.  The weight and the docid come out of the u64 key, so a sorted or ordered query compares
+// (mapped key, the key as the tie rule reads it); a relevance query (spec 0), and every query of narrow rows, compares the key alone
+// and never touches the mapped plane.  LDS for 8 lists: 64 KB narrow, 96 KB wide, 128 KB order rows (one workgroup per CU on gfx950's
+// 160 KB); half that for up to 4 lists.
 // ---------------------------------------------------------------------------------------
 // the u64 key as tie rule `tie` orders it, larger = better; the zero key is the lists' padding and stays the smallest
 template <uint32_t TIE>
@@ -228,10 +199,10 @@ __device__ __forceinline__ uint64_t tie_key(uint64_t k) {
   return TIE == 2u ? k ^ 0xFFFFFFFF00000000ull : k & 0xFFFFFFFFull; // weight ascending / the weight is no part of the order
 }
 
-template <bool SORTED, uint32_t TIE>
-static __device__ void merge_srows_rounds(uint64_t* mk, uint32_t* mm, uint32_t P) {
+template <class MK, bool SORTED, uint32_t TIE>
+static __device__ void merge_rounds(uint64_t* mk, MK* mm, uint32_t P) {
   const uint32_t tid = threadIdx.x;
-  auto less = [](uint64_t xk, uint32_t xm, uint64_t yk, uint32_t ym) -> bool {
+  auto less = [](uint64_t xk, MK xm, uint64_t yk, MK ym) -> bool {
     if (SORTED && xm != ym) return xm < ym;
     return tie_key<TIE>(xk) < tie_key<TIE>(yk);
   };
@@ -239,9 +210,9 @@ static __device__ void merge_srows_rounds(uint64_t* mk, uint32_t* mm, uint32_t P
     const uint32_t pairs = P / (2 * step);
     for (uint32_t t = tid; t < pairs * KCAP; t += WG) { // top K of A and B as a bitonic sequence, in A's place
       const uint32_t p = t / KCAP, i = t % KCAP;
-      const size_t ia = (size_t)(2 * p * step) * KCAP + i, ib = (size_t)((2 * p + 1) * step) * KCAP + (KCAP - 1 - i);
+      const uint32_t ia = 2 * p * step * KCAP + i, ib = (2 * p + 1) * step * KCAP + (KCAP - 1 - i); // (< P KCAP <= 8192)
       const uint64_t xk = mk[ia], yk = mk[ib];
-      const uint32_t xm = SORTED ? mm[ia] : 0u, ym = SORTED ? mm[ib] : 0u;
+      const MK xm = SORTED ? mm[ia] : MK(0), ym = SORTED ? mm[ib] : MK(0);
       if (less(xk, xm, yk, ym)) {
         mk[ia] = yk;
         if (SORTED) mm[ia] = ym;
@@ -251,10 +222,9 @@ static __device__ void merge_srows_rounds(uint64_t* mk, uint32_t* mm, uint32_t P
     for (uint32_t j = KCAP / 2; j > 0; j >>= 1) { // ... sorted descending by half-cleaners
       for (uint32_t t = tid; t < pairs * (KCAP / 2); t += WG) {
         const uint32_t p = t / (KCAP / 2), i0 = t % (KCAP / 2);
-        const size_t base = (size_t)(2 * p * step) * KCAP;
-        const size_t i = base + (((i0 & ~(j - 1)) << 1) | (i0 & (j - 1))), ij = i + j;
+        const uint32_t i = 2 * p * step * KCAP + (((i0 & ~(j - 1)) << 1) | (i0 & (j - 1))), ij = i + j;
         const uint64_t xk = mk[i], yk = mk[ij];
-        const uint32_t xm = SORTED ? mm[i] : 0u, ym = SORTED ? mm[ij] : 0u;
+        const MK xm = SORTED ? mm[i] : MK(0), ym = SORTED ? mm[ij] : MK(0);
         if (less(xk, xm, yk, ym)) {
           mk[i] = yk, mk[ij] = xk;
           if (SORTED) mm[i] = ym, mm[ij] = xm;
@@ -265,59 +235,69 @@ static __device__ void merge_srows_rounds(uint64_t* mk, uint32_t* mm, uint32_t P
   }
 }
 
-__global__ __launch_bounds__(WG) void merge_srows_kernel(MergeRowsArgs a, uint32_t P) { // P = power of two >= n_lists
-  extern __shared__ uint64_t mk[];                            // [P][KCAP] keys ...
-  uint32_t* mm = reinterpret_cast<uint32_t*>(mk + (size_t)P * KCAP); // ... then [P][KCAP] mapped keys
+template <class Fmt>
+__global__ __launch_bounds__(WG) void merge_xrows_kernel(MergeRowsArgs a, uint32_t P) { // P = power of two >= n_lists
+  using MK = typename Fmt::MK;
+  constexpr bool PLANE = Fmt::MK_BYTES != 0;
+  extern __shared__ uint64_t mk[];                       // [P][KCAP] keys ...
+  MK* mm = reinterpret_cast<MK*>(mk + (size_t)P * KCAP); // ... then [P][KCAP] mapped keys (narrow rows: the end of the allocation, never read or written)
   const uint32_t q = blockIdx.x, tid = threadIdx.x;
   if (q >= a.n_queries) return;
-  const uint64_t spec = a.in_rows[(uint64_t)q * SROW_WORDS + SROW_SPEC]; // list 0's; every list must agree
-  uint64_t total = 0, flags = 0, have = 0;
+  // The query's spec word, by the format's election rule
+  uint64_t spec = 0;
   bool mismatch = false;
+  if (Fmt::ELECT == SPEC_OF_LIST0) spec = a.in_rows[(uint64_t)q * Fmt::WORDS + Fmt::SPEC];
+  if (Fmt::ELECT == SPEC_OF_ANSWERING) {
+    // a shard whose planner declined the query holds no order for it and sends spec 0 (pack_xrows_kernel), so the merged row's spec
+    // word does not depend on which list declined
+    bool have_spec = false;
+    for (uint32_t l = 0; l < a.n_lists; ++l) { // (uniform: scalar loads)
+      const uint64_t* __restrict__ row = a.in_rows + ((uint64_t)l * a.list_stride + q) * Fmt::WORDS;
+      if (row[KCAP + 1] & ROW_DECLINED) continue;
+      const uint64_t sp = row[Fmt::SPEC];
+      if (!have_spec) spec = sp, have_spec = true;
+      mismatch = mismatch || sp != spec;
+    }
+  }
+  uint64_t total = 0, flags = 0, have = 0;
   for (uint32_t l = 0; l < P; ++l) {
     uint32_t cnt = 0;
     const uint64_t* __restrict__ row = nullptr;
     if (l < a.n_lists) {
-      row = a.in_rows + ((uint64_t)l * a.list_stride + q) * SROW_WORDS;
+      row = a.in_rows + ((uint64_t)l * a.list_stride + q) * Fmt::WORDS;
       cnt = (uint32_t)row[KCAP];
       if (cnt > (uint32_t)KCAP) cnt = KCAP;
       const uint64_t t = row[KCAP + 1];
       total += t & ~ROW_FLAG_MASK, flags |= t & ROW_FLAG_MASK, have += cnt;
-      mismatch = mismatch || row[SROW_SPEC] != spec;
+      if (Fmt::ELECT == SPEC_OF_LIST0) mismatch = mismatch || row[Fmt::SPEC] != spec;
     }
     for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) mk[l * KCAP + i] = i < cnt ? row[i] : 0ull;
-    if (spec) {
-      const uint32_t* __restrict__ rm = row ? reinterpret_cast<const uint32_t*>(row + SROW_MKEYS) : nullptr;
-      for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) mm[l * KCAP + i] = i < cnt ? rm[i] : 0u;
-    }
+    if (PLANE && spec)
+      for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) mm[l * KCAP + i] = i < cnt ? Fmt::load_mkey(row, i) : MK(0);
   }
   __syncthreads();
-  // lists that do not compare (differing spec words: other kind / direction / tie rule / width, or a sorted row next to a relevance
-  // row), and a sorted query some shard declined: the merged row is no answer -- MRK_ROW_DECLINED and no keys
+  // lists that do not compare (spec words differing in any bit: kind, direction of a part, width, tie rule, a sort next to a 64-bit
+  // order, a relevance row next to either), and a sorted or ordered query some shard declined: the merged row is no answer --
+  // MRK_ROW_DECLINED and no keys
   const bool none = mismatch || (spec != 0 && (flags & ROW_DECLINED) != 0);
   if (mismatch) flags |= ROW_DECLINED;
   if (!none) { // (uniform)
-    const uint32_t tie = sort_spec_tie(spec);
-    if (!spec)
-      merge_srows_rounds<false, 1u>(mk, mm, P);
+    const uint32_t tie = Fmt::spec_tie(spec);
+    if (!PLANE || !spec)
+      merge_rounds<MK, false, 1u>(mk, mm, P);
     else if (tie == 1u)
-      merge_srows_rounds<true, 1u>(mk, mm, P);
+      merge_rounds<MK, true, 1u>(mk, mm, P);
     else if (tie == 2u)
-      merge_srows_rounds<true, 2u>(mk, mm, P);
+      merge_rounds<MK, true, 2u>(mk, mm, P);
     else
-      merge_srows_rounds<true, 0u>(mk, mm, P);
+      merge_rounds<MK, true, 0u>(mk, mm, P);
   }
   const uint32_t n = none ? 0u : have < a.k ? (uint32_t)have : a.k;
-  uint64_t* __restrict__ out = a.out_rows + (uint64_t)(a.out_first + q) * SROW_WORDS;
-  for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) out[i] = i < n ? mk[i] : 0ull;
-  const uint32_t nm = spec ? n : 0u;
-  for (uint32_t i = tid; i < (uint32_t)KCAP / 2; i += WG) {
-    const uint64_t m0 = 2 * i < nm ? mm[2 * i] : 0u, m1 = 2 * i + 1 < nm ? mm[2 * i + 1] : 0u;
-    out[SROW_MKEYS + i] = m0 | (m1 << 32);
-  }
+  uint64_t* __restrict__ out = a.out_rows + (uint64_t)(a.out_first + q) * Fmt::WORDS;
+  write_row_keys(out, n, [&](uint32_t i) { return mk[i]; });
+  Fmt::store_plane(out, spec ? n : 0u, [&](uint32_t i) { return mm[i]; });
   if (tid == 0) {
-    out[KCAP] = n;
-    out[KCAP + 1] = (total & ~ROW_FLAG_MASK) | flags; // totals add up, the shards' flag bits are OR-ed through (merge_rows_kernel)
-    out[SROW_SPEC] = spec;
+    write_row_header<Fmt>(out, n, (total & ~ROW_FLAG_MASK) | flags, spec); // CSphMatchQueue::MoveTo adds the totals up; the shards' flag bits are OR-ed through
     if (a.flags_any) {
       if (flags & ROW_RERUN) a.flags_any[0] = 1u;
       if (flags & ROW_DECLINED) a.flags_any[1] = 1u;
@@ -325,177 +305,33 @@ __global__ __launch_bounds__(WG) void merge_srows_kernel(MergeRowsArgs a, uint32
   }
 }
 
-void launch_merge_srows(const MergeRowsArgs& a, void* stream) {
-  if (!a.n_queries) return;
+template <class Fmt>
+static void launch_merge_of(const MergeRowsArgs& a, void* stream) {
   uint32_t P = 1;
   while (P < a.n_lists) P <<= 1;
-  const size_t lds = (size_t)P * KCAP * (sizeof(uint64_t) + sizeof(uint32_t));
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)merge_srows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * KCAP * (int)(sizeof(uint64_t) + sizeof(uint32_t)));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(merge_srows_kernel, dim3(a.n_queries), dim3(WG), lds, (hipStream_t)stream, a, P);
-}
-
-// ---------------------------------------------------------------------------------------
-// a batch's results as ORDER rows: KCAP keys | count | total_found | KCAP mapped keys (u64) | order spec word.  Sorts and 64-bit
-// orders alike leave with their mapped keys; relevance queries with spec 0 and a zero plane.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void pack_orows_kernel(PackORowsArgs a) {
-  const uint32_t q = blockIdx.x, tid = threadIdx.x;
-  if (q >= a.n) return;
-  const DevQuery* __restrict__ Q = a.queries + q;
-  const bool declined = a.declined && a.declined[q] == 1u; // (2 = declined for narrow rows only)
-  const bool sorted = Q->sort_on != 0 && !declined;
-  if (a.skip_sorted && sorted) return; // (uniform) sort_select_kernel<DST_ORDER> wrote this row
-  const bool bad = declined || (a.flags && (a.flags[q] & (QF_OVERFLOW | QF_FSM)) != 0);
-  const uint32_t n = bad ? 0u : a.cnt[q] < (uint32_t)KCAP ? a.cnt[q] : (uint32_t)KCAP;
-  uint64_t* __restrict__ row = a.rows + (uint64_t)q * OROW_WORDS;
-  // a 64-bit key needs the 64-bit plane; a sort's key is whole in the u32 plane too (a batch that never saw a 64-bit key has no other)
-  const bool wide_ord = Q->sort_on == SORT_ON_ORDER;
-  const uint32_t nm = sorted && (a.mkeys64 || (a.mkeys && !wide_ord)) ? n : 0u;
-  for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) {
-    row[i] = i < n ? a.keys[(uint64_t)q * KCAP + i] : 0ull;
-    row[OROW_MKEYS + i] = i >= nm ? 0ull : a.mkeys64 ? a.mkeys64[(uint64_t)q * KCAP + i] : (uint64_t)a.mkeys[(uint64_t)q * KCAP + i] << 32;
-  }
-  if (tid == 0) {
-    row[KCAP] = n;
-    row[KCAP + 1] = declined ? ROW_DECLINED : bad ? ROW_RERUN : (a.total[q] & ~ROW_FLAG_MASK);
-    row[OROW_SPEC] = sorted ? order_spec_word(Q->sort_on, Q->sort_flags, Q->sort_bits, Q->ord_flags, Q->ord_bits, Q->sort_tie) : 0ull;
-  }
-}
-
-void launch_pack_orows(const PackORowsArgs& a, void* stream) {
-  if (!a.n) return;
-  hipLaunchKernelGGL(pack_orows_kernel, dim3(a.n), dim3(WG), 0, (hipStream_t)stream, a);
-}
-
-// ---------------------------------------------------------------------------------------
-// merge of <= 8 sorted ORDER rows per query: the same pairwise bitonic merges over entries of 16 bytes -- the u64 key and, in a
-// plane of its own, the u64 mapped key.  An ordered query compares (mapped key, the key as the tie rule reads it); a relevance
-// query (spec 0) compares the key alone and never touches the mapped plane: exactly merge_rows_kernel's order.
-// LDS: P lists x KCAP x 16 B = 128 KB for 8 lists (one workgroup per CU on gfx950's 160 KB; 64 KB and two workgroups for up to 4).
-// ---------------------------------------------------------------------------------------
-template <bool SORTED, uint32_t TIE>
-static __device__ void merge_orows_rounds(uint64_t* mk, uint64_t* mm, uint32_t P) {
-  const uint32_t tid = threadIdx.x;
-  auto less = [](uint64_t xk, uint64_t xm, uint64_t yk, uint64_t ym) -> bool {
-    if (SORTED && xm != ym) return xm < ym;
-    return tie_key<TIE>(xk) < tie_key<TIE>(yk);
-  };
-  for (uint32_t step = 1; step < P; step <<= 1) { // this round merges list slot 2 p step with slot (2 p + 1) step
-    const uint32_t pairs = P / (2 * step);
-    for (uint32_t t = tid; t < pairs * KCAP; t += WG) { // top K of A and B as a bitonic sequence, in A's place
-      const uint32_t p = t / KCAP, i = t % KCAP;
-      const size_t ia = (size_t)(2 * p * step) * KCAP + i, ib = (size_t)((2 * p + 1) * step) * KCAP + (KCAP - 1 - i);
-      const uint64_t xk = mk[ia], yk = mk[ib];
-      const uint64_t xm = SORTED ? mm[ia] : 0ull, ym = SORTED ? mm[ib] : 0ull;
-      if (less(xk, xm, yk, ym)) {
-        mk[ia] = yk;
-        if (SORTED) mm[ia] = ym;
-      }
-    }
-    __syncthreads();
-    for (uint32_t j = KCAP / 2; j > 0; j >>= 1) { // ... sorted descending by half-cleaners
-      for (uint32_t t = tid; t < pairs * (KCAP / 2); t += WG) {
-        const uint32_t p = t / (KCAP / 2), i0 = t % (KCAP / 2);
-        const size_t base = (size_t)(2 * p * step) * KCAP;
-        const size_t i = base + (((i0 & ~(j - 1)) << 1) | (i0 & (j - 1))), ij = i + j;
-        const uint64_t xk = mk[i], yk = mk[ij];
-        const uint64_t xm = SORTED ? mm[i] : 0ull, ym = SORTED ? mm[ij] : 0ull;
-        if (less(xk, xm, yk, ym)) {
-          mk[i] = yk, mk[ij] = xk;
-          if (SORTED) mm[i] = ym, mm[ij] = xm;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-__global__ __launch_bounds__(WG) void merge_orows_kernel(MergeRowsArgs a, uint32_t P) { // P = power of two >= n_lists
-  extern __shared__ uint64_t ok[];          // [P][KCAP] keys ...
-  uint64_t* om = ok + (size_t)P * KCAP;     // ... then [P][KCAP] mapped keys
-  const uint32_t q = blockIdx.x, tid = threadIdx.x;
-  if (q >= a.n_queries) return;
-  // The query's spec word: that of the lists which answer it, and they must agree.  A list that carries the query with MRK_ROW_DECLINED
-  // has no say: a shard whose planner declined the query holds no order for it and sends spec 0 (pack_orows_kernel), so the merged
-  // row's spec word does not depend on which list declined.
-  uint64_t spec = 0;
-  bool have_spec = false, mismatch = false;
-  for (uint32_t l = 0; l < a.n_lists; ++l) { // (uniform: scalar loads)
-    const uint64_t* __restrict__ row = a.in_rows + ((uint64_t)l * a.list_stride + q) * OROW_WORDS;
-    if (row[KCAP + 1] & ROW_DECLINED) continue;
-    const uint64_t sp = row[OROW_SPEC];
-    if (!have_spec) spec = sp, have_spec = true;
-    mismatch = mismatch || sp != spec;
-  }
-  uint64_t total = 0, flags = 0, have = 0;
-  for (uint32_t l = 0; l < P; ++l) {
-    uint32_t cnt = 0;
-    const uint64_t* __restrict__ row = nullptr;
-    if (l < a.n_lists) {
-      row = a.in_rows + ((uint64_t)l * a.list_stride + q) * OROW_WORDS;
-      cnt = (uint32_t)row[KCAP];
-      if (cnt > (uint32_t)KCAP) cnt = KCAP;
-      const uint64_t t = row[KCAP + 1];
-      total += t & ~ROW_FLAG_MASK, flags |= t & ROW_FLAG_MASK, have += cnt;
-    }
-    for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) ok[l * KCAP + i] = i < cnt ? row[i] : 0ull;
-    if (spec)
-      for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) om[l * KCAP + i] = i < cnt ? row[OROW_MKEYS + i] : 0ull;
-  }
-  __syncthreads();
-  // answering lists that do not compare (spec words differing in any bit: direction of either part, kind, width, tie rule, a sort
-  // next to a 64-bit order, a relevance row next to either), and an ordered query some shard declined: MRK_ROW_DECLINED and no keys
-  const bool none = mismatch || (spec != 0 && (flags & ROW_DECLINED) != 0);
-  if (mismatch) flags |= ROW_DECLINED;
-  if (!none) { // (uniform)
-    const uint32_t tie = order_spec_tie(spec);
-    if (!spec)
-      merge_orows_rounds<false, 1u>(ok, om, P);
-    else if (tie == 1u)
-      merge_orows_rounds<true, 1u>(ok, om, P);
-    else if (tie == 2u)
-      merge_orows_rounds<true, 2u>(ok, om, P);
-    else
-      merge_orows_rounds<true, 0u>(ok, om, P);
-  }
-  const uint32_t n = none ? 0u : have < a.k ? (uint32_t)have : a.k;
-  uint64_t* __restrict__ out = a.out_rows + (uint64_t)(a.out_first + q) * OROW_WORDS;
-  const uint32_t nm = spec ? n : 0u;
-  for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) {
-    out[i] = i < n ? ok[i] : 0ull;
-    out[OROW_MKEYS + i] = i < nm ? om[i] : 0ull;
-  }
-  if (tid == 0) {
-    out[KCAP] = n;
-    out[KCAP + 1] = (total & ~ROW_FLAG_MASK) | flags; // totals add up, the shards' flag bits are OR-ed through (merge_rows_kernel)
-    out[OROW_SPEC] = spec;
-    if (a.flags_any) {
-      if (flags & ROW_RERUN) a.flags_any[0] = 1u;
-      if (flags & ROW_DECLINED) a.flags_any[1] = 1u;
-    }
-  }
-}
-
-void launch_merge_orows(const MergeRowsArgs& a, void* stream) {
-  if (!a.n_queries) return;
-  uint32_t P = 1;
-  while (P < a.n_lists) P <<= 1;
-  const size_t lds = (size_t)P * KCAP * 2 * sizeof(uint64_t);
-  // the 128 KB of 5-8 lists need the function's limit raised, once per DEVICE (the attribute belongs to the device's copy of the
-  // kernel); contexts of several devices launch from threads of their own, so the marks are atomic -- raising twice is harmless.  A
-  // refusal is not marked: the launch then fails with the runtime's own error, which the caller's hipGetLastError reports.
+  constexpr size_t ENTRY = sizeof(uint64_t) + Fmt::MK_BYTES;
+  // 5-8 lists need more than the 64 KB a launch may ask for by default: the function's limit is raised, once per DEVICE (the attribute
+  // belongs to the device's copy of the kernel); contexts of several devices launch from threads of their own, so the marks are atomic
+  // -- raising twice is harmless.  A refusal is not marked: the launch then fails with the runtime's own error, which the caller's
+  // hipGetLastError reports.
   static std::atomic<bool> raised[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
   if (dev < 0 || !raised[dev].load(std::memory_order_acquire)) {
-    const hipError_t e = hipFuncSetAttribute((const void*)merge_orows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * KCAP * 2 * (int)sizeof(uint64_t));
+    const hipError_t e = hipFuncSetAttribute((const void*)merge_xrows_kernel<Fmt>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * KCAP * (int)ENTRY);
     if (e == hipSuccess && dev >= 0) raised[dev].store(true, std::memory_order_release);
   }
-  hipLaunchKernelGGL(merge_orows_kernel, dim3(a.n_queries), dim3(WG), lds, (hipStream_t)stream, a, P);
+  hipLaunchKernelGGL(merge_xrows_kernel<Fmt>, dim3(a.n_queries), dim3(WG), (size_t)P * KCAP * ENTRY, (hipStream_t)stream, a, P);
+}
+
+void launch_merge_xrows(RowKind kind, const MergeRowsArgs& a, void* stream) {
+  if (!a.n_queries) return;
+  if (kind == ROWS_ORDER)
+    launch_merge_of<OrderFmt>(a, stream);
+  else if (kind == ROWS_WIDE)
+    launch_merge_of<WideFmt>(a, stream);
+  else
+    launch_merge_of<NarrowFmt>(a, stream);
 }
 
 } // namespace mrk

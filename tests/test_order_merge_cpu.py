@@ -333,3 +333,18 @@ def test_order_rows_over_gloo(orc):
     together = np.concatenate([g[4] for g in got])  # the partitioned slices, rank after rank
     assert [g[2] for g in got] == [0, got[0][3]] and got[0][3] + got[1][3] == len(qs)
     assert np.array_equal(together, got[0][1])
+
+
+def test_merge_format_models_accept_every_input():
+    """tests/test_gpu_merge_formats.py's inputs (merge_formats_common) all pass through the numpy models, whole rows out; in every size
+    case the second query holds fewer entries than k and the third exactly k."""
+    import merge_formats_common as mfc
+
+    ref = mfc.references()
+    assert {key[:2] for key in ref} == {(kind, fmt) for kind in ("size", "flags") for fmt in mfc.FLAVORS}
+    for key, (rows, want) in ref.items():
+        for w in ([want] if key[0] == "size" else want.values()):
+            assert w.dtype == np.uint64 and w.shape == (mfc.NQ, mfc.words_of(key[1]))
+        if key[0] == "size":
+            k = key[4]
+            assert int(want[1, mfc.K1]) < k and int(want[2, mfc.K1]) == k

@@ -134,7 +134,7 @@ def test_merge_srows_np_is_loud_and_keeps_flags_and_totals(orc):
     rows[1, 1, dist.SROW_SPEC] = dist.sort_spec_word(kind, True, 1, 32)
     got = dist.merge_srows_np(rows, 50)
     assert int(got[1, 1025]) == totals[1] | dist.ROW_DECLINED and int(got[1, 1024]) == 0 and not got[1, :1024].any()
-    # flags OR through, totals add; a relevance query keeps its keys (merge_rows_kernel's behaviour), a sorted query that a
+    # flags OR through, totals add; a relevance query keeps its keys (the narrow merge's behaviour), a sorted query that a
     # shard declined leaves without keys
     rows = base.copy()
     rows[2, :, 1025] |= R
