@@ -406,7 +406,11 @@ int mrk_batch_export_device(mrk_batch* b, uint64_t* keys_dst, uint32_t* counts_d
 /* flag bits in a row's total_found word; mrk_topk_merge_rows ORs them through (the counts in the low 62 bits add up):
    MRK_ROW_RERUN    a shard's candidate list overflowed and the row left before mrk_batch_wait reran the query: call
                     mrk_batch_wait + mrk_batch_export_rows on that shard's batch and exchange / merge again;
-   MRK_ROW_DECLINED a shard declined the query (MRK_E_UNSUPPORTED there): the merged row is not an answer. */
+                    Only a candidate-list overflow leaves with this bit: it is the one condition a rerun repairs;
+   MRK_ROW_DECLINED a shard declined the query (MRK_E_UNSUPPORTED there): the merged row is not an answer.  That covers the
+                    declines found while the query ran (a doc with more live phrase states than the kernels keep, the generic
+                    evaluator out of hit-list memory): the kernels write such a row with this bit, no keys and count 0 themselves,
+                    so the standing row carries it before mrk_batch_wait and the exported row after it, in all three formats. */
 #define MRK_ROW_RERUN (1ull << 63)
 #define MRK_ROW_DECLINED (1ull << 62)
 int mrk_batch_export_rows(mrk_batch* b, uint64_t* rows_dst);

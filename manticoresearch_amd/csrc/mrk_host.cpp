@@ -1318,10 +1318,11 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     // (a sorted query's NARROW row is no answer to a merge by (weight, docid): in that exchange it counts as declined -- word 2,
     // which the wide rows, whose merge compares the mapped keys, do not take for a decline)
     // (a query ordered by a 64-bit key, mrk_query.order, fits neither of these two row formats: word 1; ORDER rows read words of their own, below)
-    for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || (b->rows_dst && b->sort_loc[i].bits) || b->sort_loc[i].no_row();
+    // (whether or not a narrow destination stands: mrk_batch_export_rows writes the same rows after the wait)
+    for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || b->sort_loc[i].bits || b->sort_loc[i].no_row();
     b->any_declined = any;
     if (any || b->decl_dirty) {
-      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = (b->status[i] != MRK_OK || b->sort_loc[i].no_row()) ? 1u : (b->rows_dst && b->sort_loc[i].bits) ? 2u : 0u;
+      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = (b->status[i] != MRK_OK || b->sort_loc[i].no_row()) ? 1u : b->sort_loc[i].bits ? 2u : 0u;
       HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     }
     b->decl_order = any_order;
@@ -1470,10 +1471,12 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   HIP_TRY(hipMemcpyAsync(b->d_out_keys.p + (size_t)qi * KCAP, r->d_out_keys.p, (size_t)KCAP * 8, hipMemcpyDeviceToDevice, st));
   if (sorted) HIP_TRY(hipMemcpyAsync(b->d_out_mkeys.p + (size_t)qi * KCAP, r->d_out_mkeys.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st)); // (mrk_batch_export_srows)
   if (keys64) HIP_TRY(hipMemcpyAsync(b->d_out_mkeys64.p + (size_t)qi * KCAP, r->d_out_mkeys64.p, (size_t)KCAP * 8, hipMemcpyDeviceToDevice, st)); // (mrk_batch_export_orows)
-  HIP_TRY(hipMemsetAsync(b->d_q_flags.p + qi, 0, 4, st)); // the device-side row is good again
+  // the device-side row is good again -- or carries what the rerun ran into: an exported row then leaves flagged, never with the rerun's keys
+  HIP_TRY(hipMemcpyAsync(b->d_q_flags.p + qi, r->d_q_flags.p, 4, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
+  if (flags & QF_FSM) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: a doc held more live phrase states than the device path keeps", qi);
   if (flags & QF_ARENA) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the generic evaluator ran out of hit-list memory (ctx tunable gen_spill_mb)", qi);
-  if (flags & (QF_OVERFLOW | QF_FSM)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: candidate list overflowed again on the rerun", qi);
+  if (flags & QF_OVERFLOW) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: candidate list overflowed again on the rerun", qi);
   b->decoded = false;
   return MRK_OK;
 }

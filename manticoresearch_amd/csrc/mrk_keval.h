@@ -319,14 +319,6 @@ __device__ inline bool gen_eval(const DevSegment& seg, const DevQuery* __restric
         for (uint32_t hi = 0; hi < I.n; ++hi) {
           const GenHit h = I.p[hi];
           const uint32_t hpf = gen_pwf(h.hitpos);
-          if (h.qpos == atoms[0]) {
-            if (ns == (uint32_t)GEN_FSM_STATES) {
-              atomicOr(qflags, QF_FSM);
-              break;
-            }
-            st_tag[ns] = 0, st_exp[ns] = hpf + (atoms[1] - atoms[0]);
-            ++ns;
-          }
           for (int i = (int)ns - 1; i >= 0; --i) {
             if (st_exp[i] < hpf) {
               --ns;
@@ -344,6 +336,16 @@ __device__ inline bool gen_eval(const DevSegment& seg, const DevQuery* __restric
               ns = 0; // ResetFSM
               break;
             }
+          }
+          // The state a first-word hit opens, behind the sweep: the states that died before this hit have left their slots.  (The
+          // reference opens it in front; a first-word hit neither advances nor completes a state, so the order does not show.)
+          if (h.qpos == atoms[0]) {
+            if (ns == (uint32_t)GEN_FSM_STATES) {
+              atomicOr(qflags, QF_FSM);
+              break;
+            }
+            st_tag[ns] = 0, st_exp[ns] = hpf + (atoms[1] - atoms[0]);
+            ++ns;
           }
         }
         if (!n) break;

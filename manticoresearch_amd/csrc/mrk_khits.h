@@ -76,6 +76,11 @@ struct PhraseFsm {
                                        uint32_t ap3) {
     bool emit = false;
     if (hq == (ap0 & 0xFFFFu)) {
+      // a state whose expected position lies before this hit cannot match any more (the loop below would drop it): its slot is
+      // free for the state this hit opens.  With that, a phrase of span s keeps at most s + 1 slots busy
+#pragma unroll
+      for (int i = 0; i < PHRASE_STATES; ++i)
+        if (fexp[i] < hp) fvalid &= ~(1u << i);
       const uint32_t freeb = ~fvalid & ((1u << PHRASE_STATES) - 1u);
       if (!freeb)
         over = true;

@@ -77,11 +77,15 @@ __device__ __forceinline__ void write_row_header(uint64_t* __restrict__ row, uin
   row[KCAP + 1] = total_word;
   if (Fmt::ELECT != SPEC_NONE) row[Fmt::SPEC] = spec;
 }
-// The total_found word of a row that leaves a batch.  A query whose candidate list overflowed has no trustworthy list on the device
-// until the host reran it: its row goes out empty with ROW_RERUN; a query this shard declined (MRK_E_UNSUPPORTED) goes out empty with
-// ROW_DECLINED.  The merge ORs both bits through: the receiver reruns / fails the query, never a partial answer.
-__device__ __forceinline__ uint64_t row_total_word(bool declined, bool bad, uint64_t total) {
-  return declined ? ROW_DECLINED : bad ? ROW_RERUN : (total & ~ROW_FLAG_MASK);
+// The total_found word of a row that leaves a batch.  A query whose candidate list overflowed (QF_OVERFLOW) has no trustworthy list
+// on the device until the host reran it: its row goes out empty with ROW_RERUN.  A query this shard declined (MRK_E_UNSUPPORTED) goes
+// out empty with ROW_DECLINED: at submit by the planner (`declined`), or while it ran (QF_FSM, QF_ARENA: no rerun would help, and
+// mrk_batch_wait reports MRK_E_UNSUPPORTED for it).  The merge ORs both bits through: the receiver reruns / fails the query, never a
+// partial answer.  A row leaves with its keys only when row_unflagged(): the kernels' one test for that.
+constexpr uint32_t QF_DECLINES = QF_FSM | QF_ARENA;
+__device__ __forceinline__ bool row_unflagged(bool declined, uint32_t qflags) { return !declined && !(qflags & (QF_OVERFLOW | QF_DECLINES)); }
+__device__ __forceinline__ uint64_t row_total_word(bool declined, uint32_t qflags, uint64_t total) {
+  return declined || (qflags & QF_DECLINES) ? ROW_DECLINED : (qflags & QF_OVERFLOW) ? ROW_RERUN : (total & ~ROW_FLAG_MASK);
 }
 
 } // namespace mrk

@@ -292,12 +292,12 @@ __global__ __launch_bounds__(WG) void sel_sort_kernel(SelectArgs a) {
   for (uint32_t i = tid; i < m; i += WG) a.out_keys[(uint64_t)q * KCAP + i] = s.cand[i];
   if (a.h_keys)
     for (uint32_t i = tid; i < m; i += WG) a.h_keys[(uint64_t)q * KCAP + i] = s.cand[i];
-  if (a.rows_dst) { // the row of the shard exchange: a query whose candidate list overflowed leaves empty with MRK_ROW_RERUN (pack_xrows_kernel's rule)
-    const bool bad = (a.q_flags[q] & (QF_OVERFLOW | QF_FSM)) != 0;
-    const uint32_t nr = bad ? 0u : m;
+  if (a.rows_dst) { // the row of the shard exchange: a query whose candidate list overflowed leaves empty with MRK_ROW_RERUN, a run-time decline empty with MRK_ROW_DECLINED (pack_xrows_kernel's rule)
+    const uint32_t qf = a.q_flags[q];
+    const uint32_t nr = row_unflagged(false, qf) ? m : 0u;
     uint64_t* __restrict__ row = a.rows_dst + (uint64_t)q * ROW_WORDS;
     write_row_keys(row, nr, [&](uint32_t i) { return s.cand[i]; });
-    if (tid == 0) write_row_header<NarrowFmt>(row, nr, row_total_word(false, bad, a.q_total[q]), 0ull);
+    if (tid == 0) write_row_header<NarrowFmt>(row, nr, row_total_word(false, qf, a.q_total[q]), 0ull);
   }
   if (tid == 0) {
     a.out_cnt[q] = m;

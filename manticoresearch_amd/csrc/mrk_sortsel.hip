@@ -124,17 +124,17 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
     if (a.out_mkeys64) a.out_mkeys64[(uint64_t)q * KCAP + i] = mk; // ... all of it (order rows)
   }
   // The standing destination's row.  A 64-bit key does not fit a wide row, and no exchange row carries the weight's position yet: no
-  // row is written then, and pack_xrows_kernel marks that query's row MRK_ROW_DECLINED.  sel_sort_kernel's rule: a query whose
-  // candidate list overflowed leaves empty with MRK_ROW_RERUN.
+  // row is written then, and pack_xrows_kernel marks that query's row MRK_ROW_DECLINED.  sel_sort_kernel's rule (row_total_word): a query
+  // whose candidate list overflowed leaves empty with MRK_ROW_RERUN, one that met a run-time decline empty with MRK_ROW_DECLINED.
   if constexpr (DST != DST_NONE) {
     using Fmt = std::conditional_t<DST == DST_WIDE, WideFmt, OrderFmt>;
     if (sort_on != SORT_ON_WEIGHT && (Fmt::WIDE_KEYS || sort_on != SORT_ON_ORDER)) { // (uniform)
-      const bool bad = (a.q_flags[q] & (QF_OVERFLOW | QF_FSM)) != 0;
-      const uint32_t nr = bad ? 0u : m;
+      const uint32_t qf = a.q_flags[q];
+      const uint32_t nr = row_unflagged(false, qf) ? m : 0u;
       uint64_t* __restrict__ row = (DST == DST_WIDE ? a.srows_dst : a.orows_dst) + (uint64_t)q * Fmt::WORDS;
       write_row_keys(row, nr, key_at);
       Fmt::store_plane(row, nr, [&](uint32_t i) { return Fmt::mkey_of(mkey_at(i)); });
-      if (tid == 0) write_row_header<Fmt>(row, nr, row_total_word(false, bad, a.q_total[q]), Fmt::spec_of(*Q));
+      if (tid == 0) write_row_header<Fmt>(row, nr, row_total_word(false, qf, a.q_total[q]), Fmt::spec_of(*Q));
     }
   }
   if (tid == 0) {
@@ -167,14 +167,14 @@ __global__ __launch_bounds__(WG) void pack_xrows_kernel(PackXRowsArgs a) {
   const uint32_t sort_on = PLANE ? a.queries[q].sort_on : 0u; // (narrow rows: a sorted query is a declined one)
   const bool sorted = sort_on != 0 && !declined;
   if (a.skip_sorted && sorted) return; // (uniform) sort_select_kernel wrote this row
-  const bool bad = declined || (a.flags && (a.flags[q] & (QF_OVERFLOW | QF_FSM)) != 0);
-  const uint32_t n = bad ? 0u : a.cnt[q] < (uint32_t)KCAP ? a.cnt[q] : (uint32_t)KCAP;
+  const uint32_t qf = a.flags ? a.flags[q] : 0u;
+  const uint32_t n = !row_unflagged(declined, qf) ? 0u : a.cnt[q] < (uint32_t)KCAP ? a.cnt[q] : (uint32_t)KCAP;
   uint64_t* __restrict__ row = a.rows + (uint64_t)q * Fmt::WORDS;
   // a 64-bit key needs the 64-bit plane; a sort's key is whole in the u32 plane too (a batch that never saw a 64-bit key has no other)
   const uint32_t nm = sorted && (a.mkeys64 || (a.mkeys && (!Fmt::WIDE_KEYS || sort_on != SORT_ON_ORDER))) ? n : 0u;
   write_row_keys(row, n, [&](uint32_t i) { return a.keys[(uint64_t)q * KCAP + i]; });
   Fmt::store_plane(row, nm, [&](uint32_t i) { return Fmt::mkey_of(a.mkeys64 ? a.mkeys64[(uint64_t)q * KCAP + i] : (uint64_t)a.mkeys[(uint64_t)q * KCAP + i] << 32); });
-  if (threadIdx.x == 0) write_row_header<Fmt>(row, n, row_total_word(declined, bad, a.total[q]), sorted ? Fmt::spec_of(a.queries[q]) : 0ull);
+  if (threadIdx.x == 0) write_row_header<Fmt>(row, n, row_total_word(declined, qf, a.total[q]), sorted ? Fmt::spec_of(a.queries[q]) : 0ull);
 }
 
 void launch_pack_xrows(RowKind kind, const PackXRowsArgs& a, void* stream) {
