@@ -270,6 +270,8 @@ typedef struct {
   float submit_ms;        /* host: whole mrk_batch_submit call */
   uint32_t n_rerun;       /* queries the last mrk_batch_wait ran again alone (their match queue or candidate list was full) */
   uint32_t n_bm_groups[4]; /* "bm_group": groups of 1, 2, 3 and 4 two-bitmap AND queries the last submit ran in one workgroup each */
+  uint32_t pk_lean;       /* "pair_scan": 1 = the last submit's block-scan work items ran on the lean one-/two-keyword instance, 0 = on the generic
+                             one (or the submit had no such items) */
 } mrk_batch_stats;
 
 const char* mrk_last_error(void);
@@ -296,6 +298,10 @@ int mrk_ctx_destroy(mrk_ctx* ctx);
    128: since work items of different queries interleave -- "item_order", a mask: 1 block scan, 2 bitmap AND, 4 bitmap trees, 8 also in
    batches that feed the hit pass; default 7 -- small items are the fast ones); "pk_min_items" (a batch with fewer block-scan work items
    has its block ranges cut finer, default 2048);
+   "pair_scan" (1 = a batch whose block-scan launch needs none of the generic kernel's machinery -- queries of one or two keywords under
+   NONE / BM25 / single-keyword PROXIMITY, no trees, phrases, position modifiers, filters or sort, a segment of <= 8 fields packed with
+   bitmap_inv != 0 -- runs that launch on a lean instance of the kernel: twice the waves per SIMD and a shorter chain of dependent loads per
+   wave; 0 = always the generic instance; default 1; read at submit; mrk_batch_stats.pk_lean says which one ran);
    "bm_group" (1 = a batch's two-bitmap AND queries that share a keyword run in one workgroup, a wave per member, so the shared
    keyword's bitmap and tf/field lines are fetched once per CU; 0 = a workgroup per query; default 1; read at submit);
    "prox_prune" (1 = proximity rankers: matches whose weight upper bound cannot reach the top K skip the hit pass, default);

@@ -533,6 +533,8 @@ void launch_pack_xrows(RowKind kind, const PackXRowsArgs& a, void* stream);
 
 void launch_scan(const ScanArgs& a, void* stream);
 void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen = false); // a.scand: the instances that carry the sort
+// the lean instance of the plain launch (mrk_scan_p2.hip): <= 2 keywords, weight-sum rankers, <= 8 fields, no sort; the caller checks that
+void launch_scan_p2(const ScanArgs& a, void* stream);
 constexpr int MAX_PROX_TERMS = MAX_PROX_TERMS_; // keywords whose hit streams the hit kernel merges per doc
 void launch_scan_bm(const ScanArgs& a, void* stream); // a.items: (query, window range) work items
 void launch_scan_bt(const ScanArgs& a, void* stream); // the same for TF_BTREE passes (mrk_scan_bt.hip)

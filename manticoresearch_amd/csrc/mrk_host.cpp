@@ -324,6 +324,11 @@ extern "C" int mrk_ctx_set(mrk_ctx* c, const char* key, int64_t value) {
     c->pk_min_items = (int)value;
     return MRK_OK;
   }
+  if (!strcmp(key, "pair_scan")) {
+    if (value < 0 || value > 1) return mrk_fail(MRK_E_INVAL, "pair_scan must be 0 or 1");
+    c->pair_scan = (int)value;
+    return MRK_OK;
+  }
   if (!strcmp(key, "bm_group")) {
     if (value < 0 || value > 1) return mrk_fail(MRK_E_INVAL, "bm_group must be 0 or 1");
     c->bm_group = (int)value;
@@ -648,6 +653,7 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
     }
   }
   if (packed) {
+    s->bitmaps_on = ctx->bitmap_inv > 0;
     std::vector<PackedTerm> pt(d->n_terms);
     std::vector<std::string> errs(d->n_terms);
     std::atomic<size_t> next{0};
@@ -1049,15 +1055,27 @@ static void bind_scan(const mrk_batch* b, const mrk_segment* seg, mrk::ScanArgs&
   sa.cand = b->d_cand.p;
 }
 
+// Whether a batch's block-scan items take the lean instance (mrk_scan_p2.hip, ctx key "pair_scan"): the launch that would run
+// scan_pk_kernel<false, false> -- no hit ranker, tree, position modifier, filter or sort anywhere in the batch -- over a segment of
+// <= 8 fields, at most two keywords per query, and a segment packed with bitmaps on (without them a dense keyword is block-probed, and
+// the generic instance's direct map serves that better than a binary search)
+static bool lean_scan_ok(const mrk_ctx* c, const mrk_segment* seg, bool sorted, uint32_t max_terms, bool prox, bool tree, bool ext) {
+  return c->pair_scan != 0 && !prox && !tree && !ext && !sorted && !seg->dev.pk_fmask && max_terms <= 2 && seg->bitmaps_on && c->bitmap_inv != 0;
+}
+
 // The packed path's kernels over a laid-out item array (sa.items: block-scan items, then kinds 0, 1, 2): block scan, tree
 // kernel and generic-evaluator candidates, the rank launches of the queues in use, then the two-bitmap AND kernel
 // (bm_groups: its group records on the device, or null)
 // (sa.scand set = the batch holds sorted queries: every block-scan and rank launch takes the instance that carries the sort)
+// (lean: the block-scan items go to the lean two-keyword instance -- lean_scan_ok)
 static int launch_packed(mrk::ScanArgs sa, size_t n_items_pk, const size_t n_items_kind[3], const uint64_t mq_chunks[3], uint32_t max_terms, bool prox,
-                         bool tree, bool ext, bool nearn, const BmGroup* bm_groups, hipStream_t st) {
+                         bool tree, bool ext, bool nearn, const BmGroup* bm_groups, bool lean, hipStream_t st) {
   const DevItem* items = sa.items;
   sa.n_items = (uint32_t)n_items_pk;
-  launch_scan_pk(sa, max_terms, prox, tree, ext, st);
+  if (lean)
+    launch_scan_p2(sa, st);
+  else
+    launch_scan_pk(sa, max_terms, prox, tree, ext, st);
   if (n_items_kind[1]) { // before the rank kernels: it feeds the match queue too
     ScanArgs sb = sa;
     sb.items = items + n_items_pk + n_items_kind[0];
@@ -1263,9 +1281,12 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   }
   lap("h2d+memset");
   HIP_TRY(hipEventRecord(b->ev_scan0, st));
+  b->stats.pk_lean = 0;
   if (use_packed) {
+    const bool lean = lean_scan_ok(c, seg, any_sort, max_terms, any_prox, any_tree, any_ext);
+    b->stats.pk_lean = lean && n_items_pk ? 1u : 0u;
     if ((rc = launch_packed(sa, n_items_pk, lay.n_items_kind, mq_chunks, max_terms, any_prox, any_tree, any_ext, any_nearn,
-                            n_group_slots ? (const BmGroup*)(b->d_items.p + n_items) : nullptr, st)))
+                            n_group_slots ? (const BmGroup*)(b->d_items.p + n_items) : nullptr, lean, st)))
       return rc;
   } else
     launch_scan(sa, st);
@@ -1448,7 +1469,8 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   if (chunks[0] || chunks[1] || chunks[2]) HIP_TRY(hipMemsetAsync(r->d_mq_count.p, 0, 3 * mrk::MQ_SHARDS * 4, st));
   const bool nearn = (passes[0].tree_flags & TF_GEN_NEARN) != 0;
   if (n_kind[2] && (rc = bind_gen(r, b, sa, st, 1, nearn))) return rc; // (the programs are the submit's, still on the device)
-  if ((rc = launch_packed(sa, n_pk, n_kind, chunks, b->last_max_terms, b->last_prox, b->last_tree, b->last_ext, nearn, nullptr, st))) return rc;
+  const bool lean = lean_scan_ok(b->ctx, seg, sorted, b->last_max_terms, b->last_prox, b->last_tree, b->last_ext);
+  if ((rc = launch_packed(sa, n_pk, n_kind, chunks, b->last_max_terms, b->last_prox, b->last_tree, b->last_ext, nearn, nullptr, lean, st))) return rc;
   SelectArgs se{};
   bind_select(r, seg, 1, cap, se);
   launch_select(se, st);

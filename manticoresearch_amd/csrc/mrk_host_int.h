@@ -37,6 +37,7 @@ struct mrk_ctx {
   int bm_target_items = 1 << 20;  // two-bitmap AND kernel: cap of the work items per launch ...
   int bm_min_windows = 128;       // ... and the least windows per work item (a wave's fixed costs show on short runs)
   int bm_group = 1;               // two-bitmap AND kernel: queries that share a keyword run in one workgroup, a wave per member (0 = a workgroup per query)
+  int pair_scan = 1;              // block-scan launches of plain one- and two-keyword queries take the lean instance (mrk_scan_p2.hip); 0 = the generic one
   int pk_min_items = 2048;        // block-scan kernel: a batch with fewer work items has its block ranges cut finer (>= one block per wave)
   int exchange_part = 1;          // mrk_shard_exchange partitions the merge by query (all-to-all of row slices); 0 = all-gather, every rank merges everything
   int prox_prune = 1;             // proximity rankers: matches whose weight upper bound cannot reach the top K skip the hit pass (counted, not ranked)
@@ -104,6 +105,7 @@ struct mrk_segment {
   mutable std::vector<SortRange> sort_ranges;
   void* d_bm = nullptr;
   void* d_bm_dir = nullptr;
+  bool bitmaps_on = false; // packed with bitmap_inv != 0: every keyword dense enough for the block scan's direct map carries a bitmap
 };
 
 // mrk_comm.cpp (run on the submission thread)

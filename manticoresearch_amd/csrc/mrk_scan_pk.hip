@@ -21,7 +21,7 @@
 #define MRK_EXP 0
 #endif
 #ifndef MRK_BURST
-#define MRK_BURST 4 // blocks requested back to back per stream (4 or 8); 4 keeps VGPRs <= 96 => 5 waves/SIMD
+#define MRK_BURST 4 // blocks requested back to back per stream (4 or 8); with 4 the plain instance reports 112 VGPRs = 4 waves/SIMD
 #endif
 
 namespace mrk {
