@@ -272,6 +272,10 @@ typedef struct {
   uint32_t n_bm_groups[4]; /* "bm_group": groups of 1, 2, 3 and 4 two-bitmap AND queries the last submit ran in one workgroup each */
   uint32_t pk_lean;       /* "pair_scan": 1 = the last submit's block-scan work items ran on the lean one-/two-keyword instance, 0 = on the generic
                              one (or the submit had no such items) */
+  uint32_t bm_owner_keys; /* "bm_place": distinct (owner, keyword) pairs of the last submit's two-bitmap AND launch -- an owner is a group, or a
+                             query where none were formed -- and ... */
+  uint32_t bm_class_keys; /* ... distinct (class, keyword) pairs once the owners were assigned to the eight dispatch classes (bm_place = 2:
+                             one class).  Both 0 when no placement ran (bm_place = 0, fewer than two owners, no such launch) */
 } mrk_batch_stats;
 
 const char* mrk_last_error(void);
@@ -295,7 +299,7 @@ int mrk_ctx_destroy(mrk_ctx* ctx);
    see DESIGN.md section 6; read at segment load);
    "bm_target_items" / "bt_target_items" (cap of the work items per launch the window ranges of the two-bitmap AND kernel / of the tree
    kernel over bitmap words are cut into, defaults 2^20 / 6144) and "bm_min_windows" (windows per work item of the AND kernel, default
-   128: since work items of different queries interleave -- "item_order", a mask: 1 block scan, 2 bitmap AND, 4 bitmap trees, 8 also in
+   256; 128 before "bm_place": since work items of different queries interleave -- "item_order", a mask: 1 block scan, 2 bitmap AND, 4 bitmap trees, 8 also in
    batches that feed the hit pass; default 7 -- small items are the fast ones); "pk_min_items" (a batch with fewer block-scan work items
    has its block ranges cut finer, default 2048);
    "pair_scan" (1 = a batch whose block-scan launch needs none of the generic kernel's machinery -- queries of one or two keywords under
@@ -304,6 +308,16 @@ int mrk_ctx_destroy(mrk_ctx* ctx);
    wave; 0 = always the generic instance; default 1; read at submit; mrk_batch_stats.pk_lean says which one ran);
    "bm_group" (1 = a batch's two-bitmap AND queries that share a keyword run in one workgroup, a wave per member, so the shared
    keyword's bitmap and tf/field lines are fetched once per CU; 0 = a workgroup per query; default 1; read at submit);
+   "bm_place" (the order the work items of that kernel are dispatched in, read at submit; a speed hint only: results do not depend on
+   it.  0 = the layout's piece-major order.  2 = by ascending window, then owner -- an owner is a group, or a query where none were
+   formed: the whole chip walks the corpus as one band of windows; the default, measured together with bm_min_windows = 256 at +7 to +9 %
+   queries/s on the 100 M-doc bench.  1 = workgroups are dealt round-robin over the chip's eight XCDs, each with an L2 of its own: the owners
+   are assigned to eight classes so that a class holds few distinct keywords and the classes hold about as many work items, slot 8 s + x
+   of the launch runs the s-th work item of class x, and every class runs its items by ascending window.  Measured: it takes a fifth of
+   the L2 misses away and the launch is 5 to 35 % SLOWER, because equal item counts are not equal times and each XCD runs its own
+   slots -- DESIGN.md section 6; an experiment setting.  mrk_batch_stats.bm_owner_keys / bm_class_keys count the keywords before and after);
+   "bm_place_min_items" (launches of that kernel with fewer work items keep the layout's order: the order costs host time per work item and
+   a short launch is over before the band forms; default 16384, about a 50 M-doc segment under 256 queries);
    "prox_prune" (1 = proximity rankers: matches whose weight upper bound cannot reach the top K skip the hit pass, default);
    "prox_bound_keywords" (0 = that bound takes a proximity run to be as long as the field's hits allow: always sound, default;
    1 = as long as the number of keywords in the field -- tighter, and sound where hits of different keywords at ONE position reach

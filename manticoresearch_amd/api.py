@@ -668,7 +668,8 @@ class Batch:
         return {"scan_ms": s.scan_ms, "merge_ms": s.merge_ms, "algo_bytes": int(s.algo_bytes), "n_items": int(s.n_items),
                 "dev_bytes": int(s.dev_bytes), "packed": int(s.packed), "n_cands": int(s.n_cands),
                 "n_items_bm": int(s.n_items_bm), "plan_ms": float(s.plan_ms), "submit_ms": float(s.submit_ms),
-                "n_rerun": int(s.n_rerun), "n_bm_groups": [int(x) for x in s.n_bm_groups], "pk_lean": int(s.pk_lean)}
+                "n_rerun": int(s.n_rerun), "n_bm_groups": [int(x) for x in s.n_bm_groups], "pk_lean": int(s.pk_lean),
+                "bm_owner_keys": int(s.bm_owner_keys), "bm_class_keys": int(s.bm_class_keys)}
 
     def device_results(self):
         """(keys_ptr, counts_ptr, totals_ptr) of the last finished submit, HBM addresses."""

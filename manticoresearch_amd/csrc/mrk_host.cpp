@@ -171,6 +171,7 @@ struct mrk_batch {
   DevBuf<unsigned long long> d_gen_used;
   DevBuf<uint32_t> d_gen_near; // GenArgs::near_tab
   std::vector<mrk::GenProg> gen_progs;
+  mrk::BmPlacement place; // the scan_bm section's dispatch order of the last submit ("bm_place"; kept for its buffers)
   // decoded results
   std::vector<uint32_t> rowid;
   std::vector<int32_t> weight;
@@ -332,6 +333,16 @@ extern "C" int mrk_ctx_set(mrk_ctx* c, const char* key, int64_t value) {
   if (!strcmp(key, "bm_group")) {
     if (value < 0 || value > 1) return mrk_fail(MRK_E_INVAL, "bm_group must be 0 or 1");
     c->bm_group = (int)value;
+    return MRK_OK;
+  }
+  if (!strcmp(key, "bm_place_min_items")) {
+    if (value < 0 || value > (1 << 30)) return mrk_fail(MRK_E_INVAL, "bm_place_min_items must be 0 .. 2^30");
+    c->bm_place_min_items = (int)value;
+    return MRK_OK;
+  }
+  if (!strcmp(key, "bm_place")) {
+    if (value < 0 || value > 2) return mrk_fail(MRK_E_INVAL, "bm_place must be 0, 1 or 2");
+    c->bm_place = (int)value;
     return MRK_OK;
   }
   if (!strcmp(key, "bm_min_windows")) {
@@ -1213,7 +1224,23 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   if ((rc = b->h_items.reserve(n_items + n_group_slots + 1)) || (rc = b->d_items.reserve(n_items + n_group_slots + 1)) ||
       (rc = b->d_item_cand.reserve((n_items + 1) * KCAP)) || (rc = b->d_item_cnt.reserve(n_items + 1)))
     return rc;
-  if (n_items) memcpy(b->h_items.p, lay.items.data(), n_items * sizeof(DevItem));
+  // the scan_bm section goes down in dispatch order (bm_place; by default ascending windows, the chip walking the corpus as one band)
+  // (a launch of one owner or of fewer than bm_place_min_items work items, or bm_place = 0, keeps the layout's order; the one-query
+  // launches of rerun_overflowed never come here)
+  const size_t n_items_bm0 = lay.n_items_kind[0];
+  const bool place = use_packed && c->bm_place && n_items_bm0 > 1 && n_items_bm0 >= (size_t)c->bm_place_min_items;
+  if (place) mrk::place_bm_items(b->h_queries.p, n, extra, lay, seg->dev.pk_attr1 != nullptr, c->bm_place, b->place);
+  if (place && b->place.mismatch) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: the scan_bm ranges and work items of the launch layout disagree");
+  if (place && b->place.ran) {
+    const DevItem* src = lay.items.data() + n_items_pk;
+    DevItem* dst = b->h_items.p + n_items_pk;
+    const uint32_t* disp = b->place.disp.data();
+    if (n_items_pk) memcpy(b->h_items.p, lay.items.data(), n_items_pk * sizeof(DevItem));
+    for (size_t i = 0; i < n_items_bm0; ++i) dst[i] = src[disp[i]];
+    if (n_items > n_items_pk + n_items_bm0) memcpy(dst + n_items_bm0, src + n_items_bm0, (n_items - n_items_pk - n_items_bm0) * sizeof(DevItem));
+    b->stats.bm_owner_keys = b->place.owner_keys, b->stats.bm_class_keys = b->place.class_keys;
+  } else if (n_items)
+    memcpy(b->h_items.p, lay.items.data(), n_items * sizeof(DevItem));
   if (n_group_slots) memcpy((void*)(b->h_items.p + n_items), lay.groups.data(), lay.groups.size() * sizeof(BmGroup));
   const size_t n_pass = (size_t)n + extra.size();
   if ((rc = b->h_queries.reserve_keep(n_pass, n)) || (rc = b->d_queries.reserve(n_pass))) return rc;

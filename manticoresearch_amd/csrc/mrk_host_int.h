@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <utility>
 #include <vector>
 
 #include "mrk_dev.h"
@@ -35,7 +36,9 @@ struct mrk_ctx {
   int attr_seq = 1;               // keywords with a bitmap also get their tf / field bytes in slot order (what the bitmap kernel gathers from)
   int attr_nibbles = 0;           // also build the one-byte tf/field plane the bitmap kernel can gather from (<= 4 fields)
   int bm_target_items = 1 << 20;  // two-bitmap AND kernel: cap of the work items per launch ...
-  int bm_min_windows = 128;       // ... and the least windows per work item (a wave's fixed costs show on short runs)
+  int bm_min_windows = 256;       // ... and the least windows per work item (a wave's fixed costs show on short runs; 128 until the items were dispatched in window order)
+  int bm_place = 2;               // ... and the order its work items are dispatched in: 2 = window order; 1 = owners that share keywords on one XCD, each XCD in window order (slower: DESIGN section 6); 0 = as laid out
+  int bm_place_min_items = 16384; // ... from this many work items per launch on (a shorter launch is over before the order pays for its host time)
   int bm_group = 1;               // two-bitmap AND kernel: queries that share a keyword run in one workgroup, a wave per member (0 = a workgroup per query)
   int pair_scan = 1;              // block-scan launches of plain one- and two-keyword queries take the lean instance (mrk_scan_p2.hip); 0 = the generic one
   int pk_min_items = 2048;        // block-scan kernel: a batch with fewer work items has its block ranges cut finer (>= one block per wave)
@@ -185,12 +188,59 @@ struct BatchLayout {
   size_t n_items_kind[3] = {0, 0, 0}; // ... and the others'
   std::vector<BmGroup> groups;      // grouped scan_bm: a kind-0 item's `query` indexes it (empty: it is a pass index)
   uint32_t n_bm_groups[BM_GROUP_MAX] = {}; // groups of 1 .. BM_GROUP_MAX members
+  std::vector<DevItem> bm_whole;    // the whole window ranges the kind-0 section was cut from, one per group (per query where none were formed) ...
+  std::vector<uint64_t> bm_len;     // ... each one's piece length ...
+  bool bm_piece_major = false;      // ... and the order of the pieces (place_bm_items finds an owner's k-th piece by these, without a pass over the items)
   uint64_t mq_chunks[3] = {0, 0, 0}; // chunks of each match queue (0 = unused)
   std::chrono::steady_clock::time_point t_block_items; // when the block-scan section was in order (mrk_batch_stats::plan_ms ends there)
 };
 // head[0 .. n) = the queries' head passes; takes plan.items, and writes the piece counts of the passes it cut to their n_items
 // (head and plan.extra).  nibble_plane: the segment has the one-byte tf/field plane (it halves what a keyword's walk costs a group).
 void layout_batch(DevQuery* head, uint32_t n, BatchPlan& plan, bool use_packed, bool nibble_plane, const LayoutKnobs& knobs, BatchLayout& out);
+
+// The dispatch order of a laid-out batch's scan_bm section ("bm_place", mrk_batch_submit): slot i of the launch runs item
+// disp[i] of the section.  Workgroups are dealt round-robin over the chip's eight XCDs (slot % 8), each with an L2 of its own,
+// and a keyword's lines are shared only between workgroups that sit on one XCD and walk the same windows at the same time.
+// Owners (the groups, or the queries on the ungrouped layout) are assigned to PLACE_CLASSES classes so that the bytes of the
+// distinct keywords per class, summed, are small and the classes' items balanced: owners by items, then bytes, descending,
+// each to the class that adds the fewest bytes of keywords new to it under a cap of ceil(total / 8) items + twice the smallest
+// owner's (no class under the cap: the lightest), then up to eight sweeps of single moves that lower the sum; ties go to the
+// lighter class, then the lower index.  A keyword is a (bitmap, idf) key and costs what group_bm_items charges (windows and
+// blocks x 256 B, blocks x 128 B with the nibble plane).  Inside a class the items run by ascending blk_begin, then owner:
+// the whole chip walks the corpus as one band of windows.  Slot 8 s + x takes the s-th item of class x; when a class has run
+// out, its slots take the next item of the class with the most items left (only there is the affinity lost).
+// mode 0: identity; 1: classes + window order; 2: window order alone, dealt as it comes (one class).  Fewer than two owners
+// or an empty section: identity, `ran` false.  The slot's XCD is a speed hint: nothing may depend on it.
+constexpr uint32_t PLACE_CLASSES = 8;
+struct BmPlacement {
+  std::vector<uint32_t> disp;        // n_items_kind[0] entries, relative to the section's start
+  std::vector<uint8_t> owner_class;  // per owner (group index; ungrouped: owners in the order of their first item, owner_pass names them)
+  std::vector<uint32_t> owner_pass;  // ungrouped layout: the owners' pass indexes (grouped: empty)
+  uint32_t owner_keys = 0, class_keys = 0; // distinct (owner, keyword) and (class, keyword) pairs; 0 when no placement ran
+  uint64_t owner_bytes = 0, class_bytes = 0; // ... and the bytes of those keywords
+  bool ran = false;
+  bool mismatch = false; // the ranges layout_batch handed out do not add up to the section's items: identity, and an error for the caller
+  // scratch of place_bm_items, kept so that a batch's next submit allocates nothing
+  struct Own {
+    uint32_t items = 0, begin = 0, end = 0, len = 1, nkeys = 0, key[BM_GROUP_TABS] = {};
+    uint64_t bytes = 0;
+  };
+  struct Cur {
+    uint32_t next, len, left; // blk_begin of the owner's next piece, its piece length, its pieces left
+    uint32_t idx, step, run;  // ... that piece's place in the section, the distance to the one after, and how many pieces that holds for
+    uint32_t o, k, tier;
+  };
+  struct Scratch {
+    std::vector<Own> own;
+    std::vector<Cur> mem;
+    std::vector<std::pair<uint64_t, uint32_t>> keys;
+    std::vector<uint64_t> kb;
+    std::vector<uint16_t> cnt;
+    std::vector<uint32_t> live, slot, by_load, first, rank, counts, fill, own_of, by_own, rest;
+  } scratch;
+};
+void place_bm_items(const DevQuery* head, uint32_t n, const std::vector<DevQuery>& extra, const BatchLayout& lay, bool nibble_plane, int mode,
+                    BmPlacement& out);
 
 // Least and largest field-weight sum over the masks of the first nwf (<= 32) fields, the empty mask counting as 1
 // (ExtRanker_WeightSum_c's "just fake it"): the pruning bins of the weight-sum rankers.

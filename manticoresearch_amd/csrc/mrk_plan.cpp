@@ -1774,6 +1774,250 @@ static void group_bm_items(const DevQuery* head, uint32_t n, const std::vector<D
   }
 }
 
+void mrk::place_bm_items(const DevQuery* head, uint32_t n, const std::vector<DevQuery>& extra, const BatchLayout& lay, bool nib, int mode,
+                         BmPlacement& out) {
+  const uint32_t n0 = (uint32_t)lay.n_items_kind[0];
+  const DevItem* const it = lay.items.data() + lay.n_items_pk;
+  out.disp.resize(n0);
+  out.owner_class.clear(), out.owner_pass.clear();
+  out.owner_keys = out.class_keys = 0;
+  out.owner_bytes = out.class_bytes = 0;
+  out.ran = out.mismatch = false;
+  auto identity = [&]() {
+    for (uint32_t i = 0; i < n0; ++i) out.disp[i] = i;
+  };
+  auto pass = [&](uint32_t p) -> const DevQuery& { return p < n ? head[p] : extra[p - n]; };
+  // ---- owners: the ranges layout_batch cut (groups, or queries), their piece length and count.  Nothing below reads the
+  // items themselves unless the section's order is not one of the two this function can index (see `tiers`)
+  const bool grouped = !lay.groups.empty();
+  const uint32_t n_own = (uint32_t)lay.bm_whole.size();
+  typedef BmPlacement::Own Own;
+  BmPlacement::Scratch& S = out.scratch; // (every list below lives there: a batch's next submit finds the buffers grown)
+  std::vector<Own>& own = S.own;
+  own.assign(n_own, Own{});
+  std::vector<uint32_t>& live = S.live; // owners with items, ascending
+  live.clear();
+  uint64_t total = 0;
+  uint32_t unit = ~0u;
+  for (uint32_t o = 0; o < n_own; ++o) {
+    Own& w = own[o];
+    w.begin = lay.bm_whole[o].blk_begin, w.end = lay.bm_whole[o].blk_end, w.len = (uint32_t)std::max<uint64_t>(lay.bm_len[o], 1);
+    w.items = w.end > w.begin ? (w.end - w.begin + w.len - 1) / w.len : 0;
+    if (!grouped) out.owner_pass.push_back(lay.bm_whole[o].query);
+    if (w.items) live.push_back(o), total += w.items, unit = std::min(unit, w.items);
+  }
+  out.owner_class.assign(n_own, 0);
+  out.mismatch = mode != 0 && total != n0; // (the ranges and the section disagree: never from layout_batch; the caller fails the submit)
+  if (mode == 0 || live.size() < 2 || out.mismatch) return identity();
+  // ---- keywords: dense ids of the (bitmap, idf) keys, a key's bytes as group_bm_items charges them (the largest of its holders')
+  auto tkey = [](const DevTerm& T) {
+    uint32_t idf;
+    memcpy(&idf, &T.idf, 4);
+    return std::make_pair(T.bm_off, idf);
+  };
+  auto n_terms_of = [&](uint32_t o) { return grouped ? lay.groups[o].ntab : 2u; };
+  auto owner_term = [&](uint32_t o, uint32_t j) -> const DevTerm& { // keyword j of owner o: a group's table j, a query's keyword j
+    if (!grouped) return pass(out.owner_pass[o]).t[j];
+    const BmGroup& G = lay.groups[o];
+    return pass(G.q[G.tab_src[j] >> 1]).t[G.tab_src[j] & 1u];
+  };
+  uint32_t n_terms = 0;
+  for (uint32_t o : live) n_terms += n_terms_of(o);
+  uint32_t hmask = 63;
+  while (hmask < 4 * n_terms) hmask = 2 * hmask + 1;
+  std::vector<uint32_t>& slot = S.slot; // open addressing: a slot names its key's id
+  slot.assign(hmask + 1, ~0u);
+  std::vector<std::pair<uint64_t, uint32_t>>& keys = S.keys;
+  std::vector<uint64_t>& kb = S.kb;
+  keys.clear(), kb.clear();
+  for (uint32_t o : live) {
+    Own& w = own[o];
+    for (uint32_t j = 0; j < n_terms_of(o); ++j) {
+      const DevTerm& T = owner_term(o, j);
+      const std::pair<uint64_t, uint32_t> key = tkey(T);
+      uint32_t h = (uint32_t)((key.first * 0x9E3779B97F4A7C15ull + key.second * 0xC2B2AE3D27D4EB4Full) >> 40) & hmask;
+      while (slot[h] != ~0u && keys[slot[h]] != key) h = (h + 1) & hmask;
+      if (slot[h] == ~0u) slot[h] = (uint32_t)keys.size(), keys.push_back(key), kb.push_back(0);
+      const uint32_t k = slot[h];
+      kb[k] = std::max(kb[k], (uint64_t)(w.end - w.begin) * 256 + (uint64_t)T.nblocks * (nib ? 128 : 256));
+      bool have = false;
+      for (uint32_t x = 0; x < w.nkeys; ++x) have = have || w.key[x] == k;
+      if (!have) w.key[w.nkeys++] = k;
+    }
+  }
+  const uint32_t nk = (uint32_t)keys.size();
+  for (uint32_t o : live) {
+    for (uint32_t x = 0; x < own[o].nkeys; ++x) own[o].bytes += kb[own[o].key[x]];
+    out.owner_keys += own[o].nkeys, out.owner_bytes += own[o].bytes;
+  }
+  // ---- classes.  The cap leaves two units of slack (a unit = the smallest owner's items, a lone query's): with one, the
+  // classes fill to the brim and hardly a move is possible (the benchmark's sets: 0.72-0.78 of the owners' bytes; with two,
+  // 0.66-0.71).  What the slack costs is affinity in the launch's tail only, since a class that runs out hands its slots on:
+  // under 4 % of those sets' items.
+  const uint32_t n_cls = mode == 1 ? PLACE_CLASSES : 1u;
+  std::vector<uint16_t>& cnt = S.cnt; // holders of key k in class c
+  cnt.assign((size_t)n_cls * nk, 0);
+  uint64_t load[PLACE_CLASSES] = {};
+  std::vector<uint8_t>& cls = out.owner_class;
+  auto add_cost = [&](uint32_t o, uint32_t c) {
+    uint64_t b = 0;
+    for (uint32_t x = 0; x < own[o].nkeys; ++x) b += cnt[(size_t)c * nk + own[o].key[x]] ? 0 : kb[own[o].key[x]];
+    return b;
+  };
+  auto put = [&](uint32_t o, uint32_t c, int d) {
+    for (uint32_t x = 0; x < own[o].nkeys; ++x) cnt[(size_t)c * nk + own[o].key[x]] += d;
+    load[c] += (int64_t)d * own[o].items;
+    if (d > 0) cls[o] = (uint8_t)c;
+  };
+  if (n_cls > 1) {
+    const uint64_t cap = (total + n_cls - 1) / n_cls + 2 * (uint64_t)unit;
+    std::vector<uint32_t>& by_load = S.by_load;
+    by_load.assign(live.begin(), live.end());
+    std::sort(by_load.begin(), by_load.end(), [&](uint32_t a, uint32_t b) {
+      if (own[a].items != own[b].items) return own[a].items > own[b].items;
+      if (own[a].bytes != own[b].bytes) return own[a].bytes > own[b].bytes;
+      return a < b;
+    });
+    for (uint32_t o : by_load) {
+      uint32_t best = ~0u, lightest = 0;
+      uint64_t best_cost = 0;
+      for (uint32_t c = 0; c < n_cls; ++c) {
+        if (load[c] < load[lightest]) lightest = c;
+        if (load[c] + own[o].items > cap) continue;
+        const uint64_t cost = add_cost(o, c);
+        if (best == ~0u || cost < best_cost || (cost == best_cost && load[c] < load[best])) best = c, best_cost = cost;
+      }
+      put(o, best == ~0u ? lightest : best, 1);
+    }
+    for (int sweep = 0; sweep < 8; ++sweep) { // single moves that lower the sum of the classes' bytes (in practice two or three sweeps find any)
+      bool moved = false;
+      for (uint32_t o : live) {
+        const uint32_t c0 = cls[o];
+        uint64_t freed = 0;
+        for (uint32_t x = 0; x < own[o].nkeys; ++x) freed += cnt[(size_t)c0 * nk + own[o].key[x]] == 1 ? kb[own[o].key[x]] : 0;
+        uint32_t best = ~0u;
+        uint64_t best_cost = 0;
+        for (uint32_t c = 0; c < n_cls && freed; ++c) {
+          if (c == c0 || load[c] + own[o].items > cap) continue;
+          const uint64_t cost = add_cost(o, c);
+          if (cost >= freed) continue;
+          if (best == ~0u || cost < best_cost || (cost == best_cost && load[c] < load[best])) best = c, best_cost = cost;
+        }
+        if (best == ~0u) continue;
+        put(o, c0, -1), put(o, best, 1);
+        moved = true;
+      }
+      if (!moved) break;
+    }
+  } else
+    for (uint32_t o : live) put(o, 0, 1);
+  for (uint32_t c = 0; c < n_cls; ++c)
+    for (uint32_t k = 0; k < nk; ++k)
+      if (cnt[(size_t)c * nk + k]) ++out.class_keys, out.class_bytes += kb[k];
+  // ---- where piece k of owner o sits in the section.  Query-major: behind the owners before it.  Piece-major: the pieces
+  // k of the owners that have one, in owner order; between two of the owners' distinct piece counts ("tiers": one per group
+  // size and window range) the same owners are alive, so the index is linear in k there.  More tiers than fit the table
+  // (queries with window ranges of their own): the items are read once instead.
+  constexpr uint32_t MAX_TIERS = 8;
+  std::vector<uint32_t>& first = S.first;
+  first.assign(n_own + 1, 0);
+  for (uint32_t o = 0; o < n_own; ++o) first[o + 1] = first[o] + own[o].items;
+  uint32_t tier_end[MAX_TIERS], tier_base[MAX_TIERS], tier_alive[MAX_TIERS], n_tiers = 0;
+  std::vector<uint32_t>& rank = S.rank;
+  bool tiers = lay.bm_piece_major;
+  if (tiers) {
+    std::vector<uint32_t>& counts = S.counts;
+    counts.clear();
+    for (uint32_t o : live) counts.push_back(own[o].items);
+    std::sort(counts.begin(), counts.end());
+    counts.erase(std::unique(counts.begin(), counts.end()), counts.end());
+    tiers = counts.size() <= MAX_TIERS;
+    if (tiers) {
+      n_tiers = (uint32_t)counts.size();
+      rank.assign((size_t)n_tiers * n_own, 0);
+      uint32_t base = 0, from = 0;
+      for (uint32_t j = 0; j < n_tiers; ++j) {
+        uint32_t alive = 0;
+        for (uint32_t o = 0; o < n_own; ++o)
+          if (own[o].items >= counts[j]) rank[(size_t)j * n_own + o] = alive++;
+        tier_end[j] = counts[j], tier_base[j] = base, tier_alive[j] = alive;
+        base += (counts[j] - from) * alive, from = counts[j];
+      }
+    }
+  }
+  std::vector<uint32_t>& by_own = S.by_own;
+  if (lay.bm_piece_major && !tiers) {
+    by_own.resize(n0);
+    std::vector<uint32_t>&fill = S.fill, &own_of = S.own_of;
+    fill.assign(first.begin(), first.end() - 1);
+    if (!grouped) {
+      own_of.assign((size_t)n + extra.size(), 0);
+      for (uint32_t o = 0; o < n_own; ++o) own_of[out.owner_pass[o]] = o;
+    }
+    for (uint32_t i = 0; i < n0; ++i) by_own[fill[grouped ? it[i].query : own_of[it[i].query]]++] = i;
+  }
+  // ---- inside a class: ascending blk_begin, then owner (begin by begin, the class's owners in order).  The s-th item of class
+  // x runs in slot n_cls s + x as long as every class has an s-th item; what is left then goes to `rest`, class by class
+  uint32_t least = ~0u, rest_first[PLACE_CLASSES + 1] = {};
+  for (uint32_t c = 0; c < n_cls; ++c) least = std::min<uint64_t>(least, load[c]);
+  for (uint32_t c = 0; c < n_cls; ++c) rest_first[c + 1] = rest_first[c] + (uint32_t)load[c] - least;
+  std::vector<uint32_t>& rest = S.rest;
+  rest.resize(rest_first[n_cls]);
+  typedef BmPlacement::Cur Cur;
+  auto locate = [&](Cur& m) { // the place of piece m.k of owner m.o
+    if (tiers) {
+      while (m.k >= tier_end[m.tier]) ++m.tier;
+      m.idx = tier_base[m.tier] + (m.k - (m.tier ? tier_end[m.tier - 1] : 0)) * tier_alive[m.tier] + rank[(size_t)m.tier * n_own + m.o];
+      m.step = tier_alive[m.tier], m.run = tier_end[m.tier] - m.k;
+    } else if (lay.bm_piece_major)
+      m.idx = by_own[first[m.o] + m.k], m.step = 0, m.run = 1;
+    else
+      m.idx = first[m.o] + m.k, m.step = 1, m.run = ~0u;
+  };
+  std::vector<Cur>& mem = S.mem;
+  uint32_t* const disp = out.disp.data();
+  for (uint32_t c = 0; c < n_cls; ++c) {
+    mem.clear();
+    for (uint32_t o : live)
+      if (cls[o] == c) {
+        Cur m{own[o].begin, own[o].len, own[o].items, 0, 0, 0, o, 0, 0};
+        locate(m);
+        mem.push_back(m);
+      }
+    uint32_t s = 0;
+    const uint32_t want = (uint32_t)load[c];
+    uint32_t* const own_slots = disp + c;
+    uint32_t* const spill = rest.data() + rest_first[c];
+    for (uint64_t x = 0, nx; s < want; x = nx) { // every owner whose next piece begins at x (the least begin left), then the next begin
+      nx = ~0ull;
+      for (Cur& m : mem) {
+        if (!m.left) continue;
+        if (m.next <= x) {
+          if (s < least)
+            own_slots[(size_t)s * n_cls] = m.idx;
+          else
+            spill[s - least] = m.idx;
+          ++s, ++m.k, --m.left, m.next += m.len, m.idx += m.step;
+          if (!--m.run && m.left) locate(m);
+          if (!m.left) continue;
+        }
+        nx = std::min<uint64_t>(nx, m.next);
+      }
+    }
+  }
+  // ---- the tail: a class that has run out hands its slots to the class with the most items left
+  uint32_t next[PLACE_CLASSES];
+  for (uint32_t c = 0; c < n_cls; ++c) next[c] = rest_first[c];
+  for (uint32_t i = least * n_cls; i < n0; ++i) {
+    uint32_t c = i % n_cls;
+    if (next[c] == rest_first[c + 1])
+      for (uint32_t d = 0; d < n_cls; ++d)
+        if (rest_first[d + 1] - next[d] > rest_first[c + 1] - next[c]) c = d;
+    disp[i] = rest[next[c]++];
+  }
+  out.ran = true;
+}
+
 // Walks the pieces 0, 1, ... of ranges 0 .. n_ranges (piece(r, k) emits piece k of range r, or returns false past the range's
 // end): query-major, a range's pieces back to back, or piece-major, the k-th piece of every range, then the (k+1)-th ...
 template <class Piece>
@@ -1890,6 +2134,7 @@ void mrk::layout_batch(DevQuery* head, uint32_t n, BatchPlan& plan, bool use_pac
     const bool piece_major = (knobs.item_order & (kind == 0 ? 2 : 4)) && !(kind == 1 && any_prox && !(knobs.item_order & 8));
     const size_t before = items.size();
     for_pieces(whole.size(), piece_major, [&](size_t r, uint64_t k) { return cut_piece(whole[r], len[r], k, items); });
+    if (kind == 0) out.bm_piece_major = piece_major, out.bm_whole.swap(whole), out.bm_len.swap(len);
     out.n_items_kind[kind] = items.size() - before;
   }
   for (const DevItem& it : items_bm) // the generic evaluator's candidates: block ranges, cut by the planner
