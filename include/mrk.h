@@ -193,9 +193,10 @@ typedef struct {
    mrk_order keeps its size and layout (callers built against it stay valid): then_weight says where the weight stands, behind the
    parts (0 / 1 / 2) or in front of them, so "in front and behind" cannot be said.  The same shapes of parts; _ASC also takes
    n_parts 0 ('ORDER BY weight() ASC': it reads no attribute row and needs none); _DESC without parts is relevance (leave order NULL)
-   and MRK_E_INVAL, like every other value of then_weight.  No exchange row carries the weight's position yet: a weight-first query
-   leaves in narrow, wide and order rows with MRK_ROW_DECLINED, no keys and spec word 0.  mrk_result.order_key holds the raw parts as
-   for every order (NULL without parts). */
+   and MRK_E_INVAL, like every other value of then_weight.  A weight-first query leaves in narrow and wide rows with
+   MRK_ROW_DECLINED, no keys and spec word 0, and so it does in order rows unless the batch was told to carry it there
+   (mrk_batch_orows_weight_first, below: bit 3 of the order spec word).  mrk_result.order_key holds the raw parts as for every order
+   (NULL without parts). */
 #define MRK_MAX_ORDER_PARTS 2
 typedef struct {
   int32_t kind;                  /* MRK_SORTKEY_* */
@@ -540,7 +541,7 @@ uint32_t mrk_sort_unmap_key(uint64_t spec_word, uint32_t mapped);
  *   [MRK_MAX_K+2 ..]           MRK_MAX_K u64: entry i = the 64-bit order-preserving mapped key of keys[i] (larger = better:
  *                              map32(first part) << 32 | map32(second part)); zero past count
  *   [MRK_OROW_WORDS-1]         the order spec word: 0 = a relevance query (the plane is zero and ignored); else
- *                              bit 0 ordered | bit 1 wide (a 64-bit key) | bit 2 INT64 | bits 4-5 then_weight |
+ *                              bit 0 ordered | bit 1 wide (a 64-bit key) | bit 2 INT64 | bit 3 weight-first | bits 4-5 then_weight |
  *                              part p in the 16 bits from bit 8 + 16 p: bit 0 float | bit 1 desc | bit 2 signed (the high dword
  *                              of an INT64) | bits 4-9 bit_count -- all that decides whether two shards' mapped keys and tie
  *                              rules compare and how a mapped key turns back into a raw value, nothing of where a segment
@@ -557,10 +558,22 @@ uint32_t mrk_sort_unmap_key(uint64_t spec_word, uint32_t mapped);
  * row whichever list declined): never a mis-ordered answer.  At most 8 lists.  Each function is the twin of the wide one above, argument for argument.  A batch has ONE
  * standing destination of the three kinds: setting a second kind while one stands is MRK_E_INVAL.  After an overflow rerun
  * (MRK_ROW_RERUN), mrk_batch_wait + mrk_batch_export_orows hand out the repaired row, mapped keys included.
+ * Weight-first orders (MRK_ORDER_WEIGHT_FIRST_*).  Bit 3 of the spec word says that the weight leads the order; bits 4-5 then hold
+ * the WEIGHT's direction, 1 DESC / 2 ASC (0 and 3 are no valid spec), and every other field reads as without the bit: one part of
+ * <= 32 bits (wide clear, its key in the high dword), two parts (wide), one INT64 (wide | INT64), or no part at all ('weight() ASC'
+ * alone: both part fields zero, the plane all zero).  The plane holds the parts' 64-bit mapped key; the merge orders such a query's
+ * entries by the weight as the direction says, then the mapped key, then GLOBAL docid ascending.  A spec with bit 3 and direction
+ * 0 or 3 merges to MRK_ROW_DECLINED, no keys and that spec word; a weight-first list next to any other spec is a mismatch as above.
+ * A merger that predates bit 3 cannot read such rows, so a batch writes them only when told to: mrk_batch_orows_weight_first(b, 1)
+ * (default 0; any other value MRK_E_INVAL).  It takes effect with the next submit, and all rows of a submit -- the standing
+ * order-row destination's, mrk_batch_export_orows' after the wait, the row repaired by an overflow rerun -- follow the setting that
+ * stood when it was submitted.  With it off, and in narrow and wide rows whatever it says, a weight-first query leaves with
+ * MRK_ROW_DECLINED, no keys and spec word 0.
  * ---------------------------------------------------------------------------------- */
 #define MRK_OROW_WORDS (MRK_ROW_WORDS + MRK_MAX_K + 1)
 int mrk_batch_export_orows(mrk_batch* b, uint64_t* orows_dst);
 int mrk_batch_set_orows_dst(mrk_batch* b, uint64_t* orows_dst);
+int mrk_batch_orows_weight_first(mrk_batch* b, int on);
 int mrk_topk_merge_orows(mrk_ctx* ctx, const uint64_t* orows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_orows);
 int mrk_topk_merge_orows_async(mrk_ctx* ctx, const uint64_t* orows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
                                uint64_t* out_orows, void* wait_event, uint32_t slot);
@@ -569,7 +582,8 @@ int mrk_topk_merge_orows_part(mrk_ctx* ctx, const uint64_t* orows_recv, uint32_t
 int mrk_shard_exchange_orows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* orows, uint32_t n_queries, uint32_t k, uint64_t* out_orows,
                              uint32_t slot);
 /* host only: the value behind a 64-bit mapped key of a row with this order spec word, in mrk_result.order_key's format: the raw
-   int64, or raw0 << 32 | raw1 (a sort spec: raw0 << 32).  A float's -0.0 reads +0.0. */
+   int64, or raw0 << 32 | raw1 (a sort spec: raw0 << 32).  A float's -0.0 reads +0.0.  A weight-first spec unmaps its parts as the
+   same spec without bit 3 does; one without parts unmaps to 0. */
 uint64_t mrk_order_unmap_key(uint64_t spec_word, uint64_t mapped);
 
 /* merge n_lists sorted partial top-K lists per query (device pointers; relevance order only):

@@ -180,6 +180,18 @@ inline bool MrkSorterWeightFirst ( const CSphMatchComparatorState & tState, mrk_
 	return tState.m_eKeypart[i]==SPH_KEYPART_ROWID && ( ( tState.m_uAttrDesc >> i ) & 1 )==0;
 }
 
+/// A host that merges the results of several disk chunks, RT RAM segments or rowid-range shards on the device (mrk_topk_merge_orows*,
+/// mrk_shard_exchange_orows) gives every batch its standing ORDER-row destination through this: it also lets the rows carry the
+/// weight-first orders MrkSorterWeightFirst accepts (bit 3 of the order spec word), so that such a sorter stays eligible across chunks.
+/// Every merger of these rows is this library's own, which reads the bit; a host that ships rows to an older merger calls
+/// mrk_batch_set_orows_dst alone and keeps the CPU ranker for weight-first sorters over several chunks.  pRows = NULL cancels the
+/// destination and leaves the switch as it is.
+inline int MrkBatchSetOrderRows ( mrk_batch * pBatch, uint64_t * pRows )
+{
+	const int iRes = pRows ? mrk_batch_orows_weight_first ( pBatch, 1 ) : MRK_OK;
+	return iRes!=MRK_OK ? iRes : mrk_batch_set_orows_dst ( pBatch, pRows );
+}
+
 /// Which device order is this sorter?  0 = none (keep the CPU ranker), 1 = relevance, 2 = one attribute of <= 32 bits first (tSort
 /// filled), 3 = a 64-bit attribute or two attributes first, or the weight first with attributes (or nothing, ascending) behind it
 /// (*pOrder filled; only asked for when pOrder is given).

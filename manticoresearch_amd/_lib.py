@@ -184,6 +184,7 @@ SYMBOLS = [
     ("mrk_sort_unmap_key", C.c_uint32, [C.c_uint64, C.c_uint32]),
     ("mrk_batch_export_orows", C.c_int, [C.c_void_p, C.c_void_p]),
     ("mrk_batch_set_orows_dst", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("mrk_batch_orows_weight_first", C.c_int, [C.c_void_p, C.c_int]),
     ("mrk_topk_merge_orows", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("mrk_topk_merge_orows_async", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                             C.c_uint32]),

@@ -688,6 +688,11 @@ class Batch:
         mapped keys and order spec word, relevance queries with a zero plane and spec 0."""
         check(lib().mrk_batch_export_orows(self._h, orows_dst))
 
+    def orows_weight_first(self, on: bool = True) -> None:
+        """Let ORDER rows carry weight-first queries (Order.weight_first) from the next submit on (mrk_batch_orows_weight_first): bit 3
+        of their spec word, which every merger of these rows must know.  Off by default: such a query's row leaves declined."""
+        check(lib().mrk_batch_orows_weight_first(self._h, int(on)))
+
     def search(self, seg: Segment, queries: Sequence[Query]) -> List[Matches]:
         self.submit(seg, queries)
         self.wait()

@@ -415,6 +415,7 @@ struct SortSelArgs {
   // batch never held a query ordered by a 64-bit key and has no standing order-row destination
   uint64_t* out_mkeys64;   // [n_queries][KCAP] or NULL
   uint64_t* orows_dst;     // a standing order-row destination (mrk_batch_set_orows_dst): device [n_queries][OROW_WORDS] or NULL (excludes srows_dst)
+  uint32_t orows_wfirst;   // != 0: a weight-first query's order row is written too (mrk_batch_orows_weight_first); 0: pack_xrows_kernel marks it MRK_ROW_DECLINED
 };
 void launch_sort_select(const SortSelArgs& a, void* stream);
 

@@ -114,6 +114,8 @@ struct mrk_batch {
   uint64_t* rows_dst = nullptr; // mrk_batch_set_rows_dst
   uint64_t* srows_dst = nullptr; // mrk_batch_set_srows_dst (wide rows; excludes rows_dst)
   uint64_t* orows_dst = nullptr; // mrk_batch_set_orows_dst (order rows; excludes the other two)
+  bool orows_wf = false;        // mrk_batch_orows_weight_first: order rows carry weight-first queries, from the next submit on ...
+  bool orows_wf_run = false;    // ... and what the last submit ran with: all its rows follow this
   bool host_copied = true;      // per-query keys / counts / totals of the last submit are in pinned host memory
   hipStream_t stream = nullptr; // every batch runs on its own stream: batches of one context overlap on the device
   uint32_t max_queries = 0;
@@ -184,8 +186,8 @@ struct mrk_batch {
     mrk::OrderPart p1{0, 0, 0, 0};
     // the query fits no NARROW or WIDE exchange row: a 64-bit key, or the weight in front of the parts (MRK_ORDER_WEIGHT_FIRST_*) ...
     bool no_row() const { return order == mrk::SORT_ON_ORDER || order == mrk::SORT_ON_WEIGHT; }
-    // ... and the latter no ORDER row either (the order spec word does not carry the weight's position yet)
-    bool no_orow() const { return order == mrk::SORT_ON_WEIGHT; }
+    // ... and the latter no ORDER row either, unless the batch asked for it (mrk_batch_orows_weight_first: OSPEC_WFIRST of the spec word)
+    bool no_orow(bool wfirst_rows) const { return order == mrk::SORT_ON_WEIGHT && !wfirst_rows; }
   };
   std::vector<SortLoc> sort_loc;
   std::vector<uint32_t> sort_key;
@@ -1248,8 +1250,10 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   if (use_packed && ((rc = b->d_cand.reserve(cand_total + 64)) || (rc = b->d_sel.reserve(2 * (size_t)n + mrk::sel_slice_slots(cand_total, n))))) return rc;
   const bool any_sort = use_packed && plan.sort_total != 0;
   if (any_sort && ((rc = b->d_scand.reserve(2 * plan.sort_total + 64)) || (rc = b->d_out_mkeys.reserve((size_t)b->max_queries * KCAP)))) return rc;
-  bool any_order = false; // a 64-bit key: the order rows' plane, from here on
-  for (uint32_t i = 0; i < n && any_sort; ++i) any_order = any_order || b->sort_loc[i].order == mrk::SORT_ON_ORDER;
+  bool any_order = false; // a 64-bit key, or a weight-first query that leaves in order rows: the order rows' plane, from here on
+  b->orows_wf_run = b->orows_wf;
+  for (uint32_t i = 0; i < n && any_sort; ++i)
+    any_order = any_order || b->sort_loc[i].order == mrk::SORT_ON_ORDER || (b->orows_wf_run && b->sort_loc[i].order == mrk::SORT_ON_WEIGHT);
   if (any_sort && (any_order || b->orows_dst) && (rc = b->d_out_mkeys64.reserve((size_t)b->max_queries * KCAP))) return rc;
 
   static const bool phase_timing = getenv("MRK_SUBMIT_TIMING") != nullptr;
@@ -1343,7 +1347,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
       ss.out_keys = b->d_out_keys.p, ss.out_cnt = b->d_out_cnt.p, ss.out_mkeys = b->d_out_mkeys.p;
       if (!standing) ss.h_keys = b->h_keys.p, ss.h_cnt = b->h_cnt.p;
       ss.srows_dst = b->srows_dst, ss.q_total = b->d_q_total.p, ss.q_flags = b->d_q_flags.p; // a standing wide destination: the sorted queries' rows leave here
-      ss.out_mkeys64 = b->d_out_mkeys64.p, ss.orows_dst = b->orows_dst;
+      ss.out_mkeys64 = b->d_out_mkeys64.p, ss.orows_dst = b->orows_dst, ss.orows_wfirst = b->orows_wf_run ? 1u : 0u;
       mrk::launch_sort_select(ss, st2);
     }
   } else {
@@ -1374,9 +1378,9 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
       HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     }
     b->decl_order = any_order;
-    if (any_order) { // the same words for ORDER rows, which carry a 64-bit key
+    if (any_order) { // the same words for ORDER rows, which carry a 64-bit key (and, where the batch asked for it, the weight in front)
       uint32_t* ho = b->h_decl.p + b->max_queries;
-      for (uint32_t i = 0; i < n; ++i) ho[i] = (b->status[i] != MRK_OK || b->sort_loc[i].no_orow()) ? 1u : 0u;
+      for (uint32_t i = 0; i < n; ++i) ho[i] = (b->status[i] != MRK_OK || b->sort_loc[i].no_orow(b->orows_wf_run)) ? 1u : 0u;
       HIP_TRY(hipMemcpyAsync(b->d_decl.p + b->max_queries, ho, n * 4, hipMemcpyHostToDevice, st2));
     }
     b->decl_dirty = any;
@@ -1668,6 +1672,13 @@ static int batch_set_dst(mrk_batch* b, uint64_t* dst, RowKind kind) {
 extern "C" int mrk_batch_set_rows_dst(mrk_batch* b, uint64_t* rows_dst) { return batch_set_dst(b, rows_dst, ROWS_NARROW); }
 extern "C" int mrk_batch_set_srows_dst(mrk_batch* b, uint64_t* srows_dst) { return batch_set_dst(b, srows_dst, ROWS_WIDE); }
 extern "C" int mrk_batch_set_orows_dst(mrk_batch* b, uint64_t* orows_dst) { return batch_set_dst(b, orows_dst, ROWS_ORDER); }
+// (read by the next submit only: the rows of the last one, exported or repaired later, keep what it ran with)
+extern "C" int mrk_batch_orows_weight_first(mrk_batch* b, int on) {
+  if (!b) return mrk_fail(MRK_E_INVAL, "mrk_batch_orows_weight_first: NULL batch");
+  if (on != 0 && on != 1) return mrk_fail(MRK_E_INVAL, "mrk_batch_orows_weight_first: on = %d (0 or 1)", on);
+  b->orows_wf = on != 0;
+  return MRK_OK;
+}
 
 static int mrk_batch_record_event_impl(mrk_batch* b, void* hip_event) {
   if (!b || !hip_event) return mrk_fail(MRK_E_INVAL, "mrk_batch_record_event: NULL argument");

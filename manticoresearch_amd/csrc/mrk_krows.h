@@ -56,7 +56,10 @@ struct OrderFmt {
   static constexpr bool WIDE_KEYS = true;
   using MK = uint64_t;
   static __device__ __forceinline__ uint32_t spec_tie(uint64_t spec) { return order_spec_tie(spec); }
-  static __device__ __forceinline__ uint64_t spec_of(const DevQuery& Q) { return order_spec_word(Q.sort_on, Q.sort_flags, Q.sort_bits, Q.ord_flags, Q.ord_bits, Q.sort_tie); }
+  static __device__ __forceinline__ uint64_t spec_of(const DevQuery& Q) {
+    if (Q.sort_on == SORT_ON_WEIGHT) return order_spec_word_wfirst(Q.sort_flags, Q.sort_bits, Q.ord_flags, Q.ord_bits, Q.sort_tie, Q.wf_parts);
+    return order_spec_word(Q.sort_on, Q.sort_flags, Q.sort_bits, Q.ord_flags, Q.ord_bits, Q.sort_tie);
+  }
   static __device__ __forceinline__ MK mkey_of(uint64_t mkey64) { return mkey64; }
   static __device__ __forceinline__ MK load_mkey(const uint64_t* row, uint32_t i) { return row[MKEYS + i]; }
   template <class F>

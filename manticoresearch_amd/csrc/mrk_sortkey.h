@@ -198,10 +198,13 @@ MRK_HD inline uint64_t cand_mkey(uint32_t sort_on, uint64_t hi, uint64_t lo) {
 // decides whether two shards' mapped keys and tie rules compare and how a mapped key turns back into a raw value, and nothing of
 // where a segment stores the columns.  0 = a relevance query.
 //   bit 0 ordered | bit 1 wide (a 64-bit key; clear = a sort: the 32-bit mapped key in the high dword, the low dword zero) |
-//   bit 2 INT64 (one signed 64-bit attribute) | bits 4-5 then_weight | part p in the 16 bits from bit 8 + 16 p:
+//   bit 2 INT64 (one signed 64-bit attribute) | bit 3 weight-first | bits 4-5 then_weight | part p in the 16 bits from bit 8 + 16 p:
 //   bit 0 float | bit 1 desc | bit 2 signed (the high dword of an INT64) | bits 4-9 bit_count
+// Weight-first (bit 3; MRK_ORDER_WEIGHT_FIRST_*): the weight leads the order and bits 4-5 hold ITS direction, 1 DESC / 2 ASC (0 and 3
+// are no valid spec); every other field reads as without the bit -- one part of <= 32 bits (wide clear, the key in the high dword),
+// two parts (wide), one INT64 (wide | INT64), or no part at all (weight ASC alone: both part fields zero, the mapped plane all zero).
 // ---------------------------------------------------------------------------------------
-constexpr uint64_t OSPEC_ORDERED = 1, OSPEC_WIDE = 2, OSPEC_INT64 = 4;
+constexpr uint64_t OSPEC_ORDERED = 1, OSPEC_WIDE = 2, OSPEC_INT64 = 4, OSPEC_WFIRST = 8;
 constexpr uint32_t OSPEC_PART_FLOAT = 1, OSPEC_PART_DESC = 2, OSPEC_PART_SIGNED = 4;
 MRK_HD inline uint64_t order_spec_part(uint32_t flags, uint32_t bits) {
   return ((flags & SORT_FLOAT) ? OSPEC_PART_FLOAT : 0u) | ((flags & SORT_DESC) ? OSPEC_PART_DESC : 0u) | ((flags & SORT_SIGNED) ? OSPEC_PART_SIGNED : 0u) | ((uint64_t)(bits & 63u) << 4);
@@ -214,6 +217,16 @@ MRK_HD inline uint64_t order_spec_word(uint32_t sort_on, uint32_t flags0, uint32
   if (sort_on == SORT_ON_ORDER) w |= OSPEC_WIDE | ((flags0 & SORT_SIGNED) ? OSPEC_INT64 : 0u) | (order_spec_part(flags1, bits1) << 24);
   return w;
 }
+// from a weight-first DevQuery's words (sort_on == SORT_ON_WEIGHT): sort_flags / sort_bits of the first dword behind the weight, ord_flags /
+// ord_bits of the second, sort_tie = the weight's direction, wf_parts = 0..2 dwords (an INT64 counts as its two; part 0 is SORT_SIGNED then)
+MRK_HD inline uint64_t order_spec_word_wfirst(uint32_t flags0, uint32_t bits0, uint32_t flags1, uint32_t bits1, uint32_t wf, uint32_t wf_parts) {
+  uint64_t w = OSPEC_ORDERED | OSPEC_WFIRST | ((uint64_t)(wf & 3u) << 4);
+  if (wf_parts) w |= order_spec_part(flags0, bits0) << 8;
+  if (wf_parts > 1u) w |= OSPEC_WIDE | ((flags0 & SORT_SIGNED) ? OSPEC_INT64 : 0u) | (order_spec_part(flags1, bits1) << 24);
+  return w;
+}
+// a weight-first spec word's direction of the weight is 1 or 2
+MRK_HD inline bool order_spec_wfirst_valid(uint64_t spec) { const uint32_t d = (uint32_t)(spec >> 4) & 3u; return d == 1u || d == 2u; }
 MRK_HD inline uint32_t order_spec_tie(uint64_t spec) { return spec ? (uint32_t)(spec >> 4) & 3u : 1u; } // relevance = weight desc
 // part p's SORT_FLOAT | SORT_DESC | SORT_SIGNED out of a spec word
 MRK_HD inline uint32_t order_spec_flags(uint64_t spec, uint32_t p) {
@@ -221,9 +234,11 @@ MRK_HD inline uint32_t order_spec_flags(uint64_t spec, uint32_t p) {
   return ((f & OSPEC_PART_FLOAT) ? SORT_FLOAT : 0u) | ((f & OSPEC_PART_DESC) ? SORT_DESC : 0u) | ((f & OSPEC_PART_SIGNED) ? SORT_SIGNED : 0u);
 }
 // the inverse of the 64-bit map under a spec word, in mrk_result.order_key's format: the raw int64, or raw0 << 32 | raw1 (a sort
-// spec: raw0 << 32); a float's -0.0 reads +0.0
+// spec: raw0 << 32); a float's -0.0 reads +0.0.  A weight-first spec unmaps its parts as the same spec without bit 3 does; one
+// without parts (part 0's bit count 0) unmaps to 0
 MRK_HD inline uint64_t order_unmap_key(uint64_t spec, uint64_t mapped) {
   if (!spec) return 0ull;
+  if ((spec & OSPEC_WFIRST) && !((spec >> 12) & 63u)) return 0ull;
   const uint32_t r0 = order_unmap_part((uint32_t)(mapped >> 32), order_spec_flags(spec, 0));
   if (!(spec & OSPEC_WIDE)) return (uint64_t)r0 << 32;
   return ((uint64_t)r0 << 32) | order_unmap_part((uint32_t)mapped, order_spec_flags(spec, 1));

@@ -123,12 +123,14 @@ __global__ __launch_bounds__(WG) void sort_select_kernel(SortSelArgs a) {
     a.out_mkeys[(uint64_t)q * KCAP + i] = (uint32_t)(mk >> 32); // the mapped key travels with the row (wide exchange rows)
     if (a.out_mkeys64) a.out_mkeys64[(uint64_t)q * KCAP + i] = mk; // ... all of it (order rows)
   }
-  // The standing destination's row.  A 64-bit key does not fit a wide row, and no exchange row carries the weight's position yet: no
-  // row is written then, and pack_xrows_kernel marks that query's row MRK_ROW_DECLINED.  sel_sort_kernel's rule (row_total_word): a query
+  // The standing destination's row.  A 64-bit key does not fit a wide row, and the weight's position is carried by an order row's spec
+  // word only, where the batch asked for it (a.orows_wfirst): no row is written otherwise, and pack_xrows_kernel marks that query's row
+  // MRK_ROW_DECLINED.  sel_sort_kernel's rule (row_total_word): a query
   // whose candidate list overflowed leaves empty with MRK_ROW_RERUN, one that met a run-time decline empty with MRK_ROW_DECLINED.
   if constexpr (DST != DST_NONE) {
     using Fmt = std::conditional_t<DST == DST_WIDE, WideFmt, OrderFmt>;
-    if (sort_on != SORT_ON_WEIGHT && (Fmt::WIDE_KEYS || sort_on != SORT_ON_ORDER)) { // (uniform)
+    const bool wfirst_row = DST == DST_ORDER && a.orows_wfirst != 0u;
+    if ((sort_on != SORT_ON_WEIGHT || wfirst_row) && (Fmt::WIDE_KEYS || sort_on != SORT_ON_ORDER)) { // (uniform)
       const uint32_t qf = a.q_flags[q];
       const uint32_t nr = row_unflagged(false, qf) ? m : 0u;
       uint64_t* __restrict__ row = (DST == DST_WIDE ? a.srows_dst : a.orows_dst) + (uint64_t)q * Fmt::WORDS;
@@ -188,8 +190,9 @@ void launch_pack_xrows(RowKind kind, const PackXRowsArgs& a, void* stream) {
 // one workgroup per query, all lists in LDS, merged pairwise by bitonic merges over entries of 8 + Fmt::MK_BYTES bytes -- the u64 key
 // and, in a plane of its own, the mapped key.  The weight and the docid come out of the u64 key, so a sorted or ordered query compares
 // (mapped key, the key as the tie rule reads it); a relevance query (spec 0), and every query of narrow rows, compares the key alone
-// and never touches the mapped plane.  LDS for 8 lists: 64 KB narrow, 96 KB wide, 128 KB order rows (one workgroup per CU on gfx950's
-// 160 KB); half that for up to 4 lists.
+// and never touches the mapped plane.  A weight-first order (OSPEC_WFIRST, order rows only) compares the key's weight dword as the
+// spec's direction reads it, then the mapped key, then the key's docid dword.  LDS for 8 lists: 64 KB narrow, 96 KB wide, 128 KB order
+// rows (one workgroup per CU on gfx950's 160 KB); half that for up to 4 lists.
 // ---------------------------------------------------------------------------------------
 // the u64 key as tie rule `tie` orders it, larger = better; the zero key is the lists' padding and stays the smallest
 template <uint32_t TIE>
@@ -199,10 +202,17 @@ __device__ __forceinline__ uint64_t tie_key(uint64_t k) {
   return TIE == 2u ? k ^ 0xFFFFFFFF00000000ull : k & 0xFFFFFFFFull; // weight ascending / the weight is no part of the order
 }
 
-template <class MK, bool SORTED, uint32_t TIE>
+template <class MK, bool SORTED, uint32_t TIE, bool WFIRST = false>
 static __device__ void merge_rounds(uint64_t* mk, MK* mm, uint32_t P) {
   const uint32_t tid = threadIdx.x;
   auto less = [](uint64_t xk, MK xm, uint64_t yk, MK ym) -> bool {
+    if (WFIRST) { // TIE = the weight's direction; ~docid is the low dword under either
+      const uint64_t xt = tie_key<TIE>(xk), yt = tie_key<TIE>(yk);
+      const uint32_t xw = (uint32_t)(xt >> 32), yw = (uint32_t)(yt >> 32);
+      if (xw != yw) return xw < yw;
+      if (xm != ym) return xm < ym;
+      return (uint32_t)xt < (uint32_t)yt;
+    }
     if (SORTED && xm != ym) return xm < ym;
     return tie_key<TIE>(xk) < tie_key<TIE>(yk);
   };
@@ -276,16 +286,26 @@ __global__ __launch_bounds__(WG) void merge_xrows_kernel(MergeRowsArgs a, uint32
       for (uint32_t i = tid; i < (uint32_t)KCAP; i += WG) mm[l * KCAP + i] = i < cnt ? Fmt::load_mkey(row, i) : MK(0);
   }
   __syncthreads();
+  // a weight-first spec (order rows only) whose direction of the weight is neither DESC nor ASC is no spec: a mismatch
+  const bool wfirst = Fmt::WIDE_KEYS && (spec & OSPEC_WFIRST) != 0;
+  if (wfirst && !order_spec_wfirst_valid(spec)) mismatch = true;
   // lists that do not compare (spec words differing in any bit: kind, direction of a part, width, tie rule, a sort next to a 64-bit
-  // order, a relevance row next to either), and a sorted or ordered query some shard declined: the merged row is no answer --
-  // MRK_ROW_DECLINED and no keys
+  // order, a relevance row next to either, a weight-first order next to any other), and a sorted or ordered query some shard
+  // declined: the merged row is no answer -- MRK_ROW_DECLINED and no keys
   const bool none = mismatch || (spec != 0 && (flags & ROW_DECLINED) != 0);
   if (mismatch) flags |= ROW_DECLINED;
   if (!none) { // (uniform)
     const uint32_t tie = Fmt::spec_tie(spec);
     if (!PLANE || !spec)
       merge_rounds<MK, false, 1u>(mk, mm, P);
-    else if (tie == 1u)
+    else if (wfirst) {
+      if constexpr (Fmt::WIDE_KEYS) {
+        if (tie == 1u)
+          merge_rounds<MK, true, 1u, true>(mk, mm, P);
+        else
+          merge_rounds<MK, true, 2u, true>(mk, mm, P);
+      }
+    } else if (tie == 1u)
       merge_rounds<MK, true, 1u>(mk, mm, P);
     else if (tie == 2u)
       merge_rounds<MK, true, 2u>(mk, mm, P);

@@ -131,18 +131,26 @@ def merge_srows_np(srows_all: np.ndarray, k: int) -> np.ndarray:
 OROW_WORDS = _lib.OROW_WORDS
 OROW_MKEYS, OROW_SPEC = MRK_MAX_K + 2, OROW_WORDS - 1  # word offsets of the u64 plane and of the spec word
 OSPEC_ORDERED, OSPEC_WIDE, OSPEC_INT64 = 1, 2, 4       # + then_weight << 4 + part p << (8 + 16 p) (mrk_sortkey.h, order_spec_word)
+OSPEC_WFIRST = 8                                       # the weight leads the order; bits 4-5 = ITS direction, 1 DESC / 2 ASC
 OSPEC_PART_FLOAT, OSPEC_PART_DESC, OSPEC_PART_SIGNED = 1, 2, 4  # + bit_count << 4
 
 
-def order_spec_word(parts, then_weight: int) -> int:
+def order_spec_word(parts, then_weight: int, weight_first: int = 0) -> int:
     """The spec word of an ordered query's order row.  parts: one or two objects with kind / desc / bit_count (api.OrderPart;
-    an api.Sort is one part).  One part of <= 32 bits is a sort (wide bit clear); kind SORTKEY_INT64 stands alone."""
+    an api.Sort is one part).  One part of <= 32 bits is a sort (wide bit clear); kind SORTKEY_INT64 stands alone.
+    weight_first 1 / 2 (Order.weight_first: weight DESC / ASC in front of the parts): OSPEC_WFIRST, the direction in then_weight's
+    place (then_weight itself is not read), the parts as without it; no parts at all only with weight_first 2."""
     def part(kind, desc, bits, signed=False):
         return (OSPEC_PART_FLOAT if kind == 1 else 0) | (OSPEC_PART_DESC if desc else 0) | (OSPEC_PART_SIGNED if signed else 0) | ((bits & 63) << 4)
 
     parts = list(parts)
-    assert 1 <= len(parts) <= 2
+    assert weight_first in (0, 1, 2)
+    assert 1 <= len(parts) <= 2 or (not parts and weight_first == 2)
     w = OSPEC_ORDERED | ((then_weight & 3) << 4)
+    if weight_first:
+        w = OSPEC_ORDERED | OSPEC_WFIRST | (weight_first << 4)
+        if not parts:
+            return w
     p0 = parts[0]
     if int(p0.kind) == 2:  # high dword signed, low dword plain, one direction
         assert len(parts) == 1
@@ -171,7 +179,7 @@ def unmap_order_keys(spec: int, mapped: np.ndarray) -> np.ndarray:
     """The values behind 64-bit mapped keys of a row with this order spec word (mrk_order_unmap_key per entry, in numpy), in
     Matches.order_key's format: the raw int64 as u64, or raw0 << 32 | raw1; a sort spec: raw0 << 32.  A float's -0.0 reads +0.0."""
     mapped = np.asarray(mapped, dtype=np.uint64)
-    if not spec:
+    if not spec or (spec & OSPEC_WFIRST and not (spec >> 12) & 63):  # (a weight-first spec without parts)
         return np.zeros(len(mapped), np.uint64)
     r0 = _unmap_part(mapped >> np.uint64(32), (spec >> 8) & 0xFFFF).astype(np.uint64) << np.uint64(32)
     if not spec & OSPEC_WIDE:
@@ -181,8 +189,9 @@ def unmap_order_keys(spec: int, mapped: np.ndarray) -> np.ndarray:
 
 def merge_orows_np(orows_all: np.ndarray, k: int) -> np.ndarray:
     """What merge_orows_kernel computes, in numpy: orows_all uint64 [n_lists, nq, OROW_WORDS] -> [nq, OROW_WORDS].  An ordered query
-    orders by (64-bit mapped key, the weight as then_weight says, global docid asc), a relevance query (spec 0) by (weight, docid);
-    totals add up, the two flag bits are OR-ed through; answering lists whose spec words differ in any bit, and an ordered query some
+    orders by (64-bit mapped key, the weight as then_weight says, global docid asc), a relevance query (spec 0) by (weight, docid), a
+    weight-first one (OSPEC_WFIRST) by (the weight as bits 4-5 say, 64-bit mapped key, global docid asc) -- bits 4-5 neither 1 nor 2 is
+    no spec and counts as a mismatch; totals add up, the two flag bits are OR-ed through; answering lists whose spec words differ in any bit, and an ordered query some
     list carries with ROW_DECLINED (its spec word, 0 from a shard whose planner declined, is not compared), give ROW_DECLINED and no
     keys under the answering lists' spec word.  The CPU mirror the kernel is tested against; a gloo-only host's merge."""
     orows_all = np.ascontiguousarray(orows_all, dtype=np.uint64)
@@ -199,6 +208,9 @@ def merge_orows_np(orows_all: np.ndarray, k: int) -> np.ndarray:
         specs = rows[(tf & np.uint64(ROW_DECLINED)) == 0, OROW_SPEC]
         spec = int(specs[0]) if len(specs) else 0
         mismatch = bool((specs != np.uint64(spec)).any())
+        wfirst = bool(spec & OSPEC_WFIRST)
+        if wfirst and (spec >> 4) & 3 not in (1, 2):
+            mismatch = True
         if mismatch:
             flags |= ROW_DECLINED
         out[q, MRK_MAX_K + 1] = np.uint64((total & ~(ROW_RERUN | ROW_DECLINED)) | flags)
@@ -211,7 +223,10 @@ def merge_orows_np(orows_all: np.ndarray, k: int) -> np.ndarray:
         tie = (spec >> 4) & 3 if spec else 1
         wpart = w if tie == 1 else ~w if tie == 2 else np.zeros_like(w)
         nd = keys.astype(np.uint32)                    # ~docid: larger = smaller docid
-        order = np.lexsort((nd, wpart, mk))[::-1]       # descending by (mapped key as u64, weight part, ~docid)
+        if wfirst:
+            order = np.lexsort((nd, mk, wpart))[::-1]   # descending by (weight part, mapped key as u64, ~docid)
+        else:
+            order = np.lexsort((nd, wpart, mk))[::-1]   # descending by (mapped key as u64, weight part, ~docid)
         n = min(len(keys), k)
         order = order[:n]
         out[q, :n] = keys[order]
@@ -278,8 +293,11 @@ class ShardMerger:
     synchronous form for one batch."""
 
     def __init__(self, ctx, batch, n_queries: int, k: int, world: int, device: int, n_batches: int = 1, n_sets: int = 1,
-                 sorted_rows: bool = False, order_rows: bool = False):
-        """order_rows=True (excludes sorted_rows): ORDER rows (OROW_WORDS) through the order-row entry points -- queries ordered by
+                 sorted_rows: bool = False, order_rows: bool = False, weight_first: bool = False):
+        """weight_first=True (needs order_rows): the order rows carry weight-first queries (Order.weight_first) too -- the merger's
+        batch and every batch it attaches are told so (Batch.orows_weight_first); results() hands back their order_key (None without
+        parts).  Every rank of the exchange must run a library that knows OSPEC_WFIRST.
+        order_rows=True (excludes sorted_rows): ORDER rows (OROW_WORDS) through the order-row entry points -- queries ordered by
         a 64-bit key (Query.order) and sorted queries are merged across the shards in the sorter's order; results() hands back
         order_key for the former and sort_key for the latter, decoded from the spec word alone; relevance queries travel along.
         sorted_rows=True: WIDE rows (SROW_WORDS) through the wide entry points -- sorted queries (Query.sort) are merged
@@ -298,7 +316,9 @@ class ShardMerger:
 
         if sorted_rows and order_rows:
             raise ValueError("ShardMerger: sorted_rows and order_rows are mutually exclusive (a batch has one standing destination)")
-        self.sorted_rows, self.order_rows = bool(sorted_rows), bool(order_rows)
+        if weight_first and not order_rows:
+            raise ValueError("ShardMerger: weight_first needs order_rows (no other exchange row carries the weight's position)")
+        self.sorted_rows, self.order_rows, self.weight_first = bool(sorted_rows), bool(order_rows), bool(weight_first)
         self.row_words = rw = OROW_WORDS if order_rows else SROW_WORDS if sorted_rows else ROW_WORDS
         L = lib()
         # the narrow entry points or their wide / order-row twins: same arguments
@@ -322,6 +342,8 @@ class ShardMerger:
         self.partitioned = False
         self.first, self.count = 0, self.nq
         self.timing = {} if __import__("os").environ.get("MRK_DIST_TIMING") else None  # host ms per phase, summed
+        if self.weight_first and batch is not None:
+            batch.orows_weight_first(True)
 
     def attach(self, batches, set_index: int = 0):
         """Every later submit of batches[i] writes its rows into slice i of exchange buffer `set_index`."""
@@ -329,6 +351,8 @@ class ShardMerger:
         assert len(batches) * n <= self.nq
         for i, b in enumerate(batches):
             check(self._set_dst(b._h, self.rows[set_index][i * n:].data_ptr()))
+            if self.weight_first:
+                b.orows_weight_first(True)
         self.attached[set_index] = list(batches)
 
     def merge(self):
@@ -446,7 +470,8 @@ class ShardMerger:
         """Decoded (global docid, weight) lists per query + total_found.  A query some shard declined raises MrkError
         (allow_declined=True: its entry is None instead).  With sorted_rows the entries are Matches (rowid = global docid),
         a sorted query's with sort_key (the attribute's raw value per row), a relevance query's with sort_key None.  With
-        order_rows: a 64-bit order's entry carries order_key (Matches.order_key's format), a sort's sort_key."""
+        order_rows: a 64-bit order's entry carries order_key (Matches.order_key's format), a sort's sort_key, a weight-first order's
+        order_key (None without parts) and sort_key None."""
         rows = self.finish(set_index)
         out = []
         if self.partitioned and self.world > 1:
@@ -466,7 +491,9 @@ class ShardMerger:
 
                 spec = int(rows[q, OROW_SPEC])
                 vals = unmap_order_keys(spec, orow_mkeys(rows[q])[:cnt]) if spec else None
-                if spec & OSPEC_WIDE:
+                if spec & OSPEC_WFIRST:  # order_key = the parts behind the weight; none without parts
+                    out.append(Matches(docid, weight, tot, 0, None, vals if (spec >> 12) & 63 else None))
+                elif spec & OSPEC_WIDE:
                     out.append(Matches(docid, weight, tot, 0, None, vals))
                 else:
                     out.append(Matches(docid, weight, tot, 0, (vals >> np.uint64(32)).astype(np.uint32) if spec else None))

@@ -2,7 +2,8 @@
 """tools/order_merge_time.py [--root DIR] [--lists L] [--queries N] [--k K] [--reps R] [--out FILE] -- tools/sort_merge_time.py with
 the ORDER rows' legs: synthetic sorted rows of L shards x N queries (every list full, K entries), merged by mrk_topk_merge_rows
 (narrow rows), mrk_topk_merge_srows (wide rows: all-relevance, all-sorted) and mrk_topk_merge_orows (order rows: all-relevance,
-all-ordered by a two-part 64-bit key whose both dwords decide).  Per leg: warm-up launches, then R synchronous calls timed one by
+all-ordered by a two-part 64-bit key whose both dwords decide, all weight-first -- the weight descending in front of the same
+two-part key, OSPEC_WFIRST: the "all ordered" leg's lists in the other order, one more dword compare per exchange).  Per leg: warm-up launches, then R synchronous calls timed one by
 one (wall clock around the call, which launches the kernel and waits for it) -> median, min, max in ms, the ratio to the narrow
 merge and the ratio of bytes read.  The wide and order legs' results are checked against dist.merge_srows_np / merge_orows_np in
 the same run.  --root DIR imports the package from another checkout (the commit before, built side by side): the legs that
@@ -36,7 +37,7 @@ ap.add_argument("--out", default="")
 ap.add_argument("--parent", default="", help="this script's result file of the commit before: the guard of tools/timing_guard.py over the shared legs")
 args = ap.parse_args()
 Lh, N, K, K1 = args.lists, args.queries, args.k, 1024
-has_wide, has_order = hasattr(dist, "SROW_WORDS"), hasattr(dist, "OROW_WORDS")
+has_wide, has_order, has_wfirst = hasattr(dist, "SROW_WORDS"), hasattr(dist, "OROW_WORDS"), hasattr(dist, "OSPEC_WFIRST")
 hip = C.CDLL("libamdhip64.so")
 ctx = m.Context(0)
 lib = _lib.lib()
@@ -52,17 +53,17 @@ def dmalloc(n):
 def rows_of(words, kind=None):
     """[Lh][N][words] rows: K entries per list, in the merge's order; docids are distinct over the lists of a query.  kind: None =
     relevance rows (any width); "sorted" = wide rows over a 4-valued 32-bit key; "ordered" = order rows over a two-part 64-bit key, a
-    4-valued high dword | a 16-valued low one, so that both dwords decide."""
+    4-valued high dword | a 16-valued low one, so that both dwords decide; "wfirst" = the same keys behind the weight, descending."""
     rows = np.zeros((Lh, N, words), np.uint64)
     for q in range(N):
         docid = rng.permutation(Lh * K).astype(np.uint64).reshape(Lh, K) + np.uint64(q)
         weight = rng.integers(1000, 1400, (Lh, K)).astype(np.uint64)  # few distinct weights: ties down to the docid, as BM25 gives
         keys = ((weight ^ np.uint64(0x80000000)) << np.uint64(32)) | (~docid & np.uint64(0xFFFFFFFF))
         mk = rng.integers(0, 4, (Lh, K)).astype(np.uint64) if kind else np.zeros((Lh, K), np.uint64)
-        if kind == "ordered":
+        if kind in ("ordered", "wfirst"):
             mk = (mk << np.uint64(32)) | (~rng.integers(0, 16, (Lh, K)).astype(np.uint64) & np.uint64(0xFFFFFFFF))
         for l in range(Lh):
-            order = np.lexsort((keys[l], mk[l]))[::-1]
+            order = np.lexsort((keys[l].astype(np.uint32), mk[l], keys[l] >> np.uint64(32)) if kind == "wfirst" else (keys[l], mk[l]))[::-1]
             rows[l, q, :K] = keys[l][order]
             rows[l, q, K1] = K
             rows[l, q, K1 + 1] = 100_000 + l
@@ -71,9 +72,10 @@ def rows_of(words, kind=None):
                 plane[:K] = mk[l][order].astype(np.uint32)
                 rows[l, q, dist.SROW_MKEYS:dist.SROW_SPEC] = plane.view("<u8")
                 rows[l, q, dist.SROW_SPEC] = dist.sort_spec_word(0, True, 1, 2)
-            elif kind == "ordered":
+            elif kind in ("ordered", "wfirst"):
+                parts = [m.OrderPart(0, 2, desc=True), m.OrderPart(32, 4, desc=False)]
                 rows[l, q, dist.OROW_MKEYS:dist.OROW_MKEYS + K] = mk[l][order]
-                rows[l, q, dist.OROW_SPEC] = dist.order_spec_word([m.OrderPart(0, 2, desc=True), m.OrderPart(32, 4, desc=False)], 1)
+                rows[l, q, dist.OROW_SPEC] = dist.order_spec_word(parts, 1) if kind == "ordered" else dist.order_spec_word(parts, 0, weight_first=1)
     return rows
 
 
@@ -106,6 +108,8 @@ if has_wide:
 if has_order:
     result["legs"]["order relevance"] = leg("mrk_topk_merge_orows, all relevance", lib.mrk_topk_merge_orows, rows_of(dist.OROW_WORDS), dist.merge_orows_np)
     result["legs"]["order ordered"] = leg("mrk_topk_merge_orows, all ordered", lib.mrk_topk_merge_orows, rows_of(dist.OROW_WORDS, "ordered"), dist.merge_orows_np)
+if has_wfirst:
+    result["legs"]["order weight-first"] = leg("mrk_topk_merge_orows, all weight-first", lib.mrk_topk_merge_orows, rows_of(dist.OROW_WORDS, "wfirst"), dist.merge_orows_np)
 for k_, v in result["legs"].items():
     if k_ != "narrow":
         v["ratio_to_narrow"] = v["ms_median"] / result["legs"]["narrow"]["ms_median"]
