@@ -454,8 +454,8 @@ struct SelectArgs {
   uint64_t* h_total;       // pinned host [n_queries] or NULL
   uint32_t* h_flags;       // pinned host [n_queries] or NULL
   uint32_t* h_cand_n;      // pinned host [n_queries] or NULL
-  uint64_t* rows_dst;      // device [n_queries][ROW_WORDS] or NULL: the exchange rows (keys zero-padded | count | total_found or MRK_ROW_RERUN)
-  const uint32_t* declined; // unused by the kernel (declined queries' rows are rewritten by pack_xrows_kernel)
+  uint64_t* rows_dst;      // device [n_queries][ROW_WORDS] or NULL: the exchange rows (keys zero-padded | count | total_found or MRK_ROW_RERUN);
+                           // the rows of queries the planner declined are rewritten by pack_xrows_kernel
 };
 
 // One launch instead of two copies and a memset in front of every scan: query and work-item descriptors are read from the
@@ -525,8 +525,8 @@ struct PackXRowsArgs {
   const uint64_t* total;    // [n]
   uint64_t* rows;           // [n][the format's row words]
   const uint32_t* flags;    // [n] QF_* of the scan (NULL = none): a flagged query's row is poisoned, not trusted
-  const uint32_t* declined; // [n] (NULL = none declined) 1: the planner declined the query on this segment; 2: declined for NARROW rows only
-                            // (a sorted query of a batch with a narrow standing destination) -- a wide row answers it
+  const uint32_t* declined; // [n] (NULL = no query declined in any format) the query's decline mask: bit RowKind k set = its row of format k
+                            // leaves empty with MRK_ROW_DECLINED (row_decline_mask, mrk_host_int.h; the kernel tests its own format's bit)
   uint32_t n;
   uint32_t skip_sorted;     // != 0: the sorted and ordered queries' rows are already written (sort_select_kernel with a standing destination)
 };

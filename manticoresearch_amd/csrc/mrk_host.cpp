@@ -109,11 +109,23 @@ struct PinBuf {
 // per-query scan state in front of the histograms: total u64 | tau u64 | flags u32 | cand_n, tau_bin: QSTRIDE dwords each
 constexpr size_t STATE_BYTES = 8 + 8 + 4 + 2 * 4 * mrk::QSTRIDE;
 
+// a batch's standing destination (mrk_batch_set_rows_dst / _srows_dst / _orows_dst): device rows of ONE format; p == nullptr = none
+struct RowDst {
+  uint64_t* p = nullptr;
+  RowKind kind = ROWS_NARROW;
+};
+
+// the shape of a packed launch: which instances of the scan and rank kernels it takes.  Computed once per submit, kept for the rerun
+struct LaunchShape {
+  uint32_t max_terms = 1;
+  bool prox = false, tree = false, ext = false; // hit rankers; trees; position modifiers, BEFORE, filters, a cutoff row, a sort
+  bool sort = false;                            // the batch holds sorted queries (mrk_query.sort / .order)
+  bool nearn = false;                           // ... a NEAR over 3+ operands at the root (the generic evaluator's probe launch)
+};
+
 struct mrk_batch {
   mrk_ctx* ctx = nullptr;
-  uint64_t* rows_dst = nullptr; // mrk_batch_set_rows_dst
-  uint64_t* srows_dst = nullptr; // mrk_batch_set_srows_dst (wide rows; excludes rows_dst)
-  uint64_t* orows_dst = nullptr; // mrk_batch_set_orows_dst (order rows; excludes the other two)
+  RowDst dst;                   // at most one stands (batch_set_dst)
   bool orows_wf = false;        // mrk_batch_orows_weight_first: order rows carry weight-first queries, from the next submit on ...
   bool orows_wf_run = false;    // ... and what the last submit ran with: all its rows follow this
   bool host_copied = true;      // per-query keys / counts / totals of the last submit are in pinned host memory
@@ -156,14 +168,15 @@ struct mrk_batch {
   DevBuf<uint64_t> d_out_mkeys64; // [max_queries][KCAP] the whole 64-bit mapped keys (order rows): reserved with d_scand by the first batch that holds a 64-bit order or has a standing order-row destination
   DevBuf<uint64_t> d_scand;  // 16-byte candidates of the sorted queries (two words each); reserved by the first batch that holds one
   PinBuf<uint32_t> h_flags;
-  // per query: != 0 when the planner declined it on the last submit's segment; travels in the exchange rows
-  // ([max_queries, 2 max_queries): the words as ORDER rows read them -- a 64-bit order is no decline there; uploaded when the
-  // submit holds one: decl_order)
+  // per query of the last submit: its decline mask (row_decline_mask), one bit per row format in which the query's exchange row
+  // leaves empty with MRK_ROW_DECLINED
   PinBuf<uint32_t> h_decl;
   DevBuf<uint32_t> d_decl;
-  bool decl_order = false;
-  bool decl_dirty = false; // d_decl holds non-zero words of an earlier submit
-  bool any_declined = false;
+  bool any_declined = false; // some mask of the last submit is non-zero (none: the row kernels get NULL for the masks)
+  // d_decl holds non-zero masks of an earlier submit.  d_decl always equals the last submit's masks; a submit uploads them when it
+  // has a non-zero one or when this is set.  What it saves: a decline-free submit that follows a decline-free one -- every submit of
+  // the usual run -- queues no copy for the masks
+  bool decl_dirty = false;
   // HBM match queues of the hit-ranked queries (scan kernels -> rank_kernel): [0] plain trees, [1] PHRASE & co
   DevBuf<uint32_t> d_mq_data[3], d_mq_hdr[3];
   DevBuf<uint32_t> d_mq_count; // [3][MQ_SHARDS]
@@ -184,21 +197,16 @@ struct mrk_batch {
   struct SortLoc {
     uint32_t item = 0, shift = 0, bits = 0, order = 0;
     mrk::OrderPart p1{0, 0, 0, 0};
-    // the query fits no NARROW or WIDE exchange row: a 64-bit key, or the weight in front of the parts (MRK_ORDER_WEIGHT_FIRST_*) ...
-    bool no_row() const { return order == mrk::SORT_ON_ORDER || order == mrk::SORT_ON_WEIGHT; }
-    // ... and the latter no ORDER row either, unless the batch asked for it (mrk_batch_orows_weight_first: OSPEC_WFIRST of the spec word)
-    bool no_orow(bool wfirst_rows) const { return order == mrk::SORT_ON_WEIGHT && !wfirst_rows; }
   };
   std::vector<SortLoc> sort_loc;
   std::vector<uint32_t> sort_key;
   std::vector<uint64_t> order_key;
-  bool last_sort = false;
   bool decoded = false;
   bool packed_run = false;
   // what a rerun of an overflowed query needs (mrk_batch_wait)
   mrk_segment* last_seg = nullptr;
-  uint32_t n_pass = 0, last_max_terms = 1;
-  bool last_prox = false, last_tree = false, last_ext = false;
+  uint32_t n_pass = 0;
+  LaunchShape shape;
   mrk_batch* retry = nullptr;
   mrk_batch* probe = nullptr; // cutoff_probe's launches
   hipEvent_t ev_scan0 = nullptr, ev_scan1 = nullptr, ev_merge1 = nullptr;
@@ -930,7 +938,7 @@ static int mrk_batch_create_impl(mrk_ctx* ctx, uint32_t max_queries, mrk_batch**
       (rc = b->h_total.reserve(nq)) || (rc = b->d_queries.reserve(nq)) ||
       (rc = b->d_state.reserve(nq * (STATE_BYTES + (size_t)NBINS * 4))) || (rc = b->d_list_first.reserve(nq)) || (rc = b->d_list_n.reserve(nq)) ||
       (rc = b->d_kq.reserve(nq)) || (rc = b->d_out_keys.reserve(nq * KCAP)) || (rc = b->d_out_cnt.reserve(nq)) ||
-      (rc = b->h_flags.reserve(nq)) || (rc = b->h_cand_n.reserve(nq)) || (rc = b->h_decl.reserve(2 * (size_t)nq)) || (rc = b->d_decl.reserve(2 * (size_t)nq)) || (rc = b->d_mq_count.reserve(3 * mrk::MQ_SHARDS))) {
+      (rc = b->h_flags.reserve(nq)) || (rc = b->h_cand_n.reserve(nq)) || (rc = b->h_decl.reserve(nq)) || (rc = b->d_decl.reserve(nq)) || (rc = b->d_mq_count.reserve(3 * mrk::MQ_SHARDS))) {
     mrk_batch_destroy_impl(b);
     return rc;
   }
@@ -959,8 +967,8 @@ static int mrk_batch_create_impl(mrk_ctx* ctx, uint32_t max_queries, mrk_batch**
   return MRK_OK;
 }
 
-// size the batch's match queues for `chunks[q]` chunks (0 = queue unused) and point the scan arguments at them
-static int bind_match_queues(mrk_batch* b, const uint64_t chunks[3], mrk::ScanArgs& sa) {
+// size the batch's match queues for `chunks[q]` chunks (0 = queue unused), point the scan arguments at them and clear their counters on st
+static int bind_match_queues(mrk_batch* b, const uint64_t chunks[3], mrk::ScanArgs& sa, hipStream_t st) {
   for (int i = 0; i < 3; ++i) {
     // (a segment with 9-32 fields: queues 0 / 1 carry the doc's whole field mask in one more plane)
     const int planes = i == 2 ? mrk::MQ_GEN_PLANES : mrk::MQ_PLANES + (sa.seg.pk_fmask ? 1 : 0);
@@ -975,6 +983,7 @@ static int bind_match_queues(mrk_batch* b, const uint64_t chunks[3], mrk::ScanAr
     sa.mq[i].hdr = b->d_mq_hdr[i].p;
     sa.mq[i].cap = (uint32_t)per;
   }
+  if (chunks[0] || chunks[1] || chunks[2]) HIP_TRY(hipMemsetAsync(b->d_mq_count.p, 0, 3 * mrk::MQ_SHARDS * 4, st));
   return MRK_OK;
 }
 
@@ -1068,12 +1077,27 @@ static void bind_scan(const mrk_batch* b, const mrk_segment* seg, mrk::ScanArgs&
   sa.cand = b->d_cand.p;
 }
 
+// ... and what its sorted queries add, for a scan of n queries: their candidate arena and, next to hit rankers, the histogram of the
+// attribute bin test in front of the hit pass (scan_pk_kernel, pre_prune), cleared on st.  sa.scand set = every block-scan and rank
+// launch takes the instance that carries the sort
+static int bind_sorted(mrk_batch* b, uint32_t n, bool prox, mrk::ScanArgs& sa, hipStream_t st) {
+  sa.scand = b->d_scand.p;
+  if (!prox) return MRK_OK;
+  const size_t words = (size_t)n * (NBINS + mrk::QSTRIDE);
+  int rc;
+  if ((rc = b->d_shist.reserve(words))) return rc;
+  HIP_TRY(hipMemsetAsync(b->d_shist.p, 0, words * 4, st));
+  sa.s_hist = b->d_shist.p;
+  sa.s_tau = b->d_shist.p + (size_t)n * NBINS;
+  return MRK_OK;
+}
+
 // Whether a batch's block-scan items take the lean instance (mrk_scan_p2.hip, ctx key "pair_scan"): the launch that would run
 // scan_pk_kernel<false, false> -- no hit ranker, tree, position modifier, filter or sort anywhere in the batch -- over a segment of
 // <= 8 fields, at most two keywords per query, and a segment packed with bitmaps on (without them a dense keyword is block-probed, and
 // the generic instance's direct map serves that better than a binary search)
-static bool lean_scan_ok(const mrk_ctx* c, const mrk_segment* seg, bool sorted, uint32_t max_terms, bool prox, bool tree, bool ext) {
-  return c->pair_scan != 0 && !prox && !tree && !ext && !sorted && !seg->dev.pk_fmask && max_terms <= 2 && seg->bitmaps_on && c->bitmap_inv != 0;
+static bool lean_scan_ok(const mrk_ctx* c, const mrk_segment* seg, const LaunchShape& s) {
+  return c->pair_scan != 0 && !s.prox && !s.tree && !s.ext && !s.sort && !seg->dev.pk_fmask && s.max_terms <= 2 && seg->bitmaps_on && c->bitmap_inv != 0;
 }
 
 // The packed path's kernels over a laid-out item array (sa.items: block-scan items, then kinds 0, 1, 2): block scan, tree
@@ -1081,14 +1105,14 @@ static bool lean_scan_ok(const mrk_ctx* c, const mrk_segment* seg, bool sorted, 
 // (bm_groups: its group records on the device, or null)
 // (sa.scand set = the batch holds sorted queries: every block-scan and rank launch takes the instance that carries the sort)
 // (lean: the block-scan items go to the lean two-keyword instance -- lean_scan_ok)
-static int launch_packed(mrk::ScanArgs sa, size_t n_items_pk, const size_t n_items_kind[3], const uint64_t mq_chunks[3], uint32_t max_terms, bool prox,
-                         bool tree, bool ext, bool nearn, const BmGroup* bm_groups, bool lean, hipStream_t st) {
+static int launch_packed(mrk::ScanArgs sa, size_t n_items_pk, const size_t n_items_kind[3], const uint64_t mq_chunks[3], const LaunchShape& s,
+                         const BmGroup* bm_groups, bool lean, hipStream_t st) {
   const DevItem* items = sa.items;
   sa.n_items = (uint32_t)n_items_pk;
   if (lean)
     launch_scan_p2(sa, st);
   else
-    launch_scan_pk(sa, max_terms, prox, tree, ext, st);
+    launch_scan_pk(sa, s.max_terms, s.prox, s.tree, s.ext, st);
   if (n_items_kind[1]) { // before the rank kernels: it feeds the match queue too
     ScanArgs sb = sa;
     sb.items = items + n_items_pk + n_items_kind[0];
@@ -1099,13 +1123,13 @@ static int launch_packed(mrk::ScanArgs sa, size_t n_items_pk, const size_t n_ite
     ScanArgs sg = sa;
     sg.items = items + n_items_pk + n_items_kind[0] + n_items_kind[1];
     sg.n_items = (uint32_t)n_items_kind[2];
-    launch_scan_pk(sg, max_terms, true, true, true, st, true);
+    launch_scan_pk(sg, s.max_terms, true, true, true, st, true);
   }
   // the queued matches of hit-ranked queries: hit pass + state rankers (mrk_rank.hip), behind the scans on the same stream
   if (mq_chunks[0]) launch_rank(sa, 0, st);
   if (mq_chunks[1]) launch_rank(sa, 1, st);
   int rc;
-  if (mq_chunks[2] && (rc = launch_gen_rank(sa, nearn, st))) return rc;
+  if (mq_chunks[2] && (rc = launch_gen_rank(sa, s.nearn, st))) return rc;
   if (n_items_kind[0]) {
     ScanArgs sb = sa;
     sb.items = items + n_items_pk;
@@ -1116,35 +1140,55 @@ static int launch_packed(mrk::ScanArgs sa, size_t n_items_pk, const size_t n_ite
   return MRK_OK;
 }
 
-// the top-K selection of n_queries over a batch's candidate arena of cand_total slots (d_sel reserved for them); the sub-bin
-// geometry: the segment's largest global rowid and the bits its rowid range needs
-static void bind_select(const mrk_batch* b, const mrk_segment* seg, uint32_t n_queries, uint64_t cand_total, mrk::SelectArgs& se) {
-  se.queries = b->d_queries.p;
-  se.q_hist = b->d_q_hist.p;
-  se.q_cand_n = b->d_q_cand_n.p;
-  se.cand = b->d_cand.p;
-  se.n_queries = n_queries;
-  se.rowid_base = seg->dev.rowid_base;
-  se.out_keys = b->d_out_keys.p;
-  se.out_cnt = b->d_out_cnt.p;
-  se.sel_tau = b->d_sel.p;
-  se.sel_nslice = b->d_sel.p + n_queries;
-  se.slice_cnt = b->d_sel.p + 2 * (size_t)n_queries;
-  se.max_slices = (uint32_t)std::min<uint64_t>(mrk::sel_slice_slots(cand_total, n_queries), 1u << 30);
+// The two-step selection of a scan's n queries over the batch's candidate arena of cand_total slots (d_sel reserved for them), on st:
+// the relevance top-K, then -- `sorted` -- the sorted queries' own behind it (the first saw an empty list for them and wrote a count
+// of 0).  se: the caller's pinned-host result pointers; the rest is bound here.  dst: a standing destination.  Its rows the kernels
+// write themselves: every query's narrow row (the relevance selection's sort pass), the sorted queries' wide or order rows (theirs; a
+// weight-first query's order row with orows_wf only).  The other rows, and those of queries the planner declined, are pack_xrows_kernel's.
+static void launch_selection(const mrk_batch* b, const mrk_segment* seg, uint32_t n, uint64_t cand_total, bool sorted, const RowDst& dst, bool orows_wf,
+                             mrk::SelectArgs se, hipStream_t st) {
+  se.queries = b->d_queries.p, se.q_hist = b->d_q_hist.p, se.q_cand_n = b->d_q_cand_n.p, se.cand = b->d_cand.p, se.n_queries = n;
+  se.out_keys = b->d_out_keys.p, se.out_cnt = b->d_out_cnt.p;
+  se.sel_tau = b->d_sel.p, se.sel_nslice = b->d_sel.p + n, se.slice_cnt = b->d_sel.p + 2 * (size_t)n;
+  se.max_slices = (uint32_t)std::min<uint64_t>(mrk::sel_slice_slots(cand_total, n), 1u << 30);
+  // the sub-bin geometry: the segment's largest global rowid and the bits its rowid range needs
   const uint64_t docs = std::max<uint64_t>(seg->total_docs, 1);
   uint32_t bits = 1;
   while (bits < 32 && ((docs - 1) >> bits)) ++bits;
-  se.rowid_bits = bits;
-  se.rowid_hi = (uint32_t)(seg->dev.rowid_base + docs - 1);
+  se.rowid_base = seg->dev.rowid_base, se.rowid_bits = bits, se.rowid_hi = (uint32_t)(seg->dev.rowid_base + docs - 1);
+  se.q_total = b->d_q_total.p, se.q_flags = b->d_q_flags.p;
+  se.rows_dst = dst.kind == ROWS_NARROW ? dst.p : nullptr;
+  launch_select(se, st);
+  if (!sorted) return;
+  mrk::SortSelArgs ss{};
+  ss.queries = b->d_queries.p, ss.q_hist = b->d_q_hist.p, ss.q_cand_n = b->d_q_cand_n.p, ss.scand = b->d_scand.p, ss.n_queries = n;
+  ss.out_keys = b->d_out_keys.p, ss.out_cnt = b->d_out_cnt.p, ss.out_mkeys = b->d_out_mkeys.p, ss.out_mkeys64 = b->d_out_mkeys64.p;
+  ss.h_keys = se.h_keys, ss.h_cnt = se.h_cnt;
+  ss.q_total = se.q_total, ss.q_flags = se.q_flags;
+  ss.srows_dst = dst.kind == ROWS_WIDE ? dst.p : nullptr, ss.orows_dst = dst.kind == ROWS_ORDER ? dst.p : nullptr, ss.orows_wfirst = orows_wf ? 1u : 0u;
+  mrk::launch_sort_select(ss, st);
 }
 
-// what pack_xrows_kernel reads of the batch's last submit for rows of `kind` (the caller sets rows, flags, n, skip_sorted)
-static void bind_pack_rows(mrk_batch* b, PackXRowsArgs& pa, RowKind kind) {
+// Never hand back a silently truncated result: what a query's scan flags make of its status.  A run-time decline (QF_FSM, QF_ARENA)
+// is MRK_E_UNSUPPORTED; QF_OVERFLOW -- more matches tied at the pruning threshold than the candidate list holds -- only when the run
+// was the rerun already (the first time mrk_batch_wait runs the query again, alone)
+static int flags_status(uint32_t flags, uint32_t qi, bool was_rerun) {
+  if (flags & QF_FSM) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: a doc held more live phrase states than the device path keeps", qi);
+  if (flags & QF_ARENA) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the generic evaluator ran out of hit-list memory (ctx tunable gen_spill_mb)", qi);
+  if ((flags & QF_OVERFLOW) && was_rerun) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: candidate list overflowed again on the rerun", qi);
+  return MRK_OK;
+}
+
+// The n queries of the batch's last submit as exchange rows of `kind` at rows, on st (pack_xrows_kernel).  packed: the packed path
+// ran them -- its scan flags poison a row; skip_sorted: sort_select_kernel wrote the sorted queries' rows already
+static void launch_pack_rows(const mrk_batch* b, RowKind kind, uint64_t* rows, uint32_t n, bool packed, bool skip_sorted, hipStream_t st) {
+  PackXRowsArgs pa{};
   pa.keys = b->d_out_keys.p, pa.cnt = b->d_out_cnt.p, pa.total = b->d_q_total.p;
   if (kind != ROWS_NARROW) pa.queries = b->d_queries.p, pa.mkeys = b->d_out_mkeys.p;
   if (kind == ROWS_ORDER) pa.mkeys64 = b->d_out_mkeys64.p;
-  // (a 64-bit order is word 1 -- declined -- for narrow and wide rows: the submit that held one uploaded the order rows' own words)
-  pa.declined = !b->any_declined ? nullptr : kind == ROWS_ORDER && b->decl_order ? b->d_decl.p + b->max_queries : b->d_decl.p;
+  pa.declined = b->any_declined ? b->d_decl.p : nullptr;
+  pa.rows = rows, pa.n = n, pa.flags = packed ? b->d_q_flags.p : nullptr, pa.skip_sorted = skip_sorted ? 1u : 0u;
+  launch_pack_xrows(kind, pa, st);
 }
 
 static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n) {
@@ -1203,7 +1247,6 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     b->h_list_n.p[i] = b->h_queries.p[i].n_items;
     b->h_kq.p[i] = b->h_queries.p[i].k ? b->h_queries.p[i].k : 1;
   }
-  const bool any_prox = plan.any_prox, any_tree = plan.any_tree;
   const std::vector<DevQuery>& extra = plan.extra; // passes beyond the first of tree queries; pass index = n + position
   b->gen_progs.swap(plan.gen_progs); // (copied to the device below: they live until the next submit)
   // ---- launch layout (mrk_plan.cpp): the items in launch order, the scan_bm groups, the match queues' sizes
@@ -1214,6 +1257,8 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   const float plan_ms = std::chrono::duration<float, std::milli>(lay.t_block_items - t_submit0).count(); // (up to the block-scan section in order)
   const size_t n_items = lay.items.size(), n_items_pk = lay.n_items_pk;
   const uint64_t cand_total = plan.cand_total;
+  LaunchShape shape{max_terms, plan.any_prox, plan.any_tree, any_ext, use_packed && plan.sort_total != 0, false};
+  for (uint32_t i = 0; i < n && !b->gen_progs.empty(); ++i) shape.nearn = shape.nearn || (b->h_queries.p[i].tree_flags & mrk::TF_GEN_NEARN) != 0;
   memcpy(b->stats.n_bm_groups, lay.n_bm_groups, sizeof lay.n_bm_groups);
   b->stats.algo_bytes = plan.algo_bytes;
   b->stats.dev_bytes = plan.dev_bytes;
@@ -1248,13 +1293,12 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   if ((rc = b->h_queries.reserve_keep(n_pass, n)) || (rc = b->d_queries.reserve(n_pass))) return rc;
   if (!extra.empty()) memcpy(b->h_queries.p + n, extra.data(), extra.size() * sizeof(DevQuery));
   if (use_packed && ((rc = b->d_cand.reserve(cand_total + 64)) || (rc = b->d_sel.reserve(2 * (size_t)n + mrk::sel_slice_slots(cand_total, n))))) return rc;
-  const bool any_sort = use_packed && plan.sort_total != 0;
-  if (any_sort && ((rc = b->d_scand.reserve(2 * plan.sort_total + 64)) || (rc = b->d_out_mkeys.reserve((size_t)b->max_queries * KCAP)))) return rc;
+  if (shape.sort && ((rc = b->d_scand.reserve(2 * plan.sort_total + 64)) || (rc = b->d_out_mkeys.reserve((size_t)b->max_queries * KCAP)))) return rc;
   bool any_order = false; // a 64-bit key, or a weight-first query that leaves in order rows: the order rows' plane, from here on
   b->orows_wf_run = b->orows_wf;
-  for (uint32_t i = 0; i < n && any_sort; ++i)
+  for (uint32_t i = 0; i < n && shape.sort; ++i)
     any_order = any_order || b->sort_loc[i].order == mrk::SORT_ON_ORDER || (b->orows_wf_run && b->sort_loc[i].order == mrk::SORT_ON_WEIGHT);
-  if (any_sort && (any_order || b->orows_dst) && (rc = b->d_out_mkeys64.reserve((size_t)b->max_queries * KCAP))) return rc;
+  if (shape.sort && (any_order || (b->dst.p && b->dst.kind == ROWS_ORDER)) && (rc = b->d_out_mkeys64.reserve((size_t)b->max_queries * KCAP))) return rc;
 
   static const bool phase_timing = getenv("MRK_SUBMIT_TIMING") != nullptr;
   auto lap = [&](const char* what) {
@@ -1284,16 +1328,9 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   ScanArgs sa{};
   bind_scan(b, seg, sa);
   sa.n_items = (uint32_t)n_items; // (the VLB path's one launch; launch_packed sets its sections')
-  sa.scand = any_sort ? b->d_scand.p : nullptr;
-  if (any_sort && any_prox) { // the attribute bin test in front of the hit pass (scan_pk_kernel, pre_prune)
-    const size_t words = (size_t)n * (NBINS + mrk::QSTRIDE);
-    if ((rc = b->d_shist.reserve(words))) return rc;
-    HIP_TRY(hipMemsetAsync(b->d_shist.p, 0, words * 4, st));
-    sa.s_hist = b->d_shist.p;
-    sa.s_tau = b->d_shist.p + (size_t)n * NBINS;
-  }
-  bool any_nearn = false;
-  if (use_packed && any_prox && b->ctx->prox_prune) { // pruning in front of the hit pass (mrk_kprune.h, prox_bounds)
+  if (shape.sort && (rc = bind_sorted(b, n, shape.prox, sa, st))) return rc;
+  // (submit only: the weight bounds' buffers -- a rerun's list holds every doc its drivers can deliver, it runs without this pruning)
+  if (use_packed && shape.prox && b->ctx->prox_prune) { // pruning in front of the hit pass (mrk_kprune.h, prox_bounds)
     const size_t words = (size_t)n * (2 * NBINS + mrk::QSTRIDE);
     if ((rc = b->d_lb.reserve(words))) return rc;
     HIP_TRY(hipMemsetAsync(b->d_lb.p, 0, words * 4, st));
@@ -1302,23 +1339,19 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     sa.q_tau_lb = b->d_lb.p + (size_t)n * 2 * NBINS;
   }
   const uint64_t* mq_chunks = lay.mq_chunks;
-  if ((rc = bind_match_queues(b, mq_chunks, sa))) return rc;
-  if (mq_chunks[0] || mq_chunks[1] || mq_chunks[2]) HIP_TRY(hipMemsetAsync(b->d_mq_count.p, 0, 3 * mrk::MQ_SHARDS * 4, st));
+  if ((rc = bind_match_queues(b, mq_chunks, sa, st))) return rc;
   if (!b->gen_progs.empty()) {
     if ((rc = b->d_gen_progs.reserve(b->gen_progs.size()))) return rc;
     HIP_TRY(hipMemcpyAsync(b->d_gen_progs.p, b->gen_progs.data(), b->gen_progs.size() * sizeof(mrk::GenProg), hipMemcpyHostToDevice, st)); // (pageable: the vector lives until the next submit)
-    for (uint32_t i = 0; i < n; ++i) any_nearn = any_nearn || (b->h_queries.p[i].tree_flags & mrk::TF_GEN_NEARN) != 0;
-    if ((rc = bind_gen(b, b, sa, st, n, any_nearn))) return rc;
+    if ((rc = bind_gen(b, b, sa, st, n, shape.nearn))) return rc;
   }
   lap("h2d+memset");
   HIP_TRY(hipEventRecord(b->ev_scan0, st));
   b->stats.pk_lean = 0;
   if (use_packed) {
-    const bool lean = lean_scan_ok(c, seg, any_sort, max_terms, any_prox, any_tree, any_ext);
+    const bool lean = lean_scan_ok(c, seg, shape);
     b->stats.pk_lean = lean && n_items_pk ? 1u : 0u;
-    if ((rc = launch_packed(sa, n_items_pk, lay.n_items_kind, mq_chunks, max_terms, any_prox, any_tree, any_ext, any_nearn,
-                            n_group_slots ? (const BmGroup*)(b->d_items.p + n_items) : nullptr, lean, st)))
-      return rc;
+    if ((rc = launch_packed(sa, n_items_pk, lay.n_items_kind, mq_chunks, shape, n_group_slots ? (const BmGroup*)(b->d_items.p + n_items) : nullptr, lean, st))) return rc;
   } else
     launch_scan(sa, st);
   HIP_TRY(hipEventRecord(b->ev_scan1, st));
@@ -1326,30 +1359,14 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   HIP_TRY(hipStreamWaitEvent(st2, b->ev_scan1, 0));
 
   if (use_packed) {
-    SelectArgs se{};
-    bind_select(b, seg, n, cand_total, se);
+    // (submit only: the selection runs on the batch's own stream, behind the scan's event, and hands the results to the host itself)
     // results straight into the batch's pinned host memory (a batch with a standing rows destination feeds a shard merge:
     // its own lists stay on the device unless mrk_batch_result asks for them)
-    se.q_total = b->d_q_total.p;
-    se.q_flags = b->d_q_flags.p;
+    SelectArgs se{};
     se.h_flags = b->h_flags.p;
     se.h_cand_n = b->h_cand_n.p;
-    const bool standing = b->rows_dst || b->srows_dst || b->orows_dst;
-    if (!standing) se.h_keys = b->h_keys.p, se.h_cnt = b->h_cnt.p, se.h_total = b->h_total.p;
-    // a standing rows destination (shard exchange): the sort pass writes the exchange rows itself (narrow rows; the wide
-    // rows of relevance queries are packed behind the selection, below)
-    se.rows_dst = b->rows_dst;
-    se.declined = nullptr;
-    launch_select(se, st2);
-    if (any_sort) { // the sorted queries' own selection, behind the relevance one (which wrote a count of 0 for them)
-      mrk::SortSelArgs ss{};
-      ss.queries = b->d_queries.p, ss.q_hist = b->d_q_hist.p, ss.q_cand_n = b->d_q_cand_n.p, ss.scand = b->d_scand.p, ss.n_queries = n;
-      ss.out_keys = b->d_out_keys.p, ss.out_cnt = b->d_out_cnt.p, ss.out_mkeys = b->d_out_mkeys.p;
-      if (!standing) ss.h_keys = b->h_keys.p, ss.h_cnt = b->h_cnt.p;
-      ss.srows_dst = b->srows_dst, ss.q_total = b->d_q_total.p, ss.q_flags = b->d_q_flags.p; // a standing wide destination: the sorted queries' rows leave here
-      ss.out_mkeys64 = b->d_out_mkeys64.p, ss.orows_dst = b->orows_dst, ss.orows_wfirst = b->orows_wf_run ? 1u : 0u;
-      mrk::launch_sort_select(ss, st2);
-    }
+    if (!b->dst.p) se.h_keys = b->h_keys.p, se.h_cnt = b->h_cnt.p, se.h_total = b->h_total.p;
+    launch_selection(b, seg, n, cand_total, shape.sort, b->dst, b->orows_wf_run, se, st2);
   } else {
     MergeArgs ma{};
     ma.in_keys = b->d_item_cand.p;
@@ -1366,50 +1383,26 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   }
   HIP_TRY(hipEventRecord(b->ev_merge1, st2));
   {
-    bool any = false;
-    // (a sorted query's NARROW row is no answer to a merge by (weight, docid): in that exchange it counts as declined -- word 2,
-    // which the wide rows, whose merge compares the mapped keys, do not take for a decline)
-    // (a query ordered by a 64-bit key, mrk_query.order, fits neither of these two row formats: word 1; ORDER rows read words of their own, below)
-    // (whether or not a narrow destination stands: mrk_batch_export_rows writes the same rows after the wait)
-    for (uint32_t i = 0; i < n; ++i) any = any || b->status[i] != MRK_OK || b->sort_loc[i].bits || b->sort_loc[i].no_row();
-    b->any_declined = any;
-    if (any || b->decl_dirty) {
-      for (uint32_t i = 0; i < n; ++i) b->h_decl.p[i] = (b->status[i] != MRK_OK || b->sort_loc[i].no_row()) ? 1u : b->sort_loc[i].bits ? 2u : 0u;
-      HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
-    }
-    b->decl_order = any_order;
-    if (any_order) { // the same words for ORDER rows, which carry a 64-bit key (and, where the batch asked for it, the weight in front)
-      uint32_t* ho = b->h_decl.p + b->max_queries;
-      for (uint32_t i = 0; i < n; ++i) ho[i] = (b->status[i] != MRK_OK || b->sort_loc[i].no_orow(b->orows_wf_run)) ? 1u : 0u;
-      HIP_TRY(hipMemcpyAsync(b->d_decl.p + b->max_queries, ho, n * 4, hipMemcpyHostToDevice, st2));
-    }
-    b->decl_dirty = any;
+    // the queries' decline masks, for every row format whether or not a destination stands: mrk_batch_export_* writes the same rows
+    // after the wait
+    uint32_t any = 0;
+    for (uint32_t i = 0; i < n; ++i) any |= b->h_decl.p[i] = mrk::row_decline_mask(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order, b->orows_wf_run);
+    b->any_declined = any != 0;
+    if (any || b->decl_dirty) HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
+    b->decl_dirty = any != 0;
   }
   // The standing export.  Narrow rows: the packed path's sort pass wrote them already, unless a query was declined -- those rows are
   // marked here.  Wide and order rows: relevance and declined queries' rows (sort_select_kernel wrote the others').
-  const RowKind dst_kind = b->orows_dst ? ROWS_ORDER : b->srows_dst ? ROWS_WIDE : ROWS_NARROW;
-  uint64_t* const dst = b->orows_dst ? b->orows_dst : b->srows_dst ? b->srows_dst : b->rows_dst;
-  if (dst && (dst_kind != ROWS_NARROW || !use_packed || b->any_declined)) {
-    PackXRowsArgs pa{};
-    bind_pack_rows(b, pa, dst_kind);
-    pa.rows = dst;
-    pa.flags = use_packed ? b->d_q_flags.p : nullptr;
-    pa.n = n;
-    pa.skip_sorted = dst_kind != ROWS_NARROW && use_packed && any_sort ? 1u : 0u;
-    launch_pack_xrows(dst_kind, pa, st2);
-  }
+  const RowDst& dst = b->dst;
+  if (dst.p && (dst.kind != ROWS_NARROW || !use_packed || b->any_declined)) launch_pack_rows(b, dst.kind, dst.p, n, use_packed, dst.kind != ROWS_NARROW && shape.sort, st2);
   HIP_TRY(hipGetLastError());
   b->packed_run = use_packed;
   b->last_seg = seg;
   b->n_pass = (uint32_t)n_pass;
-  b->last_max_terms = max_terms;
-  b->last_prox = any_prox;
-  b->last_tree = any_tree;
-  b->last_ext = any_ext;
-  b->last_sort = any_sort;
+  b->shape = shape;
   lap("select launched");
   // ---- results to pinned host memory: the packed path's selection wrote them itself; the VLB path copies
-  b->host_copied = b->rows_dst == nullptr && b->srows_dst == nullptr && b->orows_dst == nullptr;
+  b->host_copied = b->dst.p == nullptr;
   if (b->host_copied && !use_packed) {
     HIP_TRY(hipMemcpyAsync(b->h_cnt.p, b->d_out_cnt.p, n * 4, hipMemcpyDeviceToHost, st2));
     HIP_TRY(hipMemcpyAsync(b->h_total.p, b->d_q_total.p, n * 8, hipMemcpyDeviceToHost, st2));
@@ -1477,17 +1470,14 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   if (n_items) memcpy(r->h_items.p, items_pk.data(), n_items * sizeof(DevItem));
   HIP_TRY(hipMemcpyAsync(r->d_queries.p, r->h_queries.p, passes.size() * sizeof(DevQuery), hipMemcpyHostToDevice, st));
   if (n_items) HIP_TRY(hipMemcpyAsync(r->d_items.p, r->h_items.p, n_items * sizeof(DevItem), hipMemcpyHostToDevice, st));
+  // (rerun only: everything goes down the retry batch's one stream, and plain copies and a memset stand for the prep kernel)
   HIP_TRY(hipMemsetAsync(r->d_state.p, 0, (size_t)r->max_queries * STATE_BYTES + (size_t)NBINS * 4, st));
+  // the submit's kernel instances over ONE query (n = 1 below), but for what is this query's own: whether IT is sorted, and ITS probe launch
+  LaunchShape shape = b->shape;
+  shape.sort = sorted, shape.nearn = (passes[0].tree_flags & TF_GEN_NEARN) != 0;
   ScanArgs sa{};
   bind_scan(r, seg, sa);
-  sa.scand = sorted ? r->d_scand.p : nullptr;
-  if (sorted && b->last_prox) {
-    const size_t words = NBINS + mrk::QSTRIDE;
-    if ((rc = r->d_shist.reserve(words))) return rc;
-    HIP_TRY(hipMemsetAsync(r->d_shist.p, 0, words * 4, st));
-    sa.s_hist = r->d_shist.p;
-    sa.s_tau = r->d_shist.p + NBINS;
-  }
+  if (sorted && (rc = bind_sorted(r, 1, shape.prox, sa, st))) return rc;
   // match queues for every doc a pass can match (no cap: this run must not overflow), every pass charged the whole rerun's items
   uint64_t chunks[3] = {0, 0, 0};
   for (const DevQuery& P : passes) {
@@ -1496,22 +1486,11 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   }
   for (int i = 0; i < 3; ++i)
     if (chunks[i] > (1ull << 25)) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: match queue for the rerun too large", qi);
-  if ((rc = bind_match_queues(r, chunks, sa))) return rc;
-  if (chunks[0] || chunks[1] || chunks[2]) HIP_TRY(hipMemsetAsync(r->d_mq_count.p, 0, 3 * mrk::MQ_SHARDS * 4, st));
-  const bool nearn = (passes[0].tree_flags & TF_GEN_NEARN) != 0;
-  if (n_kind[2] && (rc = bind_gen(r, b, sa, st, 1, nearn))) return rc; // (the programs are the submit's, still on the device)
-  const bool lean = lean_scan_ok(b->ctx, seg, sorted, b->last_max_terms, b->last_prox, b->last_tree, b->last_ext);
-  if ((rc = launch_packed(sa, n_pk, n_kind, chunks, b->last_max_terms, b->last_prox, b->last_tree, b->last_ext, nearn, nullptr, lean, st))) return rc;
-  SelectArgs se{};
-  bind_select(r, seg, 1, cap, se);
-  launch_select(se, st);
-  if (sorted) {
-    mrk::SortSelArgs ss{};
-    ss.queries = r->d_queries.p, ss.q_hist = r->d_q_hist.p, ss.q_cand_n = r->d_q_cand_n.p, ss.scand = r->d_scand.p, ss.n_queries = 1;
-    ss.out_keys = r->d_out_keys.p, ss.out_cnt = r->d_out_cnt.p, ss.out_mkeys = r->d_out_mkeys.p;
-    ss.out_mkeys64 = keys64 ? r->d_out_mkeys64.p : nullptr;
-    mrk::launch_sort_select(ss, st);
-  }
+  if ((rc = bind_match_queues(r, chunks, sa, st))) return rc;
+  if (n_kind[2] && (rc = bind_gen(r, b, sa, st, 1, shape.nearn))) return rc; // (the programs are the submit's, still on the device)
+  if ((rc = launch_packed(sa, n_pk, n_kind, chunks, shape, nullptr, lean_scan_ok(b->ctx, seg, shape), st))) return rc;
+  // (rerun only: no pinned-host pointers and no destination -- the copies below repair the batch's row, and an export writes it)
+  launch_selection(r, seg, 1, cap, sorted, RowDst{}, false, SelectArgs{}, st);
   HIP_TRY(hipGetLastError());
   uint32_t flags = 0;
   HIP_TRY(hipMemcpyAsync(&flags, r->d_q_flags.p, 4, hipMemcpyDeviceToHost, st));
@@ -1527,9 +1506,7 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   // the device-side row is good again -- or carries what the rerun ran into: an exported row then leaves flagged, never with the rerun's keys
   HIP_TRY(hipMemcpyAsync(b->d_q_flags.p + qi, r->d_q_flags.p, 4, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (flags & QF_FSM) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: a doc held more live phrase states than the device path keeps", qi);
-  if (flags & QF_ARENA) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the generic evaluator ran out of hit-list memory (ctx tunable gen_spill_mb)", qi);
-  if (flags & QF_OVERFLOW) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: candidate list overflowed again on the rerun", qi);
+  if ((rc = flags_status(flags, qi, true))) return rc;
   b->decoded = false;
   return MRK_OK;
 }
@@ -1564,17 +1541,11 @@ static int mrk_batch_wait_impl(mrk_batch* b) {
   if (b->packed_run)
     for (uint32_t i = 0; i < b->n_queries; ++i) {
       if (b->status[i] != MRK_OK) continue;
-      // never hand back a silently truncated result
-      if (b->h_flags.p[i] & QF_FSM)
-        b->status[i] = mrk_fail(MRK_E_UNSUPPORTED, "query %u: a doc held more live phrase states than the device path keeps", i);
-      else if (b->h_flags.p[i] & QF_ARENA)
-        b->status[i] = mrk_fail(MRK_E_UNSUPPORTED, "query %u: the generic evaluator ran out of hit-list memory (ctx tunable gen_spill_mb)", i);
-      else if (b->h_flags.p[i] & QF_OVERFLOW) {
+      if ((b->status[i] = flags_status(b->h_flags.p[i], i, false)) == MRK_OK && (b->h_flags.p[i] & QF_OVERFLOW)) {
         // more matches tied at the pruning threshold than the candidate list holds (e.g. millions of docs with the
         // very same weight): run the query again, alone, with room for every doc its drivers can deliver
         ++b->stats.n_rerun;
-        const int rc = rerun_overflowed(b, i);
-        if (rc != MRK_OK) b->status[i] = rc;
+        b->status[i] = rerun_overflowed(b, i);
       }
     }
   return MRK_OK;
@@ -1663,10 +1634,9 @@ static int batch_set_dst(mrk_batch* b, uint64_t* dst, RowKind kind) {
   static const char* const fn[] = {"mrk_batch_set_rows_dst", "mrk_batch_set_srows_dst", "mrk_batch_set_orows_dst"};
   static const char* const what[] = {"narrow", "wide", "order-row"};
   if (!b) return mrk_fail(MRK_E_INVAL, "%s: NULL batch", fn[kind]);
-  uint64_t** const slot[] = {&b->rows_dst, &b->srows_dst, &b->orows_dst};
-  for (int o = 0; o < 3; ++o)
-    if (dst && o != kind && *slot[o]) return mrk_fail(MRK_E_INVAL, "%s: the batch has a standing %s destination (%s)", fn[kind], what[o], fn[o]);
-  *slot[kind] = dst;
+  const RowKind o = b->dst.kind;
+  if (dst && b->dst.p && o != kind) return mrk_fail(MRK_E_INVAL, "%s: the batch has a standing %s destination (%s)", fn[kind], what[o], fn[o]);
+  if (dst || o == kind) b->dst = RowDst{dst, kind}; // (NULL clears a destination of its own kind only; the other kinds' setters leave it standing)
   return MRK_OK;
 }
 extern "C" int mrk_batch_set_rows_dst(mrk_batch* b, uint64_t* rows_dst) { return batch_set_dst(b, rows_dst, ROWS_NARROW); }
@@ -1690,12 +1660,7 @@ static int mrk_batch_record_event_impl(mrk_batch* b, void* hip_event) {
 static int batch_export_rows(mrk_batch* b, uint64_t* dst, RowKind kind) {
   if (!b || !dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_%s: NULL argument", kind == ROWS_ORDER ? "orows" : kind == ROWS_WIDE ? "srows" : "rows");
   HIP_TRY(hipSetDevice(b->ctx->device));
-  PackXRowsArgs pa{};
-  bind_pack_rows(b, pa, kind);
-  pa.rows = dst;
-  pa.flags = b->packed_run ? b->d_q_flags.p : nullptr;
-  pa.n = b->n_queries;
-  launch_pack_xrows(kind, pa, b->stream); // behind the batch's selection kernels
+  launch_pack_rows(b, kind, dst, b->n_queries, b->packed_run, false, b->stream); // behind the batch's selection kernels
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(b->stream));
   b->in_flight = false;
@@ -1722,11 +1687,21 @@ static void launch_rows_merge(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n
   launch_merge(ma, ctx->merge_stream);
 }
 
+// the merge entry points' checks of k and, for wide and order rows, of the list count.  (The texts name the narrow entry point for
+// every format, but for the list count's -- as they always did; each entry point keeps the order it checked in.)
+static int merge_k_ok(const char* fn, uint32_t k) {
+  return k == 0 || k > MRK_MAX_K ? mrk_fail(MRK_E_INVAL, "%s: k %u outside 1..%d", fn, k, MRK_MAX_K) : MRK_OK;
+}
+static int merge_lists_ok(const char* sfx, uint32_t n_lists, RowKind kind) {
+  if (kind == ROWS_NARROW || (n_lists != 0 && n_lists <= 8)) return MRK_OK;
+  return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_%s%s: %u lists (1..8)", kind == ROWS_ORDER ? "orows" : "srows", sfx, n_lists);
+}
+
 static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
                                    uint64_t* out_rows, RowKind kind = ROWS_NARROW) {
   if (!ctx || !rows_all || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows: NULL argument");
-  if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows: k %u outside 1..%d", k, MRK_MAX_K);
-  if (kind != ROWS_NARROW && (n_lists == 0 || n_lists > 8)) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_%s: %u lists (1..8)", kind == ROWS_ORDER ? "orows" : "srows", n_lists);
+  int rc;
+  if ((rc = merge_k_ok("mrk_topk_merge_rows", k)) || (rc = merge_lists_ok("", n_lists, kind))) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, kind);
   HIP_TRY(hipGetLastError());
@@ -1739,7 +1714,7 @@ static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint
 static int mrk_topk_merge_rows_part_impl(mrk_ctx* ctx, const uint64_t* rows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first,
                                         uint32_t count, uint32_t k, uint64_t* out_rows, RowKind kind = ROWS_NARROW) {
   if (!ctx || !rows_recv || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: NULL argument");
-  if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: k %u outside 1..%d", k, MRK_MAX_K);
+  if (const int rc = merge_k_ok("mrk_topk_merge_rows_part", k)) return rc;
   if (n_lists == 0 || n_lists > 8 || count > list_stride) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: %u lists (1..8), %u queries of stride %u", n_lists, count, list_stride);
   HIP_TRY(hipSetDevice(ctx->device));
   launch_rows_merge(ctx, rows_recv, n_lists, list_stride, count, k, out_rows, first, nullptr, kind);
@@ -1751,8 +1726,8 @@ static int mrk_topk_merge_rows_part_impl(mrk_ctx* ctx, const uint64_t* rows_recv
 static int mrk_topk_merge_rows_async_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
                                          uint64_t* out_rows, void* wait_event, uint32_t slot, RowKind kind = ROWS_NARROW) {
   if (!ctx || !rows_all || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_async: NULL argument");
-  if (kind != ROWS_NARROW && (n_lists == 0 || n_lists > 8)) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_%s_async: %u lists (1..8)", kind == ROWS_ORDER ? "orows" : "srows", n_lists);
-  if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_async: k %u outside 1..%d", k, MRK_MAX_K);
+  int rc;
+  if ((rc = merge_lists_ok("_async", n_lists, kind)) || (rc = merge_k_ok("mrk_topk_merge_rows_async", k))) return rc;
   if (slot >= MRK_MERGE_SLOTS) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_async: slot %u of %d", slot, MRK_MERGE_SLOTS);
   HIP_TRY(hipSetDevice(ctx->device));
   if (!ctx->merge_done[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->merge_done[slot], hipEventDisableTiming));
@@ -1776,7 +1751,7 @@ static int mrk_merge_wait_impl(mrk_ctx* ctx, uint32_t slot) {
 static int mrk_topk_merge_impl(mrk_ctx* ctx, const uint64_t* in_keys, const uint32_t* in_counts, uint32_t n_lists,
                               uint32_t n_queries, uint32_t k, uint64_t* out_keys, uint32_t* out_counts) {
   if (!ctx || !in_keys || !in_counts || !out_keys || !out_counts) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge: NULL argument");
-  if (k == 0 || k > MRK_MAX_K) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge: k %u outside 1..%d", k, MRK_MAX_K);
+  if (const int rc = merge_k_ok("mrk_topk_merge", k)) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   MergeArgs ma{};
   ma.in_keys = in_keys;

@@ -242,6 +242,19 @@ struct BmPlacement {
 void place_bm_items(const DevQuery* head, uint32_t n, const std::vector<DevQuery>& extra, const BatchLayout& lay, bool nibble_plane, int mode,
                     BmPlacement& out);
 
+// A query's decline mask (PackXRowsArgs::declined): bit RowKind k set = the query's exchange row of format k leaves the batch empty
+// with MRK_ROW_DECLINED.  status: what plan_query returned for it; sort_bits / order: the batch's SortLoc facts (bits != 0: it is
+// sorted or ordered by an attribute; order: 0, or its DevQuery::sort_on when it came as mrk_query.order); orows_wf_run: the submit
+// ran with mrk_batch_orows_weight_first on.  A NARROW row is merged by (weight, docid), which answers relevance queries only; a WIDE
+// row has no room for a 64-bit key (SORT_ON_ORDER) and no word for the weight in front (SORT_ON_WEIGHT); an ORDER row carries both,
+// the latter only where the batch asked for it.  The order bit implies the wide bit, the wide bit the narrow one: some bit is set
+// exactly when the narrow bit is.
+inline uint32_t row_decline_mask(int status, uint32_t sort_bits, uint32_t order, bool orows_wf_run) {
+  const bool off = status != MRK_OK, no_row = order == SORT_ON_ORDER || order == SORT_ON_WEIGHT;
+  const bool narrow = off || sort_bits != 0 || no_row, wide = off || no_row, ord = off || (order == SORT_ON_WEIGHT && !orows_wf_run);
+  return (narrow ? 1u << ROWS_NARROW : 0u) | (wide ? 1u << ROWS_WIDE : 0u) | (ord ? 1u << ROWS_ORDER : 0u);
+}
+
 // Least and largest field-weight sum over the masks of the first nwf (<= 32) fields, the empty mask counting as 1
 // (ExtRanker_WeightSum_c's "just fake it"): the pruning bins of the weight-sum rankers.
 void weight_sum_range(const int32_t* weights, uint32_t nwf, int64_t& rmin, int64_t& rmax);

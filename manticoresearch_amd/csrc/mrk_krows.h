@@ -16,10 +16,11 @@ enum SpecElection {
   SPEC_OF_ANSWERING, // that of the first list not marked MRK_ROW_DECLINED; the other such lists must agree, a declined list has no say
 };
 
-// A format: WORDS per row; MK, an entry of the mapped-key plane, MK_BYTES of it per entry in a row and in the merge's LDS (0: no plane);
+// A format: KIND, its RowKind (the bit of a query's decline mask that pack_xrows_kernel tests); WORDS per row; MK, an entry of the mapped-key plane, MK_BYTES of it per entry in a row and in the merge's LDS (0: no plane);
 // the word offsets MKEYS and SPEC; ELECT; WIDE_KEYS: the plane holds a whole 64-bit mapped key (else its high dword); spec_tie of a
 // spec word; spec_of a query; mkey_of a 64-bit mapped key; load_mkey / store_plane of a row.
 struct NarrowFmt {
+  static constexpr RowKind KIND = ROWS_NARROW;
   static constexpr int WORDS = ROW_WORDS, MKEYS = 0, SPEC = 0, MK_BYTES = 0;
   static constexpr SpecElection ELECT = SPEC_NONE;
   static constexpr bool WIDE_KEYS = false;
@@ -33,6 +34,7 @@ struct NarrowFmt {
 };
 
 struct WideFmt {
+  static constexpr RowKind KIND = ROWS_WIDE;
   static constexpr int WORDS = SROW_WORDS, MKEYS = SROW_MKEYS, SPEC = SROW_SPEC, MK_BYTES = 4;
   static constexpr SpecElection ELECT = SPEC_OF_LIST0;
   static constexpr bool WIDE_KEYS = false;
@@ -51,6 +53,7 @@ struct WideFmt {
 };
 
 struct OrderFmt {
+  static constexpr RowKind KIND = ROWS_ORDER;
   static constexpr int WORDS = OROW_WORDS, MKEYS = OROW_MKEYS, SPEC = OROW_SPEC, MK_BYTES = 8;
   static constexpr SpecElection ELECT = SPEC_OF_ANSWERING;
   static constexpr bool WIDE_KEYS = true;

@@ -164,8 +164,7 @@ __global__ __launch_bounds__(WG) void pack_xrows_kernel(PackXRowsArgs a) {
   constexpr bool PLANE = Fmt::MK_BYTES != 0;
   const uint32_t q = blockIdx.x;
   if (q >= a.n) return;
-  const uint32_t dw = a.declined ? a.declined[q] : 0u; // (2 = declined for narrow rows only)
-  const bool declined = PLANE ? dw == 1u : dw != 0u;
+  const bool declined = a.declined && ((a.declined[q] >> Fmt::KIND) & 1u) != 0u; // (the query's decline mask: this format's bit)
   const uint32_t sort_on = PLANE ? a.queries[q].sort_on : 0u; // (narrow rows: a sorted query is a declined one)
   const bool sorted = sort_on != 0 && !declined;
   if (a.skip_sorted && sorted) return; // (uniform) sort_select_kernel wrote this row
