@@ -109,7 +109,8 @@ typedef struct {
   uint32_t hit_format;          /* MRK_HITFMT_* */
   uint32_t n_fields;            /* schema full-text fields (<= 32 on the device path; the packed path covers all 32, with one extra
                                    plane of field masks above 8 fields) */
-  uint32_t rowid_base;          /* global docid = rowid_base + rowid for shard merges */
+  uint32_t rowid_base;          /* global docid = rowid_base + rowid for shard merges; rowid_base + total_docs <= 2^32 (global
+                                   rowids are 32 bits), or mrk_segment_create / mrk_segment_validate answer MRK_E_INVAL */
 } mrk_segment_desc;
 
 /* XQNode_t flattened: nodes[] + children[] (indices into nodes[]) */

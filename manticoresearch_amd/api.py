@@ -560,10 +560,10 @@ def _segment_desc(hi: HostIndex, rowid_base: int = 0) -> "_lib.SegmentDesc":
     return d
 
 
-def validate_index(hi: HostIndex) -> None:
+def validate_index(hi: HostIndex, rowid_base: int = 0) -> None:
     """The host-only half of Segment(): limits, skiplists and a walk of every doclist (mrk_segment_validate); raises
     MrkError on bytes that must not reach a kernel.  Needs no GPU."""
-    check(lib().mrk_segment_validate(C.byref(_segment_desc(hi))))
+    check(lib().mrk_segment_validate(C.byref(_segment_desc(hi, rowid_base))))
 
 
 class Segment:

@@ -187,7 +187,7 @@ constexpr uint32_t PK_WIDE = 0xFFu;
 // atomics of DIFFERENT queries serialize on that line
 constexpr int QSTRIDE = 16; // dwords between consecutive queries' entries in ScanArgs::q_cand_n / q_tau_bin
 constexpr int NBINS = 1024; // pruning histogram bins per query
-constexpr uint32_t BIN_WEIGHT = 0, BIN_ROWID = 1;
+// (BIN_WEIGHT / BIN_ROWID, DevQuery::bin_mode: mrk_sortkey.h, with the bins themselves)
 constexpr uint32_t PN_TERM = 0, PN_AND = 1, PN_OR = 2, PN_MAYBE = 3, PN_ANDNOT = 4, PN_PHRASEFIX = 5, PN_QUORUM = 6, PN_ORDERFIX = 7, PN_NOTNEAR = 8; // prog[] opcodes
 constexpr int QUORUM_EVENTS = 8; // keywords of a quorum node = doclists that can run dry and reorder its children
 constexpr uint32_t TF_MULTIAND = 1; // the whole query is one ExtMultiAnd_T (or a single keyword)

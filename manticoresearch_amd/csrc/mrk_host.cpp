@@ -526,6 +526,9 @@ static int check_desc(const mrk_segment_desc* d) {
   if (d->hit_format != MRK_HITFMT_INLINE && d->hit_format != MRK_HITFMT_PLAIN)
     return mrk_fail(MRK_E_INVAL, "bad hit_format %u", d->hit_format);
   if (d->n_terms && !d->dict) return mrk_fail(MRK_E_INVAL, "mrk_segment_create: %u terms but no dictionary table", d->n_terms);
+  // global rowids are 32 bits everywhere behind this point (candidate keys, SelectArgs::rowid_hi): the segment's last one must be one
+  if ((uint64_t)d->rowid_base + d->total_docs > (1ull << 32))
+    return mrk_fail(MRK_E_INVAL, "mrk_segment_create: rowid_base %u + %llu docs: global rowids beyond 2^32 - 1", d->rowid_base, (unsigned long long)d->total_docs);
   return MRK_OK;
 }
 

@@ -8,10 +8,9 @@ namespace mrk {
 // Pruning bin of a match: monotone non-decreasing in the sorter's order (weight, then lower
 // rowid), so "K matches already sit in higher bins" proves a match cannot reach the top K.
 __device__ __forceinline__ uint32_t bin_of(uint32_t mode, int32_t lo, uint32_t shift, int32_t weight, uint32_t grow) {
-  static_assert(NBINS == 1024, "weight_bin (mrk_sortkey.h) holds the bin count");
-  if (mode == BIN_WEIGHT) return weight_bin(lo, shift, weight); // (one definition for host and device)
-  const uint32_t b = grow >> shift;
-  return (uint32_t)NBINS - 1u - (b < (uint32_t)NBINS ? b : (uint32_t)NBINS - 1u);
+  static_assert(NBINS == 1024, "weight_bin and rowid_bin (mrk_sortkey.h) hold the bin count");
+  if (mode == BIN_WEIGHT) return weight_bin(lo, shift, weight); // (one definition each for host and device)
+  return rowid_bin(shift, grow);
 }
 
 // Largest bin b with sum(hist[b..]) >= k (0 if the whole histogram holds fewer than k).

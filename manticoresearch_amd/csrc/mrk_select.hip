@@ -126,8 +126,7 @@ __global__ __launch_bounds__(WG) void sel_filter_kernel(SelectArgs a, uint32_t q
 // SUB sub-bins over (weight offset inside the bin, rowid from the top of the segment's range), still monotone in the
 // sorter's order -- and only the sub-bins that can reach the top K are gathered and sorted: about K + one sub-bin's share.
 constexpr int SCH = 1024; // slices handled per chunk (a list of 2^20 candidates has 512)
-constexpr int SUB = 2048; // sub-bins of the threshold bin
-constexpr int SUB_BITS = 11;
+constexpr int SUB = 1 << SUB_BITS; // sub-bins of the threshold bin: SubKey::sub (mrk_sortkey.h, with the guard that decides for them)
 
 struct __align__(16) SortSmem {
   uint64_t cand[CAND];
@@ -136,22 +135,6 @@ struct __align__(16) SortSmem {
   uint32_t wave_cnt[2 * WAVES];
   uint32_t cand_n, tau2, above;
   uint64_t tau;
-};
-
-// order of a key INSIDE its pruning bin, bigger = better, as a number of `totbits` bits
-struct SubKey {
-  uint32_t mode, shift, rbits, rhi, totbits;
-  int32_t lo;
-  __device__ __forceinline__ uint32_t sub(uint64_t key) const {
-    const uint32_t grow = key_rowid(key);
-    uint64_t ok;
-    if (mode == BIN_WEIGHT) {
-      const uint32_t woff = shift ? ((uint32_t)(key_weight(key) - lo) & ((1u << shift) - 1u)) : 0u;
-      ok = ((uint64_t)woff << rbits) | (uint64_t)(rhi - grow);
-    } else
-      ok = (uint64_t)(((1u << shift) - 1u) - (grow & ((1u << shift) - 1u)));
-    return totbits > (uint32_t)SUB_BITS ? (uint32_t)(ok >> (totbits - SUB_BITS)) : (uint32_t)ok;
-  }
 };
 
 __global__ __launch_bounds__(WG) void sel_sort_kernel(SelectArgs a) {
@@ -211,11 +194,9 @@ __global__ __launch_bounds__(WG) void sel_sort_kernel(SelectArgs a) {
     };
 
     // ---- the sub-bin pass: only when the whole list is this one chunk, does not fit one sort, and the threshold bin is
-    // an interior one (the two edge bins are open-ended: no finite sub-order)
-    SubKey sk{bin_mode, bin_shift, a.rowid_bits, a.rowid_hi, 0u, bin_lo};
-    sk.totbits = bin_mode == BIN_WEIGHT ? bin_shift + a.rowid_bits : bin_shift;
-    bool use_sub = ns <= (uint32_t)SCH && total > (uint32_t)CAND && tau_bin > 0 && sk.totbits > 0 && sk.totbits <= 56u &&
-                   (bin_mode == BIN_ROWID || tau_bin < (uint32_t)NBINS - 1u);
+    // an interior one (the two edge bins are open-ended: no finite sub-order; sub_guard)
+    const SubKey sk = sub_key(bin_mode, bin_lo, bin_shift, a.rowid_bits, a.rowid_hi);
+    const bool use_sub = ns <= (uint32_t)SCH && total > (uint32_t)CAND && sub_guard(sk, tau_bin);
     if (use_sub) {
       for (uint32_t i = tid; i < (uint32_t)SUB; i += WG) s.hist2[i] = 0;
       __syncthreads();

@@ -66,6 +66,47 @@ MRK_HD inline uint32_t weight_bin(int32_t lo, uint32_t shift, int32_t weight) {
   return b < 1024u ? b : 1023u;
 }
 
+constexpr uint32_t BIN_WEIGHT = 0, BIN_ROWID = 1; // DevQuery::bin_mode: what the relevance order's pruning histogram is keyed on
+
+// pruning bin of a GLOBAL rowid (the BIN_ROWID bins of a query whose weights are all equal: the order is rowid ascending, so lower
+// rowids sit in higher bins): monotone non-decreasing in the order, 1024 bins; shift as bins_by_rowid (mrk_plan.cpp) sets it.
+// Rowids of 1023 << shift and beyond share the clamped bin 0
+MRK_HD inline uint32_t rowid_bin(uint32_t shift, uint32_t grow) {
+  const uint32_t b = grow >> shift;
+  return 1023u - (b < 1024u ? b : 1023u);
+}
+
+// Order of a relevance key INSIDE its pruning bin, bigger = better, as a number of `totbits` bits of which sub() hands out the top
+// SUB_BITS (all of them where there are fewer): the sub-bins of the selection's sort pass (sel_sort_kernel, mrk_select.hip).
+//   BIN_WEIGHT  (weight offset inside the bin) << rbits | rhi - global rowid      rhi / rbits: the segment's largest global rowid and
+//   BIN_ROWID   2^shift - 1 - (global rowid mod 2^shift)                          the bits of its rowid count - 1
+// Only where sub_guard() holds is this an order of the bin's keys.
+constexpr uint32_t SUB_BITS = 11;
+struct SubKey {
+  uint32_t mode, shift, rbits, rhi, totbits;
+  int32_t lo;
+  MRK_HD inline uint32_t sub(uint64_t key) const {
+    const uint32_t grow = key_rowid(key);
+    uint64_t ok;
+    if (mode == BIN_WEIGHT) {
+      const uint32_t woff = shift ? (((uint32_t)key_weight(key) - (uint32_t)lo) & ((1u << shift) - 1u)) : 0u; // (unsigned: no signed overflow, as in weight_bin)
+      ok = ((uint64_t)woff << rbits) | (uint64_t)(rhi - grow);
+    } else
+      ok = (uint64_t)(((1u << shift) - 1u) - (grow & ((1u << shift) - 1u)));
+    return totbits > SUB_BITS ? (uint32_t)(ok >> (totbits - SUB_BITS)) : (uint32_t)ok;
+  }
+};
+// mode / lo / shift = DevQuery::bin_mode / bin_lo / bin_shift; rowid_bits / rowid_hi = SelectArgs' (mrk_dev.h)
+MRK_HD inline SubKey sub_key(uint32_t mode, int32_t lo, uint32_t shift, uint32_t rowid_bits, uint32_t rowid_hi) {
+  return SubKey{mode, shift, rowid_bits, rowid_hi, mode == BIN_WEIGHT ? shift + rowid_bits : shift, lo};
+}
+// May the keys of threshold bin tau_bin be told apart by sub()?  Not in the edge bins, which are open-ended (bin 0 of either mode holds
+// everything below the range or beyond the clamp, bin 1023 of the weight's everything above: no finite sub-order), not without a bit
+// to tell by, and not where the order would not fit the 64-bit arithmetic of sub() with room to spare
+MRK_HD inline bool sub_guard(const SubKey& sk, uint32_t tau_bin) {
+  return tau_bin > 0u && sk.totbits > 0u && sk.totbits <= 56u && (sk.mode == BIN_ROWID || tau_bin < 1023u);
+}
+
 // A candidate of a sorted query is 128 bits, compared as (hi, lo), larger = better:
 //   hi = mapped key << 32 | the weight as the tie rule orders it (0 where the weight is no part of the order)
 //   lo = ~global rowid << 32 | the true weight

@@ -23,9 +23,16 @@ PROBS = [0.35, 0.2, 0.1, 0.05, 0.04, 0.02, 0.01, 0.006]
 
 
 class Hip:
+    """Device buffers of the test.  Every fill and copy is finished before it returns: hipMemset and a device-to-device hipMemcpy on
+    the null stream may return before the device has done them, and the library's merge stream is non-blocking -- nothing else would
+    order a 0xEE fill, or the copies that stand in for the all-to-all, before the merge kernel that reads and writes the same rows."""
+
     def __init__(self):
         self.hip = C.CDLL("libamdhip64.so")
         self.bufs = []
+
+    def sync(self):
+        assert self.hip.hipDeviceSynchronize() == 0
 
     def malloc(self, n):
         p = C.c_void_p()
@@ -41,12 +48,15 @@ class Hip:
     def to_dev(self, p, a):
         a = np.ascontiguousarray(a, dtype=np.uint64)
         assert self.hip.hipMemcpy(p, C.c_void_p(a.ctypes.data), C.c_size_t(a.nbytes), 1) == 0
+        self.sync()
 
     def d2d(self, dst, src, n):
         assert self.hip.hipMemcpy(dst, src, C.c_size_t(n), 3) == 0
+        self.sync()
 
     def fill(self, p, byte, n):
         assert self.hip.hipMemset(p, byte, C.c_size_t(n)) == 0
+        self.sync()
 
     def free(self):
         for p in self.bufs:

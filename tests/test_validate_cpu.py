@@ -57,3 +57,16 @@ def test_synthetic_segments_pass():
     for fmt in (0, 1):
         for block in (32, 128):
             m.validate_index(m.synth_index(20000, [0.3, 0.01], seed=5, skiplist_block_size=block, hit_format=fmt, n_threads=1))
+
+
+def test_global_rowids_beyond_32_bits_are_refused():
+    """Global rowids (rowid_base + rowid) are 32 bits in every candidate key and in the selection's rowid_hi: a segment whose last one
+    would not fit is refused with MRK_E_INVAL and a message before anything is read; the one that ends exactly at 2^32 - 1 loads
+    (tests/test_gpu_select_edges.py runs on it)."""
+    hi = crafted()["good_hitlists"]
+    assert hi.total_docs == 10
+    m.validate_index(hi, rowid_base=2**32 - 10)
+    for base in (2**32 - 9, 2**32 - 1):
+        with pytest.raises(m.MrkError) as e:
+            m.validate_index(hi, rowid_base=base)
+        assert e.value.code == -1 and "2^32" in str(e.value)  # MRK_E_INVAL
