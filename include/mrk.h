@@ -267,7 +267,8 @@ typedef struct {
   uint64_t dev_bytes;     /* the same sum over the format the kernel actually read (packed or .spd) */
   uint32_t packed;        /* 1 = packed-doclist path, 0 = VLB-direct path */
   uint64_t n_cands;       /* packed path: candidates that survived in-scan pruning (all queries) */
-  uint64_t n_items_bm;    /* of n_items: work items of the two-bitmap AND kernel (dense keywords) */
+  uint64_t n_items_bm;    /* of n_items: every work item that is not a block-scan item -- the two-bitmap AND kernel's, the tree kernel's over
+                             bitmap words (n_items_bt) and the generic evaluator's */
   float plan_ms;          /* host: query planning inside mrk_batch_submit */
   float submit_ms;        /* host: whole mrk_batch_submit call */
   uint32_t n_rerun;       /* queries the last mrk_batch_wait ran again alone (their match queue or candidate list was full) */
@@ -278,6 +279,8 @@ typedef struct {
                              query where none were formed -- and ... */
   uint32_t bm_class_keys; /* ... distinct (class, keyword) pairs once the owners were assigned to the eight dispatch classes (bm_place = 2:
                              one class).  Both 0 when no placement ran (bm_place = 0, fewer than two owners, no such launch) */
+  uint32_t n_items_bt;    /* "bt_cover_inv" / "bt_phrase": of n_items_bm, the work items of the tree kernel over bitmap words (boolean trees and
+                             the candidates of root phrases of common words); 0 on the VLB-direct path */
 } mrk_batch_stats;
 
 const char* mrk_last_error(void);
