@@ -281,6 +281,9 @@ typedef struct {
                              one class).  Both 0 when no placement ran (bm_place = 0, fewer than two owners, no such launch) */
   uint32_t n_items_bt;    /* "bt_cover_inv" / "bt_phrase": of n_items_bm, the work items of the tree kernel over bitmap words (boolean trees and
                              the candidates of root phrases of common words); 0 on the VLB-direct path */
+  uint32_t mq_chunks[3];  /* match-queue chunks the planner sized in the last submit for queue 0 (the lean rank pass: plain boolean trees under a
+                             hit ranker), 1 (the full hit pass: PHRASE / PROXIMITY / BEFORE / NEAR / NOTNEAR nodes, position modifiers) and 2 (the
+                             generic evaluator); 0 = that rank launch did not run.  All three are 0 on the VLB-direct path */
 } mrk_batch_stats;
 
 const char* mrk_last_error(void);

@@ -92,7 +92,8 @@ class BatchStats(C.Structure):
                 ("dev_bytes", C.c_uint64), ("packed", C.c_uint32), ("n_cands", C.c_uint64),
                 ("n_items_bm", C.c_uint64), ("plan_ms", C.c_float), ("submit_ms", C.c_float), ("n_rerun", C.c_uint32),
                 ("n_bm_groups", C.c_uint32 * 4), ("pk_lean", C.c_uint32),
-                ("bm_owner_keys", C.c_uint32), ("bm_class_keys", C.c_uint32), ("n_items_bt", C.c_uint32)]
+                ("bm_owner_keys", C.c_uint32), ("bm_class_keys", C.c_uint32), ("n_items_bt", C.c_uint32),
+                ("mq_chunks", C.c_uint32 * 3)]
 
 
 class RtSegmentDesc(C.Structure):

@@ -669,7 +669,8 @@ class Batch:
                 "dev_bytes": int(s.dev_bytes), "packed": int(s.packed), "n_cands": int(s.n_cands),
                 "n_items_bm": int(s.n_items_bm), "plan_ms": float(s.plan_ms), "submit_ms": float(s.submit_ms),
                 "n_rerun": int(s.n_rerun), "n_bm_groups": [int(x) for x in s.n_bm_groups], "pk_lean": int(s.pk_lean),
-                "bm_owner_keys": int(s.bm_owner_keys), "bm_class_keys": int(s.bm_class_keys), "n_items_bt": int(s.n_items_bt)}
+                "bm_owner_keys": int(s.bm_owner_keys), "bm_class_keys": int(s.bm_class_keys), "n_items_bt": int(s.n_items_bt),
+                "mq_chunks": [int(x) for x in s.mq_chunks]}
 
     def device_results(self):
         """(keys_ptr, counts_ptr, totals_ptr) of the last finished submit, HBM addresses."""

@@ -1269,6 +1269,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   b->stats.n_items = n_items;
   b->stats.n_items_bm = n_items - n_items_pk;
   b->stats.n_items_bt = use_packed ? (uint32_t)lay.n_items_kind[1] : 0u;
+  for (int i = 0; i < 3; ++i) b->stats.mq_chunks[i] = (uint32_t)lay.mq_chunks[i]; // (capped by "mq_max_chunks"; all 0 on the VLB-direct path)
   // ---- reserve + stage
   int rc;
   const size_t n_group_slots = lay.groups.size() * (sizeof(BmGroup) / sizeof(DevItem)); // (the groups ride behind the work items)

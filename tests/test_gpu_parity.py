@@ -347,7 +347,8 @@ def test_random_corpus_proximity(orc, dev, block, fmt):
 
 
 def test_proximity_long_hitlists(orc, dev):
-    """Docs with hundreds of hits per keyword, 5-byte hit deltas (field jumps), phrases that do line up."""
+    """Docs with hundreds of hits per keyword, field jumps (fields 0, 1 and 7: 7 << 24 < 2^27, so the deltas are at most 4 bytes --
+    a 5-byte delta needs a field jump of 16 or more, test_gpu_hit_edges.py), phrases that do line up."""
     m, ctx, batch = dev
     if ctx_path(ctx) != 0:
         pytest.skip("proximity rankers run on the packed path")
