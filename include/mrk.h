@@ -284,6 +284,10 @@ typedef struct {
   uint32_t mq_chunks[3];  /* match-queue chunks the planner sized in the last submit for queue 0 (the lean rank pass: plain boolean trees under a
                              hit ranker), 1 (the full hit pass: PHRASE / PROXIMITY / BEFORE / NEAR / NOTNEAR nodes, position modifiers) and 2 (the
                              generic evaluator); 0 = that rank launch did not run.  All three are 0 on the VLB-direct path */
+  uint64_t bm_words_queued; /* "bm_wmax": non-empty match words the two-bitmap AND kernel queued for unpacking and scoring in the last submit, ... */
+  uint64_t bm_words_pruned; /* ... and those it dropped because the best weight the word's tf classes allow lies behind the query's pruning
+                               threshold.  Counted for the queries the bound applies to (BM25, relevance order, no field limits, a segment with
+                               the plane); both 0 otherwise.  Reruns of overflowed queries are not counted */
 } mrk_batch_stats;
 
 const char* mrk_last_error(void);
@@ -302,6 +306,12 @@ int mrk_ctx_destroy(mrk_ctx* ctx);
    AND kernel gathers from instead of the block decoder's interleaved words: the docs of a 128-byte line are then scored together and
    the line is fetched once, -2.7 % on the headline launch; +2 bytes per posting up to the last such keyword; default 1; read at
    segment load);
+   "bm_wmax" (1 = keywords with a bitmap also get one nibble per 32-rowid bitmap word, the largest hit count among the keyword's postings in
+   that word capped at 15; the two-bitmap AND kernel computes from the two nibbles of a match word the best weight any match in it can
+   have and neither unpacks the word nor fetches its tf / field bytes when that weight lies behind the query's pruning threshold --
+   exact results, BM25 in relevance order without field limits and with a positive index_weight; + 1/8 of the bitmaps' bytes, and every
+   bitmap then starts at a multiple of four windows (up to 768 B of padding per keyword); 0 = no plane, bitmaps and kernel as before;
+   default 1; read at segment load; mrk_batch_stats.bm_words_queued / bm_words_pruned count the words);
    "attr_nibbles" (1 = segments with <= 4 fields also get a one-byte tf/field plane for the bitmap kernel's gathers:
    28 % fewer bytes per dense x dense query, +14 % queries/s on the 100 M-doc bench, +1 byte per posting; default 0 --
    see DESIGN.md section 6; read at segment load);

@@ -93,7 +93,7 @@ class BatchStats(C.Structure):
                 ("n_items_bm", C.c_uint64), ("plan_ms", C.c_float), ("submit_ms", C.c_float), ("n_rerun", C.c_uint32),
                 ("n_bm_groups", C.c_uint32 * 4), ("pk_lean", C.c_uint32),
                 ("bm_owner_keys", C.c_uint32), ("bm_class_keys", C.c_uint32), ("n_items_bt", C.c_uint32),
-                ("mq_chunks", C.c_uint32 * 3)]
+                ("mq_chunks", C.c_uint32 * 3), ("bm_words_queued", C.c_uint64), ("bm_words_pruned", C.c_uint64)]
 
 
 class RtSegmentDesc(C.Structure):

@@ -670,7 +670,8 @@ class Batch:
                 "n_items_bm": int(s.n_items_bm), "plan_ms": float(s.plan_ms), "submit_ms": float(s.submit_ms),
                 "n_rerun": int(s.n_rerun), "n_bm_groups": [int(x) for x in s.n_bm_groups], "pk_lean": int(s.pk_lean),
                 "bm_owner_keys": int(s.bm_owner_keys), "bm_class_keys": int(s.bm_class_keys), "n_items_bt": int(s.n_items_bt),
-                "mq_chunks": [int(x) for x in s.mq_chunks]}
+                "mq_chunks": [int(x) for x in s.mq_chunks],
+                "bm_words_queued": int(s.bm_words_queued), "bm_words_pruned": int(s.bm_words_pruned)}
 
     def device_results(self):
         """(keys_ptr, counts_ptr, totals_ptr) of the last finished submit, HBM addresses."""

@@ -46,6 +46,10 @@ struct DevSegment {
   // 256-rowid group); a doc's rank is its slot in the packed arrays (pk_attr / pk_hit)
   const uint32_t* bm;
   const uint32_t* bm_dir;
+  // per bitmap word a 4-bit class, min(15, the largest tf among the keyword's postings in the word), 0 = empty word; the plane of
+  // the bitmap at word offset bm_off starts at 16-bit word bm_off / 4 (bitmaps start at multiples of four windows), and word
+  // (w >> 2) * 64 + l of it holds in nibble w & 3 the class of word l of window w (mrk_pack.h); NULL = not built
+  const uint16_t* bm_wmax;
   uint32_t n_windows;       // windows per bitmap = ceil(total_docs / 2048)
   const uint32_t* attrs;    // row-wise attributes (.spa rows, attr_stride dwords each) or NULL
   uint32_t attr_stride;
@@ -186,6 +190,7 @@ constexpr uint32_t PK_WIDE = 0xFFu;
 // publish, a read per few bursts): each sits in a 64-byte line of its own -- sixteen queries' counters in one line made the
 // atomics of DIFFERENT queries serialize on that line
 constexpr int QSTRIDE = 16; // dwords between consecutive queries' entries in ScanArgs::q_cand_n / q_tau_bin
+constexpr int QC_BM_QUEUED = 2, QC_BM_PRUNED = 3; // dwords of a q_cand_n entry that count scan_bm's queued / pruned match words (bm_wmax; one add per wave at its exit)
 constexpr int NBINS = 1024; // pruning histogram bins per query
 // (BIN_WEIGHT / BIN_ROWID, DevQuery::bin_mode: mrk_sortkey.h, with the bins themselves)
 constexpr uint32_t PN_TERM = 0, PN_AND = 1, PN_OR = 2, PN_MAYBE = 3, PN_ANDNOT = 4, PN_PHRASEFIX = 5, PN_QUORUM = 6, PN_ORDERFIX = 7, PN_NOTNEAR = 8; // prog[] opcodes
@@ -454,6 +459,7 @@ struct SelectArgs {
   uint64_t* h_total;       // pinned host [n_queries] or NULL
   uint32_t* h_flags;       // pinned host [n_queries] or NULL
   uint32_t* h_cand_n;      // pinned host [n_queries] or NULL
+  uint32_t* h_bm_words;    // pinned host [n_queries][2] or NULL: the two-bitmap AND kernel's queued / pruned match words (dwords 2 and 3 of the query's q_cand_n entry)
   uint64_t* rows_dst;      // device [n_queries][ROW_WORDS] or NULL: the exchange rows (keys zero-padded | count | total_found or MRK_ROW_RERUN);
                            // the rows of queries the planner declined are rewritten by pack_xrows_kernel
 };

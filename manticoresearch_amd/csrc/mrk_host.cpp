@@ -162,6 +162,7 @@ struct mrk_batch {
   // packed path: pruning histograms, candidate lists
   View<uint32_t> d_q_hist, d_q_cand_n, d_q_flags, d_q_tau_bin;
   PinBuf<uint32_t> h_cand_n;
+  PinBuf<uint32_t> h_bm_words; // [2 * i] / [2 * i + 1]: query i's queued / pruned match words of the two-bitmap AND kernel
   DevBuf<uint64_t> d_cand;
   DevBuf<uint32_t> d_shist;  // sorted hit-ranked queries: the scan's histogram of queued matches' attribute bins [n][NBINS], then the threshold words [n * QSTRIDE]
   DevBuf<uint32_t> d_out_mkeys; // [max_queries][KCAP] mapped sort keys of d_out_keys' entries (sorted queries; reserved with d_scand)
@@ -267,6 +268,11 @@ extern "C" int mrk_ctx_set(mrk_ctx* c, const char* key, int64_t value) {
   }
   if (!strcmp(key, "attr_seq")) {
     c->attr_seq = value != 0;
+    return MRK_OK;
+  }
+  if (!strcmp(key, "bm_wmax")) {
+    if (value < 0 || value > 1) return mrk_fail(MRK_E_INVAL, "bm_wmax must be 0 or 1");
+    c->bm_wmax = (int)value;
     return MRK_OK;
   }
   if (!strcmp(key, "attr_nibbles")) {
@@ -410,6 +416,7 @@ static void mrk_segment_destroy_impl(mrk_segment* s) {
   if (s->d_blobs) (void)hipFree(s->d_blobs);
   if (s->d_bm) (void)hipFree(s->d_bm);
   if (s->d_bm_dir) (void)hipFree(s->d_bm_dir);
+  if (s->d_bm_wmax) (void)hipFree(s->d_bm_wmax);
   delete s;
 }
 
@@ -661,6 +668,9 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
   std::vector<uint8_t> pk_w;
   std::vector<uint64_t> pk_exc;
   std::vector<uint32_t> bm_words, bm_dir;
+  std::vector<uint16_t> bm_wmax; // (one 16-bit word per four bitmap words: a term's plane starts at its bm_off / 4)
+  const bool want_wmax = ctx->bm_wmax != 0 && d->n_fields <= 8;
+  bool wmax_ok = want_wmax;
   std::vector<uint8_t> pk_attr1;
   std::vector<uint16_t> pk_attr2; // (indexed like pk_hit; holds zeros for keywords without a bitmap, cut after the last keyword with one)
   size_t attr2_end = 0;
@@ -692,7 +702,7 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
         // dense terms also get a bitmap of their doc set (the two-bitmap AND kernel, mrk_scan_bm.hip)
         const bool dense = ctx->bitmap_inv > 0 && d->total_docs > 0 && d->total_docs < (1ull << 32) &&
                            (uint64_t)d->dict[t].docs * (uint64_t)ctx->bitmap_inv >= d->total_docs;
-        if (!pack_term(d->spd, d->spd_len, d->dict[t], inl, dense ? d->total_docs : 0, pt[t], errs[t], d->total_docs, d->spp ? d->spp_len : 0, wide))
+        if (!pack_term(d->spd, d->spd_len, d->dict[t], inl, dense ? d->total_docs : 0, pt[t], errs[t], d->total_docs, d->spp ? d->spp_len : 0, wide, want_wmax))
           bad = true;
       }
     };
@@ -768,6 +778,14 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
             h.dir_off = bm_dir.size();
             bm_words.insert(bm_words.end(), x.bm.begin(), x.bm.end());
             bm_dir.insert(bm_dir.end(), x.bm_dir.begin(), x.bm_dir.end());
+            if (want_wmax) {
+              // with the plane every bitmap starts at a multiple of four windows, so that bm_off also names the term's place in it
+              bm_words.resize((bm_words.size() + 255) / 256 * 256, 0u);
+              if (x.wmax.size() == (bm_words.size() - h.bm_off) / 4)
+                bm_wmax.insert(bm_wmax.end(), x.wmax.begin(), x.wmax.end());
+              else
+                wmax_ok = false; // (a bitmap without its plane -- a posting without hits: the segment goes without)
+            }
           }
           x = PackedTerm();
         }
@@ -813,6 +831,15 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
         return rc;
       }
       s->device_bytes += bm_words.size() * 4 + bm_dir.size() * 4;
+      // (the plane only saves the bitmap kernel work: a segment that does not fit with it loads without it)
+      if (wmax_ok && bm_wmax.size() == bm_words.size() / 4) {
+        if (upload(&s->d_bm_wmax, bm_wmax.data(), bm_wmax.size() * 2, 256, ctx->stream) != MRK_OK) {
+          if (s->d_bm_wmax) (void)hipFree(s->d_bm_wmax);
+          s->d_bm_wmax = nullptr;
+          (void)hipGetLastError();
+        } else
+          s->device_bytes += bm_wmax.size() * 2;
+      }
     }
     s->has_packed = true;
     s->wide = wide;
@@ -845,6 +872,7 @@ static int mrk_segment_create_impl(mrk_ctx* ctx, const mrk_segment_desc* d, mrk_
   s->dev.pk_fmask = (const uint32_t*)s->d_pk_fmask;
   s->dev.bm = (const uint32_t*)s->d_bm;
   s->dev.bm_dir = (const uint32_t*)s->d_bm_dir;
+  s->dev.bm_wmax = (const uint16_t*)s->d_bm_wmax;
   s->dev.n_windows = (uint32_t)((d->total_docs + 2047) / 2048);
   s->dev.spd = (const uint8_t*)s->d_spd;
   s->dev.spp = (const uint8_t*)s->d_spp;
@@ -907,6 +935,7 @@ static void mrk_batch_destroy_impl(mrk_batch* b) {
   b->d_lb.release();
 
   b->h_cand_n.release();
+  b->h_bm_words.release();
   b->d_cand.release();
   b->d_scand.release();
   b->d_out_mkeys.release();
@@ -941,7 +970,7 @@ static int mrk_batch_create_impl(mrk_ctx* ctx, uint32_t max_queries, mrk_batch**
       (rc = b->h_total.reserve(nq)) || (rc = b->d_queries.reserve(nq)) ||
       (rc = b->d_state.reserve(nq * (STATE_BYTES + (size_t)NBINS * 4))) || (rc = b->d_list_first.reserve(nq)) || (rc = b->d_list_n.reserve(nq)) ||
       (rc = b->d_kq.reserve(nq)) || (rc = b->d_out_keys.reserve(nq * KCAP)) || (rc = b->d_out_cnt.reserve(nq)) ||
-      (rc = b->h_flags.reserve(nq)) || (rc = b->h_cand_n.reserve(nq)) || (rc = b->h_decl.reserve(nq)) || (rc = b->d_decl.reserve(nq)) || (rc = b->d_mq_count.reserve(3 * mrk::MQ_SHARDS))) {
+      (rc = b->h_flags.reserve(nq)) || (rc = b->h_cand_n.reserve(nq)) || (rc = b->h_bm_words.reserve(2 * nq)) || (rc = b->h_decl.reserve(nq)) || (rc = b->d_decl.reserve(nq)) || (rc = b->d_mq_count.reserve(3 * mrk::MQ_SHARDS))) {
     mrk_batch_destroy_impl(b);
     return rc;
   }
@@ -1370,6 +1399,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     SelectArgs se{};
     se.h_flags = b->h_flags.p;
     se.h_cand_n = b->h_cand_n.p;
+    se.h_bm_words = b->h_bm_words.p;
     if (!b->dst.p) se.h_keys = b->h_keys.p, se.h_cnt = b->h_cnt.p, se.h_total = b->h_total.p;
     launch_selection(b, seg, n, cand_total, shape.sort, b->dst, b->orows_wf_run, se, st2);
   } else {
@@ -1543,6 +1573,9 @@ static int mrk_batch_wait_impl(mrk_batch* b) {
   b->stats.n_rerun = 0;
   if (b->packed_run)
     for (uint32_t i = 0; i < b->n_queries; ++i) b->stats.n_cands += b->h_cand_n.p[i];
+  b->stats.bm_words_queued = b->stats.bm_words_pruned = 0;
+  if (b->packed_run)
+    for (uint32_t i = 0; i < b->n_queries; ++i) b->stats.bm_words_queued += b->h_bm_words.p[2 * i], b->stats.bm_words_pruned += b->h_bm_words.p[2 * i + 1];
   if (b->packed_run)
     for (uint32_t i = 0; i < b->n_queries; ++i) {
       if (b->status[i] != MRK_OK) continue;

@@ -34,6 +34,7 @@ struct mrk_ctx {
   int pack = 1;                   // build packed doclists at segment load
   int bitmap_inv = 64;            // terms in >= 1/bitmap_inv of the docs also get a bitmap (0 = never)
   int attr_seq = 1;               // keywords with a bitmap also get their tf / field bytes in slot order (what the bitmap kernel gathers from)
+  int bm_wmax = 1;                // keywords with a bitmap also get a 4-bit largest-tf class per bitmap word: the bitmap kernel drops match words whose best possible weight lies behind the threshold (0 = no plane, the kernel as before)
   int attr_nibbles = 0;           // also build the one-byte tf/field plane the bitmap kernel can gather from (<= 4 fields)
   int bm_target_items = 1 << 20;  // two-bitmap AND kernel: cap of the work items per launch ...
   int bm_min_windows = 256;       // ... and the least windows per work item (a wave's fixed costs show on short runs; 128 until the items were dispatched in window order)
@@ -108,6 +109,7 @@ struct mrk_segment {
   mutable std::vector<SortRange> sort_ranges;
   void* d_bm = nullptr;
   void* d_bm_dir = nullptr;
+  void* d_bm_wmax = nullptr;
   bool bitmaps_on = false; // packed with bitmap_inv != 0: every keyword dense enough for the block scan's direct map carries a bitmap
 };
 

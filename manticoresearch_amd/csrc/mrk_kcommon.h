@@ -66,12 +66,21 @@ __device__ __forceinline__ void wave_lds_fence() {
 // bit k of the result = byte k of w is a varint terminator (bit 7 clear)
 __device__ __forceinline__ uint32_t term4(uint32_t w) { return (((~w & 0x80808080u) >> 7) * 0x10204080u) >> 28; }
 
-__device__ __forceinline__ float term_tfidf(uint32_t tf, float idf) {
+__host__ __device__ __forceinline__ float term_tfidf(uint32_t tf, float idf) {
   // float(hits) / float(hits + 1.2f) * idf  -- searchnode.cpp:2828; no contraction (-ffp-contract=off)
   const float fh = (float)tf;
   const float den = fh + 1.2f;
   const float q = fh / den;
   return q * idf;
+}
+
+// Upper bound of a keyword's tfidf over the postings of a bitmap word whose largest-tf class is cls (DevSegment::bm_wmax: 1..14 = that
+// tf, 15 = 15 and more), in the very floats score() reads from its tfidf table.  idf >= 0: tfidf rises with tf, so the class's own
+// value bounds every posting of the word, and the idf bounds class 15 (tf / (tf + 1.2) never exceeds 1 in fp32; this covers the
+// tf >= 255 escape).  idf < 0: tfidf falls with tf and every posting has tf >= 1.  (tests/cpp/bm_wmax.cpp checks it for every tf up to 300.)
+__host__ __device__ __forceinline__ float bm_wmax_bound(uint32_t cls, float idf) {
+  if (idf < 0.0f) return term_tfidf(1u, idf);
+  return cls == 15u ? idf : term_tfidf(cls, idf);
 }
 
 // bitonic sort of c[0..len) descending, all WG threads; len = a power of two <= CAND (entries past the keys are zeros: a

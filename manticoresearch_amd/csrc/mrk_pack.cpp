@@ -103,7 +103,7 @@ bool validate_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e
 }
 
 bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bool inline_hits, uint64_t bitmap_rows,
-               PackedTerm& out, std::string& err, uint64_t total_rows, uint64_t spp_len, bool wide) {
+               PackedTerm& out, std::string& err, uint64_t total_rows, uint64_t spp_len, bool wide, bool bm_wmax) {
   out = PackedTerm();
   if (!e.docs) return true;
   if (e.doclist_off == 0 || e.doclist_off > spd_len || e.doclist_len > spd_len - e.doclist_off) {
@@ -130,10 +130,11 @@ bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bo
   uint64_t hit_position = 0; // m_uHitPosition / m_iHitlistPos (sphinx.cpp:534, 542)
   out.delta.reserve((size_t)nblk * 32 + 8);
 
-  bool want_bm = bitmap_rows != 0;
+  bool want_bm = bitmap_rows != 0, wmax_bad = false;
   if (want_bm) {
     const uint64_t windows = (bitmap_rows + BM_WINDOW - 1) / BM_WINDOW;
     out.bm.assign((size_t)windows * (BM_WINDOW / 32), 0u);
+    if (bm_wmax) out.wmax.assign(bm_wmax_words(windows), 0);
   }
   uint32_t rowid = 0xFFFFFFFFu; // decoder starts at INVALID_ROWID (sphinx.cpp:12947)
   uint32_t d[128], tf[128], fl[128], rows[128];
@@ -213,9 +214,16 @@ bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bo
       }
       rows[i] = rowid;
       if (want_bm) {
-        if (rowid < bitmap_rows)
+        if (rowid < bitmap_rows) {
           out.bm[rowid >> 5] |= 1u << (rowid & 31u);
-        else
+          if (bm_wmax) { // the word's largest hit count so far, as a class 1..15
+            // (a posting without hits is malformed; its tfidf of 0 would lie above a negative idf's bound: such a term gets no plane)
+            if (!hits) wmax_bad = true;
+            const uint32_t win = rowid >> 11, sh = (win & 3u) * 4u, cls = hits < 1u ? 1u : hits < 15u ? hits : 15u;
+            uint16_t& x = out.wmax[(size_t)(win >> 2) * 64 + ((rowid >> 5) & 63u)];
+            if (((x >> sh) & 15u) < cls) x = (uint16_t)((x & ~(15u << sh)) | (cls << sh));
+          }
+        } else
           want_bm = false; // a rowid beyond the segment's row count: no bitmap for this term
       }
       d[i] = rowid - base;
@@ -266,6 +274,7 @@ bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bo
   out.last_rowid = rowid;
   if (!want_bm) {
     out.bm.clear();
+    out.wmax.clear();
     out.attr2.clear();
   } else {
     const size_t groups = out.bm.size() / (BM_GROUP / 32);
@@ -276,6 +285,7 @@ bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bo
       for (uint32_t i = 0; i < BM_GROUP / 32; ++i) run += (uint32_t)__builtin_popcount(out.bm[g * (BM_GROUP / 32) + i]);
     }
     out.bm_dir[groups] = run;
+    if (wmax_bad) out.wmax.clear();
   }
   return true;
 }

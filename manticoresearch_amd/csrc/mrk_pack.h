@@ -35,18 +35,32 @@ struct PackedTerm {
   // A doc's rank is its slot in the packed arrays above (block = rank >> 7, slot = rank & 127).
   std::vector<uint32_t> bm;
   std::vector<uint32_t> bm_dir;
+  // ... and, with bm_wmax, one nibble per bitmap word: min(15, the largest hit count among the term's postings whose rowid
+  // falls in that word), 0 for an empty word.  Four windows share 64 16-bit words: word wmax[(w >> 2) * 64 + l] holds in nibble
+  // w & 3 the class of word l of window w, so a wave reads its lanes' classes for four aligned windows with one 128-byte load.
+  // The last group is padded with empty windows.  Empty for a term with a posting of no hits (malformed: no bound holds for it).
+  std::vector<uint16_t> wmax;
 };
 
 constexpr uint32_t BM_WINDOW = 2048; // rowids per bitmap window (64 lanes x 32 bits)
 constexpr uint32_t BM_GROUP = 256;   // rowids per rank-directory entry
+constexpr uint32_t BM_WMAX_WINDOWS = 4; // windows per group of the wmax plane (64 16-bit words)
+
+// 16-bit words of a term's wmax plane, and the class of bitmap word `word` (term-local: window * 64 + lane) in it
+inline size_t bm_wmax_words(uint64_t windows) { return (size_t)((windows + BM_WMAX_WINDOWS - 1) / BM_WMAX_WINDOWS) * 64; }
+inline uint32_t bm_wmax_class(const uint16_t* wmax, uint64_t word) {
+  const uint64_t w = word >> 6;
+  return (wmax[(w >> 2) * 64 + (word & 63u)] >> ((w & 3u) * 4u)) & 15u;
+}
 
 // returns false and sets err on input it cannot pack; err starts with "corrupt:" when the bytes are malformed (truncated
 // entries, descending rowids, rowids >= total_rows, hitlist offsets >= spp_len; the last two only when the limit is
 // given) -- as opposed to well-formed input beyond the packed format (field masks wider than 8 bits in the narrow layout)
 // bitmap_rows: 0 = no bitmap; else the segment's row count (every rowid of the term must be below it)
+// bm_wmax: with a bitmap, also build the per-word tf-class plane (PackedTerm::wmax)
 // wide: the layout of a segment with 9-32 fields -- every mask fits, it goes to out.fmask
 bool pack_term(const uint8_t* spd, uint64_t spd_len, const mrk_dict_entry& e, bool inline_hits, uint64_t bitmap_rows,
-               PackedTerm& out, std::string& err, uint64_t total_rows = 0, uint64_t spp_len = 0, bool wide = false);
+               PackedTerm& out, std::string& err, uint64_t total_rows = 0, uint64_t spp_len = 0, bool wide = false, bool bm_wmax = false);
 
 // Validate-only walk of one term's doclist: every entry decodes, rowids ascend and stay below total_rows, hitlist
 // offsets stay below spp_len, the terminator sits where the dictionary's doc count says.  false + err ("corrupt: ...")

@@ -22,6 +22,11 @@
 // dead-row words and tf / field lines are requested by the waves of one CU at nearly the same time and a shared keyword's
 // lines come from L2 for all but the first of them.  All per-query state is per wave; the tfidf tables are one per distinct
 // keyword of the group, the field-weight table one per workgroup (members have the same field weights).
+//
+// WMAX instances (a segment with the per-word tf-class plane, DevSegment::bm_wmax, ctx key bm_wmax): the lanes' classes of both
+// keywords ride along with a burst's bitmap words (one coalesced 128-byte load per keyword and four windows), and a match word
+// whose best possible weight lies in a bin behind the query's threshold is counted and dropped before it is queued -- never
+// unpacked, none of its tf / field words requested.  BM25 in relevance order without field limits; everything else runs as before.
 #include "mrk_kcommon.h"
 #include "mrk_kprune.h"
 
@@ -52,17 +57,27 @@ struct __align__(16) BmWaveLds {
   uint16_t wpre[BM_WQCAP]; // final drain: matches held by the queue entries before this one (<= 128 x 32)
 };
 
-template <bool GROUP>
-struct __align__(16) BmSmem {
+// WMAX instances: per tfidf table, the keyword's tfidf bound by tf class (bm_wmax_bound, mrk_kcommon.h); 320 B for a group -- 23360 B,
+// still 7 workgroups per CU
+template <int N>
+struct BmBound {
+  float wbound[N][16];
+};
+template <>
+struct BmBound<0> {};
+
+template <bool GROUP, bool WMAX>
+struct __align__(16) BmSmem : BmBound<WMAX ? (GROUP ? BM_GROUP_TABS : 2) : 0> {
   BmWaveLds w[WAVES];
   uint32_t rank[256];
   float tfidf[GROUP ? BM_GROUP_TABS : 2][256];
 };
 
 // SEQ: the segment holds the dense keywords' tf / field bytes in slot order (DevSegment::pk_attr2) and the gathers read those
-template <bool SEQ, bool GROUP>
+// WMAX: the segment carries the per-word tf-class plane (DevSegment::bm_wmax) -- the instances without it are the kernel as it was
+template <bool SEQ, bool GROUP, bool WMAX>
 __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
-  __shared__ BmSmem<GROUP> s;
+  __shared__ BmSmem<GROUP, WMAX> s;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   const uint32_t wave = GROUP ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6; // (GROUP: the wave's query is read with scalar loads)
   if (blockIdx.x >= a.n_items) return;
@@ -78,7 +93,10 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
     ia = (G->tab_idx >> (6u * member)) & 7u, ib = (G->tab_idx >> (6u * member + 3u)) & 7u;
     for (uint32_t j = 0; j < G->ntab; ++j) {
       const uint32_t src = G->tab_src[j];
-      s.tfidf[j][tid] = term_tfidf(tid, a.queries[G->q[src >> 1]].t[src & 1u].idf);
+      const float idf = a.queries[G->q[src >> 1]].t[src & 1u].idf;
+      s.tfidf[j][tid] = term_tfidf(tid, idf);
+      if constexpr (WMAX)
+        if (tid < 16u) s.wbound[j][tid] = bm_wmax_bound(tid, idf);
     }
   }
   const DevQuery* __restrict__ Q = a.queries + qi;
@@ -91,6 +109,8 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
   if (!GROUP) {
     s.tfidf[0][tid] = term_tfidf(tid, TA.idf);
     s.tfidf[1][tid] = term_tfidf(tid, TB.idf);
+    if constexpr (WMAX)
+      if (tid < 16u) s.wbound[0][tid] = bm_wmax_bound(tid, TA.idf), s.wbound[1][tid] = bm_wmax_bound(tid, TB.idf);
   }
   {
     const uint32_t nwr = GROUP ? (QR->n_weights < 8u ? QR->n_weights : 8u) : nw;
@@ -121,7 +141,34 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
   // rowids, so matches are counted straight off the match words, tf / field bytes are never fetched, and windows
   // that lie wholly behind the pruning threshold are not even unpacked
   const uint32_t field_all = nw >= 32u ? 0xFFFFFFFFu : (1u << nw) - 1u;
-  const bool none_fast = ranker == MRK_RANK_NONE && (TA.queried32 & field_all) == field_all && (TB.queried32 & field_all) == field_all;
+  const bool all_fields = (TA.queried32 & field_all) == field_all && (TB.queried32 & field_all) == field_all;
+  const bool none_fast = ranker == MRK_RANK_NONE && all_fields;
+  // BM25 in relevance order without field limits, over a segment with the per-word tf-class plane (DevSegment::bm_wmax): the two
+  // classes of a match word bound the weight of every match in it -- with score()'s own operations on upper bounds of its inputs,
+  // each of them monotone, so no epsilon is needed.  A word whose bound falls in a bin behind the threshold is counted and dropped
+  // before it is queued: it is never unpacked and none of its tf / field words is requested.  Every match of such a query is live
+  // (dead rows are masked out of the match word, every field is queried, a posting's field byte is never 0), so the count is exact.
+  // (the bins' fallback geometry -- bins_by_weight found weights that do not fit 32 bits -- stays out: a product may wrap there;
+  // so does an index_weight that is not positive: the planner passes a negative one through, and multiplying by it turns the order
+  // round, so an upper bound of the sum would be a lower bound of the weight)
+  const bool wprune = WMAX && ranker == MRK_RANK_BM25 && all_fields && bin_mode == BIN_WEIGHT && Q->sort_on == 0 &&
+                      (int32_t)index_weight > 0 && !(bin_lo == INT32_MIN && bin_shift == 31u);
+  const uint16_t* __restrict__ wmA = nullptr;
+  const uint16_t* __restrict__ wmB = nullptr;
+  const float* __restrict__ bndA = nullptr;
+  const float* __restrict__ bndB = nullptr;
+  if constexpr (WMAX) { // (launch_scan_bm takes these instances only for a segment with the plane)
+    wmA = a.seg.bm_wmax + (TA.bm_off >> 2), wmB = a.seg.bm_wmax + (TB.bm_off >> 2);
+    bndA = s.wbound[ia], bndB = s.wbound[ib];
+  }
+  // the largest field-weight sum a match can get: every field with a positive weight (a launch constant of the workgroup)
+  uint32_t rmax1000 = 0;
+  if (wprune) {
+    const uint32_t nwr = GROUP ? (QR->n_weights < 8u ? QR->n_weights : 8u) : nw;
+    for (uint32_t f = 0; f < nwr; ++f) rmax1000 += QR->weights[f] > 0 ? (uint32_t)QR->weights[f] : 0u;
+    rmax1000 *= 1000u;
+  }
+  uint32_t n_queued = 0, n_pruned = 0; // per lane: match words of a wprune wave that went on the queue / were dropped
 
   const uint32_t nwin = item.blk_end - item.blk_begin;
   const uint32_t part = (nwin + per - 1) / per;
@@ -295,6 +342,16 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
         if (dead) dv[i] = dead[o];
       }
     }
+    // the lane's tf classes of the burst's windows, window wb + i in nibble i: one 16-bit word per keyword where the burst starts
+    // at a multiple of four windows, the next group's word too where it does not (segment ends, ceil(nwin / per) parts)
+    uint32_t ca4 = 0, cb4 = 0;
+    if (wprune && nb) {
+      static_assert(BM_BURST <= 4, "a burst's classes come from at most two groups of four windows");
+      const uint32_t g0 = wb >> 2, g1 = (wb + nb - 1u) >> 2, sh = (wb & 3u) * 4u;
+      ca4 = wmA[(uint64_t)g0 * 64 + lane], cb4 = wmB[(uint64_t)g0 * 64 + lane];
+      if (g1 != g0) ca4 |= (uint32_t)wmA[(uint64_t)g1 * 64 + lane] << 16, cb4 |= (uint32_t)wmB[(uint64_t)g1 * 64 + lane] << 16;
+      ca4 >>= sh, cb4 >>= sh;
+    }
 #if MRK_BMEXP != 1
     // the query's shared pruning threshold rides along with every 4th burst (every wave of the query reads the one word: with
     // every burst the reads cost 0.18 of the launch's 2.76 ms, without any the candidate lists grow by a quarter)
@@ -326,6 +383,21 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
         total += __popc(m);
         m = 0;
 #endif
+        if (wprune && m) {
+          const uint32_t ca = (ca4 >> (4 * i)) & 15u, cb = (cb4 >> (4 * i)) & 15u;
+          const float ta = bndA[ca], tb = bndB[cb];
+          float acc = 0.0f + ta; // score()'s operations, in its order
+          acc = acc + tb;
+          const int32_t bmw = (int32_t)((acc + 0.5f) * 1000.0f);
+          uint32_t weight = (uint32_t)bmw + rmax1000;
+          weight *= index_weight;
+          if (weight_bin(bin_lo, bin_shift, (int32_t)weight) < tau_bin) {
+            total += (uint32_t)__popc(m); // (score() counts the matches of the words that go on)
+            m = 0;
+            ++n_pruned;
+          } else
+            ++n_queued;
+        }
         // A window holds a dozen matches in its 64 words: unpacking it on the spot would run the bit loop with a fifth of
         // the lanes busy.  Its non-empty words are queued instead (one ballot, no loop) and unpacked 64 words at a time.
         const bool has = m != 0;
@@ -394,13 +466,24 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
     for (int dlt = 32; dlt; dlt >>= 1) t += __shfl_down(t, dlt, 64);
     if (lane == 0 && t) atomicAdd((unsigned long long*)(a.q_total + oq), (unsigned long long)t);
   }
+  if (wprune) { // mrk_batch_stats.bm_words_queued / bm_words_pruned
+    uint32_t nq = n_queued, np = n_pruned;
+    for (int dlt = 32; dlt; dlt >>= 1) nq += __shfl_down(nq, dlt, 64), np += __shfl_down(np, dlt, 64);
+    if (lane == 0 && nq) atomicAdd(gcount + QC_BM_QUEUED, nq);
+    if (lane == 0 && np) atomicAdd(gcount + QC_BM_PRUNED, np);
+  }
 }
 
 void launch_scan_bm(const ScanArgs& a, void* stream) {
   if (!a.n_items) return;
   const bool seq = a.seg.pk_attr2 && !a.seg.pk_attr1;
-  void (*k)(ScanArgs) = a.bm_groups ? (seq ? scan_bm_kernel<true, true> : scan_bm_kernel<false, true>)
-                                    : (seq ? scan_bm_kernel<true, false> : scan_bm_kernel<false, false>);
+  void (*k)(ScanArgs);
+  if (a.seg.bm_wmax)
+    k = a.bm_groups ? (seq ? scan_bm_kernel<true, true, true> : scan_bm_kernel<false, true, true>)
+                    : (seq ? scan_bm_kernel<true, false, true> : scan_bm_kernel<false, false, true>);
+  else
+    k = a.bm_groups ? (seq ? scan_bm_kernel<true, true, false> : scan_bm_kernel<false, true, false>)
+                    : (seq ? scan_bm_kernel<true, false, false> : scan_bm_kernel<false, false, false>);
   hipLaunchKernelGGL(k, dim3(a.n_items), dim3(WG), 0, (hipStream_t)stream, a);
 }
 

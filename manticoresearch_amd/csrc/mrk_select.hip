@@ -286,6 +286,10 @@ __global__ __launch_bounds__(WG) void sel_sort_kernel(SelectArgs a) {
     if (a.h_total) a.h_total[q] = a.q_total[q];
     if (a.h_flags) a.h_flags[q] = a.q_flags[q];
     if (a.h_cand_n) a.h_cand_n[q] = a.q_cand_n[(size_t)q * QSTRIDE];
+    if (a.h_bm_words) {
+      a.h_bm_words[2 * q] = a.q_cand_n[(size_t)q * QSTRIDE + QC_BM_QUEUED];
+      a.h_bm_words[2 * q + 1] = a.q_cand_n[(size_t)q * QSTRIDE + QC_BM_PRUNED];
+    }
   }
 }
 
