@@ -372,12 +372,17 @@ void mrk_segment_destroy(mrk_segment* seg);
    for the context's running batches, so a search sees either the old or the new map. */
 int mrk_segment_set_dead_rows(mrk_segment* seg, const uint32_t* bitmap, uint64_t n_rows);
 /* Row-wise attribute storage (.spa: CSphRowitem rows[n_rows][stride], sphinx.cpp GetDocinfoByRowID) copied to HBM for the
-   filters of mrk_query; rows = NULL drops it.  Waits for the context's running batches like mrk_segment_set_dead_rows. */
+   filters of mrk_query; rows = NULL drops it.  Waits for the context's running batches like mrk_segment_set_dead_rows.
+   A blob pool the segment holds (mrk_segment_set_blobs) was walked against the OLD rows' blob offsets: every call here drops it,
+   and MVA filters are declined (MRK_E_UNSUPPORTED, "need the segment's blob pool") until mrk_segment_set_blobs is called again. */
 int mrk_segment_set_attrs(mrk_segment* seg, const uint32_t* rows, uint32_t stride_dwords, uint64_t n_rows);
 /* The blob pool of the attribute storage (.spb file / RtSegment_t::m_dBlobs: per row a blob row = length-size byte, cumulative
-   lengths, data; attribute.cpp:495-513) copied to HBM for MVA filters.  rows / stride / n_rows = the rows given to
-   mrk_segment_set_attrs: every row's blob row is walked here once (offset, header and lengths inside the pool), so that
-   untrusted bytes never become an out-of-bounds device read.  pool = NULL drops it. */
+   lengths, data; attribute.cpp:495-513) copied to HBM for MVA filters.  Call it AFTER mrk_segment_set_attrs: the blob row of every
+   row the segment HOLDS is walked here once (offset, header and lengths inside the pool), so that untrusted bytes never become an
+   out-of-bounds device read -- the kernels follow the blob offsets of those rows and of no others.  rows / stride / n_rows = the
+   very rows given to mrk_segment_set_attrs: MRK_E_INVAL when the segment holds no rows, or when they differ from the ones it holds
+   (stride, or any dword of the segment's rows); MRK_E_FORMAT when a blob row leaves the pool.  Nothing is installed then.
+   pool = NULL drops it. */
 int mrk_segment_set_blobs(mrk_segment* seg, const uint8_t* pool, uint64_t pool_len, uint32_t n_blob_attrs, const uint32_t* rows,
                           uint32_t stride_dwords, uint64_t n_rows);
 /* device bytes held, and the reference-format doclist bytes of one term */

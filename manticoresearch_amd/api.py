@@ -583,7 +583,8 @@ class Segment:
         return int(lib().mrk_segment_device_bytes(self._h))
 
     def set_attrs(self, rows: Optional[np.ndarray]) -> None:
-        """Upload the row-wise attribute storage (.spa rows: uint32 [n_rows, stride]) for Query.filters; None drops it."""
+        """Upload the row-wise attribute storage (.spa rows: uint32 [n_rows, stride]) for Query.filters; None drops it.
+        A blob pool given before (set_blobs) is dropped with the old rows: MVA filters are declined until set_blobs is called again."""
         if rows is None:
             check(lib().mrk_segment_set_attrs(self._h, None, 0, 0))
             self._attrs = None
@@ -594,8 +595,9 @@ class Segment:
         self._attrs = a  # (Batcher.search reads a sorted query's sort_key from it)
 
     def set_blobs(self, pool: Optional[np.ndarray], n_blob_attrs: int = 0, rows: Optional[np.ndarray] = None) -> None:
-        """Upload the blob pool (.spb bytes / an RT segment's m_dBlobs) for MVA filters; rows = the attribute rows given to
-        set_attrs (every row's blob row is bounds-checked against the pool here).  None drops it."""
+        """Upload the blob pool (.spb bytes / an RT segment's m_dBlobs) for MVA filters, after set_attrs; rows = the very attribute
+        rows given to set_attrs.  The blob row of every row the segment holds is bounds-checked against the pool here; MrkError when
+        the segment holds no rows, when `rows` differ from them, or when a blob row leaves the pool.  None drops it."""
         if pool is None:
             check(lib().mrk_segment_set_blobs(self._h, None, 0, 0, None, 0, 0))
             return

@@ -68,8 +68,9 @@ struct DevFilter { // mrk_filter with the values inline
 };
 
 // ISphFilter::Eval over the row's attributes: Filter_Values (binary search in the reference, <= 8 values here),
-// Filter_Range (EvalRange, sphinxfilter.h:130-143), FilterNot for m_bExclude; Filter_And over the query's filters
-__device__ __forceinline__ bool row_passes_filters(const DevSegment& seg, const DevFilter* __restrict__ fl, uint32_t n, uint32_t rowid) {
+// Filter_Range (EvalRange, sphinxfilter.h:130-143), FilterNot for m_bExclude; Filter_And over the query's filters.
+// (__host__ too: tests/cpp/filter_edges.cpp runs this very function on the CPU under AddressSanitizer)
+__host__ __device__ __forceinline__ bool row_passes_filters(const DevSegment& seg, const DevFilter* __restrict__ fl, uint32_t n, uint32_t rowid) {
   const uint32_t* __restrict__ row = seg.attrs + (uint64_t)rowid * seg.attr_stride;
   bool ok = true;
   for (uint32_t i = 0; i < n; ++i) {
@@ -147,7 +148,7 @@ __device__ __forceinline__ bool row_passes_filters(const DevSegment& seg, const 
       pass = false;
       for (uint32_t k = 0; k < F.n_values; ++k) pass = pass || v == F.values[k];
     } else if ((F.kind & 0xffu) == MRK_FILTER_FLOATRANGE) { // Filter_FloatRange::Eval (sphinxfilter.cpp:286-289): both bounds, always
-      const float fv = __uint_as_float((uint32_t)v), flo = __uint_as_float((uint32_t)F.lo), fhi = __uint_as_float((uint32_t)F.hi);
+      const float fv = __builtin_bit_cast(float, (uint32_t)v), flo = __builtin_bit_cast(float, (uint32_t)F.lo), fhi = __builtin_bit_cast(float, (uint32_t)F.hi);
       const bool eq_min = (F.kind >> 9) & 1u, eq_max = (F.kind >> 10) & 1u;
       pass = (eq_min ? fv >= flo : fv > flo) && (eq_max ? fv <= fhi : fv < fhi);
     } else {
@@ -162,7 +163,7 @@ __device__ __forceinline__ bool row_passes_filters(const DevSegment& seg, const 
 }
 
 // CSphQueryContext::m_pWeightFilter: Filter_WeightValues / Filter_WeightRange over the match weight (sphinxfilter.cpp:304-320)
-__device__ __forceinline__ bool weight_passes_filters(const DevFilter* __restrict__ fl, uint32_t n, int32_t weight) {
+__host__ __device__ __forceinline__ bool weight_passes_filters(const DevFilter* __restrict__ fl, uint32_t n, int32_t weight) {
   bool ok = true;
   const int64_t v = (int64_t)weight;
   for (uint32_t i = 0; i < n; ++i) {

@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "mrk_blobrow.h"
 #include "mrk_dev.h"
 #include "mrk_pack.h"
 
@@ -459,6 +460,12 @@ static int mrk_segment_set_attrs_impl(mrk_segment* s, const uint32_t* rows, uint
   }
   if (s->d_attrs) (void)hipFree(s->d_attrs);
   s->d_attrs = fresh;
+  // a blob pool was walked against the OLD rows' blob offsets: it leaves with them (MVA filters are declined until
+  // mrk_segment_set_blobs walks the new rows)
+  if (s->d_blobs) (void)hipFree(s->d_blobs);
+  s->d_blobs = nullptr;
+  s->dev.blobs = nullptr;
+  s->n_blob_attrs = 0;
   s->sort_ranges.clear(); // (the cached column ranges of sorted queries belong to the old rows)
   if (rows) {
     try {
@@ -477,29 +484,21 @@ static int mrk_segment_set_attrs_impl(mrk_segment* s, const uint32_t* rows, uint
 }
 
 // The blob pool for MVA filters.  Every row's blob row is walked on the host first (attribute.cpp:495-513: length-size byte,
-// n cumulative lengths, data): what the device later dereferences without a check was inside the pool at load.
+// n cumulative lengths, data): what the device later dereferences without a check was inside the pool at load.  The rows walked are
+// the ones the segment HOLDS (the device copy's source, h_attrs) -- the kernel reads the blob offsets of those and of no others; the
+// caller's rows must be the same ones, and a later mrk_segment_set_attrs drops the pool.
 static int mrk_segment_set_blobs_impl(mrk_segment* s, const uint8_t* pool, uint64_t len, uint32_t n_blob, const uint32_t* rows, uint32_t stride, uint64_t n_rows) {
   if (!s || !s->ctx) return mrk_fail(MRK_E_INVAL, "mrk_segment_set_blobs: NULL segment");
   if (pool) {
     if (!rows || stride < 4 || n_rows < s->total_docs) return mrk_fail(MRK_E_INVAL, "mrk_segment_set_blobs: needs the segment's attribute rows (stride >= 4 dwords: id + blob locator)");
     if (n_blob < 1 || n_blob > 255) return mrk_fail(MRK_E_INVAL, "mrk_segment_set_blobs: %u blob attributes", n_blob);
-    for (uint64_t r = 0; r < s->total_docs; ++r) {
-      const uint32_t* row = rows + r * stride;
-      const uint64_t off = (uint64_t)row[2] | ((uint64_t)row[3] << 32);
-      if (off >= len) return mrk_fail(MRK_E_FORMAT, "row %llu: blob offset %llu past the pool (%llu bytes)", (unsigned long long)r, (unsigned long long)off, (unsigned long long)len);
-      const uint8_t* br = pool + off;
-      if (br[0] > 2) return mrk_fail(MRK_E_FORMAT, "row %llu: blob row type %u", (unsigned long long)r, br[0]);
-      const uint32_t sz = br[0] == 0 ? 1u : br[0] == 1 ? 2u : 4u;
-      const uint64_t head = 1ull + (uint64_t)n_blob * sz;
-      if (len - off < head) return mrk_fail(MRK_E_FORMAT, "row %llu: blob row header past the pool", (unsigned long long)r);
-      uint64_t prev = 0;
-      for (uint32_t a = 0; a < n_blob; ++a) {
-        uint64_t l = 0;
-        for (uint32_t i = 0; i < sz; ++i) l |= (uint64_t)br[1 + a * sz + i] << (8 * i);
-        if (l < prev || l > len - off - head) return mrk_fail(MRK_E_FORMAT, "row %llu: blob attribute %u runs past the pool", (unsigned long long)r, a);
-        prev = l;
-      }
-    }
+    const size_t held = (size_t)s->total_docs * stride;
+    if (!s->dev.attrs || s->h_attrs.size() < held || s->dev.attr_stride != stride)
+      return mrk_fail(MRK_E_INVAL, "mrk_segment_set_blobs: the segment holds no attribute rows of %u dwords (mrk_segment_set_attrs comes first)", stride);
+    if (held && memcmp(rows, s->h_attrs.data(), held * 4) != 0)
+      return mrk_fail(MRK_E_INVAL, "mrk_segment_set_blobs: the rows differ from the ones given to mrk_segment_set_attrs");
+    char why[160];
+    if (!blob_rows_inside_pool(pool, len, n_blob, s->h_attrs.data(), stride, s->total_docs, why, sizeof why)) return mrk_fail(MRK_E_FORMAT, "%s", why);
   }
   HIP_TRY(hipSetDevice(s->ctx->device));
   HIP_TRY(hipDeviceSynchronize());

@@ -149,7 +149,7 @@ def build_blob_pool(rows_values, header: int = 8):
     offs = []
     for vals in rows_values:
         total = sum(len(v) for v in vals)
-        kind = 0 if total < 256 else 1 if total < 65536 else 2
+        kind = 0 if total < 0xFF else 1 if total < 0xFFFF else 2  # CalcBlobRowFlags (attribute.cpp:28-37)
         sz = (1, 2, 4)[kind]
         offs.append(len(pool))
         pool.append(kind)
