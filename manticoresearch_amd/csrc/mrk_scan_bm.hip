@@ -79,7 +79,7 @@ template <bool SEQ, bool GROUP, bool WMAX>
 __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
   __shared__ BmSmem<GROUP, WMAX> s;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
-  const uint32_t wave = GROUP ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6; // (GROUP: the wave's query is read with scalar loads)
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6); // (uniform: the wave's query is read with scalar loads, its streams have scalar bases)
   if (blockIdx.x >= a.n_items) return;
   const DevItem item = a.items[blockIdx.x];
   // the wave's query and its share of the item's windows: part `sub` of `per`
@@ -327,39 +327,57 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
     return (uint32_t)__popcll(bal);
   };
 
-  for (uint32_t wb = w0, it = 0; gsync ? it < nburst : wb < w1; wb += BM_BURST, ++it) {
-    // BM_BURST windows requested back to back (one memory round trip per burst)
-    const uint32_t nb = (gsync && wb >= w1) ? 0u : w1 - wb < (uint32_t)BM_BURST ? w1 - wb : (uint32_t)BM_BURST;
-    if (gsync && it % (BM_GSYNC > 0 ? BM_GSYNC : 1) == 0 && it) __syncthreads();
-    uint32_t av[BM_BURST], bv[BM_BURST], dv[BM_BURST];
+  // The burst after the one being worked is always in flight: its bitmap, dead-row and class words (and the threshold poll, when one
+  // is due) are requested before this burst's windows are worked and taken over at the next loop top, the one place that waits for
+  // them.  Each stream is a wave-uniform base plus the lane's 32-bit offset.  The values stay as they were loaded until then -- an
+  // operation on one of them here would wait for it at once.
+  static_assert(BM_BURST <= 4, "a burst's classes come from at most two groups of four windows");
+  uint32_t nav[BM_BURST], nbv[BM_BURST], ndv[BM_BURST], nca = 0, ncb = 0, ngt = 0;
+  auto fetch = [&](const uint32_t wb) __attribute__((always_inline)) {
+    const uint32_t nb = wb >= w1 ? 0u : w1 - wb < (uint32_t)BM_BURST ? w1 - wb : (uint32_t)BM_BURST;
+    const uint32_t* __restrict__ pa = bmA + (uint64_t)wb * BM_WORDS;
+    const uint32_t* __restrict__ pb = bmB + (uint64_t)wb * BM_WORDS;
+    const uint32_t* __restrict__ pd = dead ? dead + (uint64_t)wb * BM_WORDS : nullptr;
 #pragma unroll
     for (int i = 0; i < BM_BURST; ++i) {
-      av[i] = bv[i] = dv[i] = 0;
+      nav[i] = nbv[i] = ndv[i] = 0;
       if ((uint32_t)i < nb) {
-        const uint64_t o = (uint64_t)(wb + i) * BM_WORDS + lane;
-        av[i] = bmA[o];
-        bv[i] = bmB[o];
-        if (dead) dv[i] = dead[o];
+        nav[i] = pa[(uint32_t)i * BM_WORDS + lane];
+        nbv[i] = pb[(uint32_t)i * BM_WORDS + lane];
+        if (pd) ndv[i] = pd[(uint32_t)i * BM_WORDS + lane];
       }
     }
-    // the lane's tf classes of the burst's windows, window wb + i in nibble i: one 16-bit word per keyword where the burst starts
-    // at a multiple of four windows, the next group's word too where it does not (segment ends, ceil(nwin / per) parts)
-    uint32_t ca4 = 0, cb4 = 0;
-    if (wprune && nb) {
-      static_assert(BM_BURST <= 4, "a burst's classes come from at most two groups of four windows");
-      const uint32_t g0 = wb >> 2, g1 = (wb + nb - 1u) >> 2, sh = (wb & 3u) * 4u;
-      ca4 = wmA[(uint64_t)g0 * 64 + lane], cb4 = wmB[(uint64_t)g0 * 64 + lane];
-      if (g1 != g0) ca4 |= (uint32_t)wmA[(uint64_t)g1 * 64 + lane] << 16, cb4 |= (uint32_t)wmB[(uint64_t)g1 * 64 + lane] << 16;
-      ca4 >>= sh, cb4 >>= sh;
-    }
+    // the lane's tf classes of the burst's windows: one 16-bit word per keyword, the group of four windows the burst starts in
+    nca = ncb = 0;
+    if (wprune && nb) nca = (wmA + (uint64_t)(wb >> 2) * 64)[lane], ncb = (wmB + (uint64_t)(wb >> 2) * 64)[lane];
+    ngt = 0;
 #if MRK_BMEXP != 1
     // the query's shared pruning threshold rides along with every 4th burst (every wave of the query reads the one word: with
     // every burst the reads cost 0.18 of the launch's 2.76 ms, without any the candidate lists grow by a quarter)
-    if (((wb - w0) / BM_BURST & 3u) == 0) {
-      const uint32_t gt = __hip_atomic_load(gtaubin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (gt > tau_bin) tau_bin = gt;
-    }
+    if (nb && ((wb - w0) / BM_BURST & 3u) == 0) ngt = __hip_atomic_load(gtaubin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
+  };
+  fetch(w0);
+  // (the first burst is waited for here and not at its first use inside the loop: vmcnt counts in order, so a wait the loop body
+  // holds for the sake of its first pass would wait for the words every later pass has just requested)
+  __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
+  for (uint32_t wb = w0, it = 0; gsync ? it < nburst : wb < w1; wb += BM_BURST, ++it) {
+    const uint32_t nb = (gsync && wb >= w1) ? 0u : w1 - wb < (uint32_t)BM_BURST ? w1 - wb : (uint32_t)BM_BURST;
+    if (gsync && it % (BM_GSYNC > 0 ? BM_GSYNC : 1) == 0 && it) __syncthreads();
+    uint32_t av[BM_BURST], bv[BM_BURST], dv[BM_BURST];
+    uint32_t ca4 = 0, cb4 = 0; // the classes of window wb + i in nibble i
+#pragma unroll
+    for (int i = 0; i < BM_BURST; ++i) av[i] = nav[i], bv[i] = nbv[i], dv[i] = ndv[i];
+    // (a burst that starts off a multiple of four windows -- segment ends, ceil(nwin / per) parts -- reaches into the next group: its
+    // word is fetched here, before the next burst is requested, and waited for on the spot)
+    if (wprune && nb) {
+      const uint32_t g0 = wb >> 2, g1 = (wb + nb - 1u) >> 2, sh = (wb & 3u) * 4u;
+      ca4 = nca, cb4 = ncb;
+      if (g1 != g0) ca4 |= (uint32_t)(wmA + (uint64_t)g1 * 64)[lane] << 16, cb4 |= (uint32_t)(wmB + (uint64_t)g1 * 64)[lane] << 16;
+      ca4 >>= sh, cb4 >>= sh;
+    }
+    if (ngt > tau_bin) tau_bin = ngt;
+    fetch(wb + BM_BURST);
 #pragma unroll
     for (int i = 0; i < BM_BURST; ++i) {
       if ((uint32_t)i < nb) {
