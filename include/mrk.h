@@ -13,6 +13,8 @@
  *   mrk_batch_submit     <- sphCreateRanker + the MatchExtended loop
  *                           (sphinxsearch.cpp:4167-4380; sphinx.cpp:12190-12269):
  *                           ExtNode_i::Create, IDF setup, GetMatches() until exhausted
+ *   mrk_batch_submit_grouped <- the same with the grouping sorter in place of the plain queue for queries that carry a
+ *                           mrk_group: CSphKBufferGroupSorter::PushEx / FinalizeMatches (sphinxsort.cpp:2961-3310)
  *   mrk_result           <- what the caller reads back from ISphMatchSorter:
  *                           Flatten() order + GetTotalCount() (sphinxsort.h:39-133,
  *                           sphinxsort.cpp:627-641, 724) and CSphQueryStats (sphinx.h:2697-2705)
@@ -213,6 +215,33 @@ typedef struct {
 #define MRK_ORDER_WEIGHT_FIRST_DESC ( MRK_ORDER_WEIGHT_FIRST | 1 )
 #define MRK_ORDER_WEIGHT_FIRST_ASC ( MRK_ORDER_WEIGHT_FIRST | 2 )
 
+/* GROUP BY one integer row attribute (CSphQuery::m_sGroupBy with m_eGroupFunc = SPH_GROUPBY_ATTR; the grouping sorter
+   CSphKBufferGroupSorter, sphinxsort.cpp:2961-3310).  The group key is the locator's raw bits (1..32 bits inside one dword: uint,
+   timestamp, bool, bit-field), compared unsigned.  Per group the sorter keeps ONE head match and a counter (PushEx, :3148-3205;
+   PushIntoExistingGroup, :3112-3145): the head is the group's best match in the default within-group order -- m_sSortBy
+   "@weight desc" (searchdsql.cpp:25) / SPH_SORT_RELEVANCE: weight DESC, then global rowid ASC (MatchRelevanceLt_fn) --, @count the
+   number of the group's matches that reached the sorter (past dead rows, attribute filters and weight filters; the weight carries
+   index_weight).  The groups leave in the order sort_by names -- the group key (@groupby), @count or the head's weight, descending
+   or ascending -- then the head's global rowid ascending (MatchGeneric1_fn, :4708-4720; FinalizeMatches, :3233-3300): the best
+   min(groups, max_matches) of them, total_found = the number of groups (++m_iTotal on a new group only).
+   Exact or declined.  The reference keeps max_matches * GROUPBY_FACTOR (= 4, :2767) groups and then starts to cut the worst
+   (CutWorst, :3176), after which its answer depends on the order the matches arrived in.  A query with at most 4 * max_matches
+   distinct group values is answered exactly as the reference answers it in any arrival order; one with more is declined WHILE IT
+   RUNS: status MRK_E_UNSUPPORTED, a message that names the limit, exchange rows with MRK_ROW_DECLINED -- never a truncated answer.
+   Declined at plan time with MRK_E_UNSUPPORTED: a group next to mrk_query.sort / mrk_query.order, cutoff next to a group, a
+   blob-stored attribute (bit_offset < 0), a 64-bit one, a segment without attribute rows, the VLB-direct path.  MRK_E_INVAL before a
+   row is read: locators outside the row or straddling a dword, bit_count 0 or > 32 (other than an aligned 64 inside the row),
+   an unknown sort_by, desc outside 0 / 1.  A grouped query is routed as a sorted one (packed block-scan path; hit-ranked shapes
+   through the match queue) and whatever declines a sort declines a group.  Groups of different segments are not merged on the
+   device (that merge adds counts per key): a grouped query leaves in narrow, wide and order rows with MRK_ROW_DECLINED, no keys
+   and spec word 0.  mrk_batcher_search takes no group. */
+enum { MRK_GROUPSORT_KEY = 0, MRK_GROUPSORT_COUNT = 1, MRK_GROUPSORT_WEIGHT = 2 };
+typedef struct {
+  int32_t bit_offset, bit_count; /* CSphAttrLocator of the group-by attribute */
+  int32_t sort_by;               /* MRK_GROUPSORT_*: what orders the groups */
+  int32_t desc;                  /* 1 = descending */
+} mrk_group;
+
 /* CSphQuery fields that reach the ranker + the query tree */
 typedef struct {
   const mrk_node* nodes;
@@ -257,6 +286,9 @@ typedef struct {
   const uint64_t* order_key; /* a query with mrk_query.order: per returned row the raw 64-bit value of an INT64 part; else the first part's raw
                                 value in the high dword and the second's (or 0) in the low dword.  Read from the segment's rows like sort_key,
                                 which stays NULL for such a query; NULL for every other query and for mrk_batcher_search */
+  const uint32_t* group_key;   /* a grouped query (mrk_batch_submit_grouped): the raw group value of every returned row, whose rowid / weight
+                                  are the group's head's; NULL for every other query */
+  const uint32_t* group_count; /* ... and @count, the group's matches; NULL likewise */
 } mrk_result;
 
 typedef struct {
@@ -416,6 +448,9 @@ int mrk_batch_create(mrk_ctx* ctx, uint32_t max_queries, mrk_batch** out);
 void mrk_batch_destroy(mrk_batch* b);
 /* plan on host, copy descriptors, launch kernels, start the result copy; returns at once */
 int mrk_batch_submit(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n_queries);
+/* mrk_batch_submit with a group per query (sphCreateQueue picking the grouping sorter for a query with m_sGroupBy,
+   sphinxsort.cpp): groups[i] == NULL = query i is not grouped; groups == NULL = mrk_batch_submit */
+int mrk_batch_submit_grouped(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, uint32_t n_queries);
 /* block until the results of the last submit are in host memory; a query that fails here (its result's status != MRK_OK,
    e.g. out of generic-evaluator memory) leaves the reason in mrk_last_error() */
 int mrk_batch_wait(mrk_batch* b);

@@ -31,6 +31,17 @@
 // (attribute filters: integer VALUES / RANGE, FLOATRANGE, MVA any / all; weight filters) only if FlattenXQ could hand every
 // one of them to the device; a weight filter next to a cutoff stays on the CPU (the cutoff counts matches in rowid order
 // AFTER the weight filter, sphinx.cpp:12223-12267; the device's cutoff probe runs without weights).
+//
+// Group-by.  The library now answers ONE shape of grouping query itself (mrk_group / mrk_batch_submit_grouped, include/mrk.h):
+// CSphQuery::m_sGroupBy naming an integer row attribute with m_eGroupFunc == SPH_GROUPBY_ATTR, no m_sGroupDistinct, no aggregate
+// items besides @count / @groupby, no m_iGroupbyLimit (one head per group), the within-group order left at relevance
+// (m_sSortBy "@weight desc" / SPH_SORT_RELEVANCE) and m_sGroupSortBy one of "@groupby" / "@count" / "@weight" (weight()) asc or
+// desc -- exact while the query has at most 4 * max_matches distinct groups, declined (MRK_E_UNSUPPORTED) beyond.  Those are the
+// settings MrkEligible COULD pass.  It does not yet: the frame replay feeds rows to the reference's own sorter and a grouping sorter
+// needs every match, not one head per group, so a grouped query needs a result path of its own (rows from mrk_result.group_key /
+// group_count straight into the result set).  Until that exists MrkEligible declines every sorter with IsGroupby(), as before, and
+// all other group settings (group functions over time, MVA and JSON keys, DISTINCT, aggregates, GROUP n BY, WITHIN GROUP ORDER BY)
+// stay on the CPU for good reasons of their own.
 #pragma once
 
 #include "sphinx.h"

@@ -71,6 +71,13 @@ class Order(C.Structure):
     _fields_ = [("n_parts", C.c_int32), ("parts", OrderPart * MRK_MAX_ORDER_PARTS), ("then_weight", C.c_int32)]
 
 
+class Group(C.Structure):  # mrk_group
+    _fields_ = [("bit_offset", C.c_int32), ("bit_count", C.c_int32), ("sort_by", C.c_int32), ("desc", C.c_int32)]
+
+
+GROUPSORT_KEY, GROUPSORT_COUNT, GROUPSORT_WEIGHT = 0, 1, 2  # MRK_GROUPSORT_*
+
+
 class Query(C.Structure):
     _fields_ = [("nodes", C.POINTER(Node)), ("n_nodes", C.c_int32), ("children", C.POINTER(C.c_int32)),
                 ("root", C.c_int32), ("ranker", C.c_int32), ("max_matches", C.c_int32),
@@ -84,7 +91,7 @@ class Query(C.Structure):
 class Result(C.Structure):
     _fields_ = [("n", C.c_int32), ("total_found", C.c_int64), ("rowid", C.POINTER(C.c_uint32)),
                 ("weight", C.POINTER(C.c_int32)), ("status", C.c_int32), ("sort_key", C.POINTER(C.c_uint32)),
-                ("order_key", C.POINTER(C.c_uint64))]
+                ("order_key", C.POINTER(C.c_uint64)), ("group_key", C.POINTER(C.c_uint32)), ("group_count", C.POINTER(C.c_uint32))]
 
 
 class BatchStats(C.Structure):
@@ -159,6 +166,7 @@ SYMBOLS = [
     ("mrk_batch_create", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("mrk_batch_destroy", None, [C.c_void_p]),
     ("mrk_batch_submit", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Query), C.c_uint32]),
+    ("mrk_batch_submit_grouped", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Query), C.POINTER(C.POINTER(Group)), C.c_uint32]),
     ("mrk_batch_wait", C.c_int, [C.c_void_p]),
     ("mrk_batch_test", C.c_int, [C.c_void_p]),
     ("mrk_batch_result", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Result)]),

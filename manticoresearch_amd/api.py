@@ -332,6 +332,7 @@ class Filter:
 
 
 SORTKEY_INT, SORTKEY_FLOAT, SORTKEY_INT64 = 0, 1, 2
+GROUPSORT_KEY, GROUPSORT_COUNT, GROUPSORT_WEIGHT = 0, 1, 2  # MRK_GROUPSORT_*: what orders the groups of a grouped query
 
 
 @dataclass
@@ -373,6 +374,18 @@ class Order:
 
 
 @dataclass
+class Group:
+    """GROUP BY one integer row attribute (mrk_group, include/mrk.h): groupfunc = attr.  The head of a group is its best match by
+    relevance (weight DESC, rowid ASC), @count its matches; the groups leave ordered by sort_by (GROUPSORT_KEY = the group value,
+    GROUPSORT_COUNT, GROUPSORT_WEIGHT = the head's weight), desc or asc, then the head's rowid ascending.  Answered exactly for up
+    to 4 * max_matches distinct values; beyond that the query is declined (status MRK_E_UNSUPPORTED)."""
+    bit_offset: int
+    bit_count: int
+    sort_by: int = GROUPSORT_KEY
+    desc: bool = True
+
+
+@dataclass
 class Query:
     """CSphQuery fields that reach the ranker, plus the parsed tree."""
     root: XQNode
@@ -389,6 +402,7 @@ class Query:
     weight_filters: Optional[Sequence["Filter"]] = None  # filters on the match weight (m_pWeightFilter); locator fields unused
     sort: Optional["Sort"] = None             # None = by relevance (weight desc, rowid asc)
     order: Optional["Order"] = None           # one 64-bit attribute or two attributes first; not next to a sort
+    group: Optional["Group"] = None           # GROUP BY an integer attribute; travels beside mrk_query (mrk_batch_submit_grouped)
 
 
 class _CQueries:
@@ -397,6 +411,8 @@ class _CQueries:
     def __init__(self, queries: Sequence[Query]):
         self.keep = []
         self.arr = (_lib.Query * max(1, len(queries)))()
+        # the parallel array of group specs (NULL = that query is not grouped); None = no query has one: plain mrk_batch_submit
+        self.groups = (C.POINTER(_lib.Group) * max(1, len(queries)))() if any(q.group is not None for q in queries) else None
         for qi, q in enumerate(queries):
             nodes: List[XQNode] = []
             kids_of: List[List[int]] = []
@@ -475,6 +491,11 @@ class _CQueries:
                     co.parts[i] = _lib.OrderPart(int(p.kind), int(p.bit_offset), int(p.bit_count), int(bool(p.desc)))
                 c.order = C.pointer(co)
                 self.keep.append(co)
+            if q.group is not None:
+                desc = q.group.desc if isinstance(q.group.desc, bool) else int(q.group.desc)  # (an int outside 0 / 1 reaches the library, which refuses it)
+                cg = _lib.Group(int(q.group.bit_offset), int(q.group.bit_count), int(q.group.sort_by), int(desc))
+                self.groups[qi] = C.pointer(cg)
+                self.keep.append(cg)
             self.keep += [cn, ch]
 
 
@@ -493,6 +514,9 @@ class Matches:
     sort_key: Optional[np.ndarray] = None  # a sorted query: the primary attribute's raw value per returned row
     # a query with an Order (uint64): an INT64 part's raw 64 bits; else the first part's raw value << 32 | the second's (or 0)
     order_key: Optional[np.ndarray] = None
+    # a grouped query (Query.group): the raw group value and @count of every returned row, whose rowid / weight are the group's head's
+    group_key: Optional[np.ndarray] = None
+    group_count: Optional[np.ndarray] = None
 
 
 # --------------------------------------------------------------------------- device objects
@@ -641,12 +665,18 @@ class Batch:
     def submit(self, seg: Segment, queries: Sequence[Query]) -> None:
         self._cq = _CQueries(queries)
         self._n = len(queries)
-        check(lib().mrk_batch_submit(self._h, seg._h, self._cq.arr, self._n))
+        self._submit(seg, self._cq, self._n)
+
+    def _submit(self, seg: Segment, cq: "_CQueries", n: int) -> None:
+        if cq.groups is not None:
+            check(lib().mrk_batch_submit_grouped(self._h, seg._h, cq.arr, cq.groups, n))
+        else:
+            check(lib().mrk_batch_submit(self._h, seg._h, cq.arr, n))
 
     def submit_prepared(self, seg: Segment, cq: "_CQueries", n: int) -> None:
         """Re-submit already flattened queries (benchmarks: no Python flattening in the loop)."""
         self._cq, self._n = cq, n
-        check(lib().mrk_batch_submit(self._h, seg._h, cq.arr, n))
+        self._submit(seg, cq, n)
 
     def wait(self) -> None:
         check(lib().mrk_batch_wait(self._h))
@@ -661,7 +691,9 @@ class Batch:
             weight = np.ctypeslib.as_array(r.weight, (max(n, 1),))[:n].copy()
             sk = np.ctypeslib.as_array(r.sort_key, (max(n, 1),))[:n].copy() if r.sort_key else None
             ok = np.ctypeslib.as_array(r.order_key, (max(n, 1),))[:n].copy() if r.order_key else None
-            out.append(Matches(rowid, weight, int(r.total_found), int(r.status), sk, ok))
+            gk = np.ctypeslib.as_array(r.group_key, (max(n, 1),))[:n].copy() if r.group_key else None
+            gc = np.ctypeslib.as_array(r.group_count, (max(n, 1),))[:n].copy() if r.group_count else None
+            out.append(Matches(rowid, weight, int(r.total_found), int(r.status), sk, ok, gk, gc))
         return out
 
     def stats(self) -> dict:
@@ -767,5 +799,5 @@ def idf(term_docs: int, total_docs: int, plain: bool = False, normalized: bool =
 __all__ = ["open_rt_ram", "open_rt_segment", "SPH_RANK_PROXIMITY_BM25", "SPH_RANK_BM25", "SPH_RANK_NONE", "SPH_RANK_WORDCOUNT", "SPH_RANK_PROXIMITY",
            "SPH_RANK_MATCHANY", "SPH_RANK_FIELDMASK", "SPH_RANK_SPH04",
            "parse_query", "SPH_QUERY_TERM", "SPH_QUERY_AND", "SPH_QUERY_OR", "SPH_QUERY_MAYBE", "SPH_QUERY_ANDNOT", "SPH_QUERY_PHRASE", "SPH_QUERY_PROXIMITY", "SPH_QUERY_QUORUM", "SPH_QUERY_BEFORE", "SPH_QUERY_NEAR", "SPH_QUERY_NOTNEAR", "SPH_QUERY_SENTENCE", "SPH_QUERY_PARAGRAPH",
-           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "SORTKEY_INT64", "OrderPart", "Order", "Matches", "ROW_WORDS", "SROW_WORDS", "OROW_WORDS", "Context",
+           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "SORTKEY_INT64", "OrderPart", "Order", "Group", "GROUPSORT_KEY", "GROUPSORT_COUNT", "GROUPSORT_WEIGHT", "Matches", "ROW_WORDS", "SROW_WORDS", "OROW_WORDS", "Context",
            "Segment", "Batch", "Batcher", "prepare", "idf", "MrkError", "validate_index", "pair_stats"]

@@ -216,6 +216,7 @@ constexpr int MAX_PASSES = 8; // driver keywords per query (size of the tree's c
 constexpr uint32_t QF_OVERFLOW = 1; // candidate list overflowed: the host reruns the query with a list that holds every doc
 constexpr uint32_t QF_FSM = 2;      // more live phrase states than the kernel keeps: the query fails
 constexpr uint32_t QF_ARENA = 4;    // the generic evaluator ran out of hit-list memory (ctx tunable gen_spill_mb): the query fails
+constexpr uint32_t QF_GROUPS = 8;   // a grouped query met more distinct group values than 4 * max_matches (mrk_kgroup.h): the query fails
 constexpr int MAX_PROX_TERMS_ = 4;
 constexpr int MAPCAP = 4096; // direct-map probe window (rowids) per decoded block
 
@@ -294,6 +295,14 @@ struct DevQuery {
   // 2 ASC), bin_lo / bin_shift = the relevance bins of the weight; wf_parts = 0..2 dwords of the row behind it, located by sort_* / ord_*
   uint32_t wf_parts;
   uint32_t wf_pad;
+  // a grouped query (mrk_group, mrk_kgroup.h): every match that reaches the sorter updates the query's group table instead of a
+  // candidate list (cand_cap = sort_cap = 0, sort_on = 0, the pruning threshold stays 0).  All zero for every other query
+  uint32_t grp_on;
+  uint32_t grp_item, grp_shift, grp_bits; // the group-by attribute: dword of the row, bit offset inside it, width
+  uint32_t grp_sort_by, grp_desc;         // MRK_GROUPSORT_*, 1 = descending: the groups' order (group_select_kernel)
+  uint32_t grp_slots;                     // slots of the table, a power of two >= 2 * (4 k + 1) ...
+  uint32_t grp_pad;
+  uint64_t grp_off;                       // ... and its offset in ScanArgs::gtab, in u64 words
 };
 
 struct DevItem {
@@ -396,7 +405,33 @@ struct ScanArgs {
   uint32_t* s_hist;         // sorted hit-ranked queries: [n_queries][NBINS] attribute bins of the matches the scan queued for the hit pass, and
   uint32_t* s_tau;          // [n_queries * QSTRIDE] the threshold bin they prove (scan_pk_kernel, pre_prune); NULL = the batch holds no such query
   uint64_t* scand;          // candidates of the batch's sorted queries: [2 * i] = hi, [2 * i + 1] = lo (mrk_sortkey.h); NULL = the batch holds none
+  uint64_t* gtab;           // group tables of the batch's grouped queries (mrk_kgroup.h), DevQuery::grp_off words in; NULL = the batch holds none
+                            // (a batch with grouped queries has scand set too: the update lives in the instances that carry the sort)
 };
+
+// The groups of the grouped queries (mrk_groupsel.hip): one workgroup per grouped query, launched behind the other selections on the
+// same stream.  A query past its limit (more than 4 k claimed slots, or QF_GROUPS set by a probe that found the table full) gets
+// QF_GROUPS and no rows; else the occupied slots are ordered as the query asks and the best k leave: the head's key in the
+// relevance format, the group value and the count, q_total = the number of groups.
+struct GroupSelArgs {
+  const DevQuery* queries;
+  uint64_t* gtab;
+  uint32_t n_queries;
+  uint32_t* q_flags;  // [n_queries] QF_*
+  uint64_t* q_total;  // [n_queries]
+  uint64_t* out_keys; // [n_queries][KCAP]
+  uint32_t* out_cnt;
+  uint32_t* out_gkey; // [n_queries][KCAP] group values of out_keys' entries
+  uint32_t* out_gcnt; // [n_queries][KCAP] ... and their counts
+  // pinned host copies or NULL (as SelectArgs')
+  uint64_t* h_keys;
+  uint32_t* h_cnt;
+  uint64_t* h_total;
+  uint32_t* h_flags;
+  uint32_t* h_gkey;
+  uint32_t* h_gcnt;
+};
+void launch_group_select(const GroupSelArgs& a, void* stream);
 
 // Top-K of the sorted queries' candidate lists (mrk_sortsel.hip): one workgroup per sorted query, launched behind launch_select on
 // the same stream -- the relevance selection saw an empty list for the query and wrote a count of 0; this one overwrites it.  The rows

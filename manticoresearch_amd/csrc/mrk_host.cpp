@@ -122,6 +122,7 @@ struct LaunchShape {
   bool prox = false, tree = false, ext = false; // hit rankers; trees; position modifiers, BEFORE, filters, a cutoff row, a sort
   bool sort = false;                            // the batch holds sorted queries (mrk_query.sort / .order)
   bool nearn = false;                           // ... a NEAR over 3+ operands at the root (the generic evaluator's probe launch)
+  bool group = false;                           // ... grouped queries (mrk_group): `sort` is set too -- the update lives in the instances that carry the sort
 };
 
 struct mrk_batch {
@@ -169,6 +170,14 @@ struct mrk_batch {
   DevBuf<uint32_t> d_out_mkeys; // [max_queries][KCAP] mapped sort keys of d_out_keys' entries (sorted queries; reserved with d_scand)
   DevBuf<uint64_t> d_out_mkeys64; // [max_queries][KCAP] the whole 64-bit mapped keys (order rows): reserved with d_scand by the first batch that holds a 64-bit order or has a standing order-row destination
   DevBuf<uint64_t> d_scand;  // 16-byte candidates of the sorted queries (two words each); reserved by the first batch that holds one
+  // grouped queries (mrk_group, mrk_kgroup.h): the arena of the submit's group tables, reserved by the first submit that holds one and
+  // cleared in front of every scan that uses it; the returned groups' values and counts next to d_out_keys / h_keys; and which
+  // queries of the last submit were grouped (answered ones only)
+  DevBuf<uint64_t> d_gtab;
+  DevBuf<uint32_t> d_out_gkey, d_out_gcnt; // [max_queries][KCAP]
+  PinBuf<uint32_t> h_gkey, h_gcnt;         // [max_queries][KCAP]
+  std::vector<uint8_t> grouped;
+  bool any_grouped = false;
   PinBuf<uint32_t> h_flags;
   // per query of the last submit: its decline mask (row_decline_mask), one bit per row format in which the query's exchange row
   // leaves empty with MRK_ROW_DECLINED
@@ -940,6 +949,7 @@ static void mrk_batch_destroy_impl(mrk_batch* b) {
   b->d_out_mkeys.release();
   b->d_out_mkeys64.release();
   b->d_shist.release();
+  b->d_gtab.release(), b->d_out_gkey.release(), b->d_out_gcnt.release(), b->h_gkey.release(), b->h_gcnt.release();
   b->h_flags.release();
   b->h_decl.release();
   b->d_decl.release();
@@ -993,6 +1003,7 @@ static int mrk_batch_create_impl(mrk_ctx* ctx, uint32_t max_queries, mrk_batch**
   b->sort_key.resize(nq * KCAP);
   b->order_key.resize(nq * KCAP);
   b->sort_loc.assign(nq, mrk_batch::SortLoc{});
+  b->grouped.assign(nq, 0);
   b->status.assign(nq, MRK_OK);
   *out = b;
   return MRK_OK;
@@ -1052,7 +1063,7 @@ static int launch_gen_rank(mrk::ScanArgs& sa, bool nearn, hipStream_t st) {
   return MRK_OK;
 }
 
-static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n);
+static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups = nullptr);
 static int mrk_batch_wait_impl(mrk_batch* b);
 static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out);
 
@@ -1123,6 +1134,18 @@ static int bind_sorted(mrk_batch* b, uint32_t n, bool prox, mrk::ScanArgs& sa, h
   return MRK_OK;
 }
 
+// ... and its grouped queries: the arena of their tables (`words` u64), cleared on st in front of the scan -- every submit, and the
+// rerun of one query, starts from empty tables: a rerun over the submit's table would double its counts.  The rows' value and count
+// planes come with it
+static int bind_groups(mrk_batch* b, uint64_t words, mrk::ScanArgs& sa, hipStream_t st) {
+  int rc;
+  const size_t rows = (size_t)b->max_queries * KCAP;
+  if ((rc = b->d_gtab.reserve(words)) || (rc = b->d_out_gkey.reserve(rows)) || (rc = b->d_out_gcnt.reserve(rows)) || (rc = b->h_gkey.reserve(rows)) || (rc = b->h_gcnt.reserve(rows))) return rc;
+  HIP_TRY(hipMemsetAsync(b->d_gtab.p, 0, words * 8, st));
+  sa.gtab = b->d_gtab.p;
+  return MRK_OK;
+}
+
 // Whether a batch's block-scan items take the lean instance (mrk_scan_p2.hip, ctx key "pair_scan"): the launch that would run
 // scan_pk_kernel<false, false> -- no hit ranker, tree, position modifier, filter or sort anywhere in the batch -- over a segment of
 // <= 8 fields, at most two keywords per query, and a segment packed with bitmaps on (without them a dense keyword is block-probed, and
@@ -1176,7 +1199,8 @@ static int launch_packed(mrk::ScanArgs sa, size_t n_items_pk, const size_t n_ite
 // of 0).  se: the caller's pinned-host result pointers; the rest is bound here.  dst: a standing destination.  Its rows the kernels
 // write themselves: every query's narrow row (the relevance selection's sort pass), the sorted queries' wide or order rows (theirs; a
 // weight-first query's order row with orows_wf only).  The other rows, and those of queries the planner declined, are pack_xrows_kernel's.
-static void launch_selection(const mrk_batch* b, const mrk_segment* seg, uint32_t n, uint64_t cand_total, bool sorted, const RowDst& dst, bool orows_wf,
+// `grouped`: the grouped queries' groups last (group_select_kernel; the other two saw empty lists for them).
+static void launch_selection(const mrk_batch* b, const mrk_segment* seg, uint32_t n, uint64_t cand_total, bool sorted, bool grouped, const RowDst& dst, bool orows_wf,
                              mrk::SelectArgs se, hipStream_t st) {
   se.queries = b->d_queries.p, se.q_hist = b->d_q_hist.p, se.q_cand_n = b->d_q_cand_n.p, se.cand = b->d_cand.p, se.n_queries = n;
   se.out_keys = b->d_out_keys.p, se.out_cnt = b->d_out_cnt.p;
@@ -1190,6 +1214,14 @@ static void launch_selection(const mrk_batch* b, const mrk_segment* seg, uint32_
   se.q_total = b->d_q_total.p, se.q_flags = b->d_q_flags.p;
   se.rows_dst = dst.kind == ROWS_NARROW ? dst.p : nullptr;
   launch_select(se, st);
+  if (grouped) {
+    mrk::GroupSelArgs gs{};
+    gs.queries = b->d_queries.p, gs.gtab = b->d_gtab.p, gs.n_queries = n, gs.q_flags = b->d_q_flags.p, gs.q_total = b->d_q_total.p;
+    gs.out_keys = b->d_out_keys.p, gs.out_cnt = b->d_out_cnt.p, gs.out_gkey = b->d_out_gkey.p, gs.out_gcnt = b->d_out_gcnt.p;
+    gs.h_keys = se.h_keys, gs.h_cnt = se.h_cnt, gs.h_total = se.h_total, gs.h_flags = se.h_flags;
+    if (se.h_keys) gs.h_gkey = b->h_gkey.p, gs.h_gcnt = b->h_gcnt.p;
+    mrk::launch_group_select(gs, st);
+  }
   if (!sorted) return;
   mrk::SortSelArgs ss{};
   ss.queries = b->d_queries.p, ss.q_hist = b->d_q_hist.p, ss.q_cand_n = b->d_q_cand_n.p, ss.scand = b->d_scand.p, ss.n_queries = n;
@@ -1200,10 +1232,13 @@ static void launch_selection(const mrk_batch* b, const mrk_segment* seg, uint32_
   mrk::launch_sort_select(ss, st);
 }
 
-// Never hand back a silently truncated result: what a query's scan flags make of its status.  A run-time decline (QF_FSM, QF_ARENA)
-// is MRK_E_UNSUPPORTED; QF_OVERFLOW -- more matches tied at the pruning threshold than the candidate list holds -- only when the run
+// Never hand back a silently truncated result: what a query's scan flags make of its status.  A run-time decline (QF_FSM, QF_ARENA,
+// QF_GROUPS -- k: the query's max_matches, for that message) is MRK_E_UNSUPPORTED; QF_OVERFLOW -- more matches tied at the pruning threshold than the candidate list holds -- only when the run
 // was the rerun already (the first time mrk_batch_wait runs the query again, alone)
-static int flags_status(uint32_t flags, uint32_t qi, bool was_rerun) {
+static int flags_status(uint32_t flags, uint32_t qi, bool was_rerun, uint32_t k) {
+  if (flags & QF_GROUPS)
+    return mrk_fail(MRK_E_UNSUPPORTED, "query %u: more than %u distinct groups (GROUPBY_FACTOR %u x max_matches %u): the grouping sorter would cut groups in arrival order", qi,
+                    mrk::group_limit(k), mrk::GROUPBY_FACTOR, k);
   if (flags & QF_FSM) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: a doc held more live phrase states than the device path keeps", qi);
   if (flags & QF_ARENA) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the generic evaluator ran out of hit-list memory (ctx tunable gen_spill_mb)", qi);
   if ((flags & QF_OVERFLOW) && was_rerun) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: candidate list overflowed again on the rerun", qi);
@@ -1222,7 +1257,7 @@ static void launch_pack_rows(const mrk_batch* b, RowKind kind, uint64_t* rows, u
   launch_pack_xrows(kind, pa, st);
 }
 
-static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n) {
+static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups) {
   if (!b || !seg || (!queries && n)) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: NULL argument");
   if (n > b->max_queries) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: %u queries > batch capacity %u", n, b->max_queries);
   if (seg->ctx != b->ctx) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: segment and batch belong to different contexts");
@@ -1240,7 +1275,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   if (!n) return MRK_OK;
   std::vector<uint32_t> rowid_max;
   for (uint32_t i = 0; i < n; ++i)
-    if (queries[i].cutoff > 0) {
+    if (queries[i].cutoff > 0 && !(groups && groups[i])) { // (cutoff next to a group: plan_query declines it, no probe)
       rowid_max.assign(n, 0xFFFFFFFFu);
       const int rc = cutoff_probe(b, seg, queries, n, rowid_max);
       if (rc != MRK_OK) return rc;
@@ -1257,7 +1292,8 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   const bool use_packed = seg->has_packed && b->ctx->path != 1;
   for (uint32_t i = 0; i < n; ++i) {
     const mrk::BatchPlan::Mark before = plan.mark();
-    int rc = plan_query(seg, queries[i], b->ctx->item_bytes, use_packed, b->h_queries.p[i], n, i, plan, rowid_max.empty() ? 0xFFFFFFFFu : rowid_max[i]);
+    const mrk_group* group = groups ? groups[i] : nullptr;
+    int rc = plan_query(seg, queries[i], b->ctx->item_bytes, use_packed, b->h_queries.p[i], n, i, plan, rowid_max.empty() || group ? 0xFFFFFFFFu : rowid_max[i], group);
     b->status[i] = rc;
     if (rc == MRK_E_INVAL) return rc;
     if (rc != MRK_OK) { // unsupported: reported per query, runs no device work
@@ -1265,10 +1301,12 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
       b->h_queries.p[i].n_items = 0;
       b->h_queries.p[i].n_terms = 0;
       b->h_queries.p[i].sort_on = 0;
+      b->h_queries.p[i].grp_on = 0;
     }
+    b->grouped[i] = rc == MRK_OK && b->h_queries.p[i].grp_on != 0;
     max_terms = std::max(max_terms, b->h_queries.p[i].n_terms);
     any_ext = any_ext || (b->h_queries.p[i].tree_flags & (mrk::TF_TERMPOS | mrk::TF_ORDER | mrk::TF_PHRASE_LEAF | mrk::TF_NOTNEAR)) != 0 || b->h_queries.p[i].n_filters != 0 || b->h_queries.p[i].n_wfilters != 0 ||
-              b->h_queries.p[i].rowid_max != 0xFFFFFFFFu || b->h_queries.p[i].sort_on != 0;
+              b->h_queries.p[i].rowid_max != 0xFFFFFFFFu || b->h_queries.p[i].sort_on != 0 || b->h_queries.p[i].grp_on != 0;
     b->sort_loc[i] = mrk_batch::SortLoc{};
     if (rc == MRK_OK && b->h_queries.p[i].sort_on) {
       const DevQuery& hq = b->h_queries.p[i];
@@ -1288,7 +1326,8 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   const float plan_ms = std::chrono::duration<float, std::milli>(lay.t_block_items - t_submit0).count(); // (up to the block-scan section in order)
   const size_t n_items = lay.items.size(), n_items_pk = lay.n_items_pk;
   const uint64_t cand_total = plan.cand_total;
-  LaunchShape shape{max_terms, plan.any_prox, plan.any_tree, any_ext, use_packed && plan.sort_total != 0, false};
+  LaunchShape shape{max_terms, plan.any_prox, plan.any_tree, any_ext, use_packed && (plan.sort_total != 0 || plan.group_total != 0), false, use_packed && plan.group_total != 0};
+  b->any_grouped = shape.group;
   for (uint32_t i = 0; i < n && !b->gen_progs.empty(); ++i) shape.nearn = shape.nearn || (b->h_queries.p[i].tree_flags & mrk::TF_GEN_NEARN) != 0;
   memcpy(b->stats.n_bm_groups, lay.n_bm_groups, sizeof lay.n_bm_groups);
   b->stats.algo_bytes = plan.algo_bytes;
@@ -1362,6 +1401,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   bind_scan(b, seg, sa);
   sa.n_items = (uint32_t)n_items; // (the VLB path's one launch; launch_packed sets its sections')
   if (shape.sort && (rc = bind_sorted(b, n, shape.prox, sa, st))) return rc;
+  if (shape.group && (rc = bind_groups(b, plan.group_total, sa, st))) return rc;
   // (submit only: the weight bounds' buffers -- a rerun's list holds every doc its drivers can deliver, it runs without this pruning)
   if (use_packed && shape.prox && b->ctx->prox_prune) { // pruning in front of the hit pass (mrk_kprune.h, prox_bounds)
     const size_t words = (size_t)n * (2 * NBINS + mrk::QSTRIDE);
@@ -1400,7 +1440,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     se.h_cand_n = b->h_cand_n.p;
     se.h_bm_words = b->h_bm_words.p;
     if (!b->dst.p) se.h_keys = b->h_keys.p, se.h_cnt = b->h_cnt.p, se.h_total = b->h_total.p;
-    launch_selection(b, seg, n, cand_total, shape.sort, b->dst, b->orows_wf_run, se, st2);
+    launch_selection(b, seg, n, cand_total, plan.sort_total != 0, shape.group, b->dst, b->orows_wf_run, se, st2);
   } else {
     MergeArgs ma{};
     ma.in_keys = b->d_item_cand.p;
@@ -1420,7 +1460,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     // the queries' decline masks, for every row format whether or not a destination stands: mrk_batch_export_* writes the same rows
     // after the wait
     uint32_t any = 0;
-    for (uint32_t i = 0; i < n; ++i) any |= b->h_decl.p[i] = mrk::row_decline_mask(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order, b->orows_wf_run);
+    for (uint32_t i = 0; i < n; ++i) any |= b->h_decl.p[i] = mrk::query_decline_mask(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order, b->orows_wf_run, b->grouped[i] != 0);
     b->any_declined = any != 0;
     if (any || b->decl_dirty) HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     b->decl_dirty = any != 0;
@@ -1428,7 +1468,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   // The standing export.  Narrow rows: the packed path's sort pass wrote them already, unless a query was declined -- those rows are
   // marked here.  Wide and order rows: relevance and declined queries' rows (sort_select_kernel wrote the others').
   const RowDst& dst = b->dst;
-  if (dst.p && (dst.kind != ROWS_NARROW || !use_packed || b->any_declined)) launch_pack_rows(b, dst.kind, dst.p, n, use_packed, dst.kind != ROWS_NARROW && shape.sort, st2);
+  if (dst.p && (dst.kind != ROWS_NARROW || !use_packed || b->any_declined)) launch_pack_rows(b, dst.kind, dst.p, n, use_packed, dst.kind != ROWS_NARROW && plan.sort_total != 0, st2);
   HIP_TRY(hipGetLastError());
   b->packed_run = use_packed;
   b->last_seg = seg;
@@ -1476,6 +1516,8 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
     P.cand_cap = P.sort_on ? 0u : (uint32_t)cap;
     P.sort_off = 0;
     P.sort_cap = P.sort_on ? (uint32_t)cap : 0u;
+    P.grp_off = 0; // (a grouped query: the retry batch's one table, cleared below -- the submit's holds what the abandoned run counted)
+    if (P.grp_on) P.cand_cap = 0;
     const bool bm = (P.tree_flags & TF_BITMAP) != 0, bt = (P.tree_flags & TF_BTREE) != 0;
     const uint32_t n = (bm || bt) ? seg->dev.n_windows : P.t[0].nblocks, step = (bm || bt) ? 1024u : 256u;
     for (uint32_t x = 0; x < n; x += step) {
@@ -1498,6 +1540,8 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
     return rc;
   const bool sorted = passes[0].sort_on != 0; // (the query's order travels with its passes: sort_* of the DevQuery planned at submit)
   if (sorted && ((rc = r->d_scand.reserve(2 * cap + 64)) || (rc = r->d_out_mkeys.reserve((size_t)r->max_queries * KCAP)))) return rc;
+  const bool grouped = passes[0].grp_on != 0; // (likewise: grp_* of the DevQuery planned at submit)
+  if (grouped && (rc = r->d_scand.reserve(64))) return rc; // (ScanArgs::scand set = the instances that carry the sort, and with it the group update)
   const bool keys64 = sorted && b->d_out_mkeys64.p != nullptr; // the batch keeps the 64-bit mapped keys (order rows)
   if (keys64 && (rc = r->d_out_mkeys64.reserve((size_t)r->max_queries * KCAP))) return rc;
   memcpy(r->h_queries.p, passes.data(), passes.size() * sizeof(DevQuery));
@@ -1508,10 +1552,11 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   HIP_TRY(hipMemsetAsync(r->d_state.p, 0, (size_t)r->max_queries * STATE_BYTES + (size_t)NBINS * 4, st));
   // the submit's kernel instances over ONE query (n = 1 below), but for what is this query's own: whether IT is sorted, and ITS probe launch
   LaunchShape shape = b->shape;
-  shape.sort = sorted, shape.nearn = (passes[0].tree_flags & TF_GEN_NEARN) != 0;
+  shape.sort = sorted || grouped, shape.group = grouped, shape.nearn = (passes[0].tree_flags & TF_GEN_NEARN) != 0;
   ScanArgs sa{};
   bind_scan(r, seg, sa);
-  if (sorted && (rc = bind_sorted(r, 1, shape.prox, sa, st))) return rc;
+  if (shape.sort && (rc = bind_sorted(r, 1, shape.prox, sa, st))) return rc;
+  if (grouped && (rc = bind_groups(r, mrk::group_table_words(passes[0].grp_slots), sa, st))) return rc;
   // match queues for every doc a pass can match (no cap: this run must not overflow), every pass charged the whole rerun's items
   uint64_t chunks[3] = {0, 0, 0};
   for (const DevQuery& P : passes) {
@@ -1524,7 +1569,7 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   if (n_kind[2] && (rc = bind_gen(r, b, sa, st, 1, shape.nearn))) return rc; // (the programs are the submit's, still on the device)
   if ((rc = launch_packed(sa, n_pk, n_kind, chunks, shape, nullptr, lean_scan_ok(b->ctx, seg, shape), st))) return rc;
   // (rerun only: no pinned-host pointers and no destination -- the copies below repair the batch's row, and an export writes it)
-  launch_selection(r, seg, 1, cap, sorted, RowDst{}, false, SelectArgs{}, st);
+  launch_selection(r, seg, 1, cap, sorted, grouped, RowDst{}, false, SelectArgs{}, st);
   HIP_TRY(hipGetLastError());
   uint32_t flags = 0;
   HIP_TRY(hipMemcpyAsync(&flags, r->d_q_flags.p, 4, hipMemcpyDeviceToHost, st));
@@ -1537,10 +1582,16 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   HIP_TRY(hipMemcpyAsync(b->d_out_keys.p + (size_t)qi * KCAP, r->d_out_keys.p, (size_t)KCAP * 8, hipMemcpyDeviceToDevice, st));
   if (sorted) HIP_TRY(hipMemcpyAsync(b->d_out_mkeys.p + (size_t)qi * KCAP, r->d_out_mkeys.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st)); // (mrk_batch_export_srows)
   if (keys64) HIP_TRY(hipMemcpyAsync(b->d_out_mkeys64.p + (size_t)qi * KCAP, r->d_out_mkeys64.p, (size_t)KCAP * 8, hipMemcpyDeviceToDevice, st)); // (mrk_batch_export_orows)
+  if (grouped) { // the groups' values and counts, on the host and next to the batch's device-side rows
+    HIP_TRY(hipMemcpyAsync(b->h_gkey.p + (size_t)qi * KCAP, r->d_out_gkey.p, (size_t)KCAP * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b->h_gcnt.p + (size_t)qi * KCAP, r->d_out_gcnt.p, (size_t)KCAP * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b->d_out_gkey.p + (size_t)qi * KCAP, r->d_out_gkey.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->d_out_gcnt.p + (size_t)qi * KCAP, r->d_out_gcnt.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st));
+  }
   // the device-side row is good again -- or carries what the rerun ran into: an exported row then leaves flagged, never with the rerun's keys
   HIP_TRY(hipMemcpyAsync(b->d_q_flags.p + qi, r->d_q_flags.p, 4, hipMemcpyDeviceToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if ((rc = flags_status(flags, qi, true))) return rc;
+  if ((rc = flags_status(flags, qi, true, passes[0].k))) return rc;
   b->decoded = false;
   return MRK_OK;
 }
@@ -1578,7 +1629,7 @@ static int mrk_batch_wait_impl(mrk_batch* b) {
   if (b->packed_run)
     for (uint32_t i = 0; i < b->n_queries; ++i) {
       if (b->status[i] != MRK_OK) continue;
-      if ((b->status[i] = flags_status(b->h_flags.p[i], i, false)) == MRK_OK && (b->h_flags.p[i] & QF_OVERFLOW)) {
+      if ((b->status[i] = flags_status(b->h_flags.p[i], i, false, b->h_queries.p[i].k)) == MRK_OK && (b->h_flags.p[i] & QF_OVERFLOW)) {
         // more matches tied at the pruning threshold than the candidate list holds (e.g. millions of docs with the
         // very same weight): run the query again, alone, with room for every doc its drivers can deliver
         ++b->stats.n_rerun;
@@ -1598,6 +1649,10 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
     HIP_TRY(hipMemcpyAsync(b->h_cnt.p, b->d_out_cnt.p, n * 4, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(b->h_total.p, b->d_q_total.p, n * 8, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(b->h_keys.p, b->d_out_keys.p, n * KCAP * 8, hipMemcpyDeviceToHost, b->stream));
+    if (b->any_grouped) {
+      HIP_TRY(hipMemcpyAsync(b->h_gkey.p, b->d_out_gkey.p, n * KCAP * 4, hipMemcpyDeviceToHost, b->stream));
+      HIP_TRY(hipMemcpyAsync(b->h_gcnt.p, b->d_out_gcnt.p, n * KCAP * 4, hipMemcpyDeviceToHost, b->stream));
+    }
     HIP_TRY(hipStreamSynchronize(b->stream));
     b->host_copied = true;
   }
@@ -1635,6 +1690,9 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
   out->weight = b->weight.data() + (size_t)q * KCAP;
   out->sort_key = b->status[q] == MRK_OK && b->sort_loc[q].bits && !b->sort_loc[q].order ? b->sort_key.data() + (size_t)q * KCAP : nullptr;
   out->order_key = b->status[q] == MRK_OK && b->sort_loc[q].order && b->sort_loc[q].bits ? b->order_key.data() + (size_t)q * KCAP : nullptr;
+  const bool grouped = b->status[q] == MRK_OK && b->grouped[q] && b->any_grouped;
+  out->group_key = grouped ? b->h_gkey.p + (size_t)q * KCAP : nullptr;
+  out->group_count = grouped ? b->h_gcnt.p + (size_t)q * KCAP : nullptr;
   return MRK_OK;
 }
 
@@ -1972,6 +2030,9 @@ extern "C" void mrk_batch_destroy(mrk_batch* b) {
 }
 extern "C" int mrk_batch_submit(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n) {
   return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_submit_impl(b, seg, queries, n); });
+}
+extern "C" int mrk_batch_submit_grouped(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, uint32_t n) {
+  return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_submit_impl(b, seg, queries, n, groups); });
 }
 
 // The wait polls instead of parking the worker in hipStreamSynchronize: while the batch's stream is still busy AND

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "mrk_dev.h"
+#include "mrk_kgroup.h"
 
 int mrk_fail(int code, const char* fmt, ...);
 
@@ -142,6 +143,7 @@ struct BatchPlan {
   std::vector<GenProg> gen_progs;  // programs of the generic evaluator (DevQuery::gen_prog indexes it)
   uint64_t algo_bytes = 0, dev_bytes = 0, cand_total = 0;
   uint64_t sort_total = 0;         // 16-byte candidate slots of the batch's sorted queries (mrk_query.sort); 0 = it holds none
+  uint64_t group_total = 0;        // u64 words of the batch's group tables (mrk_group, mrk_kgroup.h); 0 = it holds no grouped query
   bool any_prox = false, any_tree = false;
   // a declined query runs no device work: what it appended is taken back (the byte counts and flags stay as plan_query left them)
   struct Mark { size_t extra, items, items_bm, gen_progs; };
@@ -152,9 +154,10 @@ struct BatchPlan {
 // Plans one query of a batch: validates it, builds the reference-shaped evaluation tree, computes IDFs, pruning
 // histogram geometry and candidate capacity, and emits the query's passes and work items into `plan`.  Returns MRK_OK, or
 // MRK_E_UNSUPPORTED / MRK_E_INVAL with the message set.  dq = the query's head pass (index qi); further passes go to
-// plan.extra and get pass indices n_queries + position.
+// plan.extra and get pass indices n_queries + position.  group: the query's mrk_group (mrk_batch_submit_grouped) or NULL -- a grouped
+// query gets a table of plan.group_total's arena instead of a candidate list (DevQuery::grp_*; all zero for every other query).
 int plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
-               BatchPlan& plan, uint32_t rowid_max = 0xFFFFFFFFu);
+               BatchPlan& plan, uint32_t rowid_max = 0xFFFFFFFFu, const mrk_group* group = nullptr);
 
 // Groups of a batch's scan_bm queries for the grouped bitmap kernel ("bm_group", mrk_batch_submit).  A member names its two
 // keywords (key: bitmap offset + idf bits, so that members sharing a key share its tfidf table too), the bytes a walk of each
@@ -250,11 +253,16 @@ void place_bm_items(const DevQuery* head, uint32_t n, const std::vector<DevQuery
 // ran with mrk_batch_orows_weight_first on.  A NARROW row is merged by (weight, docid), which answers relevance queries only; a WIDE
 // row has no room for a 64-bit key (SORT_ON_ORDER) and no word for the weight in front (SORT_ON_WEIGHT); an ORDER row carries both,
 // the latter only where the batch asked for it.  The order bit implies the wide bit, the wide bit the narrow one: some bit is set
-// exactly when the narrow bit is.
+// exactly when the narrow bit is.  (A grouped query leaves in no row format -- merging groups adds counts per key, which no merge here
+// does: its mask is all three bits, set where this function is called -- query_decline_mask.)
 inline uint32_t row_decline_mask(int status, uint32_t sort_bits, uint32_t order, bool orows_wf_run) {
   const bool off = status != MRK_OK, no_row = order == SORT_ON_ORDER || order == SORT_ON_WEIGHT;
   const bool narrow = off || sort_bits != 0 || no_row, wide = off || no_row, ord = off || (order == SORT_ON_WEIGHT && !orows_wf_run);
   return (narrow ? 1u << ROWS_NARROW : 0u) | (wide ? 1u << ROWS_WIDE : 0u) | (ord ? 1u << ROWS_ORDER : 0u);
+}
+
+inline uint32_t query_decline_mask(int status, uint32_t sort_bits, uint32_t order, bool orows_wf_run, bool grouped) {
+  return grouped ? (1u << ROWS_NARROW) | (1u << ROWS_WIDE) | (1u << ROWS_ORDER) : row_decline_mask(status, sort_bits, order, orows_wf_run);
 }
 
 // Least and largest field-weight sum over the masks of the first nwf (<= 32) fields, the empty mask counting as 1

@@ -1,0 +1,179 @@
+// mrk_kgroup.h -- GROUP BY one integer row attribute: the per-query group table and its update.
+//
+// Stands in for CSphKBufferGroupSorter (sphinxsort.cpp:2961-3310) while it has not cut: PushEx (:3148-3205) finds the match's group
+// in a hash of group keys; a new group gets the match as its head and a count of 1 (++m_iTotal), an existing one
+// (PushIntoExistingGroup, :3112-3145) a count + 1 and the match as its new head when it beats the old one under the within-group
+// order -- MatchRelevanceLt_fn: weight DESC, rowid ASC, i.e. the larger make_key(weight, global rowid).  Up to max_matches *
+// GROUPBY_FACTOR (:2767) groups none of this depends on the order the matches arrive in, so a group here is one slot claim, one
+// 32-bit add and one 64-bit max; beyond that limit the reference starts CutWorst (:3176) and the device declines the query.
+//
+// Table of S slots (a power of two >= 2 * (4 K + 1), so that a query inside the limit never fills it), in the batch's arena of
+// u64 words at DevQuery::grp_off:   [0] claimed slots (low dword)   [1 .. S] tag | group value   [S+1 .. 2S] head key
+// [2S+1 ..] S counts (u32).  An empty slot's key word is 0; a claimed one holds GRP_TAG | value, so values 0 and 0xFFFFFFFF are
+// ordinary keys.  Linear probing from group_hash(value); nothing is ever removed.
+//
+// The probe, the claim and the hash are written over an "atomic ops" policy: GroupDevOps on the device (relaxed, agent scope --
+// nothing reads the table before the selection launch), GroupSeqOps sequentially on the host (tests/cpp/group_table.cpp).
+#pragma once
+#include <stdint.h>
+
+#include "../../include/mrk.h"
+#include "mrk_sortkey.h"
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define MRK_GHD __host__ __device__ inline
+#else
+#define MRK_GHD inline
+#endif
+
+namespace mrk {
+
+constexpr uint32_t GROUPBY_FACTOR = 4; // sphinxsort.cpp:2767
+constexpr uint64_t GRP_TAG = 1ull << 63;
+constexpr uint32_t GRP_MAX_GROUPS = GROUPBY_FACTOR * MRK_MAX_K; // what group_select_kernel sorts in LDS
+
+MRK_GHD uint32_t group_limit(uint32_t k) { return GROUPBY_FACTOR * k; }
+MRK_GHD uint32_t group_slots_for(uint32_t k) {
+  const uint32_t need = 2u * (group_limit(k) + 1u);
+  uint32_t s = 8;
+  while (s < need) s <<= 1;
+  return s;
+}
+MRK_GHD uint64_t group_table_words(uint32_t slots) { return 1ull + 2ull * slots + slots / 2u; }
+
+struct GroupTable {
+  uint32_t* claimed;
+  uint64_t* keys;
+  uint64_t* heads;
+  uint32_t* counts;
+  uint32_t slots;
+};
+MRK_GHD GroupTable group_table_at(uint64_t* base, uint32_t slots) {
+  return GroupTable{reinterpret_cast<uint32_t*>(base), base + 1, base + 1 + slots, reinterpret_cast<uint32_t*>(base + 1 + 2ull * slots), slots};
+}
+
+MRK_GHD uint32_t group_hash(uint32_t value, uint32_t slots) {
+  uint32_t h = value * 0x9E3779B1u;
+  h ^= h >> 15;
+  return h & (slots - 1u);
+}
+
+struct GroupSeqOps {
+  static uint64_t load64(const uint64_t* p) { return *p; }
+  static uint64_t cas64(uint64_t* p, uint64_t expected, uint64_t desired) {
+    const uint64_t old = *p;
+    if (old == expected) *p = desired;
+    return old;
+  }
+  static void add32(uint32_t* p, uint32_t v) { *p += v; }
+  static void max64(uint64_t* p, uint64_t v) {
+    if (v > *p) *p = v;
+  }
+};
+
+// `count` matches of group `value`, the best of them `head`.  false: neither the value nor an empty slot within `slots` probes --
+// the table is full of other groups, the query is past its limit (the caller sets QF_GROUPS) and the matches are dropped.
+// A slot is counted (claimed) by the one caller that won its compare-and-swap, so the counter is the number of distinct values in
+// the table whatever races the claims ran.
+template <class Ops>
+MRK_GHD bool group_update(const GroupTable& T, uint32_t value, uint32_t count, uint64_t head) {
+  const uint64_t word = GRP_TAG | value;
+  uint32_t i = group_hash(value, T.slots);
+  for (uint32_t step = 0; step < T.slots; ++step, i = (i + 1u) & (T.slots - 1u)) {
+    uint64_t cur = Ops::load64(T.keys + i);
+    if (cur == 0ull) {
+      cur = Ops::cas64(T.keys + i, 0ull, word);
+      if (cur == 0ull) {
+        Ops::add32(T.claimed, 1u);
+        cur = word;
+      }
+    }
+    if (cur == word) {
+      Ops::add32(T.counts + i, count);
+      Ops::max64(T.heads + i, head);
+      return true;
+    }
+  }
+  return false;
+}
+
+// The groups' order (MatchGeneric1_fn, sphinxsort.cpp:4708-4720): one of group value / count / head weight, ascending or
+// descending, then the head's global rowid ascending.  Larger = better; heads are distinct rows, so no two groups tie.
+MRK_GHD uint64_t group_order_key(uint32_t sort_by, uint32_t desc, uint32_t value, uint32_t count, uint64_t head) {
+  const uint32_t p = sort_by == MRK_GROUPSORT_COUNT ? count : sort_by == MRK_GROUPSORT_KEY ? value : (uint32_t)(head >> 32);
+  return ((uint64_t)(desc ? p : ~p) << 32) | (uint32_t)head;
+}
+
+#if defined(__HIPCC__)
+struct GroupDevOps {
+  static __device__ uint64_t load64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  static __device__ uint64_t cas64(uint64_t* p, uint64_t expected, uint64_t desired) {
+    __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return expected; // (the value found: `expected` itself when the exchange happened)
+  }
+  static __device__ void add32(uint32_t* p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  static __device__ void max64(uint64_t* p, uint64_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint64_t group_dpp_max64(uint64_t x) { // (keys are unsigned: the 0 a lane without a source reads is the identity)
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)x, CTRL, ROW_MASK, 0xf, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(x >> 32), CTRL, ROW_MASK, 0xf, false);
+  const uint64_t y = ((uint64_t)hi << 32) | lo;
+  return y > x ? y : x;
+}
+__device__ __forceinline__ uint64_t group_wave_max64(uint64_t v) {
+  v = group_dpp_max64<0x111, 0xf>(v); // row_shr:1
+  v = group_dpp_max64<0x112, 0xf>(v); // row_shr:2
+  v = group_dpp_max64<0x114, 0xf>(v); // row_shr:4
+  v = group_dpp_max64<0x118, 0xf>(v); // row_shr:8
+  v = group_dpp_max64<0x142, 0xa>(v); // row_bcast:15 -> rows 1, 3
+  v = group_dpp_max64<0x143, 0xc>(v); // row_bcast:31 -> rows 2, 3
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+}
+
+// A wave's buffered matches of ONE grouped query go to its table: cbuf[i] = make_key(weight, global rowid), cbuf2[i] = the group
+// value, i < cn <= 128.  Equal values are combined first -- count = their number, head = their largest key -- and the distinct ones
+// written back to the front of the two buffers (the lanes hold the entries in registers by then: no LDS beyond the buffers), so a
+// column of four values costs four table updates per flush, not one same-address atomic per match.  Then one lane per distinct value
+// runs group_update.  All 64 lanes call it; false (uniform) = some update found the table full.
+__device__ __forceinline__ bool group_flush_wave(const GroupTable& T, uint64_t* cbuf, uint64_t* cbuf2, uint32_t cn, uint32_t lane) {
+  const bool v0 = lane < cn, v1 = lane + 64u < cn;
+  const uint64_t k0 = v0 ? cbuf[lane] : 0ull, k1 = v1 ? cbuf[lane + 64u] : 0ull;
+  const uint32_t g0 = v0 ? (uint32_t)cbuf2[lane] : 0u, g1 = v1 ? (uint32_t)cbuf2[lane + 64u] : 0u;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  uint64_t p0 = __ballot(v0), p1 = __ballot(v1);
+  uint32_t nd = 0;
+  while (p0 | p1) { // (uniform) one round per distinct value
+    const uint32_t src = (uint32_t)__builtin_ctzll(p0 ? p0 : p1);
+    const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)(p0 ? g0 : g1), (int)src);
+    const bool m0 = v0 && g0 == v, m1 = v1 && g1 == v; // (entries of one value are pending together)
+    const uint64_t b0 = __ballot(m0), b1 = __ballot(m1);
+    const uint64_t a = m0 ? k0 : 0ull, b = m1 ? k1 : 0ull;
+    const uint64_t h = group_wave_max64(a > b ? a : b);
+    if (lane == 0) {
+      cbuf[nd] = h;
+      cbuf2[nd] = (uint64_t)v | ((uint64_t)(uint32_t)(__popcll(b0) + __popcll(b1)) << 32);
+    }
+    ++nd;
+    p0 &= ~b0, p1 &= ~b1;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  bool ok = true;
+  for (uint32_t j = lane; j < nd; j += 64u) {
+    const uint64_t vc = cbuf2[j];
+    ok = group_update<GroupDevOps>(T, (uint32_t)vc, (uint32_t)(vc >> 32), cbuf[j]) && ok;
+  }
+  const bool all_ok = __ballot(!ok) == 0ull;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  return all_ok;
+}
+#endif // __HIPCC__
+
+} // namespace mrk

@@ -774,6 +774,7 @@ struct PlanState {
   const mrk_query& q;
   const bool use_packed;
   const uint32_t qi;
+  const mrk_group* const group; // mrk_batch_submit_grouped's spec for this query, or NULL
   // what the stages work out, in their order
   KeySpec order;
   bool filtered = false; // the query reads attribute rows: the packed block scan's EXT instances only
@@ -872,6 +873,39 @@ struct PlanState {
     P.range = &seg->sort_ranges[column_range(seg, P.bit_offset, P.bit_count, P.kind)];
     if (P.range->has_nan) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: the float sort column holds a NaN (no strict weak order)", qi);
     return MRK_OK;
+  }
+
+  // mrk_group: validated exactly as the sort's locator is, before anything is read; what declines a sort declines a group
+  int resolve_group() const {
+    if (!group) return MRK_OK;
+    const mrk_group& G = *group;
+    if (G.sort_by != MRK_GROUPSORT_KEY && G.sort_by != MRK_GROUPSORT_COUNT && G.sort_by != MRK_GROUPSORT_WEIGHT)
+      return mrk_fail(MRK_E_INVAL, "query %u: group sort_by %d", qi, G.sort_by);
+    if (G.desc != 0 && G.desc != 1) return mrk_fail(MRK_E_INVAL, "query %u: group desc %d (0 or 1)", qi, G.desc);
+    if (G.bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: group by a blob-stored or computed attribute (no row locator)", qi);
+    if (G.bit_count == 64 && (G.bit_offset & 31) == 0 && seg->dev.attrs && (uint64_t)G.bit_offset + 64 <= (uint64_t)seg->dev.attr_stride * 32)
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: group by a 64-bit attribute (device path: <= 32 bits)", qi);
+    if (int rc = check_key_locator(qi, "group", "group key", MRK_SORTKEY_INT, G.bit_offset, G.bit_count)) return rc;
+    if (seg->dev.attrs && seg->dev.attr_stride)
+      if (int rc = check_key_in_row(seg, qi, "group", G.bit_offset, G.bit_count)) return rc;
+    if (q.sort || q.order) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: a group next to mrk_query.sort / mrk_query.order (the within-group order is relevance)", qi);
+    if (!seg->dev.attrs || seg->h_attrs.empty())
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: grouping by an attribute needs the segment's attribute rows (mrk_segment_set_attrs)", qi);
+    if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: grouped queries run on the packed path only", qi);
+    if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to a group (which rows count depends on the scan order)", qi);
+    return MRK_OK;
+  }
+  // ... and its words of the descriptor: where the key lies in the row, the groups' order, the query's table in the batch's arena.
+  // A grouped query publishes no candidates and needs no pruning threshold
+  void reserve_group(DevQuery& dq, BatchPlan& plan) const {
+    const mrk_group& G = *group;
+    dq.cand_cap = dq.sort_cap = 0;
+    dq.grp_on = 1;
+    dq.grp_item = (uint32_t)G.bit_offset >> 5, dq.grp_shift = (uint32_t)G.bit_offset & 31u, dq.grp_bits = (uint32_t)G.bit_count;
+    dq.grp_sort_by = (uint32_t)G.sort_by, dq.grp_desc = (uint32_t)G.desc;
+    dq.grp_slots = group_slots_for((uint32_t)q.max_matches);
+    dq.grp_off = plan.group_total;
+    plan.group_total += group_table_words(dq.grp_slots);
   }
 
   // what plan_query checks of the query itself before the tree is walked
@@ -1552,17 +1586,18 @@ struct PlanState {
 };
 
 int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
-                    BatchPlan& plan, uint32_t rowid_max) {
+                    BatchPlan& plan, uint32_t rowid_max, const mrk_group* group) {
   memset(&dq, 0, sizeof dq);
-  PlanState S{seg, q, use_packed, qi};
+  PlanState S{seg, q, use_packed, qi, group};
   // validate: hostile order / sort specs are MRK_E_INVAL before a row is read
   if (int rc = S.resolve_order()) return rc;
   dq.item_first = (uint32_t)plan.items.size();
   dq.out_q = qi;
   if (int rc = S.check_query()) return rc;
   if (int rc = S.resolve_sort()) return rc;
-  // (a sorted query reads attribute rows like a filtered one: the packed block scan's EXT instances only)
-  S.filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || S.order.sorted();
+  if (int rc = S.resolve_group()) return rc;
+  // (a sorted or grouped query reads attribute rows like a filtered one: the packed block scan's EXT instances only)
+  S.filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || S.order.sorted() || group != nullptr;
   // the evaluation tree and who evaluates it
   if (int rc = S.shape_query()) return rc;
   dq.rowid_max = rowid_max;
@@ -1579,7 +1614,10 @@ int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_byt
     PlanState::bins_by_rowid(seg, dq);
   else
     S.bins_by_weight(dq);
-  S.reserve_candidates(dq, plan);
+  if (group)
+    S.reserve_group(dq, plan);
+  else
+    S.reserve_candidates(dq, plan);
   if (S.empty) {
     dq.n_terms = (uint32_t)S.n;
     dq.n_items = 0;

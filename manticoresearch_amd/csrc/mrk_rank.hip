@@ -11,6 +11,7 @@
 #include "mrk_kprune.h"
 #include "mrk_keval.h"
 #include "mrk_sortkey.h"
+#include "mrk_kgroup.h"
 
 namespace mrk {
 
@@ -76,9 +77,20 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   OrderPart op1{0u, 0u, 32u, 0u};
   OrderGeom og{0u, 0u, 0u, 0u};
   uint64_t* scand = nullptr;
+  // a grouped query (uniform per logical query; mrk_kgroup.h): its matches go to its group table
+  bool grouped = false;
+  uint32_t gr_item = 0, gr_shift = 0, gr_bits = 32;
+  GroupTable gtable = group_table_at(nullptr, 8u);
   uint32_t *ghist = nullptr, *gcount = nullptr, *gtaubin = nullptr;
 
   auto publish = [&]() {
+    if constexpr (SORT) {
+      if (grouped) { // (see scan_pk_kernel) one claim / add / max per distinct group value of the buffer
+        if (cn && !group_flush_wave(gtable, L.cbuf, L.cbuf2, cn, lane) && lane == 0) atomicOr(a.q_flags + cur_oq, QF_GROUPS);
+        cn = 0;
+        return;
+      }
+    }
     if (cn) {
       uint32_t basep = 0;
       if (lane == 0) basep = atomicAdd(gcount, cn);
@@ -239,6 +251,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
       const uint32_t son_ = SORT ? U(Q->sort_on) : 0u, si_ = SORT ? U(Q->sort_item) : 0u, ss_ = SORT ? U(Q->sort_shift) : 0u, sb_ = SORT ? U(Q->sort_bits) : 32u,
                      sf_ = SORT ? U(Q->sort_flags) : 0u, st_ = SORT ? U(Q->sort_tie) : 0u, sc_ = SORT ? U(Q->sort_cap) : 0u;
       const uint64_t so_ = SORT ? ((uint64_t)U((uint32_t)(Q->sort_off >> 32)) << 32) | U((uint32_t)Q->sort_off) : 0ull;
+      const uint32_t gon_ = SORT ? U(Q->grp_on) : 0u;
       if (oq != cur_oq) {
         leave_query();
         cur_oq = oq;
@@ -257,6 +270,12 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
           if (wfirst) { // (uniform; the parts behind the weight)
             op1 = OrderPart{U(Q->ord_item), U(Q->ord_shift), U(Q->ord_bits), U(Q->ord_flags)};
             wf_parts = U(Q->wf_parts);
+          }
+          grouped = gon_ != 0;
+          if (grouped) { // (uniform; rare)
+            gr_item = U(Q->grp_item), gr_shift = U(Q->grp_shift), gr_bits = U(Q->grp_bits);
+            const uint64_t go = ((uint64_t)U((uint32_t)(Q->grp_off >> 32)) << 32) | U((uint32_t)Q->grp_off);
+            gtable = group_table_at(a.gtab + go, U(Q->grp_slots));
           }
         }
         ghist = a.q_hist + (uint64_t)oq * NBINS;
@@ -382,7 +401,11 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
     if (is_live) {
       ++total;
       const uint32_t grow = a.seg.rowid_base + rowid;
-      if (SORT && wfirst) { // the weight, final here, leads and takes the bin; the row's parts only break its ties
+      if (SORT && grouped) { // every match counts: the head is the largest key, the group the row's attribute
+        key = make_key((int32_t)weight, grow);
+        key2 = sort_extract(a.seg.attrs[(uint64_t)rowid * a.seg.attr_stride + gr_item], gr_shift, gr_bits);
+        push = true;
+      } else if (SORT && wfirst) { // the weight, final here, leads and takes the bin; the row's parts only break its ties
         const uint64_t pk = wfirst_row_key(a.seg.attrs + (uint64_t)rowid * a.seg.attr_stride, wf_parts, OrderPart{so_item, so_shift, so_bits, so_flags}, op1);
         key = wfirst_hi(so_tie, (int32_t)weight, pk);
         key2 = wfirst_lo(pk, grow);

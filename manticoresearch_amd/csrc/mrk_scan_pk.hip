@@ -14,6 +14,7 @@
 #include "mrk_kpk.h"
 #include "mrk_kmq.h"
 #include "mrk_sortkey.h"
+#include "mrk_kgroup.h"
 
 #include <type_traits>
 
@@ -30,6 +31,7 @@ namespace mrk {
 #define MRK_CBUF 128
 #endif
 constexpr int CBUF = MRK_CBUF; // candidates a wave collects before it publishes them
+static_assert(CBUF <= 128, "group_flush_wave (mrk_kgroup.h) takes two buffered matches per lane");
 constexpr int MQCAP = 128;     // matched docs a wave queues for the hit pass (processed 64 at a time)
 
 // WIDE: the instance for segments with 9-32 fields -- field masks come from the pk_fmask plane instead of pk_attr's bytes
@@ -76,8 +78,10 @@ struct __align__(16) PkSmem {
 // the whole mask in one more plane
 // SORT: the batch holds queries ordered by a row attribute (mrk_query.sort); instances of their own, so that the ones relevance-only
 // batches launch stay as they are
+// (the WIDE instance that carries the sort sat at 168 VGPRs, the most that lets three waves share a SIMD; the group update's two more
+// would cost it the third wave, so that instance asks the register allocator for three -- every other instance is compiled as before)
 template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false>
-__global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE && SORT && NREF == MAX_PROX_TERMS ? 3 : 1))) void scan_pk_kernel(ScanArgs a) {
   constexpr int NF = WIDE ? 32 : 8;
   constexpr bool GEN = NREF > MAX_PROX_TERMS;
   extern __shared__ __align__(16) uint8_t smem_raw[];
@@ -156,6 +160,10 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   // (the second part and the bins' geometry are read from the descriptor where they are used: scalar loads on a rare branch)
   auto ord_key = [&](uint32_t row) { return order_row_key(a.seg.attrs + (uint64_t)row * a.seg.attr_stride, OrderPart{so_item, so_shift, so_bits, so_flags}, OrderPart{Q->ord_item, Q->ord_shift, Q->ord_bits, Q->ord_flags}); };
   uint64_t* __restrict__ scand = sorted ? a.scand + 2 * Q->sort_off : nullptr;
+  // (uniform) a grouped query (mrk_kgroup.h): its matches are buffered like candidates -- cbuf the key, cbuf2 the group value -- and a
+  // flush takes them to the query's group table; no candidate list, no histogram, no threshold
+  // (the locator and the table are read from the descriptor where they are used: scalar loads on a rare branch, no registers held)
+  const bool grouped = SORT && Q->grp_on != 0;
   const uint32_t cand_cap = sorted ? Q->sort_cap : Q->cand_cap;
   uint64_t* __restrict__ cand = a.cand + Q->cand_off;
   uint32_t* __restrict__ ghist = a.q_hist + (uint64_t)oq * NBINS;
@@ -199,6 +207,13 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
   // publish the wave's buffered candidates: reserve a slice of the query's list with ONE atomic,
   // write it coalesced, add the per-bin counts to the global histogram, re-read the threshold
   auto publish = [&]() {
+    if constexpr (SORT) {
+      if (grouped) { // one claim / add / max per distinct group value of the buffer
+        if (cn && !group_flush_wave(group_table_at(a.gtab + Q->grp_off, Q->grp_slots), L.cbuf, L.cbuf2, cn, lane) && lane == 0) atomicOr(a.q_flags + oq, QF_GROUPS);
+        cn = 0;
+        return;
+      }
+    }
     if (cn) {
       uint32_t basep = 0;
       if (lane == 0) basep = atomicAdd(gcount, cn);
@@ -271,7 +286,11 @@ __global__ __launch_bounds__(WG) void scan_pk_kernel(ScanArgs a) {
       ++total;
       const uint32_t grow = rowid_base + rowid;
       uint32_t bin;
-      if (SORT && wfirst) { // the weight leads and takes the bin; the row's parts (0..2 dwords) only break its ties
+      if (SORT && grouped) { // every match counts: the head is the largest key, the group the row's attribute
+        key = make_key((int32_t)weight, grow);
+        key2 = sort_extract(a.seg.attrs[(uint64_t)rowid * a.seg.attr_stride + Q->grp_item], Q->grp_shift, Q->grp_bits);
+        push = true;
+      } else if (SORT && wfirst) { // the weight leads and takes the bin; the row's parts (0..2 dwords) only break its ties
         const uint64_t pk = wfirst_row_key(a.seg.attrs + (uint64_t)rowid * a.seg.attr_stride, Q->wf_parts, OrderPart{so_item, so_shift, so_bits, so_flags},
                                            OrderPart{Q->ord_item, Q->ord_shift, Q->ord_bits, Q->ord_flags});
         bin = wfirst_bin(so_tie, bin_lo, bin_shift, (int32_t)weight);
