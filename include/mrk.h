@@ -232,9 +232,9 @@ typedef struct {
    blob-stored attribute (bit_offset < 0), a 64-bit one, a segment without attribute rows, the VLB-direct path.  MRK_E_INVAL before a
    row is read: locators outside the row or straddling a dword, bit_count 0 or > 32 (other than an aligned 64 inside the row),
    an unknown sort_by, desc outside 0 / 1.  A grouped query is routed as a sorted one (packed block-scan path; hit-ranked shapes
-   through the match queue) and whatever declines a sort declines a group.  Groups of different segments are not merged on the
-   device (that merge adds counts per key): a grouped query leaves in narrow, wide and order rows with MRK_ROW_DECLINED, no keys
-   and spec word 0.  mrk_batcher_search takes no group. */
+   through the match queue) and whatever declines a sort declines a group.  Groups of different segments are merged on the device
+   through GROUP rows (MRK_GROW_WORDS, below: that merge adds counts per key, which no top-K merge does): a grouped query leaves
+   in narrow, wide and order rows with MRK_ROW_DECLINED, no keys and spec word 0.  mrk_batcher_search takes no group. */
 enum { MRK_GROUPSORT_KEY = 0, MRK_GROUPSORT_COUNT = 1, MRK_GROUPSORT_WEIGHT = 2 };
 typedef struct {
   int32_t bit_offset, bit_count; /* CSphAttrLocator of the group-by attribute */
@@ -642,6 +642,60 @@ int mrk_shard_exchange_orows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* oro
    int64, or raw0 << 32 | raw1 (a sort spec: raw0 << 32).  A float's -0.0 reads +0.0.  A weight-first spec unmaps its parts as the
    same spec without bit 3 does; one without parts unmaps to 0. */
 uint64_t mrk_order_unmap_key(uint64_t spec_word, uint64_t mapped);
+
+/* ------------------------------------------------------------------------------------
+ * Group rows: grouped queries (mrk_group) across segments and shards.  The yardstick is ONE grouping sorter fed with the matches
+ * of all segments, as the reference searches the chunks of one index: RtIndex_c::MultiQuery hands the same sorters to every disk
+ * chunk (QueryDiskChunks, sphinxrt.cpp:6018-6077: each chunk's MultiQuery pushes into dSorters, :6541) and then to every RAM
+ * segment (PerformFullTextSearch, :6302-6346: ARRAY_FOREACH over dRamChunks into the same dSorters, :6431).  Its distributed
+ * master / agent setups are NOT the yardstick: an agent returns max_matches groups only, so their counts are approximate.
+ * The three top-K merges above take the best K of a union of entries; groups need their counts ADDED per key and the better head
+ * kept, and a group outside a shard's own top K may be inside the merged top K.  So a group row carries ALL groups of its list.
+ * One row of MRK_GROW_WORDS u64 per query, G = MRK_GROW_GROUPS = 4 * MRK_MAX_K:
+ *   [0 .. G-1]        the head keys of the row's groups, in GROUP ORDER, best first, zero past the count
+ *   [G] [G+1]         number of entries | total_found with MRK_ROW_RERUN / MRK_ROW_DECLINED, as in every row
+ *   [G+2 .. 2G+1]     per entry: the group value in the high dword, @count in the low dword; zero past the count
+ *   [2G+2]            the group spec word: 0 = a relevance query; else bit 0 grouped | bits 1-2 sort_by (MRK_GROUPSORT_*) |
+ *                     bit 3 desc | bits 8-13 bit_count | bits 16-26 max_matches, every other bit zero -- what every merger needs
+ *                     to apply the same 4 * max_matches limit and take the same first max_matches, nothing of where a segment
+ *                     stores the column
+ * A grouped query's row holds all its groups (at most 4 * max_matches), sorted; the first min(n, max_matches) entries are what
+ * mrk_result gives.  total_found is the number of groups.  A relevance query travels in group rows too, so a mixed batch needs one
+ * exchange: its top-K keys in words [0, MRK_MAX_K), a zero plane and spec 0.  A mrk_query.sort / .order query leaves with
+ * MRK_ROW_DECLINED, no keys and spec 0, and so does a grouped query that was declined, at plan time or while it ran (more than
+ * 4 * max_matches groups).
+ * The merge, per group value: @count = the sum of the lists' counts, head = the largest head key (weight DESC, global rowid ASC),
+ * the groups ordered as the spec says, total_found = the number of distinct merged groups (NOT the sum of the lists' totals).  Both
+ * steps are associative and commutative: a staged merge (segments, then shards) gives the same words as one merge of all lists,
+ * and a decline anywhere stays one.  A spec-0 query merges exactly as mrk_topk_merge_rows does (words [0, MRK_MAX_K), [G] and [G+1]
+ * equal that merge's keys, count and total word).  For a grouped query:
+ *   any list with MRK_ROW_RERUN            -> MRK_ROW_RERUN, no entries
+ *   any list with MRK_ROW_DECLINED, answering lists whose spec words differ in any bit, a grouped list next to a spec-0 one, more
+ *   than 4 * max_matches merged groups, a sum of counts above 2^32 - 1 (never wrapped or saturated)
+ *                                          -> MRK_ROW_DECLINED, no entries, the spec word of the first answering list
+ * The spec word is elected among the answering lists: every list but one that comes MRK_ROW_DECLINED under spec word 0 (a shard
+ * whose planner declined the query; such a list's spec is not compared, so the merged row does not depend on which list declined).
+ * A list declined under its own spec word -- over the limit while it ran, or the merged row of lists that were -- keeps its say.
+ * A list whose entry count exceeds G, or whose spec word is neither 0 nor a grouped spec as above, is read as a list with
+ * MRK_ROW_DECLINED, no entries and spec 0: hostile rows never make the merge read or write out of bounds.
+ * k: the largest max_matches of the call's queries; it sizes the merge's tables (a context-owned scratch arena) and is the k of
+ * the spec-0 merge.  A grouped row whose max_matches exceeds k merges to MRK_ROW_DECLINED.  At most 8 lists.
+ * mrk_batch_export_grows is called after mrk_batch_wait (the batch's group tables stay alive until its next grouped submit); a
+ * query rerun after a match-queue overflow leaves with its repaired groups.  There is no standing destination for group rows and
+ * ShardMerger does not carry them: both are left.  Group functions other than one integer attribute are left too.
+ * ---------------------------------------------------------------------------------- */
+#define MRK_GROW_GROUPS (4 * MRK_MAX_K)
+#define MRK_GROW_WORDS (2 * MRK_GROW_GROUPS + 3)
+int mrk_batch_export_grows(mrk_batch* b, uint64_t* grows_dst);
+int mrk_topk_merge_grows(mrk_ctx* ctx, const uint64_t* grows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_grows);
+int mrk_topk_merge_grows_async(mrk_ctx* ctx, const uint64_t* grows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
+                               uint64_t* out_grows, void* wait_event, uint32_t slot);
+int mrk_topk_merge_grows_part(mrk_ctx* ctx, const uint64_t* grows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
+                              uint32_t k, uint64_t* out_grows);
+int mrk_shard_exchange_grows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* grows, uint32_t n_queries, uint32_t k, uint64_t* out_grows,
+                             uint32_t slot);
+/* host only: the group spec word of a query (0 where the fields are no valid spec) */
+uint64_t mrk_group_spec_word(uint32_t sort_by, uint32_t desc, uint32_t bit_count, uint32_t max_matches);
 
 /* merge n_lists sorted partial top-K lists per query (device pointers; relevance order only):
    in_keys[(l*n_queries + q)*MRK_MAX_K + i], in_counts[l*n_queries + q] -> out_keys[q*MRK_MAX_K + i],

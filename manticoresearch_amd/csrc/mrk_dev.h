@@ -532,7 +532,9 @@ struct MergeArgs {
 // The three exchange-row formats (include/mrk.h; the kernels' view of them: mrk_krows.h).  Every row starts KCAP keys | count |
 // total_found; a WIDE row (MRK_SROW_WORDS) goes on with KCAP mapped keys (u32) | sort spec word, an ORDER row (MRK_OROW_WORDS) with
 // KCAP mapped keys (u64) | order spec word.
-enum RowKind { ROWS_NARROW, ROWS_WIDE, ROWS_ORDER };
+// A GROUP row (MRK_GROW_WORDS; mrk_groupsel.hip writes and merges it) has a header of its own: GROW_GROUPS head keys | count |
+// total_found | GROW_GROUPS (group value << 32 | count) | group spec word.
+enum RowKind { ROWS_NARROW, ROWS_WIDE, ROWS_ORDER, ROWS_GROUP };
 constexpr int ROW_WORDS = MRK_ROW_WORDS;
 constexpr uint64_t ROW_RERUN = MRK_ROW_RERUN, ROW_DECLINED = MRK_ROW_DECLINED, ROW_FLAG_MASK = MRK_ROW_RERUN | MRK_ROW_DECLINED;
 constexpr int SROW_WORDS = MRK_SROW_WORDS;
@@ -573,6 +575,25 @@ struct PackXRowsArgs {
   uint32_t skip_sorted;     // != 0: the sorted and ordered queries' rows are already written (sort_select_kernel with a standing destination)
 };
 void launch_pack_xrows(RowKind kind, const PackXRowsArgs& a, void* stream);
+
+// Group rows (mrk_groupsel.hip).  pack_grows_kernel: a batch's results as group rows -- a grouped query's whole table, compacted and
+// sorted as group_select_kernel does it; a relevance query's keys over a zero plane; every other query declined.
+// (the row's word offsets, its reader and its spec word: mrk_kgroup.h)
+struct PackGRowsArgs {
+  const DevQuery* queries;
+  const uint64_t* gtab;     // the batch's group tables (NULL: its last submit held no grouped query)
+  const uint64_t* keys;     // [n][KCAP] relevance queries' keys
+  const uint32_t* cnt;      // [n]
+  const uint64_t* total;    // [n]
+  uint64_t* rows;           // [n][GROW_WORDS]
+  const uint32_t* flags;    // [n] QF_* of the scan or NULL
+  const uint32_t* declined; // [n] decline masks (bit ROWS_GROUP) or NULL
+  uint32_t n;
+};
+void launch_pack_grows(const PackGRowsArgs& a, void* stream);
+// merge_grows_kernel: MergeRowsArgs over group rows; gtab = scratch for one table per query of the call, tab_words u64 apart, each
+// large enough for group_slots_for(a.k) slots and ZERO at launch
+void launch_merge_grows(const MergeRowsArgs& a, uint64_t* gtab, uint64_t tab_words, void* stream);
 
 void launch_scan(const ScanArgs& a, void* stream);
 void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen = false); // a.scand: the instances that carry the sort

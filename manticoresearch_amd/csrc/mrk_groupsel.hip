@@ -11,8 +11,11 @@
 //     head key, group value, count; q_total = the number of groups.
 // 4096 x (8-byte key + 4-byte slot index) = 48 KB of the 64 KB static LDS.  Slots are compacted in whatever order the atomics fall;
 // the order keys are distinct (heads are distinct rows), so the sorted result is the same from run to run.
+// The same compaction and sort (group_compact_sort) serve the GROUP rows further down: pack_grows_kernel writes all the groups of a
+// query's table as its exchange row, merge_grows_kernel adds up to 8 such rows into one table and writes the merged row.
 #include "mrk_kcommon.h"
 #include "mrk_kgroup.h"
+#include "mrk_krows.h"
 
 namespace mrk {
 
@@ -22,47 +25,10 @@ struct __align__(16) GroupSelSmem {
   uint32_t n;
 };
 
-__global__ __launch_bounds__(WG) void group_select_kernel(GroupSelArgs a) {
-  __shared__ GroupSelSmem s;
-  const uint32_t q = blockIdx.x, tid = threadIdx.x;
-  if (q >= a.n_queries) return;
-  const DevQuery* __restrict__ Q = a.queries + q;
-  if (!Q->grp_on) return; // (uniform: another selection answered this query)
-  const uint32_t K = Q->k ? (Q->k < (uint32_t)KCAP ? Q->k : (uint32_t)KCAP) : 1u;
-  const uint32_t S = Q->grp_slots;
-  const GroupTable T = group_table_at(a.gtab + Q->grp_off, S);
-  const uint32_t claimed = *T.claimed, qf = a.q_flags[q];
-  if (tid == 0) s.n = 0;
-  if (qf & QF_OVERFLOW) { // its match queue was full: mrk_batch_wait reruns the query alone, over a cleared table
-    if (tid == 0) {
-      a.out_cnt[q] = 0;
-      if (a.h_cnt) a.h_cnt[q] = 0;
-    }
-    return;
-  }
-  if (claimed > group_limit(K) || claimed > GRP_MAX_GROUPS || (qf & QF_GROUPS)) {
-    if (tid == 0) {
-      a.q_flags[q] = qf | QF_GROUPS;
-      a.out_cnt[q] = 0;
-      if (a.h_flags) a.h_flags[q] = qf | QF_GROUPS;
-      if (a.h_cnt) a.h_cnt[q] = 0;
-    }
-    return;
-  }
-  __syncthreads();
-  const uint32_t sort_by = Q->grp_sort_by, desc = Q->grp_desc;
-  for (uint32_t i = tid; i < S; i += WG) {
-    const uint64_t kw = T.keys[i];
-    if (kw) {
-      const uint32_t at = atomicAdd(&s.n, 1u); // (< claimed <= GRP_MAX_GROUPS: a slot is counted once)
-      if (at < GRP_MAX_GROUPS) {
-        s.key[at] = group_order_key(sort_by, desc, (uint32_t)kw, T.counts[i], T.heads[i]);
-        s.idx[at] = i;
-      }
-    }
-  }
-  __syncthreads();
-  const uint32_t n = s.n < GRP_MAX_GROUPS ? s.n : GRP_MAX_GROUPS;
+// s.key / s.idx [0, n), n <= GRP_MAX_GROUPS, sorted descending by (key, the lower idx first), by the whole workgroup.  The entries are
+// written and the workgroup in step when it is called; it ends behind a barrier.
+__device__ __forceinline__ void group_sort_desc(GroupSelSmem& s, uint32_t n) {
+  const uint32_t tid = threadIdx.x;
   uint32_t len = 64;
   while (len < n) len <<= 1;
   for (uint32_t i = n + tid; i < len; i += WG) s.key[i] = 0, s.idx[i] = 0xFFFFFFFFu; // (padding loses every tie: a real entry may have key 0)
@@ -79,6 +45,73 @@ __global__ __launch_bounds__(WG) void group_select_kernel(GroupSelArgs a) {
       }
       __syncthreads();
     }
+}
+
+// The occupied slots of T (the caller checked: at most GRP_MAX_GROUPS claimed) compacted into s with their order key and sorted, best
+// group first: s.idx[0 .. n) are the groups' slots in group order.  The one compact-and-sort of group_select_kernel, pack_grows_kernel
+// and merge_grows_kernel; by the whole workgroup, which reads T with plain loads (a kernel that filled T itself fences first).
+__device__ __forceinline__ uint32_t group_compact_sort(GroupSelSmem& s, const GroupTable& T, uint32_t sort_by, uint32_t desc) {
+  const uint32_t tid = threadIdx.x;
+  if (tid == 0) s.n = 0;
+  __syncthreads();
+  for (uint32_t i = tid; i < T.slots; i += WG) {
+    const uint64_t kw = T.keys[i];
+    if (kw) {
+      const uint32_t at = atomicAdd(&s.n, 1u); // (< claimed <= GRP_MAX_GROUPS: a slot is counted once)
+      if (at < GRP_MAX_GROUPS) {
+        s.key[at] = group_order_key(sort_by, desc, (uint32_t)kw, T.counts[i], T.heads[i]);
+        s.idx[at] = i;
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t n = s.n < GRP_MAX_GROUPS ? s.n : GRP_MAX_GROUPS;
+  group_sort_desc(s, n);
+  return n;
+}
+
+// ---- a group row (MRK_GROW_WORDS), by the whole workgroup: n entries, entry i = key_at(i) over plane_at(i), zero past n
+template <class KF, class PF>
+__device__ __forceinline__ void write_grow(uint64_t* __restrict__ row, uint32_t n, KF key_at, PF plane_at, uint64_t total_word, uint64_t spec) {
+  for (uint32_t i = threadIdx.x; i < (uint32_t)GROW_GROUPS; i += WG) {
+    row[i] = i < n ? key_at(i) : 0ull;
+    row[GROW_PLANE + i] = i < n ? plane_at(i) : 0ull;
+  }
+  if (threadIdx.x == 0) row[GROW_CNT] = n, row[GROW_TOTAL] = total_word, row[GROW_SPEC] = spec;
+}
+// ... all the groups of T, s.idx[0 .. n) their slots in group order (group_compact_sort)
+__device__ __forceinline__ void write_grow_groups(uint64_t* __restrict__ row, uint32_t n, const GroupSelSmem& s, const GroupTable& T, uint64_t total_word, uint64_t spec) {
+  write_grow(
+      row, n, [&](uint32_t i) { return T.heads[s.idx[i]]; }, [&](uint32_t i) { return group_plane_word((uint32_t)T.keys[s.idx[i]], T.counts[s.idx[i]]); }, total_word, spec);
+}
+
+__global__ __launch_bounds__(WG) void group_select_kernel(GroupSelArgs a) {
+  __shared__ GroupSelSmem s;
+  const uint32_t q = blockIdx.x, tid = threadIdx.x;
+  if (q >= a.n_queries) return;
+  const DevQuery* __restrict__ Q = a.queries + q;
+  if (!Q->grp_on) return; // (uniform: another selection answered this query)
+  const uint32_t K = Q->k ? (Q->k < (uint32_t)KCAP ? Q->k : (uint32_t)KCAP) : 1u;
+  const uint32_t S = Q->grp_slots;
+  const GroupTable T = group_table_at(a.gtab + Q->grp_off, S);
+  const uint32_t claimed = *T.claimed, qf = a.q_flags[q];
+  if (qf & QF_OVERFLOW) { // its match queue was full: mrk_batch_wait reruns the query alone, over a cleared table
+    if (tid == 0) {
+      a.out_cnt[q] = 0;
+      if (a.h_cnt) a.h_cnt[q] = 0;
+    }
+    return;
+  }
+  if (claimed > group_limit(K) || claimed > GRP_MAX_GROUPS || (qf & QF_GROUPS)) {
+    if (tid == 0) {
+      a.q_flags[q] = qf | QF_GROUPS;
+      a.out_cnt[q] = 0;
+      if (a.h_flags) a.h_flags[q] = qf | QF_GROUPS;
+      if (a.h_cnt) a.h_cnt[q] = 0;
+    }
+    return;
+  }
+  const uint32_t n = group_compact_sort(s, T, Q->grp_sort_by, Q->grp_desc);
   const uint32_t m = n < K ? n : K;
   for (uint32_t i = tid; i < m; i += WG) {
     const uint32_t slot = s.idx[i];
@@ -100,6 +133,170 @@ __global__ __launch_bounds__(WG) void group_select_kernel(GroupSelArgs a) {
 void launch_group_select(const GroupSelArgs& a, void* stream) {
   if (!a.n_queries) return;
   hipLaunchKernelGGL(group_select_kernel, dim3(a.n_queries), dim3(WG), 0, (hipStream_t)stream, a);
+}
+
+// ---------------------------------------------------------------------------------------
+// a batch's results as group rows (mrk_batch_export_grows, behind the batch's selection): one workgroup per query.  A grouped query
+// leaves with ALL the groups of its table -- group_select_kernel's compaction and sort, every entry written instead of the best k;
+// a relevance query with its keys over a zero plane and spec 0; a sorted or ordered one, and whatever the planner declined, with
+// MRK_ROW_DECLINED.  A grouped query the scan flagged leaves empty under its own spec word: MRK_ROW_RERUN is an answering list to
+// the merge and takes part in the election of the spec.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void pack_grows_kernel(PackGRowsArgs a) {
+  __shared__ GroupSelSmem s;
+  const uint32_t q = blockIdx.x;
+  if (q >= a.n) return;
+  const DevQuery* __restrict__ Q = a.queries + q;
+  const bool declined = a.declined && ((a.declined[q] >> ROWS_GROUP) & 1u) != 0u;
+  const uint32_t qf = a.flags ? a.flags[q] : 0u;
+  uint64_t* __restrict__ row = a.rows + (uint64_t)q * GROW_WORDS;
+  auto zero = [](uint32_t) { return 0ull; };
+  if (!declined && Q->grp_on && a.gtab) { // (uniform)
+    const uint32_t K = Q->k ? (Q->k < (uint32_t)KCAP ? Q->k : (uint32_t)KCAP) : 1u;
+    const uint64_t spec = group_spec_word(Q->grp_sort_by, Q->grp_desc, Q->grp_bits, K);
+    const GroupTable T = group_table_at(const_cast<uint64_t*>(a.gtab) + Q->grp_off, Q->grp_slots);
+    const uint32_t claimed = *T.claimed;
+    const uint32_t over = claimed > group_limit(K) || claimed > GRP_MAX_GROUPS ? QF_GROUPS : 0u; // (group_select_kernel set it already)
+    if (!row_unflagged(false, qf | over)) {
+      write_grow(row, 0u, zero, zero, row_total_word(false, qf | over, 0ull), spec);
+      return;
+    }
+    const uint32_t n = group_compact_sort(s, T, Q->grp_sort_by, Q->grp_desc);
+    write_grow_groups(row, n, s, T, n, spec); // total_found = the number of groups
+    return;
+  }
+  const uint32_t n = !row_unflagged(declined, qf) ? 0u : a.cnt[q] < (uint32_t)KCAP ? a.cnt[q] : (uint32_t)KCAP;
+  write_grow(
+      row, n, [&](uint32_t i) { return a.keys[(uint64_t)q * KCAP + i]; }, zero, row_total_word(declined, qf, a.total[q]), 0ull);
+}
+
+void launch_pack_grows(const PackGRowsArgs& a, void* stream) {
+  if (!a.n) return;
+  hipLaunchKernelGGL(pack_grows_kernel, dim3(a.n), dim3(WG), 0, (hipStream_t)stream, a);
+}
+
+// ---------------------------------------------------------------------------------------
+// merge of <= 8 group rows per query: ONE grouping sorter over the matches of all lists (the reference hands the same sorter to every
+// chunk of an index, sphinxrt.cpp:6018-6077 and :6302-6346).  One workgroup per query.
+//   spec 0 (a relevance query): the narrow merge of the rows' first ROW_WORDS words -- the lists' keys gathered in the sort area, at
+//     most 4 lists of KCAP at a time, sorted, the best KCAP kept for the next round; words [0, KCAP), count and total word come out as
+//     merge_xrows_kernel<NarrowFmt> writes them.
+//   grouped: every entry of every list goes through group_update into the query's table of the scratch arena (zero at launch; the
+//     count is added, the head key max-ed), then the shared compact-and-sort orders the merged groups and all of them leave.
+// What makes the merged row MRK_ROW_DECLINED or MRK_ROW_RERUN instead: include/mrk.h.  A count past 2^32 - 1 is found without a
+// second pass over the lists: the 64-bit sum of all counts that went in must equal the sum of the table's 32-bit counts, and a slot
+// that wrapped is short by 2^32.
+// LDS: the 48 KB sort area, the lists' counts and three words.  The table is read back with plain loads behind an agent-scope fence pair.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void merge_grows_kernel(MergeRowsArgs a, uint64_t* gtab, uint64_t tab_words) {
+  __shared__ GroupSelSmem s;
+  __shared__ unsigned long long sum_in, sum_out;
+  // the lists' entry counts go through group_row_head ONCE and wait in LDS for the loops below.  (A first version called the reader
+  // again in front of each loop, through an early-return form of it: the entry loop of every grouped list came out of the device
+  // compiler with a bound of 0 -- an empty merged row under a good spec word, which the GPU tests caught against the numpy mirror.)
+  __shared__ uint32_t full, l_cnt[8];
+  const uint32_t q = blockIdx.x, tid = threadIdx.x;
+  if (q >= a.n_queries) return;
+  const uint64_t* __restrict__ rows = a.in_rows + (uint64_t)q * GROW_WORDS;
+  const uint64_t list_words = (uint64_t)a.list_stride * GROW_WORDS;
+  if (a.n_lists > 8u) return; // (the launch's contract; l_cnt holds 8)
+  uint64_t spec = 0, flags = 0, total = 0, have = 0;
+  bool have_spec = false, mismatch = false;
+  for (uint32_t l = 0; l < a.n_lists; ++l) {
+    uint64_t t, sp; // (uniform) the list's total word and spec word; a hostile list reads as declined and empty
+    const uint32_t c = group_row_head(rows + l * list_words, t, sp);
+    if (tid == 0) l_cnt[l] = c;
+    flags |= t & ROW_FLAG_MASK, total += t & ~ROW_FLAG_MASK, have += c < (uint32_t)KCAP ? c : (uint32_t)KCAP;
+    if (!group_row_has_say(t, sp)) continue; // (declined without a spec: the merged row does not depend on which list declined)
+    if (!have_spec) spec = sp, have_spec = true;
+    mismatch = mismatch || sp != spec;
+  }
+  __syncthreads();
+  uint64_t* __restrict__ out = a.out_rows + (uint64_t)(a.out_first + q) * GROW_WORDS;
+  auto zero = [](uint32_t) { return 0ull; };
+  auto finish = [&](uint64_t f) {
+    if (tid == 0 && a.flags_any) {
+      if (f & ROW_RERUN) a.flags_any[0] = 1u;
+      if (f & ROW_DECLINED) a.flags_any[1] = 1u;
+    }
+  };
+  if (mismatch) flags |= ROW_DECLINED;
+  if (spec == 0ull) { // ---- a relevance query: the narrow merge
+    uint32_t acc = 0;
+    if (!mismatch)
+      for (uint32_t l = 0; l < a.n_lists; ++l) {
+        uint32_t c = l_cnt[l];
+        if (c > (uint32_t)KCAP) c = KCAP;
+        if (!c) continue;
+        if (acc + c > GRP_MAX_GROUPS) { // the area is full: keep the best KCAP of what it holds
+          __syncthreads();
+          group_sort_desc(s, acc);
+          acc = acc < (uint32_t)KCAP ? acc : (uint32_t)KCAP;
+        }
+        const uint64_t* __restrict__ row = rows + l * list_words;
+        for (uint32_t i = tid; i < c; i += WG) s.key[acc + i] = row[i], s.idx[acc + i] = 0u;
+        acc += c;
+      }
+    __syncthreads();
+    group_sort_desc(s, acc);
+    const uint32_t n = mismatch ? 0u : have < a.k ? (uint32_t)have : a.k;
+    write_grow(
+        out, n, [&](uint32_t i) { return s.key[i]; }, zero, (total & ~ROW_FLAG_MASK) | flags, 0ull);
+    finish(flags);
+    return;
+  }
+  // ---- a grouped query
+  GroupSpec gs;
+  (void)group_spec_unpack(spec, gs); // (an answering list's spec word: list_head saw it unpack)
+  if (gs.k > a.k) flags |= ROW_DECLINED; // (its table would not fit the arena's stride)
+  uint32_t n = 0;
+  GroupTable T{};
+  if (!flags) { // (uniform)
+    T = group_table_at(gtab + (uint64_t)q * tab_words, group_slots_for(gs.k));
+    if (tid == 0) sum_in = 0ull, sum_out = 0ull, full = 0u;
+    __syncthreads();
+    unsigned long long mine = 0;
+    bool ok = true;
+    for (uint32_t l = 0; l < a.n_lists; ++l) {
+      const uint32_t c = l_cnt[l];
+      const uint64_t* __restrict__ row = rows + l * list_words;
+      for (uint32_t i = tid; i < c; i += WG) {
+        const uint64_t pw = row[GROW_PLANE + i];
+        ok = group_update<GroupDevOps>(T, (uint32_t)(pw >> 32), (uint32_t)pw, row[i]) && ok;
+        mine += (uint32_t)pw;
+      }
+    }
+    if (mine) atomicAdd(&sum_in, mine);
+    if (!ok) atomicOr(&full, 1u);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const uint32_t claimed = *T.claimed;
+    if (full || claimed > group_limit(gs.k) || claimed > GRP_MAX_GROUPS)
+      flags |= ROW_DECLINED; // one sorter over all the lists would have cut groups by now
+    else {
+      n = group_compact_sort(s, T, gs.sort_by, gs.desc);
+      mine = 0;
+      for (uint32_t i = tid; i < n; i += WG) mine += T.counts[s.idx[i]];
+      if (mine) atomicAdd(&sum_out, mine);
+      __syncthreads();
+      if (sum_out != sum_in) flags |= ROW_DECLINED, n = 0; // some group's count passed 2^32 - 1
+    }
+  }
+  if (flags)
+    write_grow(out, 0u, zero, zero, flags, spec);
+  else
+    write_grow_groups(out, n, s, T, n, spec);
+  finish(flags);
+#ifdef MRK_GDBG
+  __syncthreads();
+  if (tid == 0) out[4090] = sum_in, out[4091] = T.claimed ? *T.claimed : 77u, out[4092] = n, out[4093] = full, out[4094] = T.slots, out[4095] = sum_out, out[4089] = flags, out[4088] = a.n_lists;
+#endif
+}
+
+void launch_merge_grows(const MergeRowsArgs& a, uint64_t* gtab, uint64_t tab_words, void* stream) {
+  if (!a.n_queries) return;
+  hipLaunchKernelGGL(merge_grows_kernel, dim3(a.n_queries), dim3(WG), 0, (hipStream_t)stream, a, gtab, tab_words);
 }
 
 } // namespace mrk

@@ -255,6 +255,7 @@ static void mrk_ctx_destroy_impl(mrk_ctx* c) {
   mrk_comm_destroy_impl(c);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->merge_stream) (void)hipStreamDestroy(c->merge_stream);
+  if (c->gmerge) (void)hipFree(c->gmerge);
   for (hipEvent_t e : c->merge_done)
     if (e) (void)hipEventDestroy(e);
   delete c;
@@ -1460,7 +1461,8 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     // the queries' decline masks, for every row format whether or not a destination stands: mrk_batch_export_* writes the same rows
     // after the wait
     uint32_t any = 0;
-    for (uint32_t i = 0; i < n; ++i) any |= b->h_decl.p[i] = mrk::query_decline_mask(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order, b->orows_wf_run, b->grouped[i] != 0);
+    for (uint32_t i = 0; i < n; ++i) any |= b->h_decl.p[i] = mrk::query_decline_mask(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order, b->orows_wf_run, b->grouped[i] != 0) |
+                                                    mrk::group_row_decline_bit(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order);
     b->any_declined = any != 0;
     if (any || b->decl_dirty) HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     b->decl_dirty = any != 0;
@@ -1587,6 +1589,8 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
     HIP_TRY(hipMemcpyAsync(b->h_gcnt.p + (size_t)qi * KCAP, r->d_out_gcnt.p, (size_t)KCAP * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(b->d_out_gkey.p + (size_t)qi * KCAP, r->d_out_gkey.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_out_gcnt.p + (size_t)qi * KCAP, r->d_out_gcnt.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st));
+    // ... and the rerun's whole table in the place of the abandoned run's (same k, same slots): mrk_batch_export_grows packs from there
+    HIP_TRY(hipMemcpyAsync(b->d_gtab.p + b->h_queries.p[qi].grp_off, r->d_gtab.p, mrk::group_table_words(passes[0].grp_slots) * 8, hipMemcpyDeviceToDevice, st));
   }
   // the device-side row is good again -- or carries what the rerun ran into: an exported row then leaves flagged, never with the rerun's keys
   HIP_TRY(hipMemcpyAsync(b->d_q_flags.p + qi, r->d_q_flags.p, 4, hipMemcpyDeviceToDevice, st));
@@ -1753,12 +1757,36 @@ static int mrk_batch_record_event_impl(mrk_batch* b, void* hip_event) {
 }
 
 static int batch_export_rows(mrk_batch* b, uint64_t* dst, RowKind kind) {
-  if (!b || !dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_%s: NULL argument", kind == ROWS_ORDER ? "orows" : kind == ROWS_WIDE ? "srows" : "rows");
+  if (!b || !dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_%s: NULL argument", kind == ROWS_GROUP ? "grows" : kind == ROWS_ORDER ? "orows" : kind == ROWS_WIDE ? "srows" : "rows");
   HIP_TRY(hipSetDevice(b->ctx->device));
-  launch_pack_rows(b, kind, dst, b->n_queries, b->packed_run, false, b->stream); // behind the batch's selection kernels
+  if (kind == ROWS_GROUP) { // (the tables in d_gtab are the last submit's until the next grouped scan clears them)
+    if (b->in_flight) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_grows: call mrk_batch_wait first");
+    mrk::PackGRowsArgs pg{};
+    pg.queries = b->d_queries.p, pg.gtab = b->any_grouped ? b->d_gtab.p : nullptr, pg.keys = b->d_out_keys.p, pg.cnt = b->d_out_cnt.p, pg.total = b->d_q_total.p;
+    pg.rows = dst, pg.flags = b->packed_run ? b->d_q_flags.p : nullptr, pg.declined = b->any_declined ? b->d_decl.p : nullptr, pg.n = b->n_queries;
+    mrk::launch_pack_grows(pg, b->stream);
+  } else
+    launch_pack_rows(b, kind, dst, b->n_queries, b->packed_run, false, b->stream); // behind the batch's selection kernels
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(b->stream));
   b->in_flight = false;
+  return MRK_OK;
+}
+
+// A group-row merge's tables: one per query of the call, group_table_words(group_slots_for(k)) rounded up to whole 128-byte lines (no
+// two workgroups' tables share one), in the context's arena -- grown here, and cleared on the merge stream in front of the kernel.
+// Merges of one context run one after another on that stream, so one arena serves them all; growing it frees the old one, which
+// hipFree does only after the device has drained.
+static uint64_t group_merge_tab_words(uint32_t k) { return (mrk::group_table_words(mrk::group_slots_for(k)) + 15ull) & ~15ull; }
+static int reserve_group_merge(mrk_ctx* ctx, uint32_t n_queries, uint32_t k) {
+  const size_t words = (size_t)group_merge_tab_words(k) * std::max<uint32_t>(n_queries, 1u);
+  if (words > ctx->gmerge_words) {
+    if (ctx->gmerge) (void)hipFree(ctx->gmerge);
+    ctx->gmerge = nullptr, ctx->gmerge_words = 0;
+    HIP_TRY(hipMalloc((void**)&ctx->gmerge, words * 8));
+    ctx->gmerge_words = words;
+  }
+  HIP_TRY(hipMemsetAsync(ctx->gmerge, 0, words * 8, ctx->merge_stream));
   return MRK_OK;
 }
 
@@ -1770,7 +1798,10 @@ static void launch_rows_merge(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n
     mrk::MergeRowsArgs mr{};
     mr.in_rows = rows_all, mr.n_lists = n_lists, mr.list_stride = list_stride, mr.n_queries = n_queries, mr.k = k;
     mr.out_rows = out_rows, mr.out_first = out_first, mr.flags_any = flags_any;
-    launch_merge_xrows(kind, mr, ctx->merge_stream);
+    if (kind == ROWS_GROUP) // (the caller reserved and cleared the arena: reserve_group_merge)
+      mrk::launch_merge_grows(mr, ctx->gmerge, group_merge_tab_words(k), ctx->merge_stream);
+    else
+      launch_merge_xrows(kind, mr, ctx->merge_stream);
     return;
   }
   MergeArgs ma{}; // many lists (one GPU serving many segments): the general kernel; same layout only when the stride is the query count
@@ -1789,7 +1820,7 @@ static int merge_k_ok(const char* fn, uint32_t k) {
 }
 static int merge_lists_ok(const char* sfx, uint32_t n_lists, RowKind kind) {
   if (kind == ROWS_NARROW || (n_lists != 0 && n_lists <= 8)) return MRK_OK;
-  return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_%s%s: %u lists (1..8)", kind == ROWS_ORDER ? "orows" : "srows", sfx, n_lists);
+  return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_%s%s: %u lists (1..8)", kind == ROWS_GROUP ? "grows" : kind == ROWS_ORDER ? "orows" : "srows", sfx, n_lists);
 }
 
 static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
@@ -1798,6 +1829,7 @@ static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint
   int rc;
   if ((rc = merge_k_ok("mrk_topk_merge_rows", k)) || (rc = merge_lists_ok("", n_lists, kind))) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
+  if (kind == ROWS_GROUP && (rc = reserve_group_merge(ctx, n_queries, k))) return rc;
   launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, kind);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->merge_stream));
@@ -1812,6 +1844,8 @@ static int mrk_topk_merge_rows_part_impl(mrk_ctx* ctx, const uint64_t* rows_recv
   if (const int rc = merge_k_ok("mrk_topk_merge_rows_part", k)) return rc;
   if (n_lists == 0 || n_lists > 8 || count > list_stride) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: %u lists (1..8), %u queries of stride %u", n_lists, count, list_stride);
   HIP_TRY(hipSetDevice(ctx->device));
+  if (kind == ROWS_GROUP)
+    if (const int rc = reserve_group_merge(ctx, count, k)) return rc;
   launch_rows_merge(ctx, rows_recv, n_lists, list_stride, count, k, out_rows, first, nullptr, kind);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->merge_stream));
@@ -1827,6 +1861,7 @@ static int mrk_topk_merge_rows_async_impl(mrk_ctx* ctx, const uint64_t* rows_all
   HIP_TRY(hipSetDevice(ctx->device));
   if (!ctx->merge_done[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->merge_done[slot], hipEventDisableTiming));
   if (wait_event) HIP_TRY(hipStreamWaitEvent(ctx->merge_stream, (hipEvent_t)wait_event, 0));
+  if (kind == ROWS_GROUP && (rc = reserve_group_merge(ctx, n_queries, k))) return rc;
   launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, kind);
   HIP_TRY(hipGetLastError());
 
@@ -2128,6 +2163,25 @@ extern "C" int mrk_topk_merge_orows_part(mrk_ctx* ctx, const uint64_t* orows_rec
                                          uint32_t k, uint64_t* out_orows) {
   return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, orows_recv, n_lists, list_stride, first, count, k, out_orows, ROWS_ORDER); });
 }
+extern "C" int mrk_batch_export_grows(mrk_batch* b, uint64_t* grows_dst) {
+  return on_worker(b ? b->ctx : nullptr, [&] { return batch_export_rows(b, grows_dst, ROWS_GROUP); });
+}
+extern "C" int mrk_topk_merge_grows(mrk_ctx* ctx, const uint64_t* grows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_grows) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_impl(ctx, grows_all, n_lists, n_queries, k, out_grows, ROWS_GROUP); });
+}
+extern "C" int mrk_topk_merge_grows_async(mrk_ctx* ctx, const uint64_t* grows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
+                                          uint64_t* out_grows, void* wait_event, uint32_t slot) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_async_impl(ctx, grows_all, n_lists, n_queries, k, out_grows, wait_event, slot, ROWS_GROUP); });
+}
+extern "C" int mrk_topk_merge_grows_part(mrk_ctx* ctx, const uint64_t* grows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
+                                         uint32_t k, uint64_t* out_grows) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, grows_recv, n_lists, list_stride, first, count, k, out_grows, ROWS_GROUP); });
+}
+extern "C" uint64_t mrk_group_spec_word(uint32_t sort_by, uint32_t desc, uint32_t bit_count, uint32_t max_matches) {
+  mrk::GroupSpec gs;
+  const uint64_t w = mrk::group_spec_word(sort_by, desc, bit_count, max_matches);
+  return sort_by <= 3u && desc <= 1u && bit_count <= 63u && max_matches <= 2047u && mrk::group_spec_unpack(w, gs) ? w : 0ull;
+}
 extern "C" uint64_t mrk_order_unmap_key(uint64_t spec_word, uint64_t mapped) { return mrk::order_unmap_key(spec_word, mapped); }
 extern "C" uint32_t mrk_sort_unmap_key(uint64_t spec_word, uint32_t mapped) { return mrk::sort_unmap_key(spec_word, mapped); }
 extern "C" int mrk_merge_wait(mrk_ctx* ctx, uint32_t slot) {
@@ -2157,11 +2211,11 @@ extern "C" int mrk_comm_allreduce_i64(mrk_ctx* ctx, int64_t* values, uint64_t n)
   if (!ctx || (!values && n)) return mrk_fail(MRK_E_INVAL, "mrk_comm_allreduce_i64: NULL argument");
   return on_worker(ctx, [&] { return mrk_comm_allreduce_i64_impl(ctx, values, n); });
 }
-// one body for narrow rows (MRK_ROW_WORDS), wide ones (MRK_SROW_WORDS) and order rows (MRK_OROW_WORDS): the row width and the merge
-// kernel are all that differ
+// one body for narrow rows (MRK_ROW_WORDS), wide ones (MRK_SROW_WORDS), order rows (MRK_OROW_WORDS) and group rows (MRK_GROW_WORDS):
+// the row width and the merge kernel are all that differ
 static int shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, uint32_t n_queries, uint32_t k, uint64_t* out_rows, uint32_t slot,
                           RowKind kind) {
-  const uint32_t row_words = kind == ROWS_ORDER ? MRK_OROW_WORDS : kind == ROWS_WIDE ? MRK_SROW_WORDS : MRK_ROW_WORDS;
+  const uint32_t row_words = kind == ROWS_GROUP ? MRK_GROW_WORDS : kind == ROWS_ORDER ? MRK_OROW_WORDS : kind == ROWS_WIDE ? MRK_SROW_WORDS : MRK_ROW_WORDS;
   if (!ctx || !rows || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: NULL argument");
   if (slot >= MRK_MERGE_SLOTS) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: slot %u of %d", slot, MRK_MERGE_SLOTS);
   if (batch && batch->ctx != ctx) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: batch and context do not belong together");
@@ -2185,6 +2239,7 @@ static int shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, 
       uint32_t* flags_dev = nullptr;
       HIP_TRY(hipStreamWaitEvent(ctx->merge_stream, gathered, 0));
       if ((rc = mrk_comm_flags_begin(ctx, slot, &flags_dev))) return rc;
+      if (count && kind == ROWS_GROUP && (rc = reserve_group_merge(ctx, count, k))) return rc;
       if (count) launch_rows_merge(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), per, count, k, out_rows, first, flags_dev, kind);
       HIP_TRY(hipGetLastError());
       return mrk_comm_flags_finish(ctx, slot);
@@ -2205,6 +2260,10 @@ extern "C" int mrk_shard_exchange_srows(mrk_ctx* ctx, mrk_batch* batch, const ui
 extern "C" int mrk_shard_exchange_orows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* orows, uint32_t n_queries, uint32_t k, uint64_t* out_orows,
                                         uint32_t slot) {
   return shard_exchange(ctx, batch, orows, n_queries, k, out_orows, slot, ROWS_ORDER);
+}
+extern "C" int mrk_shard_exchange_grows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* grows, uint32_t n_queries, uint32_t k, uint64_t* out_grows,
+                                        uint32_t slot) {
+  return shard_exchange(ctx, batch, grows, n_queries, k, out_grows, slot, ROWS_GROUP);
 }
 extern "C" int mrk_shard_slice(uint32_t n_queries, int n_ranks, int rank, uint32_t* first, uint32_t* count) {
   if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return mrk_fail(MRK_E_INVAL, "mrk_shard_slice: rank %d of %d", rank, n_ranks);

@@ -30,6 +30,8 @@ struct mrk_ctx {
   hipStream_t merge_stream = nullptr; // mrk_topk_merge: never queued behind the scans of a following batch
   hipEvent_t merge_done[MRK_MERGE_SLOTS] = {};
   bool merge_used[MRK_MERGE_SLOTS] = {};
+  uint64_t* gmerge = nullptr;     // group-row merges (mrk_topk_merge_grows*): the scratch arena of their tables, one per query of a call, ...
+  size_t gmerge_words = 0;        // ... grown on demand, cleared on merge_stream in front of every merge
   int64_t item_bytes = 128 << 10; // target doclist bytes per work item
   int path = 0;                   // 0 = packed doclists when the segment has them, 1 = VLB (.spd) direct, 2 = packed only
   int pack = 1;                   // build packed doclists at segment load
@@ -253,8 +255,9 @@ void place_bm_items(const DevQuery* head, uint32_t n, const std::vector<DevQuery
 // ran with mrk_batch_orows_weight_first on.  A NARROW row is merged by (weight, docid), which answers relevance queries only; a WIDE
 // row has no room for a 64-bit key (SORT_ON_ORDER) and no word for the weight in front (SORT_ON_WEIGHT); an ORDER row carries both,
 // the latter only where the batch asked for it.  The order bit implies the wide bit, the wide bit the narrow one: some bit is set
-// exactly when the narrow bit is.  (A grouped query leaves in no row format -- merging groups adds counts per key, which no merge here
-// does: its mask is all three bits, set where this function is called -- query_decline_mask.)
+// exactly when the narrow bit is.  (A grouped query leaves in none of these three formats -- merging groups adds counts per key,
+// which no top-K merge does: its mask is all three bits, set where this function is called -- query_decline_mask.  It travels in
+// GROUP rows, whose bit is group_row_decline_bit's, below.)
 inline uint32_t row_decline_mask(int status, uint32_t sort_bits, uint32_t order, bool orows_wf_run) {
   const bool off = status != MRK_OK, no_row = order == SORT_ON_ORDER || order == SORT_ON_WEIGHT;
   const bool narrow = off || sort_bits != 0 || no_row, wide = off || no_row, ord = off || (order == SORT_ON_WEIGHT && !orows_wf_run);
@@ -263,6 +266,11 @@ inline uint32_t row_decline_mask(int status, uint32_t sort_bits, uint32_t order,
 
 inline uint32_t query_decline_mask(int status, uint32_t sort_bits, uint32_t order, bool orows_wf_run, bool grouped) {
   return grouped ? (1u << ROWS_NARROW) | (1u << ROWS_WIDE) | (1u << ROWS_ORDER) : row_decline_mask(status, sort_bits, order, orows_wf_run);
+}
+// The fourth bit of the mask, OR-ed to the three above where a batch fills it: a GROUP row (MRK_GROW_WORDS) carries grouped and
+// relevance queries and declines the rest -- a query the planner declined, and a sorted or ordered one.  It implies the narrow bit.
+inline uint32_t group_row_decline_bit(int status, uint32_t sort_bits, uint32_t order) {
+  return status != MRK_OK || sort_bits != 0 || order != 0 ? 1u << ROWS_GROUP : 0u;
 }
 
 // Least and largest field-weight sum over the masks of the first nwf (<= 32) fields, the empty mask counting as 1

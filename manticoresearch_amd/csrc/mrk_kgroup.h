@@ -104,6 +104,43 @@ MRK_GHD uint64_t group_order_key(uint32_t sort_by, uint32_t desc, uint32_t value
   return ((uint64_t)(desc ? p : ~p) << 32) | (uint32_t)head;
 }
 
+// The group spec word of a GROUP row (MRK_GROW_WORDS, include/mrk.h): what every merger of a grouped query's rows must agree on --
+// the groups' order, the key's width and the query's max_matches (the 4 k limit and the first k) -- and nothing of where a segment
+// stores the column.  0 = a relevance query.
+//   bit 0 grouped | bits 1-2 sort_by | bit 3 desc | bits 8-13 bit_count | bits 16-26 max_matches
+struct GroupSpec {
+  uint32_t sort_by, desc, bit_count, k;
+};
+MRK_GHD uint64_t group_spec_word(uint32_t sort_by, uint32_t desc, uint32_t bit_count, uint32_t k) {
+  return 1ull | ((uint64_t)(sort_by & 3u) << 1) | ((uint64_t)(desc & 1u) << 3) | ((uint64_t)(bit_count & 63u) << 8) | ((uint64_t)(k & 2047u) << 16);
+}
+// false: not a word group_spec_word writes for a query this library answers (a stray bit, an unknown order, a width or a max_matches
+// out of range); the merge reads such a list as declined
+MRK_GHD bool group_spec_unpack(uint64_t w, GroupSpec& s) {
+  s.sort_by = (uint32_t)(w >> 1) & 3u, s.desc = (uint32_t)(w >> 3) & 1u, s.bit_count = (uint32_t)(w >> 8) & 63u, s.k = (uint32_t)(w >> 16) & 2047u;
+  return (w & 1ull) && w == group_spec_word(s.sort_by, s.desc, s.bit_count, s.k) && s.sort_by <= (uint32_t)MRK_GROUPSORT_WEIGHT && s.bit_count >= 1u &&
+         s.bit_count <= 32u && s.k >= 1u && s.k <= (uint32_t)MRK_MAX_K;
+}
+// A group row's word offsets; an entry of its plane (the group value over its count); and its reader -- the one every merger goes
+// through, on the device and in tests/cpp/group_merge.cpp: the entry count, the total word and the spec word of a list's row.  A
+// hostile row (more entries than a row holds, a spec word that does not unpack) reads as MRK_ROW_DECLINED with no entries and spec
+// word 0, so nothing behind it indexes past the row.  group_row_has_say: whether the list takes part in the election of the query's
+// spec word -- every list but a declined one without a spec (a shard whose planner declined the query sends 0).  A list declined
+// under its spec word (over the limit while it ran, or the merged row of such lists) keeps its say, so that a staged merge elects
+// the spec a one-step merge elects.
+constexpr int GROW_GROUPS = MRK_GROW_GROUPS, GROW_WORDS = MRK_GROW_WORDS;
+constexpr int GROW_CNT = GROW_GROUPS, GROW_TOTAL = GROW_GROUPS + 1, GROW_PLANE = GROW_GROUPS + 2, GROW_SPEC = GROW_WORDS - 1;
+MRK_GHD uint64_t group_plane_word(uint32_t value, uint32_t count) { return ((uint64_t)value << 32) | count; }
+MRK_GHD uint32_t group_row_head(const uint64_t* row, uint64_t& tword, uint64_t& spec) {
+  const uint64_t c = row[GROW_CNT], t = row[GROW_TOTAL], sp = row[GROW_SPEC];
+  GroupSpec gs;
+  const bool hostile = c > (uint64_t)GROW_GROUPS || (sp != 0ull && !group_spec_unpack(sp, gs));
+  tword = hostile ? (t & MRK_ROW_RERUN) | MRK_ROW_DECLINED : t;
+  spec = hostile ? 0ull : sp;
+  return hostile ? 0u : (uint32_t)c;
+}
+MRK_GHD bool group_row_has_say(uint64_t tword, uint64_t spec) { return !(tword & MRK_ROW_DECLINED) || spec != 0ull; }
+
 #if defined(__HIPCC__)
 struct GroupDevOps {
   static __device__ uint64_t load64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

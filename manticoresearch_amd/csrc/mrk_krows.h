@@ -88,6 +88,7 @@ __device__ __forceinline__ void write_row_header(uint64_t* __restrict__ row, uin
 // out empty with ROW_DECLINED: at submit by the planner (`declined`), or while it ran (QF_FSM, QF_ARENA: no rerun would help, and
 // mrk_batch_wait reports MRK_E_UNSUPPORTED for it).  The merge ORs both bits through: the receiver reruns / fails the query, never a
 // partial answer.  A row leaves with its keys only when row_unflagged(): the kernels' one test for that.
+// (The fourth format, the GROUP row of mrk_groupsel.hip, has a header and a writer of its own and shares only what follows.)
 constexpr uint32_t QF_DECLINES = QF_FSM | QF_ARENA | QF_GROUPS;
 __device__ __forceinline__ bool row_unflagged(bool declined, uint32_t qflags) { return !declined && !(qflags & (QF_OVERFLOW | QF_DECLINES)); }
 __device__ __forceinline__ uint64_t row_total_word(bool declined, uint32_t qflags, uint64_t total) {

@@ -236,9 +236,122 @@ def merge_orows_np(orows_all: np.ndarray, k: int) -> np.ndarray:
     return out
 
 
+# MRK_GROW_WORDS, the group row that carries a grouped query (api.Group) across segments and shards -- ALL the groups of its list:
+#   GROW_GROUPS head keys in group order | count | total_found | GROW_GROUPS (group value << 32 | @count) | group spec word
+GROW_WORDS, GROW_GROUPS = _lib.GROW_WORDS, _lib.GROW_GROUPS
+GROW_CNT, GROW_TOTAL, GROW_PLANE, GROW_SPEC = GROW_GROUPS, GROW_GROUPS + 1, GROW_GROUPS + 2, GROW_WORDS - 1  # word offsets
+GROUPBY_FACTOR = 4
+
+
+def group_spec_word(sort_by: int, desc, bit_count: int, max_matches: int) -> int:
+    """The spec word of a grouped query's group row (mrk_kgroup.h, group_spec_word): bit 0 grouped | bits 1-2 sort_by
+    (GROUPSORT_*) | bit 3 desc | bits 8-13 bit_count | bits 16-26 max_matches.  0 = a relevance query."""
+    return 1 | ((int(sort_by) & 3) << 1) | ((1 if desc else 0) << 3) | ((int(bit_count) & 63) << 8) | ((int(max_matches) & 2047) << 16)
+
+
+def group_spec_unpack(spec: int):
+    """(sort_by, desc, bit_count, max_matches) of a grouped spec word, or None where it is not one group_spec_word writes for a query
+    the library answers (a stray bit, sort_by 3, bit_count outside 1..32, max_matches outside 1..MRK_MAX_K)."""
+    spec = int(spec)
+    sort_by, desc, bits, k = (spec >> 1) & 3, (spec >> 3) & 1, (spec >> 8) & 63, (spec >> 16) & 2047
+    if not spec & 1 or spec != group_spec_word(sort_by, desc, bits, k) or sort_by > 2 or not 1 <= bits <= 32 or not 1 <= k <= MRK_MAX_K:
+        return None
+    return sort_by, desc, bits, k
+
+
+def group_order_keys(sort_by: int, desc: int, value: np.ndarray, count: np.ndarray, head: np.ndarray) -> np.ndarray:
+    """mrk_kgroup.h group_order_key per group: the part the groups are ordered by, in its direction, over ~head rowid; larger = better."""
+    head = np.asarray(head, np.uint64)
+    p = (np.asarray(count, np.uint32) if sort_by == 1 else np.asarray(value, np.uint32) if sort_by == 0 else (head >> np.uint64(32)).astype(np.uint32))
+    p = p if desc else ~p
+    return (p.astype(np.uint64) << np.uint64(32)) | (head & np.uint64(0xFFFFFFFF))
+
+
+def grow_groups(row: np.ndarray):
+    """A group row's answer -> (head rowid, head weight, group key, @count, total_found): the first min(n, max_matches) entries of a
+    grouped row (all of a spec-0 row's, with key and count None).  rowids are GLOBAL.  A flagged row gives empty arrays and total None."""
+    row = np.asarray(row, dtype=np.uint64)
+    n, tf, spec = int(row[GROW_CNT]), int(row[GROW_TOTAL]), int(row[GROW_SPEC])
+    flagged = bool(tf & (ROW_RERUN | ROW_DECLINED))
+    un = group_spec_unpack(spec) if spec else None
+    n = 0 if flagged else min(n, un[3]) if un else min(n, MRK_MAX_K)
+    keys = row[:n]
+    rowid = ~keys.astype(np.uint32)
+    weight = ((keys >> np.uint64(32)).astype(np.uint32) ^ np.uint32(0x80000000)).astype(np.int32)
+    plane = row[GROW_PLANE:GROW_PLANE + n]
+    gkey = (plane >> np.uint64(32)).astype(np.uint32) if un else None
+    gcnt = plane.astype(np.uint32) if un else None
+    return rowid, weight, gkey, gcnt, None if flagged else tf
+
+
+def merge_grows_np(grows_all: np.ndarray, k: int) -> np.ndarray:
+    """What merge_grows_kernel computes, in numpy, word for word: grows_all uint64 [n_lists, nq, GROW_WORDS] -> [nq, GROW_WORDS].
+    A list with more than GROW_GROUPS entries or a spec word that does not unpack reads as ROW_DECLINED and empty.  The spec word is
+    that of the first list that is not ROW_DECLINED under spec 0; the other such lists must agree in every bit.  Spec 0: merge_rows_np over the first
+    ROW_WORDS words (keys, count, total word; flags OR-ed through).  Grouped: counts add per group value, the largest head key stays,
+    the groups leave ordered by group_order_keys, ALL of them, total_found = their number.  Any flag, a mismatch, a max_matches
+    above k, more than 4 * max_matches merged groups or a count above 2^32 - 1: no entries, the flags (ROW_DECLINED for the latter
+    four) and the spec word.  The CPU mirror the kernel is tested against; a gloo-only host's merge."""
+    grows_all = np.ascontiguousarray(grows_all, dtype=np.uint64)
+    n_lists, nq, _ = grows_all.shape
+    out = np.zeros((nq, GROW_WORDS), dtype=np.uint64)
+    fmask = ROW_RERUN | ROW_DECLINED
+    for q in range(nq):
+        rows = grows_all[:, q]
+        cnt, tw, specs = [], [], []
+        for l in range(n_lists):
+            c, t, sp = int(rows[l, GROW_CNT]), int(rows[l, GROW_TOTAL]), int(rows[l, GROW_SPEC])
+            if c > GROW_GROUPS or (sp and group_spec_unpack(sp) is None):
+                c, t, sp = 0, (t & ROW_RERUN) | ROW_DECLINED, 0
+            cnt.append(c), tw.append(t), specs.append(sp)
+        flags = 0
+        for t in tw:
+            flags |= t & fmask
+        answering = [specs[l] for l in range(n_lists) if not tw[l] & ROW_DECLINED or specs[l]]  # (declined without a spec: no say)
+        spec = answering[0] if answering else 0
+        mismatch = any(sp != spec for sp in answering)
+        if mismatch:
+            flags |= ROW_DECLINED
+        out[q, GROW_SPEC] = np.uint64(spec)
+        if spec == 0:
+            total = sum(t & ~fmask for t in tw) & 0xFFFFFFFFFFFFFFFF
+            out[q, GROW_TOTAL] = np.uint64((total & ~fmask) | flags)
+            if mismatch:
+                continue
+            keys = np.concatenate([rows[l, :min(cnt[l], MRK_MAX_K)] for l in range(n_lists)])
+            n = min(len(keys), k)
+            out[q, :n] = np.sort(keys)[::-1][:n]
+            out[q, GROW_CNT] = np.uint64(n)
+            continue
+        sort_by, desc, _bits, kq = group_spec_unpack(spec)
+        if kq > k:
+            flags |= ROW_DECLINED
+        if not flags:
+            heads = np.concatenate([rows[l, :cnt[l]] for l in range(n_lists)])
+            plane = np.concatenate([rows[l, GROW_PLANE:GROW_PLANE + cnt[l]] for l in range(n_lists)])
+            values, inv = np.unique((plane >> np.uint64(32)).astype(np.uint32), return_inverse=True)
+            inv = inv.reshape(-1)
+            counts = np.zeros(len(values), np.uint64)
+            np.add.at(counts, inv, plane & np.uint64(0xFFFFFFFF))
+            head = np.zeros(len(values), np.uint64)
+            np.maximum.at(head, inv, heads)
+            if len(values) > GROUPBY_FACTOR * kq or (len(values) and int(counts.max()) > 0xFFFFFFFF):
+                flags |= ROW_DECLINED
+            else:
+                order = np.argsort(group_order_keys(sort_by, desc, values, counts.astype(np.uint32), head))[::-1]
+                n = len(values)
+                out[q, :n] = head[order]
+                out[q, GROW_PLANE:GROW_PLANE + n] = (values[order].astype(np.uint64) << np.uint64(32)) | counts[order]
+                out[q, GROW_CNT] = np.uint64(n)
+                out[q, GROW_TOTAL] = np.uint64(n)
+        if flags:
+            out[q, GROW_TOTAL] = np.uint64(flags)
+    return out
+
+
 def exchange_rows(rows):
-    """ONE all-gather of [nq, W] result rows -> [world, nq, W] (gloo on CPU tensors, RCCL on device); W = ROW_WORDS, SROW_WORDS or
-    OROW_WORDS: the row width is the tensor's."""
+    """ONE all-gather of [nq, W] result rows -> [world, nq, W] (gloo on CPU tensors, RCCL on device); W = ROW_WORDS, SROW_WORDS,
+    OROW_WORDS or GROW_WORDS: the row width is the tensor's."""
     import torch
     import torch.distributed as dist
 
@@ -259,7 +372,7 @@ def shard_slice(n_queries: int, world: int, rank: int):
 def exchange_rows_partitioned(rows):
     """The exchange partitioned by QUERY over torch.distributed (gloo on CPU tensors, RCCL on device tensors): every rank sends each
     owner its rows of the owner's queries and receives every shard's rows of its own -> (recv [world, per, W], first, count), W the
-    rows' own width (narrow, wide or order rows).
+    rows' own width (narrow, wide, order or group rows).
     The same all-to-all of row slices mrk_shard_exchange issues through the library's communicator (grouped ncclSend / ncclRecv)."""
     import torch
     import torch.distributed as dist
