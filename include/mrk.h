@@ -242,6 +242,47 @@ typedef struct {
   int32_t desc;                  /* 1 = descending */
 } mrk_group;
 
+/* Aggregates of a grouped query: SUM / MIN / MAX of one integer row attribute over the group's matches that reached the sorter --
+   the set @count counts.  The reference's grouping sorter carries a list of aggregate functions next to the counter (m_dAggregates,
+   sphinxsort.cpp:2608-2693) and updates them on every push (AggrSum_t / AggrMin_t / AggrMax_t, :1902-1979).  Typing, as the
+   reference types the select item:
+     kind MRK_SORTKEY_INT (1..32 bits inside one dword)  the locator's raw bits, unsigned.  SUM(attr) is SPH_ATTR_INTEGER and runs
+         AggrSum_t<DWORD> (:2623): the sum WRAPS modulo 2^32.  MIN / MAX compare unsigned (AggrMin_t<DWORD> :2663, AggrMax_t<DWORD> :2674).
+     ... with MRK_AGGR_WIDEN                              the value zero-extended and aggregated as a 64-bit integer: SUM(BIGINT(attr)),
+         which people write to avoid the wrap.
+     kind MRK_SORTKEY_INT64 (an aligned 64 inside the row, as mrk_order takes it)  signed: AggrSum_t<int64_t> (:2624, the sum in two's
+         complement), AggrMin_t<int64_t> (:2664), AggrMax_t<int64_t> (:2675).
+   None of these depends on the order the matches arrive in, so an aggregate is exact wherever the group is (the 4 * max_matches limit
+   and its run-time decline are the group's).
+   Not offered: AVG -- the reference forces it to float and accumulates float in arrival order (sphinxsort.cpp:5980-5984,
+   AggrAvg_t<float> :1919-1949): no order-independent answer to be exact against; a caller derives an average from a widened SUM
+   and @count.  MRK_SORTKEY_FLOAT sources are declined per query with MRK_E_UNSUPPORTED: a float SUM depends on the arrival order,
+   float MIN / MAX depend on it at NaN and +-0.  GROUP_CONCAT, COUNT(DISTINCT) and aggregates over expressions are out of scope.
+   order_by: -1 = mrk_group.sort_by orders the groups; 0..n-1 = that aggregate does (ORDER BY SUM(x) DESC), mrk_group.sort_by must
+   then be MRK_GROUPSORT_KEY: compared unsigned in the direction mrk_group.desc gives, then by the head's global rowid ascending,
+   exactly as @count is.  Only an aggregate with a 32-bit result (an INT source without WIDEN) may order; a 64-bit one is declined
+   with MRK_E_UNSUPPORTED (the selection sorts 64-bit keys, half of which is the head's rowid).
+   MRK_E_INVAL before a row is read: n outside 1..MRK_MAX_AGGRS, an unknown func, kind or flag, a locator outside the row or
+   straddling a dword, a 64 that is not aligned, WIDEN on an INT64 source, order_by out of range or next to another sort_by,
+   aggregates without a group.  MRK_E_UNSUPPORTED per query: a FLOAT source, a blob-stored source (bit_offset < 0), a 64-bit order,
+   and everything that declines the group.
+   Exchange rows: a query with aggregates leaves in GROUP rows, as in narrow, wide and order rows, with MRK_ROW_DECLINED, no entries
+   and spec word 0 -- the group row has no room for the accumulators.  Carrying them across segments and shards is the follow-up. */
+enum { MRK_AGGR_SUM = 1, MRK_AGGR_MIN = 2, MRK_AGGR_MAX = 3 };
+#define MRK_AGGR_WIDEN 1 /* mrk_aggr.flags: an INT source aggregated as a 64-bit integer */
+#define MRK_MAX_AGGRS 4
+typedef struct {
+  int32_t func;                  /* MRK_AGGR_* */
+  int32_t kind;                  /* MRK_SORTKEY_INT or MRK_SORTKEY_INT64 */
+  int32_t bit_offset, bit_count; /* CSphAttrLocator of the source attribute */
+  int32_t flags;                 /* MRK_AGGR_WIDEN or 0 */
+} mrk_aggr;
+typedef struct {
+  int32_t n;        /* 1..MRK_MAX_AGGRS */
+  int32_t order_by; /* -1, or the aggregate that orders the groups */
+  mrk_aggr a[MRK_MAX_AGGRS];
+} mrk_aggrs;
+
 /* CSphQuery fields that reach the ranker + the query tree */
 typedef struct {
   const mrk_node* nodes;
@@ -451,6 +492,13 @@ int mrk_batch_submit(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, u
 /* mrk_batch_submit with a group per query (sphCreateQueue picking the grouping sorter for a query with m_sGroupBy,
    sphinxsort.cpp): groups[i] == NULL = query i is not grouped; groups == NULL = mrk_batch_submit */
 int mrk_batch_submit_grouped(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, uint32_t n_queries);
+/* ... and with aggregates per grouped query (mrk_aggrs, above): aggrs[i] == NULL = query i has none; aggrs == NULL =
+   mrk_batch_submit_grouped.  Aggregates without a group are MRK_E_INVAL */
+int mrk_batch_submit_aggr(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, const mrk_aggrs* const* aggrs, uint32_t n_queries);
+/* The aggregates of query i's returned rows, after mrk_batch_wait: *values = n x *n_aggrs words, row-major, in the order of the result's
+   rows (mrk_batch_result); a 32-bit result zero-extended, a 64-bit one the integer's bits.  NULL / 0 for every query without
+   aggregates and for a failed one.  Valid until the batch is resubmitted or destroyed */
+int mrk_batch_result_aggrs(mrk_batch* b, uint32_t i, const uint64_t** values, int32_t* n_aggrs);
 /* block until the results of the last submit are in host memory; a query that fails here (its result's status != MRK_OK,
    e.g. out of generic-evaluator memory) leaves the reason in mrk_last_error() */
 int mrk_batch_wait(mrk_batch* b);

@@ -79,6 +79,18 @@ class Group(C.Structure):  # mrk_group
 
 GROUPSORT_KEY, GROUPSORT_COUNT, GROUPSORT_WEIGHT = 0, 1, 2  # MRK_GROUPSORT_*
 
+AGGR_SUM, AGGR_MIN, AGGR_MAX = 1, 2, 3  # MRK_AGGR_*
+AGGR_WIDEN = 1                          # MRK_AGGR_WIDEN (mrk_aggr.flags)
+MRK_MAX_AGGRS = 4
+
+
+class Aggr(C.Structure):  # mrk_aggr
+    _fields_ = [("func", C.c_int32), ("kind", C.c_int32), ("bit_offset", C.c_int32), ("bit_count", C.c_int32), ("flags", C.c_int32)]
+
+
+class Aggrs(C.Structure):  # mrk_aggrs
+    _fields_ = [("n", C.c_int32), ("order_by", C.c_int32), ("a", Aggr * MRK_MAX_AGGRS)]
+
 
 class Query(C.Structure):
     _fields_ = [("nodes", C.POINTER(Node)), ("n_nodes", C.c_int32), ("children", C.POINTER(C.c_int32)),
@@ -169,6 +181,8 @@ SYMBOLS = [
     ("mrk_batch_destroy", None, [C.c_void_p]),
     ("mrk_batch_submit", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Query), C.c_uint32]),
     ("mrk_batch_submit_grouped", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Query), C.POINTER(C.POINTER(Group)), C.c_uint32]),
+    ("mrk_batch_submit_aggr", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Query), C.POINTER(C.POINTER(Group)), C.POINTER(C.POINTER(Aggrs)), C.c_uint32]),
+    ("mrk_batch_result_aggrs", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int32)]),
     ("mrk_batch_wait", C.c_int, [C.c_void_p]),
     ("mrk_batch_test", C.c_int, [C.c_void_p]),
     ("mrk_batch_result", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(Result)]),

@@ -385,6 +385,23 @@ class Group:
     desc: bool = True
 
 
+AGGR_SUM, AGGR_MIN, AGGR_MAX = _lib.AGGR_SUM, _lib.AGGR_MIN, _lib.AGGR_MAX  # MRK_AGGR_*
+MAX_AGGRS = _lib.MRK_MAX_AGGRS
+
+
+@dataclass
+class Aggr:
+    """One aggregate of a grouped query (mrk_aggr, include/mrk.h): SUM / MIN / MAX of an integer row attribute over the group's
+    matches.  A SORTKEY_INT source is the locator's raw bits, unsigned: its SUM wraps modulo 2^32 (the reference's AggrSum_t<DWORD>)
+    unless widen is set, which aggregates the zero-extended value in 64 bits (SUM(BIGINT(attr))).  A SORTKEY_INT64 source (an aligned
+    64 inside the row) is signed.  SORTKEY_FLOAT sources are declined."""
+    func: int
+    bit_offset: int
+    bit_count: int
+    kind: int = SORTKEY_INT
+    widen: bool = False
+
+
 @dataclass
 class Query:
     """CSphQuery fields that reach the ranker, plus the parsed tree."""
@@ -403,6 +420,8 @@ class Query:
     sort: Optional["Sort"] = None             # None = by relevance (weight desc, rowid asc)
     order: Optional["Order"] = None           # one 64-bit attribute or two attributes first; not next to a sort
     group: Optional["Group"] = None           # GROUP BY an integer attribute; travels beside mrk_query (mrk_batch_submit_grouped)
+    aggrs: Optional[List["Aggr"]] = None      # aggregates of a grouped query, 1..MAX_AGGRS; travel beside the group (mrk_batch_submit_aggr)
+    aggr_order: int = -1                      # -1 = group.sort_by orders the groups; else that aggregate (32-bit results only) does
 
 
 class _CQueries:
@@ -413,6 +432,11 @@ class _CQueries:
         self.arr = (_lib.Query * max(1, len(queries)))()
         # the parallel array of group specs (NULL = that query is not grouped); None = no query has one: plain mrk_batch_submit
         self.groups = (C.POINTER(_lib.Group) * max(1, len(queries)))() if any(q.group is not None for q in queries) else None
+        # ... and the third, of aggregate lists, only when some query has aggregates (then the group array stands too, NULL where a query
+        # has no group: aggregates without a group are the library's to refuse)
+        self.aggrs = (C.POINTER(_lib.Aggrs) * max(1, len(queries)))() if any(q.aggrs is not None for q in queries) else None
+        if self.aggrs is not None and self.groups is None:
+            self.groups = (C.POINTER(_lib.Group) * max(1, len(queries)))()
         for qi, q in enumerate(queries):
             nodes: List[XQNode] = []
             kids_of: List[List[int]] = []
@@ -496,6 +520,14 @@ class _CQueries:
                 cg = _lib.Group(int(q.group.bit_offset), int(q.group.bit_count), int(q.group.sort_by), int(desc))
                 self.groups[qi] = C.pointer(cg)
                 self.keep.append(cg)
+            if q.aggrs is not None:
+                ca = _lib.Aggrs()
+                ca.n, ca.order_by = len(q.aggrs), int(q.aggr_order)  # (more than MAX_AGGRS, or none: n says so and the library refuses)
+                for i, a in enumerate(q.aggrs[: _lib.MRK_MAX_AGGRS]):
+                    widen = (_lib.AGGR_WIDEN if a.widen else 0) if isinstance(a.widen, bool) else int(a.widen)  # (an int reaches the library as the flags word)
+                    ca.a[i] = _lib.Aggr(int(a.func), int(a.kind), int(a.bit_offset), int(a.bit_count), widen)
+                self.aggrs[qi] = C.pointer(ca)
+                self.keep.append(ca)
             self.keep += [cn, ch]
 
 
@@ -519,6 +551,8 @@ class Matches:
     # a grouped query (Query.group): the raw group value and @count of every returned row, whose rowid / weight are the group's head's
     group_key: Optional[np.ndarray] = None
     group_count: Optional[np.ndarray] = None
+    # a grouped query with aggregates (Query.aggrs): uint64 (n, n_aggrs), a 32-bit result zero-extended, a 64-bit one the integer's bits
+    aggr: Optional[np.ndarray] = None
 
 
 # --------------------------------------------------------------------------- device objects
@@ -670,7 +704,9 @@ class Batch:
         self._submit(seg, self._cq, self._n)
 
     def _submit(self, seg: Segment, cq: "_CQueries", n: int) -> None:
-        if cq.groups is not None:
+        if cq.aggrs is not None:
+            check(lib().mrk_batch_submit_aggr(self._h, seg._h, cq.arr, cq.groups, cq.aggrs, n))
+        elif cq.groups is not None:
             check(lib().mrk_batch_submit_grouped(self._h, seg._h, cq.arr, cq.groups, n))
         else:
             check(lib().mrk_batch_submit(self._h, seg._h, cq.arr, n))
@@ -695,7 +731,13 @@ class Batch:
             ok = np.ctypeslib.as_array(r.order_key, (max(n, 1),))[:n].copy() if r.order_key else None
             gk = np.ctypeslib.as_array(r.group_key, (max(n, 1),))[:n].copy() if r.group_key else None
             gc = np.ctypeslib.as_array(r.group_count, (max(n, 1),))[:n].copy() if r.group_count else None
-            out.append(Matches(rowid, weight, int(r.total_found), int(r.status), sk, ok, gk, gc))
+            ag = None
+            if self._cq is not None and getattr(self._cq, "aggrs", None) is not None:
+                vals, na = C.POINTER(C.c_uint64)(), C.c_int32()
+                check(lib().mrk_batch_result_aggrs(self._h, i, C.byref(vals), C.byref(na)))
+                if vals and na.value:
+                    ag = np.ctypeslib.as_array(vals, (max(n, 1) * na.value,))[: n * na.value].copy().reshape(n, na.value)
+            out.append(Matches(rowid, weight, int(r.total_found), int(r.status), sk, ok, gk, gc, ag))
         return out
 
     def stats(self) -> dict:
@@ -807,5 +849,5 @@ def idf(term_docs: int, total_docs: int, plain: bool = False, normalized: bool =
 __all__ = ["open_rt_ram", "open_rt_segment", "SPH_RANK_PROXIMITY_BM25", "SPH_RANK_BM25", "SPH_RANK_NONE", "SPH_RANK_WORDCOUNT", "SPH_RANK_PROXIMITY",
            "SPH_RANK_MATCHANY", "SPH_RANK_FIELDMASK", "SPH_RANK_SPH04",
            "parse_query", "SPH_QUERY_TERM", "SPH_QUERY_AND", "SPH_QUERY_OR", "SPH_QUERY_MAYBE", "SPH_QUERY_ANDNOT", "SPH_QUERY_PHRASE", "SPH_QUERY_PROXIMITY", "SPH_QUERY_QUORUM", "SPH_QUERY_BEFORE", "SPH_QUERY_NEAR", "SPH_QUERY_NOTNEAR", "SPH_QUERY_SENTENCE", "SPH_QUERY_PARAGRAPH",
-           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "SORTKEY_INT64", "OrderPart", "Order", "Group", "GROUPSORT_KEY", "GROUPSORT_COUNT", "GROUPSORT_WEIGHT", "Matches", "ROW_WORDS", "SROW_WORDS", "OROW_WORDS", "GROW_WORDS", "GROW_GROUPS", "Context",
+           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "SORTKEY_INT64", "OrderPart", "Order", "Group", "GROUPSORT_KEY", "GROUPSORT_COUNT", "GROUPSORT_WEIGHT", "Aggr", "AGGR_SUM", "AGGR_MIN", "AGGR_MAX", "MAX_AGGRS", "Matches", "ROW_WORDS", "SROW_WORDS", "OROW_WORDS", "GROW_WORDS", "GROW_GROUPS", "Context",
            "Segment", "Batch", "Batcher", "prepare", "idf", "MrkError", "validate_index", "pair_stats"]

@@ -303,6 +303,11 @@ struct DevQuery {
   uint32_t grp_slots;                     // slots of the table, a power of two >= 2 * (4 k + 1) ...
   uint32_t grp_pad;
   uint64_t grp_off;                       // ... and its offset in ScanArgs::gtab, in u64 words
+  // ... with aggregates (mrk_aggrs, mrk_kgroup.h): grp_naggr u64 accumulator planes behind the table's counts.  All zero otherwise
+  uint32_t grp_naggr;
+  uint32_t grp_order_aggr;                // 1 + the aggregate that orders the groups; 0 = grp_sort_by does
+  uint32_t grp_aggr_item[MRK_MAX_AGGRS];  // the source attribute's (low) dword of the row
+  uint32_t grp_aggr_op[MRK_MAX_AGGRS];    // group_aggr_op: shift | bits | func | 64-bit source | widen
 };
 
 struct DevItem {
@@ -407,6 +412,8 @@ struct ScanArgs {
   uint64_t* scand;          // candidates of the batch's sorted queries: [2 * i] = hi, [2 * i + 1] = lo (mrk_sortkey.h); NULL = the batch holds none
   uint64_t* gtab;           // group tables of the batch's grouped queries (mrk_kgroup.h), DevQuery::grp_off words in; NULL = the batch holds none
                             // (a batch with grouped queries has scand set too: the update lives in the instances that carry the sort)
+  uint32_t grp_aggr;        // the batch holds a grouped query with aggregates (DevQuery::grp_naggr): the sort instances with the accumulators' flush
+  uint32_t grp_aggr_pad;
 };
 
 // The groups of the grouped queries (mrk_groupsel.hip): one workgroup per grouped query, launched behind the other selections on the
@@ -430,6 +437,9 @@ struct GroupSelArgs {
   uint32_t* h_flags;
   uint32_t* h_gkey;
   uint32_t* h_gcnt;
+  // queries with aggregates: [n_queries][KCAP][MRK_MAX_AGGRS] values of out_keys' entries and the pinned mirror; NULL = the batch holds none
+  uint64_t* out_aggr;
+  uint64_t* h_aggr;
 };
 void launch_group_select(const GroupSelArgs& a, void* stream);
 

@@ -9,6 +9,8 @@
 //   - else the occupied slots (<= 4096) are compacted into LDS with their order key -- the part the query sorts its groups by, in
 //     its direction, over ~head rowid (group_order_key) -- and sorted descending, bitonic as in mrk_sortsel.hip.  The best k leave:
 //     head key, group value, count; q_total = the number of groups.
+// A query with aggregates (mrk_aggrs) may order its groups by an aggregate's 32-bit value in the place of that part, and the best k
+// rows' aggregates leave next to them, the accumulators' mapping undone.
 // 4096 x (8-byte key + 4-byte slot index) = 48 KB of the 64 KB static LDS.  Slots are compacted in whatever order the atomics fall;
 // the order keys are distinct (heads are distinct rows), so the sorted result is the same from run to run.
 // The same compaction and sort (group_compact_sort) serve the GROUP rows further down: pack_grows_kernel writes all the groups of a
@@ -50,7 +52,8 @@ __device__ __forceinline__ void group_sort_desc(GroupSelSmem& s, uint32_t n) {
 // The occupied slots of T (the caller checked: at most GRP_MAX_GROUPS claimed) compacted into s with their order key and sorted, best
 // group first: s.idx[0 .. n) are the groups' slots in group order.  The one compact-and-sort of group_select_kernel, pack_grows_kernel
 // and merge_grows_kernel; by the whole workgroup, which reads T with plain loads (a kernel that filled T itself fences first).
-__device__ __forceinline__ uint32_t group_compact_sort(GroupSelSmem& s, const GroupTable& T, uint32_t sort_by, uint32_t desc) {
+// order_aggr: 1 + the aggregate whose 32-bit value orders the groups in the place of sort_by (its op word: aggr_op), 0 = none.
+__device__ __forceinline__ uint32_t group_compact_sort(GroupSelSmem& s, const GroupTable& T, uint32_t sort_by, uint32_t desc, uint32_t order_aggr = 0u, uint32_t aggr_op = 0u) {
   const uint32_t tid = threadIdx.x;
   if (tid == 0) s.n = 0;
   __syncthreads();
@@ -59,7 +62,8 @@ __device__ __forceinline__ uint32_t group_compact_sort(GroupSelSmem& s, const Gr
     if (kw) {
       const uint32_t at = atomicAdd(&s.n, 1u); // (< claimed <= GRP_MAX_GROUPS: a slot is counted once)
       if (at < GRP_MAX_GROUPS) {
-        s.key[at] = group_order_key(sort_by, desc, (uint32_t)kw, T.counts[i], T.heads[i]);
+        s.key[at] = order_aggr ? group_order_key_aggr(desc, (uint32_t)aggr_unmap(aggr_op, T.aggr[(uint64_t)(order_aggr - 1u) * T.slots + i]), T.heads[i])
+                               : group_order_key(sort_by, desc, (uint32_t)kw, T.counts[i], T.heads[i]);
         s.idx[at] = i;
       }
     }
@@ -111,7 +115,9 @@ __global__ __launch_bounds__(WG) void group_select_kernel(GroupSelArgs a) {
     }
     return;
   }
-  const uint32_t n = group_compact_sort(s, T, Q->grp_sort_by, Q->grp_desc);
+  const uint32_t n_aggr = a.out_aggr ? (Q->grp_naggr < (uint32_t)MRK_MAX_AGGRS ? Q->grp_naggr : (uint32_t)MRK_MAX_AGGRS) : 0u; // (uniform)
+  const uint32_t ord = n_aggr && Q->grp_order_aggr <= n_aggr ? Q->grp_order_aggr : 0u;
+  const uint32_t n = group_compact_sort(s, T, Q->grp_sort_by, Q->grp_desc, ord, ord ? Q->grp_aggr_op[ord - 1u] : 0u);
   const uint32_t m = n < K ? n : K;
   for (uint32_t i = tid; i < m; i += WG) {
     const uint32_t slot = s.idx[i];
@@ -121,6 +127,11 @@ __global__ __launch_bounds__(WG) void group_select_kernel(GroupSelArgs a) {
     a.out_keys[o] = head, a.out_gkey[o] = value, a.out_gcnt[o] = count;
     if (a.h_keys) a.h_keys[o] = head;
     if (a.h_gkey) a.h_gkey[o] = value, a.h_gcnt[o] = count;
+    for (uint32_t ai = 0; ai < n_aggr; ++ai) { // the accumulators' mapping undone (aggr_unmap): the aggregates' values, row-major
+      const uint64_t v = aggr_unmap(Q->grp_aggr_op[ai], T.aggr[(uint64_t)ai * S + slot]);
+      a.out_aggr[o * MRK_MAX_AGGRS + ai] = v;
+      if (a.h_aggr) a.h_aggr[o * MRK_MAX_AGGRS + ai] = v;
+    }
   }
   if (tid == 0) {
     a.out_cnt[q] = m;

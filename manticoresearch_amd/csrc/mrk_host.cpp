@@ -178,6 +178,14 @@ struct mrk_batch {
   PinBuf<uint32_t> h_gkey, h_gcnt;         // [max_queries][KCAP]
   std::vector<uint8_t> grouped;
   bool any_grouped = false;
+  // ... with aggregates (mrk_aggrs): the returned rows' values [max_queries][KCAP][MRK_MAX_AGGRS] on the device and pinned, reserved by
+  // the first submit that holds such a query; how many aggregates each query of the last submit has (answered ones only); and the
+  // values as mrk_batch_result_aggrs hands them out, n x n_aggrs per query
+  DevBuf<uint64_t> d_out_aggr;
+  PinBuf<uint64_t> h_aggr;
+  std::vector<uint8_t> n_aggr;
+  std::vector<uint64_t> aggr_vals;
+  bool any_aggr = false;
   PinBuf<uint32_t> h_flags;
   // per query of the last submit: its decline mask (row_decline_mask), one bit per row format in which the query's exchange row
   // leaves empty with MRK_ROW_DECLINED
@@ -1005,6 +1013,7 @@ static int mrk_batch_create_impl(mrk_ctx* ctx, uint32_t max_queries, mrk_batch**
   b->order_key.resize(nq * KCAP);
   b->sort_loc.assign(nq, mrk_batch::SortLoc{});
   b->grouped.assign(nq, 0);
+  b->n_aggr.assign(nq, 0);
   b->status.assign(nq, MRK_OK);
   *out = b;
   return MRK_OK;
@@ -1064,7 +1073,7 @@ static int launch_gen_rank(mrk::ScanArgs& sa, bool nearn, hipStream_t st) {
   return MRK_OK;
 }
 
-static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups = nullptr);
+static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups = nullptr, const mrk_aggrs* const* aggrs = nullptr);
 static int mrk_batch_wait_impl(mrk_batch* b);
 static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out);
 
@@ -1137,13 +1146,16 @@ static int bind_sorted(mrk_batch* b, uint32_t n, bool prox, mrk::ScanArgs& sa, h
 
 // ... and its grouped queries: the arena of their tables (`words` u64), cleared on st in front of the scan -- every submit, and the
 // rerun of one query, starts from empty tables: a rerun over the submit's table would double its counts.  The rows' value and count
-// planes come with it
-static int bind_groups(mrk_batch* b, uint64_t words, mrk::ScanArgs& sa, hipStream_t st) {
+// planes come with it; aggr: the scan holds a query with aggregates -- the rows' value plane and its pinned mirror too (the
+// accumulators are part of the tables: `words` counts them, and the one memset clears them)
+static int bind_groups(mrk_batch* b, uint64_t words, bool aggr, mrk::ScanArgs& sa, hipStream_t st) {
   int rc;
   const size_t rows = (size_t)b->max_queries * KCAP;
   if ((rc = b->d_gtab.reserve(words)) || (rc = b->d_out_gkey.reserve(rows)) || (rc = b->d_out_gcnt.reserve(rows)) || (rc = b->h_gkey.reserve(rows)) || (rc = b->h_gcnt.reserve(rows))) return rc;
+  if (aggr && ((rc = b->d_out_aggr.reserve(rows * MRK_MAX_AGGRS)) || (rc = b->h_aggr.reserve(rows * MRK_MAX_AGGRS)))) return rc;
   HIP_TRY(hipMemsetAsync(b->d_gtab.p, 0, words * 8, st));
   sa.gtab = b->d_gtab.p;
+  sa.grp_aggr = aggr ? 1u : 0u;
   return MRK_OK;
 }
 
@@ -1221,6 +1233,7 @@ static void launch_selection(const mrk_batch* b, const mrk_segment* seg, uint32_
     gs.out_keys = b->d_out_keys.p, gs.out_cnt = b->d_out_cnt.p, gs.out_gkey = b->d_out_gkey.p, gs.out_gcnt = b->d_out_gcnt.p;
     gs.h_keys = se.h_keys, gs.h_cnt = se.h_cnt, gs.h_total = se.h_total, gs.h_flags = se.h_flags;
     if (se.h_keys) gs.h_gkey = b->h_gkey.p, gs.h_gcnt = b->h_gcnt.p;
+    if (b->any_aggr) gs.out_aggr = b->d_out_aggr.p, gs.h_aggr = se.h_keys ? b->h_aggr.p : nullptr;
     mrk::launch_group_select(gs, st);
   }
   if (!sorted) return;
@@ -1258,7 +1271,7 @@ static void launch_pack_rows(const mrk_batch* b, RowKind kind, uint64_t* rows, u
   launch_pack_xrows(kind, pa, st);
 }
 
-static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups) {
+static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups, const mrk_aggrs* const* aggrs) {
   if (!b || !seg || (!queries && n)) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: NULL argument");
   if (n > b->max_queries) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: %u queries > batch capacity %u", n, b->max_queries);
   if (seg->ctx != b->ctx) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: segment and batch belong to different contexts");
@@ -1289,12 +1302,13 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   plan.items.reserve(n * 4);
   uint32_t max_terms = 1;
   bool any_ext = false; // position modifiers, BEFORE, attribute filters
+  bool any_aggr = false; // a grouped query with aggregates
   if (b->ctx->path == 2 && !seg->has_packed) return mrk_fail(MRK_E_UNSUPPORTED, "path=packed but the segment has no packed doclists");
   const bool use_packed = seg->has_packed && b->ctx->path != 1;
   for (uint32_t i = 0; i < n; ++i) {
     const mrk::BatchPlan::Mark before = plan.mark();
     const mrk_group* group = groups ? groups[i] : nullptr;
-    int rc = plan_query(seg, queries[i], b->ctx->item_bytes, use_packed, b->h_queries.p[i], n, i, plan, rowid_max.empty() || group ? 0xFFFFFFFFu : rowid_max[i], group);
+    int rc = plan_query(seg, queries[i], b->ctx->item_bytes, use_packed, b->h_queries.p[i], n, i, plan, rowid_max.empty() || group ? 0xFFFFFFFFu : rowid_max[i], group, aggrs ? aggrs[i] : nullptr);
     b->status[i] = rc;
     if (rc == MRK_E_INVAL) return rc;
     if (rc != MRK_OK) { // unsupported: reported per query, runs no device work
@@ -1303,8 +1317,11 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
       b->h_queries.p[i].n_terms = 0;
       b->h_queries.p[i].sort_on = 0;
       b->h_queries.p[i].grp_on = 0;
+      b->h_queries.p[i].grp_naggr = 0;
     }
     b->grouped[i] = rc == MRK_OK && b->h_queries.p[i].grp_on != 0;
+    b->n_aggr[i] = b->grouped[i] ? (uint8_t)b->h_queries.p[i].grp_naggr : 0;
+    any_aggr = any_aggr || b->n_aggr[i] != 0;
     max_terms = std::max(max_terms, b->h_queries.p[i].n_terms);
     any_ext = any_ext || (b->h_queries.p[i].tree_flags & (mrk::TF_TERMPOS | mrk::TF_ORDER | mrk::TF_PHRASE_LEAF | mrk::TF_NOTNEAR)) != 0 || b->h_queries.p[i].n_filters != 0 || b->h_queries.p[i].n_wfilters != 0 ||
               b->h_queries.p[i].rowid_max != 0xFFFFFFFFu || b->h_queries.p[i].sort_on != 0 || b->h_queries.p[i].grp_on != 0;
@@ -1329,6 +1346,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   const uint64_t cand_total = plan.cand_total;
   LaunchShape shape{max_terms, plan.any_prox, plan.any_tree, any_ext, use_packed && (plan.sort_total != 0 || plan.group_total != 0), false, use_packed && plan.group_total != 0};
   b->any_grouped = shape.group;
+  b->any_aggr = shape.group && any_aggr;
   for (uint32_t i = 0; i < n && !b->gen_progs.empty(); ++i) shape.nearn = shape.nearn || (b->h_queries.p[i].tree_flags & mrk::TF_GEN_NEARN) != 0;
   memcpy(b->stats.n_bm_groups, lay.n_bm_groups, sizeof lay.n_bm_groups);
   b->stats.algo_bytes = plan.algo_bytes;
@@ -1402,7 +1420,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   bind_scan(b, seg, sa);
   sa.n_items = (uint32_t)n_items; // (the VLB path's one launch; launch_packed sets its sections')
   if (shape.sort && (rc = bind_sorted(b, n, shape.prox, sa, st))) return rc;
-  if (shape.group && (rc = bind_groups(b, plan.group_total, sa, st))) return rc;
+  if (shape.group && (rc = bind_groups(b, plan.group_total, b->any_aggr, sa, st))) return rc;
   // (submit only: the weight bounds' buffers -- a rerun's list holds every doc its drivers can deliver, it runs without this pruning)
   if (use_packed && shape.prox && b->ctx->prox_prune) { // pruning in front of the hit pass (mrk_kprune.h, prox_bounds)
     const size_t words = (size_t)n * (2 * NBINS + mrk::QSTRIDE);
@@ -1461,8 +1479,9 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     // the queries' decline masks, for every row format whether or not a destination stands: mrk_batch_export_* writes the same rows
     // after the wait
     uint32_t any = 0;
+    // (a query with aggregates leaves declined in GROUP rows too: the row has no room for the accumulators)
     for (uint32_t i = 0; i < n; ++i) any |= b->h_decl.p[i] = mrk::query_decline_mask(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order, b->orows_wf_run, b->grouped[i] != 0) |
-                                                    mrk::group_row_decline_bit(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order);
+                                                    mrk::group_row_decline_bit(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order) | (b->n_aggr[i] ? 1u << ROWS_GROUP : 0u);
     b->any_declined = any != 0;
     if (any || b->decl_dirty) HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     b->decl_dirty = any != 0;
@@ -1558,7 +1577,9 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   ScanArgs sa{};
   bind_scan(r, seg, sa);
   if (shape.sort && (rc = bind_sorted(r, 1, shape.prox, sa, st))) return rc;
-  if (grouped && (rc = bind_groups(r, mrk::group_table_words(passes[0].grp_slots), sa, st))) return rc;
+  const uint32_t n_aggr = grouped ? passes[0].grp_naggr : 0u; // (the accumulators ride behind the table: cleared with it, copied back with it)
+  r->any_aggr = n_aggr != 0;
+  if (grouped && (rc = bind_groups(r, mrk::group_table_words(passes[0].grp_slots, n_aggr), n_aggr != 0, sa, st))) return rc;
   // match queues for every doc a pass can match (no cap: this run must not overflow), every pass charged the whole rerun's items
   uint64_t chunks[3] = {0, 0, 0};
   for (const DevQuery& P : passes) {
@@ -1590,7 +1611,11 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
     HIP_TRY(hipMemcpyAsync(b->d_out_gkey.p + (size_t)qi * KCAP, r->d_out_gkey.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_out_gcnt.p + (size_t)qi * KCAP, r->d_out_gcnt.p, (size_t)KCAP * 4, hipMemcpyDeviceToDevice, st));
     // ... and the rerun's whole table in the place of the abandoned run's (same k, same slots): mrk_batch_export_grows packs from there
-    HIP_TRY(hipMemcpyAsync(b->d_gtab.p + b->h_queries.p[qi].grp_off, r->d_gtab.p, mrk::group_table_words(passes[0].grp_slots) * 8, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->d_gtab.p + b->h_queries.p[qi].grp_off, r->d_gtab.p, mrk::group_table_words(passes[0].grp_slots, n_aggr) * 8, hipMemcpyDeviceToDevice, st));
+    if (n_aggr) { // the rows' aggregate values likewise
+      HIP_TRY(hipMemcpyAsync(b->h_aggr.p + (size_t)qi * KCAP * MRK_MAX_AGGRS, r->d_out_aggr.p, (size_t)KCAP * MRK_MAX_AGGRS * 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(b->d_out_aggr.p + (size_t)qi * KCAP * MRK_MAX_AGGRS, r->d_out_aggr.p, (size_t)KCAP * MRK_MAX_AGGRS * 8, hipMemcpyDeviceToDevice, st));
+    }
   }
   // the device-side row is good again -- or carries what the rerun ran into: an exported row then leaves flagged, never with the rerun's keys
   HIP_TRY(hipMemcpyAsync(b->d_q_flags.p + qi, r->d_q_flags.p, 4, hipMemcpyDeviceToDevice, st));
@@ -1656,6 +1681,7 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
     if (b->any_grouped) {
       HIP_TRY(hipMemcpyAsync(b->h_gkey.p, b->d_out_gkey.p, n * KCAP * 4, hipMemcpyDeviceToHost, b->stream));
       HIP_TRY(hipMemcpyAsync(b->h_gcnt.p, b->d_out_gcnt.p, n * KCAP * 4, hipMemcpyDeviceToHost, b->stream));
+      if (b->any_aggr) HIP_TRY(hipMemcpyAsync(b->h_aggr.p, b->d_out_aggr.p, n * KCAP * MRK_MAX_AGGRS * 8, hipMemcpyDeviceToHost, b->stream));
     }
     HIP_TRY(hipStreamSynchronize(b->stream));
     b->host_copied = true;
@@ -1697,6 +1723,23 @@ static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out) {
   const bool grouped = b->status[q] == MRK_OK && b->grouped[q] && b->any_grouped;
   out->group_key = grouped ? b->h_gkey.p + (size_t)q * KCAP : nullptr;
   out->group_count = grouped ? b->h_gcnt.p + (size_t)q * KCAP : nullptr;
+  return MRK_OK;
+}
+
+// The aggregates of query q's returned rows: the pinned plane's [KCAP][MRK_MAX_AGGRS] rows packed to n x n_aggrs
+static int mrk_batch_result_aggrs_impl(mrk_batch* b, uint32_t q, const uint64_t** values, int32_t* n_aggrs) {
+  if (!b || !values || !n_aggrs) return mrk_fail(MRK_E_INVAL, "mrk_batch_result_aggrs: NULL argument");
+  mrk_result res;
+  if (int rc = mrk_batch_result_impl(b, q, &res)) return rc; // (the same checks, and the host copy where a destination stands)
+  *values = nullptr, *n_aggrs = 0;
+  const uint32_t na = b->status[q] == MRK_OK && b->grouped[q] && b->any_aggr ? b->n_aggr[q] : 0u;
+  if (!na) return MRK_OK;
+  if (b->aggr_vals.size() < (size_t)b->max_queries * KCAP * MRK_MAX_AGGRS) b->aggr_vals.resize((size_t)b->max_queries * KCAP * MRK_MAX_AGGRS);
+  uint64_t* out = b->aggr_vals.data() + (size_t)q * KCAP * MRK_MAX_AGGRS;
+  const uint64_t* in = b->h_aggr.p + (size_t)q * KCAP * MRK_MAX_AGGRS;
+  for (int32_t j = 0; j < res.n; ++j)
+    for (uint32_t a = 0; a < na; ++a) out[(size_t)j * na + a] = in[(size_t)j * MRK_MAX_AGGRS + a];
+  *values = out, *n_aggrs = (int32_t)na;
   return MRK_OK;
 }
 
@@ -2068,6 +2111,12 @@ extern "C" int mrk_batch_submit(mrk_batch* b, mrk_segment* seg, const mrk_query*
 }
 extern "C" int mrk_batch_submit_grouped(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, uint32_t n) {
   return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_submit_impl(b, seg, queries, n, groups); });
+}
+extern "C" int mrk_batch_submit_aggr(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, const mrk_aggrs* const* aggrs, uint32_t n) {
+  return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_submit_impl(b, seg, queries, n, groups, aggrs); });
+}
+extern "C" int mrk_batch_result_aggrs(mrk_batch* b, uint32_t i, const uint64_t** values, int32_t* n_aggrs) {
+  return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_result_aggrs_impl(b, i, values, n_aggrs); });
 }
 
 // The wait polls instead of parking the worker in hipStreamSynchronize: while the batch's stream is still busy AND

@@ -158,8 +158,10 @@ struct BatchPlan {
 // MRK_E_UNSUPPORTED / MRK_E_INVAL with the message set.  dq = the query's head pass (index qi); further passes go to
 // plan.extra and get pass indices n_queries + position.  group: the query's mrk_group (mrk_batch_submit_grouped) or NULL -- a grouped
 // query gets a table of plan.group_total's arena instead of a candidate list (DevQuery::grp_*; all zero for every other query).
+// aggrs: the grouped query's mrk_aggrs (mrk_batch_submit_aggr) or NULL -- its table gets one accumulator plane per aggregate behind the
+// counts (DevQuery::grp_naggr, grp_aggr_*, grp_order_aggr); a query without them plans word for word as without the argument.
 int plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
-               BatchPlan& plan, uint32_t rowid_max = 0xFFFFFFFFu, const mrk_group* group = nullptr);
+               BatchPlan& plan, uint32_t rowid_max = 0xFFFFFFFFu, const mrk_group* group = nullptr, const mrk_aggrs* aggrs = nullptr);
 
 // Groups of a batch's scan_bm queries for the grouped bitmap kernel ("bm_group", mrk_batch_submit).  A member names its two
 // keywords (key: bitmap offset + idf bits, so that members sharing a key share its tfidf table too), the bytes a walk of each

@@ -12,6 +12,17 @@
 // [2S+1 ..] S counts (u32).  An empty slot's key word is 0; a claimed one holds GRP_TAG | value, so values 0 and 0xFFFFFFFF are
 // ordinary keys.  Linear probing from group_hash(value); nothing is ever removed.
 //
+// Aggregates (mrk_aggrs, include/mrk.h: SUM / MIN / MAX of an integer row attribute, m_dAggregates, sphinxsort.cpp:2608-2693 with
+// AggrSum_t / AggrMin_t / AggrMax_t, :1902-1979): a table with n_aggr of them has n_aggr planes of S u64 accumulators BEHIND the
+// counts, [2S+1+S/2 + a S ..], so whoever reads the first three planes reads them where they were.  Every accumulator is an ADD or an
+// UNSIGNED MAX over a word that starts at zero -- the arena's one memset stays the table's only initialisation: SUM adds the value
+// (a DWORD sum is the low dword of the 64-bit one: it wraps modulo 2^32 as AggrSum_t<DWORD> does, :2623), MAX takes the value, MIN
+// the value's complement, and a signed (INT64) value has its top bit flipped first (aggr_map).  A group's slot sees at least one
+// update of every accumulator, so zero is a safe identity; group_select_kernel undoes the mapping (aggr_unmap).
+// Where the flush gets the values: it READS THE ROWS AGAIN.  A buffered match's key holds its global rowid, and rowid - rowid_base is
+// the row, so group_flush_wave_aggr needs no LDS beyond the two buffers (cbuf2's spare upper half could carry one 32-bit value, not
+// four of 64), and the rows are in cache: the scan read the group attribute from them when it buffered the match.
+//
 // The probe, the claim and the hash are written over an "atomic ops" policy: GroupDevOps on the device (relaxed, agent scope --
 // nothing reads the table before the selection launch), GroupSeqOps sequentially on the host (tests/cpp/group_table.cpp).
 #pragma once
@@ -39,7 +50,7 @@ MRK_GHD uint32_t group_slots_for(uint32_t k) {
   while (s < need) s <<= 1;
   return s;
 }
-MRK_GHD uint64_t group_table_words(uint32_t slots) { return 1ull + 2ull * slots + slots / 2u; }
+MRK_GHD uint64_t group_table_words(uint32_t slots, uint32_t n_aggr = 0) { return 1ull + 2ull * slots + slots / 2u + (uint64_t)n_aggr * slots; }
 
 struct GroupTable {
   uint32_t* claimed;
@@ -47,9 +58,39 @@ struct GroupTable {
   uint64_t* heads;
   uint32_t* counts;
   uint32_t slots;
+  uint64_t* aggr; // accumulator a of slot i: aggr[a * slots + i] (there for a table sized with n_aggr > a only)
 };
 MRK_GHD GroupTable group_table_at(uint64_t* base, uint32_t slots) {
-  return GroupTable{reinterpret_cast<uint32_t*>(base), base + 1, base + 1 + slots, reinterpret_cast<uint32_t*>(base + 1 + 2ull * slots), slots};
+  return GroupTable{reinterpret_cast<uint32_t*>(base), base + 1, base + 1 + slots, reinterpret_cast<uint32_t*>(base + 1 + 2ull * slots), slots, base + 1 + 2ull * slots + slots / 2u};
+}
+
+// An aggregate's op word (DevQuery::grp_aggr_op): bits 0-4 shift | bits 5-10 bit_count | bits 11-12 func (MRK_AGGR_*) |
+// bit 13 the source is an aligned signed 64 (dwords item, item + 1) | bit 14 an INT source widened to 64 bits
+constexpr uint32_t AGGR_SRC64 = 1u << 13, AGGR_WIDEN = 1u << 14;
+constexpr uint64_t AGGR_SIGN = 1ull << 63;
+MRK_GHD uint32_t aggr_op_word(uint32_t func, uint32_t shift, uint32_t bits, bool src64, bool widen) {
+  return (shift & 31u) | ((bits & 63u) << 5) | ((func & 3u) << 11) | (src64 ? AGGR_SRC64 : 0u) | (widen ? AGGR_WIDEN : 0u);
+}
+MRK_GHD uint32_t aggr_func(uint32_t op) { return (op >> 11) & 3u; }
+MRK_GHD bool aggr_is_add(uint32_t op) { return aggr_func(op) == (uint32_t)MRK_AGGR_SUM; }
+MRK_GHD bool aggr_result64(uint32_t op) { return (op & (AGGR_SRC64 | AGGR_WIDEN)) != 0u; }
+// the source's value in a row: the locator's raw bits zero-extended, or the 64's bits
+MRK_GHD uint64_t aggr_source(const uint32_t* row, uint32_t item, uint32_t op) {
+  return (op & AGGR_SRC64) ? ((uint64_t)row[item + 1u] << 32) | row[item] : (uint64_t)sort_extract(row[item], op & 31u, (op >> 5) & 63u);
+}
+// what goes into the accumulator (an add for SUM, an unsigned max for MIN / MAX) ...
+MRK_GHD uint64_t aggr_map(uint32_t op, uint64_t v) {
+  const uint32_t f = aggr_func(op);
+  if (f == (uint32_t)MRK_AGGR_SUM) return v;
+  const uint64_t x = (op & AGGR_SRC64) ? v ^ AGGR_SIGN : v;
+  return f == (uint32_t)MRK_AGGR_MAX ? x : ~x;
+}
+// ... and the aggregate's value from it: a 32-bit result zero-extended, a 64-bit one the integer's bits
+MRK_GHD uint64_t aggr_unmap(uint32_t op, uint64_t acc) {
+  const uint32_t f = aggr_func(op);
+  uint64_t x = f == (uint32_t)MRK_AGGR_MIN ? ~acc : acc;
+  if (f != (uint32_t)MRK_AGGR_SUM && (op & AGGR_SRC64)) x ^= AGGR_SIGN;
+  return aggr_result64(op) ? x : (uint64_t)(uint32_t)x;
 }
 
 MRK_GHD uint32_t group_hash(uint32_t value, uint32_t slots) {
@@ -66,6 +107,7 @@ struct GroupSeqOps {
     return old;
   }
   static void add32(uint32_t* p, uint32_t v) { *p += v; }
+  static void add64(uint64_t* p, uint64_t v) { *p += v; }
   static void max64(uint64_t* p, uint64_t v) {
     if (v > *p) *p = v;
   }
@@ -97,12 +139,54 @@ MRK_GHD bool group_update(const GroupTable& T, uint32_t value, uint32_t count, u
   return false;
 }
 
+// group_update that also tells the slot (0xFFFFFFFF: the table is full), for the callers that go on to the slot's accumulators ...
+template <class Ops>
+MRK_GHD uint32_t group_update_slot(const GroupTable& T, uint32_t value, uint32_t count, uint64_t head) {
+  const uint64_t word = GRP_TAG | value;
+  uint32_t i = group_hash(value, T.slots);
+  for (uint32_t step = 0; step < T.slots; ++step, i = (i + 1u) & (T.slots - 1u)) {
+    uint64_t cur = Ops::load64(T.keys + i);
+    if (cur == 0ull) {
+      cur = Ops::cas64(T.keys + i, 0ull, word);
+      if (cur == 0ull) {
+        Ops::add32(T.claimed, 1u);
+        cur = word;
+      }
+    }
+    if (cur == word) {
+      Ops::add32(T.counts + i, count);
+      Ops::max64(T.heads + i, head);
+      return i;
+    }
+  }
+  return 0xFFFFFFFFu;
+}
+// ... one accumulator's update with a MAPPED value (aggr_map), or with the sum / the maximum of several
+template <class Ops>
+MRK_GHD void group_aggr_update(const GroupTable& T, uint32_t slot, uint32_t a, uint32_t op, uint64_t mapped) {
+  uint64_t* p = T.aggr + (uint64_t)a * T.slots + slot;
+  if (aggr_is_add(op))
+    Ops::add64(p, mapped);
+  else
+    Ops::max64(p, mapped);
+}
+// ... and the whole: `count` matches of group `value` whose aggregates' mapped values combine to mapped[0 .. n_aggr)
+template <class Ops>
+MRK_GHD bool group_update(const GroupTable& T, uint32_t value, uint32_t count, uint64_t head, uint32_t n_aggr, const uint32_t* ops, const uint64_t* mapped) {
+  const uint32_t slot = group_update_slot<Ops>(T, value, count, head);
+  if (slot == 0xFFFFFFFFu) return false;
+  for (uint32_t a = 0; a < n_aggr; ++a) group_aggr_update<Ops>(T, slot, a, ops[a], mapped[a]);
+  return true;
+}
+
 // The groups' order (MatchGeneric1_fn, sphinxsort.cpp:4708-4720): one of group value / count / head weight, ascending or
 // descending, then the head's global rowid ascending.  Larger = better; heads are distinct rows, so no two groups tie.
 MRK_GHD uint64_t group_order_key(uint32_t sort_by, uint32_t desc, uint32_t value, uint32_t count, uint64_t head) {
   const uint32_t p = sort_by == MRK_GROUPSORT_COUNT ? count : sort_by == MRK_GROUPSORT_KEY ? value : (uint32_t)(head >> 32);
   return ((uint64_t)(desc ? p : ~p) << 32) | (uint32_t)head;
 }
+// ... or an aggregate's 32-bit value (mrk_aggrs::order_by), exactly as @count is taken
+MRK_GHD uint64_t group_order_key_aggr(uint32_t desc, uint32_t aggr_value, uint64_t head) { return ((uint64_t)(desc ? aggr_value : ~aggr_value) << 32) | (uint32_t)head; }
 
 // The group spec word of a GROUP row (MRK_GROW_WORDS, include/mrk.h): what every merger of a grouped query's rows must agree on --
 // the groups' order, the key's width and the query's max_matches (the 4 k limit and the first k) -- and nothing of where a segment
@@ -149,6 +233,7 @@ struct GroupDevOps {
     return expected; // (the value found: `expected` itself when the exchange happened)
   }
   static __device__ void add32(uint32_t* p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  static __device__ void add64(uint64_t* p, uint64_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   static __device__ void max64(uint64_t* p, uint64_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 };
 
@@ -206,6 +291,116 @@ __device__ __forceinline__ bool group_flush_wave(const GroupTable& T, uint64_t* 
     ok = group_update<GroupDevOps>(T, (uint32_t)vc, (uint32_t)(vc >> 32), cbuf[j]) && ok;
   }
   const bool all_ok = __ballot(!ok) == 0ull;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  return all_ok;
+}
+
+// ---- the flush of a query WITH aggregates.  A function of its own, chosen by a uniform branch on DevQuery::grp_naggr where the
+// kernels publish, so that a grouped query without aggregates runs group_flush_wave as it stands -- and only in kernel INSTANCES of
+// their own (the AGGR template flag of scan_pk_kernel / rank_kernel, launched for batches that hold a query with aggregates), so that
+// the instances every other sorted or grouped batch launches report the registers they reported before (DESIGN section 4c'').
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint64_t group_dpp_add64(uint64_t x) { // (a lane without a source reads 0)
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)x, CTRL, ROW_MASK, 0xf, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(x >> 32), CTRL, ROW_MASK, 0xf, false);
+  return x + (((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ uint64_t group_wave_add64(uint64_t v) { // (the ladder of group_wave_max64: lane 63 ends with the wave's sum, modulo 2^64)
+  v = group_dpp_add64<0x111, 0xf>(v);
+  v = group_dpp_add64<0x112, 0xf>(v);
+  v = group_dpp_add64<0x114, 0xf>(v);
+  v = group_dpp_add64<0x118, 0xf>(v);
+  v = group_dpp_add64<0x142, 0xa>(v);
+  v = group_dpp_add64<0x143, 0xc>(v);
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+}
+
+// group_flush_wave for a query with n_aggr aggregates (aggr_item / aggr_op: DevQuery::grp_aggr_item / grp_aggr_op).  Its three steps: the same combine per distinct value (count, head);
+// one lane per distinct value claims or finds the slot and leaves it in cbuf2 (value | slot << 32); then, one aggregate at a time
+// (two mapped values per lane, re-read from the rows attrs + (key_rowid(key) - rowid_base) * attr_stride: see the header), one round
+// per distinct value reduces the aggregate across the wave -- a 64-bit add or max over the DPP ladder -- and lane 0 issues the
+// slot's one atomic; a buffer of mostly distinct values (fewer than four entries to a value) skips the rounds and every entry updates
+// its slot itself.  The locators are read from the descriptor here, on the rare branch.
+__device__ __forceinline__ bool group_flush_wave_aggr(const GroupTable& T, uint64_t* cbuf, uint64_t* cbuf2, uint32_t cn, uint32_t lane, const uint32_t* __restrict__ attrs,
+                                                      uint32_t attr_stride, uint32_t rowid_base, uint32_t n_aggr, const uint32_t* __restrict__ aggr_item, const uint32_t* __restrict__ aggr_op) {
+  const bool v0 = lane < cn, v1 = lane + 64u < cn;
+  const uint64_t k0 = v0 ? cbuf[lane] : 0ull, k1 = v1 ? cbuf[lane + 64u] : 0ull;
+  const uint32_t g0 = v0 ? (uint32_t)cbuf2[lane] : 0u, g1 = v1 ? (uint32_t)cbuf2[lane + 64u] : 0u;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  uint64_t p0 = __ballot(v0), p1 = __ballot(v1);
+  uint32_t nd = 0, e0 = 0, e1 = 0; // (e0 / e1: which distinct value the lane's entries are)
+  while (p0 | p1) { // (uniform) one round per distinct value
+    const uint32_t src = (uint32_t)__builtin_ctzll(p0 ? p0 : p1);
+    const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)(p0 ? g0 : g1), (int)src);
+    const bool m0 = v0 && g0 == v, m1 = v1 && g1 == v;
+    const uint64_t b0 = __ballot(m0), b1 = __ballot(m1);
+    const uint64_t a = m0 ? k0 : 0ull, b = m1 ? k1 : 0ull;
+    const uint64_t h = group_wave_max64(a > b ? a : b);
+    if (lane == 0) {
+      cbuf[nd] = h;
+      cbuf2[nd] = (uint64_t)v | ((uint64_t)(uint32_t)(__popcll(b0) + __popcll(b1)) << 32);
+    }
+    e0 = m0 ? nd : e0, e1 = m1 ? nd : e1;
+    ++nd;
+    p0 &= ~b0, p1 &= ~b1;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  bool ok = true;
+  for (uint32_t j = lane; j < nd; j += 64u) { // (nd <= cn <= 128: a lane's own entries only)
+    const uint64_t vc = cbuf2[j];
+    const uint32_t slot = group_update_slot<GroupDevOps>(T, (uint32_t)vc, (uint32_t)(vc >> 32), cbuf[j]);
+    ok = ok && slot != 0xFFFFFFFFu;
+    cbuf2[j] = (uint64_t)(uint32_t)vc | ((uint64_t)slot << 32);
+  }
+  const bool all_ok = __ballot(!ok) == 0ull;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  const uint32_t* __restrict__ row0 = attrs + (uint64_t)(v0 ? key_rowid(k0) - rowid_base : 0u) * attr_stride;
+  const uint32_t* __restrict__ row1 = attrs + (uint64_t)(v1 ? key_rowid(k1) - rowid_base : 0u) * attr_stride;
+  // (uniform) mostly distinct values -- fewer than four entries to a value: a round per value would reduce next to nothing, so every
+  // entry goes to its slot's accumulator itself (the few that share a slot meet in the atomic unit)
+  const bool direct = nd * 4u > cn;
+  const uint32_t s0 = direct && v0 ? (uint32_t)(cbuf2[e0] >> 32) : 0xFFFFFFFFu, s1 = direct && v1 ? (uint32_t)(cbuf2[e1] >> 32) : 0xFFFFFFFFu;
+  for (uint32_t ai = 0; ai < n_aggr && ai < (uint32_t)MRK_MAX_AGGRS; ++ai) { // (uniform)
+    const uint32_t item = aggr_item[ai], op = aggr_op[ai];
+    const uint64_t x0 = v0 ? aggr_map(op, aggr_source(row0, item, op)) : 0ull, x1 = v1 ? aggr_map(op, aggr_source(row1, item, op)) : 0ull;
+    uint64_t* __restrict__ plane = T.aggr + (uint64_t)ai * T.slots;
+    const bool add = aggr_is_add(op);
+    if (direct) {
+      if (s0 != 0xFFFFFFFFu) {
+        if (add)
+          GroupDevOps::add64(plane + s0, x0);
+        else
+          GroupDevOps::max64(plane + s0, x0);
+      }
+      if (s1 != 0xFFFFFFFFu) {
+        if (add)
+          GroupDevOps::add64(plane + s1, x1);
+        else
+          GroupDevOps::max64(plane + s1, x1);
+      }
+      continue;
+    }
+    for (uint32_t j = 0; j < nd; ++j) { // (uniform) the entries of distinct value j
+      const uint64_t vc = cbuf2[j]; // (one address: a broadcast read)
+      const uint32_t v = (uint32_t)vc, slot = (uint32_t)(vc >> 32);
+      const uint64_t a = v0 && g0 == v ? x0 : 0ull, b = v1 && g1 == v ? x1 : 0ull;
+      const uint64_t r = add ? group_wave_add64(a + b) : group_wave_max64(a > b ? a : b);
+      if (lane == 0 && slot != 0xFFFFFFFFu) {
+        if (add)
+          GroupDevOps::add64(plane + slot, r);
+        else
+          GroupDevOps::max64(plane + slot, r);
+      }
+    }
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");

@@ -775,6 +775,7 @@ struct PlanState {
   const bool use_packed;
   const uint32_t qi;
   const mrk_group* const group; // mrk_batch_submit_grouped's spec for this query, or NULL
+  const mrk_aggrs* const aggrs; // mrk_batch_submit_aggr's aggregates for this (grouped) query, or NULL
   // what the stages work out, in their order
   KeySpec order;
   bool filtered = false; // the query reads attribute rows: the packed block scan's EXT instances only
@@ -895,6 +896,48 @@ struct PlanState {
     if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to a group (which rows count depends on the scan order)", qi);
     return MRK_OK;
   }
+  // mrk_aggrs: the aggregate stage, next to the group's.  check_aggrs, in front of resolve_group: everything hostile is MRK_E_INVAL
+  // before a row is read, whatever the group turns out to be.  decline_aggrs, behind it: what the device declines, each message naming
+  // the aggregate it declines
+  int check_aggrs() const {
+    if (!aggrs) return MRK_OK;
+    const mrk_aggrs& A = *aggrs;
+    if (!group) return mrk_fail(MRK_E_INVAL, "query %u: aggregates without a group", qi);
+    if (A.n < 1 || A.n > MRK_MAX_AGGRS) return mrk_fail(MRK_E_INVAL, "query %u: %d aggregates (1..%d)", qi, A.n, MRK_MAX_AGGRS);
+    if (A.order_by < -1 || A.order_by >= A.n) return mrk_fail(MRK_E_INVAL, "query %u: aggregate order_by %d of %d aggregates", qi, A.order_by, A.n);
+    if (A.order_by >= 0 && group->sort_by != MRK_GROUPSORT_KEY)
+      return mrk_fail(MRK_E_INVAL, "query %u: aggregate order_by %d next to group sort_by %d (MRK_GROUPSORT_KEY with an aggregate order)", qi, A.order_by, group->sort_by);
+    for (int i = 0; i < A.n; ++i) {
+      const mrk_aggr& G = A.a[i];
+      if (G.func != MRK_AGGR_SUM && G.func != MRK_AGGR_MIN && G.func != MRK_AGGR_MAX) return mrk_fail(MRK_E_INVAL, "query %u: aggregate %d: function %d", qi, i, G.func);
+      if (G.kind != MRK_SORTKEY_INT && G.kind != MRK_SORTKEY_FLOAT && G.kind != MRK_SORTKEY_INT64) return mrk_fail(MRK_E_INVAL, "query %u: aggregate %d: source kind %d", qi, i, G.kind);
+      if (G.flags & ~MRK_AGGR_WIDEN) return mrk_fail(MRK_E_INVAL, "query %u: aggregate %d: flags 0x%x", qi, i, (unsigned)G.flags);
+      if ((G.flags & MRK_AGGR_WIDEN) && G.kind != MRK_SORTKEY_INT) return mrk_fail(MRK_E_INVAL, "query %u: aggregate %d: MRK_AGGR_WIDEN on a source of kind %d (an INT source only)", qi, i, G.kind);
+      if (G.bit_offset < 0) continue; // (a blob-stored source: declined below, once every aggregate's shape has been checked)
+      if (G.kind == MRK_SORTKEY_INT64) {
+        if (G.bit_count != 64 || (G.bit_offset & 31) != 0) return mrk_fail(MRK_E_INVAL, "query %u: aggregate %d: locator %d/%d is not 64 dword-aligned bits", qi, i, G.bit_offset, G.bit_count);
+      } else if (int rc = check_key_locator(qi, "aggregate", "aggregate source", G.kind, G.bit_offset, G.bit_count))
+        return rc;
+      if (seg->dev.attrs && seg->dev.attr_stride)
+        if (int rc = check_key_in_row(seg, qi, "aggregate", G.bit_offset, G.bit_count)) return rc;
+    }
+    return MRK_OK;
+  }
+  int decline_aggrs() const {
+    if (!aggrs) return MRK_OK;
+    const mrk_aggrs& A = *aggrs;
+    static const char* const fn[] = {"", "SUM", "MIN", "MAX"};
+    for (int i = 0; i < A.n; ++i) {
+      const mrk_aggr& G = A.a[i];
+      if (G.kind == MRK_SORTKEY_FLOAT)
+        return mrk_fail(MRK_E_UNSUPPORTED, "query %u: aggregate %d: %s of a float attribute (a float SUM depends on the arrival order, float MIN / MAX at NaN and +-0)", qi, i, fn[G.func]);
+      if (G.bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: aggregate %d: %s of a blob-stored or computed attribute (no row locator)", qi, i, fn[G.func]);
+    }
+    if (A.order_by >= 0 && (A.a[A.order_by].kind == MRK_SORTKEY_INT64 || (A.a[A.order_by].flags & MRK_AGGR_WIDEN)))
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: groups ordered by aggregate %d, %s with a 64-bit result (device path: a 32-bit aggregate orders)", qi, A.order_by, fn[A.a[A.order_by].func]);
+    return MRK_OK;
+  }
+
   // ... and its words of the descriptor: where the key lies in the row, the groups' order, the query's table in the batch's arena.
   // A grouped query publishes no candidates and needs no pruning threshold
   void reserve_group(DevQuery& dq, BatchPlan& plan) const {
@@ -905,7 +948,16 @@ struct PlanState {
     dq.grp_sort_by = (uint32_t)G.sort_by, dq.grp_desc = (uint32_t)G.desc;
     dq.grp_slots = group_slots_for((uint32_t)q.max_matches);
     dq.grp_off = plan.group_total;
-    plan.group_total += group_table_words(dq.grp_slots);
+    if (aggrs) { // one accumulator plane per aggregate behind the counts (mrk_kgroup.h)
+      dq.grp_naggr = (uint32_t)aggrs->n, dq.grp_order_aggr = (uint32_t)(aggrs->order_by + 1);
+      for (int i = 0; i < aggrs->n; ++i) {
+        const mrk_aggr& A = aggrs->a[i];
+        const bool src64 = A.kind == MRK_SORTKEY_INT64;
+        dq.grp_aggr_item[i] = (uint32_t)A.bit_offset >> 5;
+        dq.grp_aggr_op[i] = aggr_op_word((uint32_t)A.func, (uint32_t)A.bit_offset & 31u, src64 ? 0u : (uint32_t)A.bit_count, src64, (A.flags & MRK_AGGR_WIDEN) != 0);
+      }
+    }
+    plan.group_total += group_table_words(dq.grp_slots, dq.grp_naggr);
   }
 
   // what plan_query checks of the query itself before the tree is walked
@@ -1586,16 +1638,18 @@ struct PlanState {
 };
 
 int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
-                    BatchPlan& plan, uint32_t rowid_max, const mrk_group* group) {
+                    BatchPlan& plan, uint32_t rowid_max, const mrk_group* group, const mrk_aggrs* aggrs) {
   memset(&dq, 0, sizeof dq);
-  PlanState S{seg, q, use_packed, qi, group};
+  PlanState S{seg, q, use_packed, qi, group, aggrs};
   // validate: hostile order / sort specs are MRK_E_INVAL before a row is read
   if (int rc = S.resolve_order()) return rc;
   dq.item_first = (uint32_t)plan.items.size();
   dq.out_q = qi;
   if (int rc = S.check_query()) return rc;
   if (int rc = S.resolve_sort()) return rc;
+  if (int rc = S.check_aggrs()) return rc;
   if (int rc = S.resolve_group()) return rc;
+  if (int rc = S.decline_aggrs()) return rc;
   // (a sorted or grouped query reads attribute rows like a filtered one: the packed block scan's EXT instances only)
   S.filtered = q.n_filters > 0 || rowid_max != 0xFFFFFFFFu || S.order.sorted() || group != nullptr;
   // the evaluation tree and who evaluates it

@@ -36,7 +36,8 @@ struct __align__(16) RkSmem {
 // WIDE: a segment with 9-32 fields -- 32 field weights and ranker bytes; queues 0 / 1 carry the doc's whole field mask in one more
 // plane behind the narrow entry (the generic evaluator reads it from pk_fmask itself)
 // SORT: the batch holds queries ordered by a row attribute (mrk_query.sort); instances of their own (see scan_pk_kernel)
-template <int MODE, bool WIDE = false, bool SORT = false>
+// AGGR: the batch holds grouped queries with aggregates: the SORT instances once more with the accumulators' flush (see scan_pk_kernel)
+template <int MODE, bool WIDE = false, bool SORT = false, bool AGGR = false>
 __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   constexpr bool FAT = MODE == 1, GEN = MODE == 2;
   constexpr int NF = WIDE ? 32 : 8;
@@ -81,11 +82,20 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   bool grouped = false;
   uint32_t gr_item = 0, gr_shift = 0, gr_bits = 32;
   GroupTable gtable = group_table_at(nullptr, 8u);
+  const DevQuery* gr_q = a.queries; // the descriptor the aggregates' locators are read from at a flush (any pass of the query holds them)
   uint32_t *ghist = nullptr, *gcount = nullptr, *gtaubin = nullptr;
 
-  auto publish = [&]() {
+  auto publish = [&]() __attribute__((always_inline)) { // (always_inline: with the aggregates' flush in it the AGGR instances would call it, closure and kernel arguments in scratch)
     if constexpr (SORT) {
       if (grouped) { // (see scan_pk_kernel) one claim / add / max per distinct group value of the buffer
+        if constexpr (AGGR) {
+          if (cn && gr_q->grp_naggr) { // (uniform) ... and the aggregates' accumulators behind them, from the rows
+            if (!group_flush_wave_aggr(gtable, L.cbuf, L.cbuf2, cn, lane, a.seg.attrs, a.seg.attr_stride, a.seg.rowid_base, gr_q->grp_naggr, gr_q->grp_aggr_item, gr_q->grp_aggr_op) && lane == 0)
+              atomicOr(a.q_flags + cur_oq, QF_GROUPS);
+            cn = 0;
+            return;
+          }
+        }
         if (cn && !group_flush_wave(gtable, L.cbuf, L.cbuf2, cn, lane) && lane == 0) atomicOr(a.q_flags + cur_oq, QF_GROUPS);
         cn = 0;
         return;
@@ -276,6 +286,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
             gr_item = U(Q->grp_item), gr_shift = U(Q->grp_shift), gr_bits = U(Q->grp_bits);
             const uint64_t go = ((uint64_t)U((uint32_t)(Q->grp_off >> 32)) << 32) | U((uint32_t)Q->grp_off);
             gtable = group_table_at(a.gtab + go, U(Q->grp_slots));
+            if constexpr (AGGR) gr_q = Q;
           }
         }
         ghist = a.q_hist + (uint64_t)oq * NBINS;
@@ -444,6 +455,23 @@ void launch_rank(const ScanArgs& a, int which, void* stream) {
   // persistent grid: enough workgroups to fill every CU at the kernel's occupancy; late ones find the cursor past the
   // count and leave at once
   const dim3 grid(256 * 8), block(WG);
+  if (a.scand && a.grp_aggr) { // ... and grouped queries with aggregates: the sort instances with the accumulators' flush
+    hipStream_t st = (hipStream_t)stream;
+    if (a.seg.pk_fmask) {
+      if (which == 2)
+        hipLaunchKernelGGL((rank_kernel<2, true, true, true>), dim3(GEN_GRID), block, 0, st, a);
+      else if (which == 1)
+        hipLaunchKernelGGL((rank_kernel<1, true, true, true>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((rank_kernel<0, true, true, true>), grid, block, 0, st, a);
+    } else if (which == 2)
+      hipLaunchKernelGGL((rank_kernel<2, false, true, true>), dim3(GEN_GRID), block, 0, st, a);
+    else if (which == 1)
+      hipLaunchKernelGGL((rank_kernel<1, false, true, true>), grid, block, 0, st, a);
+    else
+      hipLaunchKernelGGL((rank_kernel<0, false, true, true>), grid, block, 0, st, a);
+    return;
+  }
   if (a.scand) { // the batch holds sorted queries
     hipStream_t st = (hipStream_t)stream;
     if (a.seg.pk_fmask) {

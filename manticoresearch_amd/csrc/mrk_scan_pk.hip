@@ -80,8 +80,10 @@ struct __align__(16) PkSmem {
 // batches launch stay as they are
 // (the WIDE instance that carries the sort sat at 168 VGPRs, the most that lets three waves share a SIMD; the group update's two more
 // would cost it the third wave, so that instance asks the register allocator for three -- every other instance is compiled as before)
-template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false>
-__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE && SORT && NREF == MAX_PROX_TERMS ? 3 : 1))) void scan_pk_kernel(ScanArgs a) {
+// AGGR: the batch holds grouped queries with aggregates (mrk_aggrs): the SORT instances once more with the accumulators' flush
+// (group_flush_wave_aggr), so that the ones every other sorted or grouped batch launches stay as they are
+template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false, bool AGGR = false>
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE && SORT && !AGGR && NREF == MAX_PROX_TERMS ? 3 : 1))) void scan_pk_kernel(ScanArgs a) {
   constexpr int NF = WIDE ? 32 : 8;
   constexpr bool GEN = NREF > MAX_PROX_TERMS;
   extern __shared__ __align__(16) uint8_t smem_raw[];
@@ -206,9 +208,19 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE && SORT
 
   // publish the wave's buffered candidates: reserve a slice of the query's list with ONE atomic,
   // write it coalesced, add the per-bin counts to the global histogram, re-read the threshold
-  auto publish = [&]() {
+  auto publish = [&]() __attribute__((always_inline)) { // (always_inline: with the aggregates' flush in it the AGGR instances would call it, closure and kernel arguments in scratch)
     if constexpr (SORT) {
       if (grouped) { // one claim / add / max per distinct group value of the buffer
+        if constexpr (AGGR) {
+          if (cn && Q->grp_naggr) { // (uniform) ... and the aggregates' accumulators behind them, from the rows
+            if (!group_flush_wave_aggr(group_table_at(a.gtab + Q->grp_off, Q->grp_slots), L.cbuf, L.cbuf2, cn, lane, a.seg.attrs, a.seg.attr_stride, a.seg.rowid_base, Q->grp_naggr,
+                                       Q->grp_aggr_item, Q->grp_aggr_op) &&
+                lane == 0)
+              atomicOr(a.q_flags + oq, QF_GROUPS);
+            cn = 0;
+            return;
+          }
+        }
         if (cn && !group_flush_wave(group_table_at(a.gtab + Q->grp_off, Q->grp_slots), L.cbuf, L.cbuf2, cn, lane) && lane == 0) atomicOr(a.q_flags + oq, QF_GROUPS);
         cn = 0;
         return;
@@ -994,9 +1006,9 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE && SORT
   }
 }
 
-template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false>
+template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false, bool AGGR = false>
 static void launch_pk(const ScanArgs& a, size_t tail, hipStream_t st) {
-  hipLaunchKernelGGL((scan_pk_kernel<PROX, TREE, EXT, NREF, WIDE, SORT>), dim3(a.n_items), dim3(WG), sizeof(PkSmem<PROX, TREE, NREF, WIDE, SORT>) + tail, st, a);
+  hipLaunchKernelGGL((scan_pk_kernel<PROX, TREE, EXT, NREF, WIDE, SORT, AGGR>), dim3(a.n_items), dim3(WG), sizeof(PkSmem<PROX, TREE, NREF, WIDE, SORT>) + tail, st, a);
 }
 
 void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen) {
@@ -1004,6 +1016,13 @@ void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree,
   if (max_terms < 1) max_terms = 1;
   const size_t tail = (size_t)(max_terms - 1) * 256 * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
+  if (a.scand && a.grp_aggr) { // ... and grouped queries with aggregates: the same instances with the accumulators' flush
+    if (a.seg.pk_fmask)
+      gen ? launch_pk<true, true, true, MRK_MAX_AND_TERMS, true, true, true>(a, tail, st) : launch_pk<true, true, true, MAX_PROX_TERMS, true, true, true>(a, tail, st);
+    else
+      gen ? launch_pk<true, true, true, MRK_MAX_AND_TERMS, false, true, true>(a, tail, st) : launch_pk<true, true, true, MAX_PROX_TERMS, false, true, true>(a, tail, st);
+    return;
+  }
   if (a.scand) { // the batch holds sorted queries (they set `ext`): the full instances with the sort
     if (a.seg.pk_fmask)
       gen ? launch_pk<true, true, true, MRK_MAX_AND_TERMS, true, true>(a, tail, st) : launch_pk<true, true, true, MAX_PROX_TERMS, true, true>(a, tail, st);
