@@ -83,6 +83,45 @@ __host__ __device__ __forceinline__ float bm_wmax_bound(uint32_t cls, float idf)
   return cls == 15u ? idf : term_tfidf(cls, idf);
 }
 
+// The bound's pruning test as a cutoff on bmw, the (int32_t)((acc + 0.5f) * 1000.0f) of the bound's float sum: the smallest x with
+//   weight_bin(bin_lo, bin_shift, (int32_t)(((uint32_t)x + rmax1000) * index_weight)) >= tau_bin,
+// so that "the word's best weight lies in a bin behind the threshold" is x < bm_wmax_cut(..).  tau_bin == 0 drops nothing (INT32_MIN).
+// Otherwise, with w = (x + rmax1000) * index_weight: weight_bin(w) >= tau_bin  <=>  w >= T = bin_lo + (tau_bin << bin_shift) (the
+// clamp to bin 1023 does not matter for tau_bin <= 1023)  <=>  x >= ceil(T / index_weight) - rmax1000, for index_weight > 0.
+// Preconditions, the ones the kernel's wprune holds: index_weight > 0 and a geometry of bins_by_weight (mrk_plan.cpp) that is not its
+// fallback.  That one is only set when every corner (bm_lo|bm_hi + (rmin|rmax) * 1000) * index_weight of the weights lies strictly
+// inside int32, bm_hi being above every float sum of two tfidf bounds and rmax the sum of the positive field weights: so
+// (x + rmax1000) * index_weight fits int32 for every x the bound can produce, the kernel's uint32 product never wraps there, and the
+// equivalences above hold in plain integers.  bin_shift <= 22 then (a span below 2^32 in 1024 bins), so tau_bin << bin_shift fits
+// uint32 and |T| < 2^33.
+// No division runs per threshold: the caller keeps inv = bm_cut_inv(index_weight), worked out once per wave, and the quotient comes from a
+// 32-bit multiply-high with one fix-up, all of it scalar work on wave-uniform values.
+//  - T is first capped at INT32_MAX (in uint32, as an offset from bin_lo): no weight of such a geometry reaches INT32_MAX, so
+//    "w >= T" is false for every T from there up all the same, and the capped T fits int32.
+//  - floor(n / d) for uint32 n: inv = floor((2^32 - 1) / d) lies in (2^32 / d - 1, 2^32 / d], so n * inv / 2^32 lies in (n / d - 1, n / d]
+//    and its floor q0 is floor(n / d) or one below; the remainder n - q0 * d tells which.
+//  - ceil(T / d) is floor((T - 1) / d) + 1 for T > 0 and -floor(-T / d) for T <= 0.
+// The result is clamped to int32: a cutoff below INT32_MIN drops nothing, as it should, and one above INT32_MAX cannot occur (T <= INT32_MAX).
+// (tests/cpp/bm_cut.cpp checks it against the expression above.)
+__host__ __device__ __forceinline__ uint32_t bm_cut_inv(uint32_t index_weight) { return 0xFFFFFFFFu / index_weight; }
+
+__host__ __device__ __forceinline__ int32_t bm_wmax_cut(int32_t bin_lo, uint32_t bin_shift, uint32_t tau_bin, uint32_t rmax1000, uint32_t index_weight,
+                                                        uint32_t inv) {
+  if (!tau_bin) return INT32_MIN;
+  const uint32_t room = 0x7FFFFFFFu - (uint32_t)bin_lo; // INT32_MAX - bin_lo, in [0, 2^32)
+  uint32_t off = tau_bin << bin_shift;
+  off = off < room ? off : room;
+  const int32_t T = (int32_t)((uint32_t)bin_lo + off); // (in range: no wrap)
+  const uint32_t n = T > 0 ? (uint32_t)T - 1u : 0u - (uint32_t)T;
+  uint32_t q = (uint32_t)(((uint64_t)n * inv) >> 32);
+  if (n - q * index_weight >= index_weight) ++q;
+  const int64_t c = (T > 0 ? (int64_t)q + 1 : -(int64_t)q) - (int64_t)rmax1000;
+  return c < (int64_t)INT32_MIN ? INT32_MIN : (int32_t)c;
+}
+__host__ __device__ __forceinline__ int32_t bm_wmax_cut(int32_t bin_lo, uint32_t bin_shift, uint32_t tau_bin, uint32_t rmax1000, uint32_t index_weight) {
+  return bm_wmax_cut(bin_lo, bin_shift, tau_bin, rmax1000, index_weight, bm_cut_inv(index_weight));
+}
+
 // bitonic sort of c[0..len) descending, all WG threads; len = a power of two <= CAND (entries past the keys are zeros: a
 // short list sorts a short network -- 15 stages for 32 keys instead of the 66 of the full buffer)
 __device__ void sort_cand_desc(uint64_t* c, uint32_t len = (uint32_t)CAND) {

@@ -27,6 +27,8 @@
 // keywords ride along with a burst's bitmap words (one coalesced 128-byte load per keyword and four windows), and a match word
 // whose best possible weight lies in a bin behind the query's threshold is counted and dropped before it is queued -- never
 // unpacked, none of its tf / field words requested.  BM25 in relevance order without field limits; everything else runs as before.
+// The test is one compare per word: the bound's integer part against a cutoff (bm_wmax_cut, mrk_kcommon.h) that the wave works out
+// whenever its threshold bin has moved -- everything behind the bound's cast is a function of wave-uniform values alone.
 #include "mrk_kcommon.h"
 #include "mrk_kprune.h"
 
@@ -57,14 +59,20 @@ struct __align__(16) BmWaveLds {
   uint16_t wpre[BM_WQCAP]; // final drain: matches held by the queue entries before this one (<= 128 x 32)
 };
 
-// WMAX instances: per tfidf table, the keyword's tfidf bound by tf class (bm_wmax_bound, mrk_kcommon.h); 320 B for a group -- 23360 B,
-// still 7 workgroups per CU
+// WMAX instances: per tfidf table, the keyword's tfidf bound by tf class (bm_wmax_bound, mrk_kcommon.h) with score()'s leading
+// `0.0f +` applied (bm_bound_entry below); 320 B for a group -- 23360 B, still 7 workgroups per CU
 template <int N>
 struct BmBound {
   float wbound[N][16];
 };
 template <>
 struct BmBound<0> {};
+
+// A bound table's entry: score() starts its sum with `0.0f + ta`, and the bound has to run score()'s operations.  The addition is done
+// here, once per class, instead of once per match word: it is the same fp32 operation on the same value (round to nearest, no
+// contraction, denormals kept, as everywhere in this file), so the stored float has the bits score()'s `0.0f + ta` yields for this ta
+// -- ta itself, but for a -0.0f, which becomes +0.0f here as it does there.
+__device__ __forceinline__ float bm_bound_entry(uint32_t cls, float idf) { return 0.0f + bm_wmax_bound(cls, idf); }
 
 template <bool GROUP, bool WMAX>
 struct __align__(16) BmSmem : BmBound<WMAX ? (GROUP ? BM_GROUP_TABS : 2) : 0> {
@@ -96,7 +104,7 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
       const float idf = a.queries[G->q[src >> 1]].t[src & 1u].idf;
       s.tfidf[j][tid] = term_tfidf(tid, idf);
       if constexpr (WMAX)
-        if (tid < 16u) s.wbound[j][tid] = bm_wmax_bound(tid, idf);
+        if (tid < 16u) s.wbound[j][tid] = bm_bound_entry(tid, idf);
     }
   }
   const DevQuery* __restrict__ Q = a.queries + qi;
@@ -110,7 +118,7 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
     s.tfidf[0][tid] = term_tfidf(tid, TA.idf);
     s.tfidf[1][tid] = term_tfidf(tid, TB.idf);
     if constexpr (WMAX)
-      if (tid < 16u) s.wbound[0][tid] = bm_wmax_bound(tid, TA.idf), s.wbound[1][tid] = bm_wmax_bound(tid, TB.idf);
+      if (tid < 16u) s.wbound[0][tid] = bm_bound_entry(tid, TA.idf), s.wbound[1][tid] = bm_bound_entry(tid, TB.idf);
   }
   {
     const uint32_t nwr = GROUP ? (QR->n_weights < 8u ? QR->n_weights : 8u) : nw;
@@ -155,11 +163,8 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
                       (int32_t)index_weight > 0 && !(bin_lo == INT32_MIN && bin_shift == 31u);
   const uint16_t* __restrict__ wmA = nullptr;
   const uint16_t* __restrict__ wmB = nullptr;
-  const float* __restrict__ bndA = nullptr;
-  const float* __restrict__ bndB = nullptr;
   if constexpr (WMAX) { // (launch_scan_bm takes these instances only for a segment with the plane)
     wmA = a.seg.bm_wmax + (TA.bm_off >> 2), wmB = a.seg.bm_wmax + (TB.bm_off >> 2);
-    bndA = s.wbound[ia], bndB = s.wbound[ib];
   }
   // the largest field-weight sum a match can get: every field with a positive weight (a launch constant of the workgroup)
   uint32_t rmax1000 = 0;
@@ -168,7 +173,17 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
     for (uint32_t f = 0; f < nwr; ++f) rmax1000 += QR->weights[f] > 0 ? (uint32_t)QR->weights[f] : 0u;
     rmax1000 *= 1000u;
   }
-  uint32_t n_queued = 0, n_pruned = 0; // per lane: match words of a wprune wave that went on the queue / were dropped
+  // byte offsets of the wave's two bound tables in wbound, one VGPR each in the grouped instances (the empty asm hides that they are
+  // uniform): as scalars they are spilled, and every window read them back with a v_readlane in front of its table addresses
+  uint32_t boA = ia * (uint32_t)sizeof(float[16]), boB = ib * (uint32_t)sizeof(float[16]);
+  if (GROUP && WMAX) asm volatile("" : "+v"(boA), "+v"(boB));
+  uint32_t n_queued = 0, n_pruned = 0; // (uniform) match words of a wprune wave that went on the queue / were dropped
+  // The pruning test of a match word, `weight_bin(bin_lo, bin_shift, (bmw + rmax1000) * index_weight) < tau_bin`, is `bmw < cut` with
+  // cut = bm_wmax_cut(.., cut_tau, ..): both uniform, worked out again at a burst's top when tau_bin has left cut_tau behind.  Between
+  // two bursts cut may lag a tau_bin that publish() has raised -- a lower cutoff drops fewer words, never a wrong one.
+  int32_t cut = INT32_MIN;
+  uint32_t cut_tau = 0;
+  const uint32_t cut_inv = wprune ? bm_cut_inv(index_weight) : 0u; // (the one division, out of the loop)
 
   const uint32_t nwin = item.blk_end - item.blk_begin;
   const uint32_t part = (nwin + per - 1) / per;
@@ -377,6 +392,29 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
       ca4 >>= sh, cb4 >>= sh;
     }
     if (ngt > tau_bin) tau_bin = ngt;
+    if constexpr (WMAX) {
+      const uint32_t tu = (uint32_t)__builtin_amdgcn_readfirstlane((int)tau_bin);
+      if (wprune && tu != cut_tau) {
+        cut_tau = tu;
+        cut = bm_wmax_cut(bin_lo, bin_shift, tu, rmax1000, index_weight, cut_inv);
+      }
+    }
+    // The bounds of the burst's four windows, here and not window by window: the class nibbles of all four are in registers, so the
+    // eight table reads go out back to back and are waited for together, not as four round trips in a row, each in front of its
+    // window's queueing.  (bmw[i] = the integer part of window i's best tfidf sum, with score()'s operations in its order: (0.0f + ta) + tb, + 0.5f,
+    // * 1000.0f, cast.  A table entry's byte address is the table's 64-byte-aligned offset OR'ed with the nibble moved to bits 2..5.)
+    int32_t bmw[BM_BURST];
+    if constexpr (WMAX) {
+      if (wprune) {
+        const char* wbase = (const char*)&s.wbound[0][0];
+#pragma unroll
+        for (int i = 0; i < BM_BURST; ++i) {
+          const uint32_t oa = ((i ? ca4 >> (4 * i - 2) : ca4 << 2) & 60u) | boA, ob = ((i ? cb4 >> (4 * i - 2) : cb4 << 2) & 60u) | boB;
+          const float acc = *(const float*)(wbase + oa) + *(const float*)(wbase + ob);
+          bmw[i] = (int32_t)((acc + 0.5f) * 1000.0f);
+        }
+      }
+    }
     fetch(wb + BM_BURST);
 #pragma unroll
     for (int i = 0; i < BM_BURST; ++i) {
@@ -401,20 +439,11 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
         total += __popc(m);
         m = 0;
 #endif
-        if (wprune && m) {
-          const uint32_t ca = (ca4 >> (4 * i)) & 15u, cb = (cb4 >> (4 * i)) & 15u;
-          const float ta = bndA[ca], tb = bndB[cb];
-          float acc = 0.0f + ta; // score()'s operations, in its order
-          acc = acc + tb;
-          const int32_t bmw = (int32_t)((acc + 0.5f) * 1000.0f);
-          uint32_t weight = (uint32_t)bmw + rmax1000;
-          weight *= index_weight;
-          if (weight_bin(bin_lo, bin_shift, (int32_t)weight) < tau_bin) {
-            total += (uint32_t)__popc(m); // (score() counts the matches of the words that go on)
-            m = 0;
-            ++n_pruned;
-          } else
-            ++n_queued;
+        if (WMAX && wprune) { // (every lane: an empty word has class 0 and drops nothing)
+          const uint32_t md = bmw[i] < cut ? m : 0u; // the word's matches, if it is dropped
+          total += (uint32_t)__popc(md); // (score() counts the matches of the words that go on)
+          m ^= md;
+          n_pruned += (uint32_t)__popcll(__ballot(md != 0));
         }
         // A window holds a dozen matches in its 64 words: unpacking it on the spot would run the bit loop with a fifth of
         // the lanes busy.  Its non-empty words are queued instead (one ballot, no loop) and unpacked 64 words at a time.
@@ -427,6 +456,7 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
             L.wqr[pos] = make_uint2(ra0, rb0);
           }
           wqn += (uint32_t)__popcll(bal);
+          if (WMAX && wprune) n_queued += (uint32_t)__popcll(bal);
           while (wqn >= 64u) wqn = wqn - 64u + unpack(wqn - 64u, 64u);
         }
       }
@@ -485,10 +515,8 @@ __global__ __launch_bounds__(WG) void scan_bm_kernel(ScanArgs a) {
     if (lane == 0 && t) atomicAdd((unsigned long long*)(a.q_total + oq), (unsigned long long)t);
   }
   if (wprune) { // mrk_batch_stats.bm_words_queued / bm_words_pruned
-    uint32_t nq = n_queued, np = n_pruned;
-    for (int dlt = 32; dlt; dlt >>= 1) nq += __shfl_down(nq, dlt, 64), np += __shfl_down(np, dlt, 64);
-    if (lane == 0 && nq) atomicAdd(gcount + QC_BM_QUEUED, nq);
-    if (lane == 0 && np) atomicAdd(gcount + QC_BM_PRUNED, np);
+    if (lane == 0 && n_queued) atomicAdd(gcount + QC_BM_QUEUED, n_queued);
+    if (lane == 0 && n_pruned) atomicAdd(gcount + QC_BM_PRUNED, n_pruned);
   }
 }
 
