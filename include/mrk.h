@@ -266,8 +266,9 @@ typedef struct {
    straddling a dword, a 64 that is not aligned, WIDEN on an INT64 source, order_by out of range or next to another sort_by,
    aggregates without a group.  MRK_E_UNSUPPORTED per query: a FLOAT source, a blob-stored source (bit_offset < 0), a 64-bit order,
    and everything that declines the group.
-   Exchange rows: a query with aggregates leaves in GROUP rows, as in narrow, wide and order rows, with MRK_ROW_DECLINED, no entries
-   and spec word 0 -- the group row has no room for the accumulators.  Carrying them across segments and shards is the follow-up. */
+   Exchange rows: aggregates travel in aggregate rows (MRK_AROW_WORDS, below); the other four kinds decline them -- a query with
+   aggregates leaves in GROUP rows, as in narrow, wide and order rows, with MRK_ROW_DECLINED, no entries and spec word 0: the
+   group row has no room for the accumulators. */
 enum { MRK_AGGR_SUM = 1, MRK_AGGR_MIN = 2, MRK_AGGR_MAX = 3 };
 #define MRK_AGGR_WIDEN 1 /* mrk_aggr.flags: an INT source aggregated as a 64-bit integer */
 #define MRK_MAX_AGGRS 4
@@ -744,6 +745,57 @@ int mrk_shard_exchange_grows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* gro
                              uint32_t slot);
 /* host only: the group spec word of a query (0 where the fields are no valid spec) */
 uint64_t mrk_group_spec_word(uint32_t sort_by, uint32_t desc, uint32_t bit_count, uint32_t max_matches);
+
+/* ------------------------------------------------------------------------------------
+ * Aggregate rows: grouped queries WITH their aggregates (mrk_aggrs) across segments and shards.  The yardstick is the group rows':
+ * ONE grouping sorter fed with the matches of all segments (the citations above), not the reference's master / agent merge.  The
+ * accumulators are adds and maxima, associative and commutative as the counts and heads are, so a group row's contract carries
+ * over word for word; the row grows by MRK_MAX_AGGRS planes and a second spec word.
+ * One row of MRK_AROW_WORDS = 6 G + 4 u64 per query, G = MRK_GROW_GROUPS:
+ *   [0 .. 2G+1]         head keys | count | total word | group value << 32 | @count: as in a group row
+ *   [2G+2 + a*G + i]    aggregate a (< MRK_MAX_AGGRS) of entry i: the VALUE, exactly as mrk_batch_result_aggrs gives it -- a 32-bit
+ *                       result zero-extended, a 64-bit one the integer's bits.  Zero past the count, for a >= n and in a row
+ *                       without aggregates
+ *   [6G+2]              the group spec word, unchanged
+ *   [6G+3]              the aggregate spec word: 0 = no aggregates; else bit 0 set | bits 1-3 n (1..4) | bits 4-6 1 + order_by (0 =
+ *                       none) | for aggregate a, bits 8+4a .. 11+4a: func (MRK_AGGR_*, the low 2 bits) | bit 2 a signed 64-bit
+ *                       source | bit 3 widened; every other bit zero.  Nothing of where a segment stores the column.
+ * What travels: a grouped query with aggregates, with all its groups; a grouped query without, with zero planes and aggregate spec
+ * 0 (its words [0, 2G+2) and its group spec word equal its group row); a relevance query as in group rows (keys in [0, MRK_MAX_K),
+ * both specs 0).  A mrk_query.sort / .order query and one the planner declined leave MRK_ROW_DECLINED under spec words 0; a grouped
+ * query declined while it ran (more than 4 * max_matches groups) leaves MRK_ROW_DECLINED, one the scan flagged MRK_ROW_RERUN, both
+ * without entries under their own two spec words.  The other four row kinds decline a query with aggregates.
+ * The merge: the group spec is elected as in group rows, and the aggregate spec words of the lists that have a say must be equal in
+ * every bit -- "grouped with aggregates" next to "grouped without" included -- or the merged row is MRK_ROW_DECLINED without
+ * entries under the first answering list's two spec words.  MRK_ROW_RERUN, a decline in any list, the 4 * max_matches limit over
+ * all lists, a count sum past 2^32 - 1 and max_matches > k: as in group rows.  Per group value counts add, the larger head stays,
+ * SUM adds (modulo 2^32 for a 32-bit result, modulo 2^64 otherwise), MIN / MAX compare unsigned for INT sources (widened or not) and
+ * signed for INT64 sources.  The groups are ordered by the group spec, or by the ordering aggregate's MERGED 32-bit value in the
+ * group spec's direction, then by head rowid ascending; total_found = the number of merged groups.  A staged merge equals a
+ * one-step merge word for word; a spec-0 query merges exactly as mrk_topk_merge_grows merges it.
+ * Hostile lists read as MRK_ROW_DECLINED, no entries, both spec words 0: an entry count above G, a group spec that does not unpack,
+ * an aggregate spec with a stray bit, n out of range, func 0 inside n or a nonzero field beyond it, both width bits, an order that
+ * names a 64-bit result or an index >= n, an order next to a group spec whose sort_by is not MRK_GROUPSORT_KEY, or a nonzero
+ * aggregate spec over group spec 0.
+ * Limits shared with the group rows: at most 8 lists; k = the largest max_matches of the call (it sizes the context's scratch arena,
+ * here with room for MRK_MAX_AGGRS planes per table); the merge is synchronous on the merge stream (_async: behind it);
+ * mrk_batch_export_arows is called after mrk_batch_wait, and a rerun query leaves with its repaired groups and aggregates.
+ * Left, as for group rows: there is no standing destination for aggregate rows, and ShardMerger does not carry them.  AVG and
+ * float sources are not offered (mrk_aggrs above).
+ * ---------------------------------------------------------------------------------- */
+#define MRK_AROW_WORDS (6 * MRK_GROW_GROUPS + 4)
+int mrk_batch_export_arows(mrk_batch* b, uint64_t* arows_dst);
+int mrk_topk_merge_arows(mrk_ctx* ctx, const uint64_t* arows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_arows);
+int mrk_topk_merge_arows_async(mrk_ctx* ctx, const uint64_t* arows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
+                               uint64_t* out_arows, void* wait_event, uint32_t slot);
+int mrk_topk_merge_arows_part(mrk_ctx* ctx, const uint64_t* arows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
+                              uint32_t k, uint64_t* out_arows);
+int mrk_shard_exchange_arows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* arows, uint32_t n_queries, uint32_t k, uint64_t* out_arows,
+                             uint32_t slot);
+/* host only: the aggregate spec word of a query's aggregates next to a group with this sort_by (0 where the fields are no valid
+   spec: NULL, n or order_by out of range, an unknown func, kind or flag, WIDEN on an INT64 source, a 64-bit order, an order next to
+   another sort_by) */
+uint64_t mrk_aggr_spec_word(const mrk_aggrs* aggrs, uint32_t group_sort_by);
 
 /* merge n_lists sorted partial top-K lists per query (device pointers; relevance order only):
    in_keys[(l*n_queries + q)*MRK_MAX_K + i], in_counts[l*n_queries + q] -> out_keys[q*MRK_MAX_K + i],

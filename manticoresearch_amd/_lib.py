@@ -18,6 +18,7 @@ MRK_MAX_K = 1024
 OROW_WORDS = MRK_MAX_K + 2 + MRK_MAX_K + 1  # MRK_OROW_WORDS: keys | count | total_found | MRK_MAX_K mapped keys (u64) | order spec word
 GROW_GROUPS = 4 * MRK_MAX_K                  # MRK_GROW_GROUPS: the groups a group row holds (GROUPBY_FACTOR x MRK_MAX_K)
 GROW_WORDS = 2 * GROW_GROUPS + 3             # MRK_GROW_WORDS: head keys | count | total_found | value << 32 | count per entry | group spec word
+AROW_WORDS = 6 * GROW_GROUPS + 4             # MRK_AROW_WORDS: a group row's 2 G + 2 words | 4 planes of G aggregate values | group spec word | aggregate spec word
 MRK_MAX_AND_TERMS = 8
 
 
@@ -222,6 +223,13 @@ SYMBOLS = [
     ("mrk_topk_merge_grows_part", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("mrk_shard_exchange_grows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
     ("mrk_group_spec_word", C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("mrk_batch_export_arows", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("mrk_topk_merge_arows", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("mrk_topk_merge_arows_async", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_uint32]),
+    ("mrk_topk_merge_arows_part", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("mrk_shard_exchange_arows", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]),
+    ("mrk_aggr_spec_word", C.c_uint64, [C.POINTER(Aggrs), C.c_uint32]),
     ("mrk_order_unmap_key", C.c_uint64, [C.c_uint64, C.c_uint64]),
     ("mrk_idf", C.c_float, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float]),
     ("mrk_index_from_hits", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -535,6 +535,7 @@ ROW_WORDS = _lib.MRK_MAX_K + 2                     # MRK_ROW_WORDS: keys | count
 SROW_WORDS = ROW_WORDS + _lib.MRK_MAX_K // 2 + 1   # MRK_SROW_WORDS: ... | MRK_MAX_K mapped sort keys (u32) | sort spec word
 OROW_WORDS = _lib.OROW_WORDS                       # MRK_OROW_WORDS: ... | MRK_MAX_K mapped order keys (u64) | order spec word
 GROW_WORDS = _lib.GROW_WORDS                       # MRK_GROW_WORDS: GROW_GROUPS head keys | count | total_found | GROW_GROUPS (value << 32 | @count) | group spec word
+AROW_WORDS = _lib.AROW_WORDS                       # MRK_AROW_WORDS: a group row's first 2 G + 2 words | MAX_AGGRS planes of G aggregate values | group spec word | aggregate spec word
 GROW_GROUPS = _lib.GROW_GROUPS                     # MRK_GROW_GROUPS: 4 x MRK_MAX_K, all the groups a grouped query may hold
 
 
@@ -774,6 +775,12 @@ class Batch:
         ordered one declined.  What dist.merge_grows_np and mrk_topk_merge_grows merge across segments and shards."""
         check(lib().mrk_batch_export_grows(self._h, grows_dst))
 
+    def export_arows(self, arows_dst: int) -> None:
+        """The last submit's results as AGGREGATE rows (mrk_batch_export_arows) into a caller-owned device buffer [n_queries][AROW_WORDS],
+        after wait(): a grouped query with all its groups and its aggregates' values, one without aggregates under zero planes, a
+        relevance query with its keys, a sorted or ordered one declined.  What dist.merge_arows_np and mrk_topk_merge_arows merge."""
+        check(lib().mrk_batch_export_arows(self._h, arows_dst))
+
     def orows_weight_first(self, on: bool = True) -> None:
         """Let ORDER rows carry weight-first queries (Order.weight_first) from the next submit on (mrk_batch_orows_weight_first): bit 3
         of their spec word, which every merger of these rows must know.  Off by default: such a query's row leaves declined."""
@@ -849,5 +856,5 @@ def idf(term_docs: int, total_docs: int, plain: bool = False, normalized: bool =
 __all__ = ["open_rt_ram", "open_rt_segment", "SPH_RANK_PROXIMITY_BM25", "SPH_RANK_BM25", "SPH_RANK_NONE", "SPH_RANK_WORDCOUNT", "SPH_RANK_PROXIMITY",
            "SPH_RANK_MATCHANY", "SPH_RANK_FIELDMASK", "SPH_RANK_SPH04",
            "parse_query", "SPH_QUERY_TERM", "SPH_QUERY_AND", "SPH_QUERY_OR", "SPH_QUERY_MAYBE", "SPH_QUERY_ANDNOT", "SPH_QUERY_PHRASE", "SPH_QUERY_PROXIMITY", "SPH_QUERY_QUORUM", "SPH_QUERY_BEFORE", "SPH_QUERY_NEAR", "SPH_QUERY_NOTNEAR", "SPH_QUERY_SENTENCE", "SPH_QUERY_PARAGRAPH",
-           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "SORTKEY_INT64", "OrderPart", "Order", "Group", "GROUPSORT_KEY", "GROUPSORT_COUNT", "GROUPSORT_WEIGHT", "Aggr", "AGGR_SUM", "AGGR_MIN", "AGGR_MAX", "MAX_AGGRS", "Matches", "ROW_WORDS", "SROW_WORDS", "OROW_WORDS", "GROW_WORDS", "GROW_GROUPS", "Context",
+           "SPH_HIT_FORMAT_PLAIN", "SPH_HIT_FORMAT_INLINE", "ALL_FIELDS", "DICT_DTYPE", "HostIndex", "open_index", "index_from_hits", "synth_index", "XQKeyword", "XQNode", "Query", "Filter", "Sort", "SORTKEY_INT", "SORTKEY_FLOAT", "SORTKEY_INT64", "OrderPart", "Order", "Group", "GROUPSORT_KEY", "GROUPSORT_COUNT", "GROUPSORT_WEIGHT", "Aggr", "AGGR_SUM", "AGGR_MIN", "AGGR_MAX", "MAX_AGGRS", "Matches", "ROW_WORDS", "SROW_WORDS", "OROW_WORDS", "GROW_WORDS", "GROW_GROUPS", "AROW_WORDS", "Context",
            "Segment", "Batch", "Batcher", "prepare", "idf", "MrkError", "validate_index", "pair_stats"]

@@ -544,7 +544,9 @@ struct MergeArgs {
 // KCAP mapped keys (u64) | order spec word.
 // A GROUP row (MRK_GROW_WORDS; mrk_groupsel.hip writes and merges it) has a header of its own: GROW_GROUPS head keys | count |
 // total_found | GROW_GROUPS (group value << 32 | count) | group spec word.
-enum RowKind { ROWS_NARROW, ROWS_WIDE, ROWS_ORDER, ROWS_GROUP };
+// An AGGREGATE row (MRK_AROW_WORDS; mrk_groupsel.hip too) goes on behind a GROUP row's first 2 GROW_GROUPS + 2 words: MRK_MAX_AGGRS planes of
+// GROW_GROUPS aggregate values | group spec word | aggregate spec word.
+enum RowKind { ROWS_NARROW, ROWS_WIDE, ROWS_ORDER, ROWS_GROUP, ROWS_AGGR };
 constexpr int ROW_WORDS = MRK_ROW_WORDS;
 constexpr uint64_t ROW_RERUN = MRK_ROW_RERUN, ROW_DECLINED = MRK_ROW_DECLINED, ROW_FLAG_MASK = MRK_ROW_RERUN | MRK_ROW_DECLINED;
 constexpr int SROW_WORDS = MRK_SROW_WORDS;
@@ -604,6 +606,10 @@ void launch_pack_grows(const PackGRowsArgs& a, void* stream);
 // merge_grows_kernel: MergeRowsArgs over group rows; gtab = scratch for one table per query of the call, tab_words u64 apart, each
 // large enough for group_slots_for(a.k) slots and ZERO at launch
 void launch_merge_grows(const MergeRowsArgs& a, uint64_t* gtab, uint64_t tab_words, void* stream);
+// Aggregate rows: the same two over rows of AROW_WORDS (PackGRowsArgs::rows [n][AROW_WORDS], the decline masks' bit ROWS_AGGR); the merge's
+// tables tab_words apart with room for MRK_MAX_AGGRS accumulator planes behind group_slots_for(a.k) slots, ZERO at launch
+void launch_pack_arows(const PackGRowsArgs& a, void* stream);
+void launch_merge_arows(const MergeRowsArgs& a, uint64_t* gtab, uint64_t tab_words, void* stream);
 
 void launch_scan(const ScanArgs& a, void* stream);
 void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree, bool ext, void* stream, bool gen = false); // a.scand: the instances that carry the sort

@@ -15,6 +15,9 @@
 // the order keys are distinct (heads are distinct rows), so the sorted result is the same from run to run.
 // The same compaction and sort (group_compact_sort) serve the GROUP rows further down: pack_grows_kernel writes all the groups of a
 // query's table as its exchange row, merge_grows_kernel adds up to 8 such rows into one table and writes the merged row.
+// The AGGREGATE rows behind them carry a query's aggregates too: pack_arows_kernel writes the groups with their aggregates' values,
+// merge_arows_kernel adds / max-es the lists' values per group through the accumulators' own update -- kernels of their own, so that
+// the three above compile to what they compiled to.
 #include "mrk_kcommon.h"
 #include "mrk_kgroup.h"
 #include "mrk_krows.h"
@@ -74,19 +77,37 @@ __device__ __forceinline__ uint32_t group_compact_sort(GroupSelSmem& s, const Gr
   return n;
 }
 
-// ---- a group row (MRK_GROW_WORDS), by the whole workgroup: n entries, entry i = key_at(i) over plane_at(i), zero past n
-template <class KF, class PF>
+// ---- a group row (MRK_GROW_WORDS), by the whole workgroup: n entries, entry i = key_at(i) over plane_at(i), zero past n.  SPEC_AT:
+// where the layout keeps the group spec word (an aggregate row shares the words in front of it)
+template <int SPEC_AT = GROW_SPEC, class KF, class PF>
 __device__ __forceinline__ void write_grow(uint64_t* __restrict__ row, uint32_t n, KF key_at, PF plane_at, uint64_t total_word, uint64_t spec) {
   for (uint32_t i = threadIdx.x; i < (uint32_t)GROW_GROUPS; i += WG) {
     row[i] = i < n ? key_at(i) : 0ull;
     row[GROW_PLANE + i] = i < n ? plane_at(i) : 0ull;
   }
-  if (threadIdx.x == 0) row[GROW_CNT] = n, row[GROW_TOTAL] = total_word, row[GROW_SPEC] = spec;
+  if (threadIdx.x == 0) row[GROW_CNT] = n, row[GROW_TOTAL] = total_word, row[SPEC_AT] = spec;
 }
 // ... all the groups of T, s.idx[0 .. n) their slots in group order (group_compact_sort)
+template <int SPEC_AT = GROW_SPEC>
 __device__ __forceinline__ void write_grow_groups(uint64_t* __restrict__ row, uint32_t n, const GroupSelSmem& s, const GroupTable& T, uint64_t total_word, uint64_t spec) {
-  write_grow(
+  write_grow<SPEC_AT>(
       row, n, [&](uint32_t i) { return T.heads[s.idx[i]]; }, [&](uint32_t i) { return group_plane_word((uint32_t)T.keys[s.idx[i]], T.counts[s.idx[i]]); }, total_word, spec);
+}
+// ---- what an aggregate row (MRK_AROW_WORDS) holds behind a group row's words: the MRK_MAX_AGGRS planes -- aggregate a of entry i =
+// the VALUE of T's accumulator (aggr_unmap under op_of(a)) for a < n_aggr and i < n, zero elsewhere -- and the aggregate spec word.
+// Every word is written.  T.aggr is read only where a < n_aggr: the table holds no more planes.
+template <class OF>
+__device__ __forceinline__ void write_arow_planes(uint64_t* __restrict__ row, uint32_t n, uint32_t n_aggr, const GroupSelSmem& s, const GroupTable& T, OF op_of, uint64_t aspec) {
+  for (uint32_t a = 0; a < (uint32_t)MRK_MAX_AGGRS; ++a) { // (uniform)
+    uint64_t* __restrict__ plane = row + AROW_AGGR + a * (uint32_t)GROW_GROUPS;
+    if (a < n_aggr) {
+      const uint32_t op = op_of(a);
+      const uint64_t* __restrict__ acc = T.aggr + (uint64_t)a * T.slots;
+      for (uint32_t i = threadIdx.x; i < (uint32_t)GROW_GROUPS; i += WG) plane[i] = i < n ? aggr_unmap(op, acc[s.idx[i]]) : 0ull;
+    } else
+      for (uint32_t i = threadIdx.x; i < (uint32_t)GROW_GROUPS; i += WG) plane[i] = 0ull;
+  }
+  if (threadIdx.x == 0) row[AROW_ASPEC] = aspec;
 }
 
 __global__ __launch_bounds__(WG) void group_select_kernel(GroupSelArgs a) {
@@ -184,6 +205,54 @@ __global__ __launch_bounds__(WG) void pack_grows_kernel(PackGRowsArgs a) {
 void launch_pack_grows(const PackGRowsArgs& a, void* stream) {
   if (!a.n) return;
   hipLaunchKernelGGL(pack_grows_kernel, dim3(a.n), dim3(WG), 0, (hipStream_t)stream, a);
+}
+
+// ---------------------------------------------------------------------------------------
+// a batch's results as AGGREGATE rows (mrk_batch_export_arows): pack_grows_kernel's cases under the decline bit ROWS_AGGR, which a
+// query's aggregates do not set.  A grouped query leaves with all its groups in the QUERY's group order -- by its ordering aggregate
+// where it has one -- and, behind the group row's words, its aggregates' values; one without aggregates with zero planes and
+// aggregate spec 0; a relevance query as in group rows.  The table is the batch's, laid out with the query's grp_naggr planes.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void pack_arows_kernel(PackGRowsArgs a) {
+  __shared__ GroupSelSmem s;
+  const uint32_t q = blockIdx.x;
+  if (q >= a.n) return;
+  const DevQuery* __restrict__ Q = a.queries + q;
+  const bool declined = a.declined && ((a.declined[q] >> ROWS_AGGR) & 1u) != 0u;
+  const uint32_t qf = a.flags ? a.flags[q] : 0u;
+  uint64_t* __restrict__ row = a.rows + (uint64_t)q * AROW_WORDS;
+  const GroupTable none{};
+  auto zero = [](uint32_t) { return 0ull; };
+  auto no_op = [](uint32_t) { return 0u; };
+  if (!declined && Q->grp_on && a.gtab) { // (uniform)
+    const uint32_t K = Q->k ? (Q->k < (uint32_t)KCAP ? Q->k : (uint32_t)KCAP) : 1u;
+    const uint64_t spec = group_spec_word(Q->grp_sort_by, Q->grp_desc, Q->grp_bits, K);
+    const uint32_t n_aggr = Q->grp_naggr < (uint32_t)MRK_MAX_AGGRS ? Q->grp_naggr : (uint32_t)MRK_MAX_AGGRS;
+    const uint32_t ord = n_aggr && Q->grp_order_aggr <= n_aggr ? Q->grp_order_aggr : 0u;
+    const uint64_t aspec = n_aggr ? aggr_spec_word(n_aggr, ord, Q->grp_aggr_op) : 0ull;
+    const GroupTable T = group_table_at(const_cast<uint64_t*>(a.gtab) + Q->grp_off, Q->grp_slots);
+    const uint32_t claimed = *T.claimed;
+    const uint32_t over = claimed > group_limit(K) || claimed > GRP_MAX_GROUPS ? QF_GROUPS : 0u; // (group_select_kernel set it already)
+    if (!row_unflagged(false, qf | over)) {
+      write_grow<AROW_GSPEC>(row, 0u, zero, zero, row_total_word(false, qf | over, 0ull), spec);
+      write_arow_planes(row, 0u, 0u, s, none, no_op, aspec);
+      return;
+    }
+    const uint32_t n = group_compact_sort(s, T, Q->grp_sort_by, Q->grp_desc, ord, ord ? Q->grp_aggr_op[ord - 1u] : 0u);
+    write_grow_groups<AROW_GSPEC>(row, n, s, T, n, spec); // total_found = the number of groups
+    write_arow_planes(
+        row, n, n_aggr, s, T, [&](uint32_t ai) { return Q->grp_aggr_op[ai]; }, aspec);
+    return;
+  }
+  const uint32_t n = !row_unflagged(declined, qf) ? 0u : a.cnt[q] < (uint32_t)KCAP ? a.cnt[q] : (uint32_t)KCAP;
+  write_grow<AROW_GSPEC>(
+      row, n, [&](uint32_t i) { return a.keys[(uint64_t)q * KCAP + i]; }, zero, row_total_word(declined, qf, a.total[q]), 0ull);
+  write_arow_planes(row, 0u, 0u, s, none, no_op, 0ull);
+}
+
+void launch_pack_arows(const PackGRowsArgs& a, void* stream) {
+  if (!a.n) return;
+  hipLaunchKernelGGL(pack_arows_kernel, dim3(a.n), dim3(WG), 0, (hipStream_t)stream, a);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -308,6 +377,138 @@ __global__ __launch_bounds__(WG) void merge_grows_kernel(MergeRowsArgs a, uint64
 void launch_merge_grows(const MergeRowsArgs& a, uint64_t* gtab, uint64_t tab_words, void* stream) {
   if (!a.n_queries) return;
   hipLaunchKernelGGL(merge_grows_kernel, dim3(a.n_queries), dim3(WG), 0, (hipStream_t)stream, a, gtab, tab_words);
+}
+
+// ---------------------------------------------------------------------------------------
+// merge of <= 8 AGGREGATE rows per query: merge_grows_kernel's steps, in a kernel of its own so that merge_grows_kernel stays the
+// code it was.  The lists are read through aggr_row_head; the election is over both spec words (the aggregate spec words of the
+// answering lists must be equal in every bit, "without aggregates" included).  Spec 0: the narrow merge, under zero planes.  Grouped:
+// every entry claims or finds its slot (group_update_slot) and then, per aggregate, updates the slot's accumulator with the MAPPED
+// value (aggr_map under the op word rebuilt from the spec's nibble: a 32-bit MIN maps as ~v over 64 bits and aggr_unmap takes the
+// low dword back; a 32-bit SUM is the low dword of the 64-bit one).  The table is the arena's, zero at launch and tab_words apart,
+// which leaves room for MRK_MAX_AGGRS planes behind group_slots_for(a.k) slots; the planes go from the rows to the table and from
+// the table to the merged row, never through LDS.  The groups leave ordered by the group spec or by the ordering aggregate's merged
+// 32-bit value (group_compact_sort).  The count check, the fence pair and the lists' heads read once into LDS: as above.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void merge_arows_kernel(MergeRowsArgs a, uint64_t* gtab, uint64_t tab_words) {
+  __shared__ GroupSelSmem s;
+  __shared__ unsigned long long sum_in, sum_out;
+  __shared__ uint32_t full, l_cnt[8];
+  const uint32_t q = blockIdx.x, tid = threadIdx.x;
+  if (q >= a.n_queries) return;
+  const uint64_t* __restrict__ rows = a.in_rows + (uint64_t)q * AROW_WORDS;
+  const uint64_t list_words = (uint64_t)a.list_stride * AROW_WORDS;
+  if (a.n_lists > 8u) return; // (the launch's contract; l_cnt holds 8)
+  uint64_t spec = 0, aspec = 0, flags = 0, total = 0, have = 0;
+  bool have_spec = false, mismatch = false;
+  for (uint32_t l = 0; l < a.n_lists; ++l) {
+    uint64_t t, sp, asp; // (uniform) the list's total word and spec words; a hostile list reads as declined and empty
+    const uint32_t c = aggr_row_head(rows + l * list_words, t, sp, asp);
+    if (tid == 0) l_cnt[l] = c;
+    flags |= t & ROW_FLAG_MASK, total += t & ~ROW_FLAG_MASK, have += c < (uint32_t)KCAP ? c : (uint32_t)KCAP;
+    if (!group_row_has_say(t, sp)) continue;
+    if (!have_spec) spec = sp, aspec = asp, have_spec = true;
+    mismatch = mismatch || sp != spec || asp != aspec;
+  }
+  __syncthreads();
+  uint64_t* __restrict__ out = a.out_rows + (uint64_t)(a.out_first + q) * AROW_WORDS;
+  const GroupTable none{};
+  auto zero = [](uint32_t) { return 0ull; };
+  auto no_op = [](uint32_t) { return 0u; };
+  auto finish = [&](uint64_t f) {
+    if (tid == 0 && a.flags_any) {
+      if (f & ROW_RERUN) a.flags_any[0] = 1u;
+      if (f & ROW_DECLINED) a.flags_any[1] = 1u;
+    }
+  };
+  if (mismatch) flags |= ROW_DECLINED;
+  if (spec == 0ull) { // ---- a relevance query: the narrow merge (aspec is 0: the reader lets no aggregate spec stand over group spec 0)
+    uint32_t acc = 0;
+    if (!mismatch)
+      for (uint32_t l = 0; l < a.n_lists; ++l) {
+        uint32_t c = l_cnt[l];
+        if (c > (uint32_t)KCAP) c = KCAP;
+        if (!c) continue;
+        if (acc + c > GRP_MAX_GROUPS) { // the area is full: keep the best KCAP of what it holds
+          __syncthreads();
+          group_sort_desc(s, acc);
+          acc = acc < (uint32_t)KCAP ? acc : (uint32_t)KCAP;
+        }
+        const uint64_t* __restrict__ row = rows + l * list_words;
+        for (uint32_t i = tid; i < c; i += WG) s.key[acc + i] = row[i], s.idx[acc + i] = 0u;
+        acc += c;
+      }
+    __syncthreads();
+    group_sort_desc(s, acc);
+    const uint32_t n = mismatch ? 0u : have < a.k ? (uint32_t)have : a.k;
+    write_grow<AROW_GSPEC>(
+        out, n, [&](uint32_t i) { return s.key[i]; }, zero, (total & ~ROW_FLAG_MASK) | flags, 0ull);
+    write_arow_planes(out, 0u, 0u, s, none, no_op, 0ull);
+    finish(flags);
+    return;
+  }
+  // ---- a grouped query
+  GroupSpec gs;
+  AggrSpec as{0u, 0u};
+  (void)group_spec_unpack(spec, gs); // (an answering list's spec words: aggr_row_head saw them unpack)
+  if (aspec) (void)aggr_spec_unpack(aspec, gs.sort_by, as);
+  const uint32_t n_aggr = as.n < (uint32_t)MRK_MAX_AGGRS ? as.n : (uint32_t)MRK_MAX_AGGRS; // (the planes the arena's stride has room for)
+  const uint32_t ord = as.order <= n_aggr ? as.order : 0u;
+  if (gs.k > a.k) flags |= ROW_DECLINED; // (its table would not fit the arena's stride)
+  uint32_t n = 0;
+  GroupTable T{};
+  if (!flags) { // (uniform)
+    T = group_table_at(gtab + (uint64_t)q * tab_words, group_slots_for(gs.k));
+    if (tid == 0) sum_in = 0ull, sum_out = 0ull, full = 0u;
+    __syncthreads();
+    unsigned long long mine = 0;
+    bool ok = true;
+    for (uint32_t l = 0; l < a.n_lists; ++l) {
+      const uint32_t c = l_cnt[l];
+      const uint64_t* __restrict__ row = rows + l * list_words;
+      for (uint32_t i = tid; i < c; i += WG) {
+        const uint64_t pw = row[GROW_PLANE + i];
+        const uint32_t slot = group_update_slot<GroupDevOps>(T, (uint32_t)(pw >> 32), (uint32_t)pw, row[i]);
+        ok = ok && slot != 0xFFFFFFFFu;
+        mine += (uint32_t)pw;
+        if (slot != 0xFFFFFFFFu)
+          for (uint32_t ai = 0; ai < n_aggr; ++ai) { // (uniform bound)
+            const uint32_t op = aggr_spec_op(aspec, ai);
+            group_aggr_update<GroupDevOps>(T, slot, ai, op, aggr_map(op, row[AROW_AGGR + ai * (uint32_t)GROW_GROUPS + i]));
+          }
+      }
+    }
+    if (mine) atomicAdd(&sum_in, mine);
+    if (!ok) atomicOr(&full, 1u);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const uint32_t claimed = *T.claimed;
+    if (full || claimed > group_limit(gs.k) || claimed > GRP_MAX_GROUPS)
+      flags |= ROW_DECLINED; // one sorter over all the lists would have cut groups by now
+    else {
+      n = group_compact_sort(s, T, gs.sort_by, gs.desc, ord, ord ? aggr_spec_op(aspec, ord - 1u) : 0u);
+      mine = 0;
+      for (uint32_t i = tid; i < n; i += WG) mine += T.counts[s.idx[i]];
+      if (mine) atomicAdd(&sum_out, mine);
+      __syncthreads();
+      if (sum_out != sum_in) flags |= ROW_DECLINED, n = 0; // some group's count passed 2^32 - 1
+    }
+  }
+  if (flags) {
+    write_grow<AROW_GSPEC>(out, 0u, zero, zero, flags, spec);
+    write_arow_planes(out, 0u, 0u, s, none, no_op, aspec);
+  } else {
+    write_grow_groups<AROW_GSPEC>(out, n, s, T, n, spec);
+    write_arow_planes(
+        out, n, n_aggr, s, T, [&](uint32_t ai) { return aggr_spec_op(aspec, ai); }, aspec);
+  }
+  finish(flags);
+}
+
+void launch_merge_arows(const MergeRowsArgs& a, uint64_t* gtab, uint64_t tab_words, void* stream) {
+  if (!a.n_queries) return;
+  hipLaunchKernelGGL(merge_arows_kernel, dim3(a.n_queries), dim3(WG), 0, (hipStream_t)stream, a, gtab, tab_words);
 }
 
 } // namespace mrk

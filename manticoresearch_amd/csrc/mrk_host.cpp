@@ -1479,9 +1479,10 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
     // the queries' decline masks, for every row format whether or not a destination stands: mrk_batch_export_* writes the same rows
     // after the wait
     uint32_t any = 0;
-    // (a query with aggregates leaves declined in GROUP rows too: the row has no room for the accumulators)
+    // (a query with aggregates leaves declined in GROUP rows too: the row has no room for the accumulators.  It travels in AGGREGATE rows)
     for (uint32_t i = 0; i < n; ++i) any |= b->h_decl.p[i] = mrk::query_decline_mask(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order, b->orows_wf_run, b->grouped[i] != 0) |
-                                                    mrk::group_row_decline_bit(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order) | (b->n_aggr[i] ? 1u << ROWS_GROUP : 0u);
+                                                    mrk::group_row_decline_bit(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order) | (b->n_aggr[i] ? 1u << ROWS_GROUP : 0u) |
+                                                    mrk::aggr_row_decline_bit(b->status[i], b->sort_loc[i].bits, b->sort_loc[i].order);
     b->any_declined = any != 0;
     if (any || b->decl_dirty) HIP_TRY(hipMemcpyAsync(b->d_decl.p, b->h_decl.p, n * 4, hipMemcpyHostToDevice, st2));
     b->decl_dirty = any != 0;
@@ -1799,15 +1800,25 @@ static int mrk_batch_record_event_impl(mrk_batch* b, void* hip_event) {
   return MRK_OK;
 }
 
+// the exchange-row formats by kind: the name in the entry points' messages, the row's words, whether its merge runs over group tables
+static const char* row_kind_name(RowKind kind) { return kind == ROWS_AGGR ? "arows" : kind == ROWS_GROUP ? "grows" : kind == ROWS_ORDER ? "orows" : kind == ROWS_WIDE ? "srows" : "rows"; }
+static uint32_t row_kind_words(RowKind kind) {
+  return kind == ROWS_AGGR ? MRK_AROW_WORDS : kind == ROWS_GROUP ? MRK_GROW_WORDS : kind == ROWS_ORDER ? MRK_OROW_WORDS : kind == ROWS_WIDE ? MRK_SROW_WORDS : MRK_ROW_WORDS;
+}
+static bool row_kind_groups(RowKind kind) { return kind == ROWS_GROUP || kind == ROWS_AGGR; }
+
 static int batch_export_rows(mrk_batch* b, uint64_t* dst, RowKind kind) {
-  if (!b || !dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_%s: NULL argument", kind == ROWS_GROUP ? "grows" : kind == ROWS_ORDER ? "orows" : kind == ROWS_WIDE ? "srows" : "rows");
+  if (!b || !dst) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_%s: NULL argument", row_kind_name(kind));
   HIP_TRY(hipSetDevice(b->ctx->device));
-  if (kind == ROWS_GROUP) { // (the tables in d_gtab are the last submit's until the next grouped scan clears them)
-    if (b->in_flight) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_grows: call mrk_batch_wait first");
+  if (row_kind_groups(kind)) { // (the tables in d_gtab are the last submit's until the next grouped scan clears them)
+    if (b->in_flight) return mrk_fail(MRK_E_INVAL, "mrk_batch_export_%s: call mrk_batch_wait first", row_kind_name(kind));
     mrk::PackGRowsArgs pg{};
     pg.queries = b->d_queries.p, pg.gtab = b->any_grouped ? b->d_gtab.p : nullptr, pg.keys = b->d_out_keys.p, pg.cnt = b->d_out_cnt.p, pg.total = b->d_q_total.p;
     pg.rows = dst, pg.flags = b->packed_run ? b->d_q_flags.p : nullptr, pg.declined = b->any_declined ? b->d_decl.p : nullptr, pg.n = b->n_queries;
-    mrk::launch_pack_grows(pg, b->stream);
+    if (kind == ROWS_AGGR)
+      mrk::launch_pack_arows(pg, b->stream);
+    else
+      mrk::launch_pack_grows(pg, b->stream);
   } else
     launch_pack_rows(b, kind, dst, b->n_queries, b->packed_run, false, b->stream); // behind the batch's selection kernels
   HIP_TRY(hipGetLastError());
@@ -1820,9 +1831,12 @@ static int batch_export_rows(mrk_batch* b, uint64_t* dst, RowKind kind) {
 // two workgroups' tables share one), in the context's arena -- grown here, and cleared on the merge stream in front of the kernel.
 // Merges of one context run one after another on that stream, so one arena serves them all; growing it frees the old one, which
 // hipFree does only after the device has drained.
-static uint64_t group_merge_tab_words(uint32_t k) { return (mrk::group_table_words(mrk::group_slots_for(k)) + 15ull) & ~15ull; }
-static int reserve_group_merge(mrk_ctx* ctx, uint32_t n_queries, uint32_t k) {
-  const size_t words = (size_t)group_merge_tab_words(k) * std::max<uint32_t>(n_queries, 1u);
+// An aggregate-row merge cannot know a query's aggregates before it reads the rows: its tables have room for MRK_MAX_AGGRS planes
+// (n_planes); a group-row merge reserves and clears what it always did (n_planes 0).
+static uint32_t row_kind_planes(RowKind kind) { return kind == ROWS_AGGR ? MRK_MAX_AGGRS : 0u; }
+static uint64_t group_merge_tab_words(uint32_t k, uint32_t n_planes) { return (mrk::group_table_words(mrk::group_slots_for(k), n_planes) + 15ull) & ~15ull; }
+static int reserve_group_merge(mrk_ctx* ctx, uint32_t n_queries, uint32_t k, uint32_t n_planes) {
+  const size_t words = (size_t)group_merge_tab_words(k, n_planes) * std::max<uint32_t>(n_queries, 1u);
   if (words > ctx->gmerge_words) {
     if (ctx->gmerge) (void)hipFree(ctx->gmerge);
     ctx->gmerge = nullptr, ctx->gmerge_words = 0;
@@ -1841,8 +1855,10 @@ static void launch_rows_merge(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n
     mrk::MergeRowsArgs mr{};
     mr.in_rows = rows_all, mr.n_lists = n_lists, mr.list_stride = list_stride, mr.n_queries = n_queries, mr.k = k;
     mr.out_rows = out_rows, mr.out_first = out_first, mr.flags_any = flags_any;
-    if (kind == ROWS_GROUP) // (the caller reserved and cleared the arena: reserve_group_merge)
-      mrk::launch_merge_grows(mr, ctx->gmerge, group_merge_tab_words(k), ctx->merge_stream);
+    if (kind == ROWS_AGGR) // (the caller reserved and cleared the arena: reserve_group_merge)
+      mrk::launch_merge_arows(mr, ctx->gmerge, group_merge_tab_words(k, row_kind_planes(kind)), ctx->merge_stream);
+    else if (kind == ROWS_GROUP)
+      mrk::launch_merge_grows(mr, ctx->gmerge, group_merge_tab_words(k, 0u), ctx->merge_stream);
     else
       launch_merge_xrows(kind, mr, ctx->merge_stream);
     return;
@@ -1863,7 +1879,7 @@ static int merge_k_ok(const char* fn, uint32_t k) {
 }
 static int merge_lists_ok(const char* sfx, uint32_t n_lists, RowKind kind) {
   if (kind == ROWS_NARROW || (n_lists != 0 && n_lists <= 8)) return MRK_OK;
-  return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_%s%s: %u lists (1..8)", kind == ROWS_GROUP ? "grows" : kind == ROWS_ORDER ? "orows" : "srows", sfx, n_lists);
+  return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_%s%s: %u lists (1..8)", row_kind_name(kind), sfx, n_lists);
 }
 
 static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
@@ -1872,7 +1888,7 @@ static int mrk_topk_merge_rows_impl(mrk_ctx* ctx, const uint64_t* rows_all, uint
   int rc;
   if ((rc = merge_k_ok("mrk_topk_merge_rows", k)) || (rc = merge_lists_ok("", n_lists, kind))) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
-  if (kind == ROWS_GROUP && (rc = reserve_group_merge(ctx, n_queries, k))) return rc;
+  if (row_kind_groups(kind) && (rc = reserve_group_merge(ctx, n_queries, k, row_kind_planes(kind)))) return rc;
   launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, kind);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->merge_stream));
@@ -1887,8 +1903,8 @@ static int mrk_topk_merge_rows_part_impl(mrk_ctx* ctx, const uint64_t* rows_recv
   if (const int rc = merge_k_ok("mrk_topk_merge_rows_part", k)) return rc;
   if (n_lists == 0 || n_lists > 8 || count > list_stride) return mrk_fail(MRK_E_INVAL, "mrk_topk_merge_rows_part: %u lists (1..8), %u queries of stride %u", n_lists, count, list_stride);
   HIP_TRY(hipSetDevice(ctx->device));
-  if (kind == ROWS_GROUP)
-    if (const int rc = reserve_group_merge(ctx, count, k)) return rc;
+  if (row_kind_groups(kind))
+    if (const int rc = reserve_group_merge(ctx, count, k, row_kind_planes(kind))) return rc;
   launch_rows_merge(ctx, rows_recv, n_lists, list_stride, count, k, out_rows, first, nullptr, kind);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->merge_stream));
@@ -1904,7 +1920,7 @@ static int mrk_topk_merge_rows_async_impl(mrk_ctx* ctx, const uint64_t* rows_all
   HIP_TRY(hipSetDevice(ctx->device));
   if (!ctx->merge_done[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->merge_done[slot], hipEventDisableTiming));
   if (wait_event) HIP_TRY(hipStreamWaitEvent(ctx->merge_stream, (hipEvent_t)wait_event, 0));
-  if (kind == ROWS_GROUP && (rc = reserve_group_merge(ctx, n_queries, k))) return rc;
+  if (row_kind_groups(kind) && (rc = reserve_group_merge(ctx, n_queries, k, row_kind_planes(kind)))) return rc;
   launch_rows_merge(ctx, rows_all, n_lists, n_queries, n_queries, k, out_rows, 0, nullptr, kind);
   HIP_TRY(hipGetLastError());
 
@@ -2226,6 +2242,34 @@ extern "C" int mrk_topk_merge_grows_part(mrk_ctx* ctx, const uint64_t* grows_rec
                                          uint32_t k, uint64_t* out_grows) {
   return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, grows_recv, n_lists, list_stride, first, count, k, out_grows, ROWS_GROUP); });
 }
+extern "C" int mrk_batch_export_arows(mrk_batch* b, uint64_t* arows_dst) {
+  return on_worker(b ? b->ctx : nullptr, [&] { return batch_export_rows(b, arows_dst, ROWS_AGGR); });
+}
+extern "C" int mrk_topk_merge_arows(mrk_ctx* ctx, const uint64_t* arows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k, uint64_t* out_arows) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_impl(ctx, arows_all, n_lists, n_queries, k, out_arows, ROWS_AGGR); });
+}
+extern "C" int mrk_topk_merge_arows_async(mrk_ctx* ctx, const uint64_t* arows_all, uint32_t n_lists, uint32_t n_queries, uint32_t k,
+                                          uint64_t* out_arows, void* wait_event, uint32_t slot) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_async_impl(ctx, arows_all, n_lists, n_queries, k, out_arows, wait_event, slot, ROWS_AGGR); });
+}
+extern "C" int mrk_topk_merge_arows_part(mrk_ctx* ctx, const uint64_t* arows_recv, uint32_t n_lists, uint32_t list_stride, uint32_t first, uint32_t count,
+                                         uint32_t k, uint64_t* out_arows) {
+  return on_worker(ctx, [&] { return mrk_topk_merge_rows_part_impl(ctx, arows_recv, n_lists, list_stride, first, count, k, out_arows, ROWS_AGGR); });
+}
+// (the checks mrk_batch_submit_aggr makes of what the word holds: func, kind, flags, order_by; the locators do not travel)
+extern "C" uint64_t mrk_aggr_spec_word(const mrk_aggrs* aggrs, uint32_t group_sort_by) {
+  if (!aggrs || aggrs->n < 1 || aggrs->n > MRK_MAX_AGGRS || aggrs->order_by < -1 || aggrs->order_by >= aggrs->n || group_sort_by > (uint32_t)MRK_GROUPSORT_WEIGHT) return 0ull;
+  uint32_t ops[MRK_MAX_AGGRS] = {};
+  for (int32_t i = 0; i < aggrs->n; ++i) {
+    const mrk_aggr& g = aggrs->a[i];
+    const bool src64 = g.kind == MRK_SORTKEY_INT64;
+    if (g.func < MRK_AGGR_SUM || g.func > MRK_AGGR_MAX || (g.kind != MRK_SORTKEY_INT && !src64) || (g.flags & ~MRK_AGGR_WIDEN) || (src64 && g.flags)) return 0ull;
+    ops[i] = mrk::aggr_op_word((uint32_t)g.func, 0u, 0u, src64, g.flags != 0);
+  }
+  mrk::AggrSpec as;
+  const uint64_t w = mrk::aggr_spec_word((uint32_t)aggrs->n, (uint32_t)(aggrs->order_by + 1), ops);
+  return mrk::aggr_spec_unpack(w, group_sort_by, as) ? w : 0ull;
+}
 extern "C" uint64_t mrk_group_spec_word(uint32_t sort_by, uint32_t desc, uint32_t bit_count, uint32_t max_matches) {
   mrk::GroupSpec gs;
   const uint64_t w = mrk::group_spec_word(sort_by, desc, bit_count, max_matches);
@@ -2260,11 +2304,12 @@ extern "C" int mrk_comm_allreduce_i64(mrk_ctx* ctx, int64_t* values, uint64_t n)
   if (!ctx || (!values && n)) return mrk_fail(MRK_E_INVAL, "mrk_comm_allreduce_i64: NULL argument");
   return on_worker(ctx, [&] { return mrk_comm_allreduce_i64_impl(ctx, values, n); });
 }
-// one body for narrow rows (MRK_ROW_WORDS), wide ones (MRK_SROW_WORDS), order rows (MRK_OROW_WORDS) and group rows (MRK_GROW_WORDS):
+// one body for narrow rows (MRK_ROW_WORDS), wide ones (MRK_SROW_WORDS), order rows (MRK_OROW_WORDS), group rows (MRK_GROW_WORDS) and
+// aggregate rows (MRK_AROW_WORDS):
 // the row width and the merge kernel are all that differ
 static int shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, uint32_t n_queries, uint32_t k, uint64_t* out_rows, uint32_t slot,
                           RowKind kind) {
-  const uint32_t row_words = kind == ROWS_GROUP ? MRK_GROW_WORDS : kind == ROWS_ORDER ? MRK_OROW_WORDS : kind == ROWS_WIDE ? MRK_SROW_WORDS : MRK_ROW_WORDS;
+  const uint32_t row_words = row_kind_words(kind);
   if (!ctx || !rows || !out_rows) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: NULL argument");
   if (slot >= MRK_MERGE_SLOTS) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: slot %u of %d", slot, MRK_MERGE_SLOTS);
   if (batch && batch->ctx != ctx) return mrk_fail(MRK_E_INVAL, "mrk_shard_exchange: batch and context do not belong together");
@@ -2288,7 +2333,7 @@ static int shard_exchange(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* rows, 
       uint32_t* flags_dev = nullptr;
       HIP_TRY(hipStreamWaitEvent(ctx->merge_stream, gathered, 0));
       if ((rc = mrk_comm_flags_begin(ctx, slot, &flags_dev))) return rc;
-      if (count && kind == ROWS_GROUP && (rc = reserve_group_merge(ctx, count, k))) return rc;
+      if (count && row_kind_groups(kind) && (rc = reserve_group_merge(ctx, count, k, row_kind_planes(kind)))) return rc;
       if (count) launch_rows_merge(ctx, rows_all, (uint32_t)mrk_comm_ranks(ctx), per, count, k, out_rows, first, flags_dev, kind);
       HIP_TRY(hipGetLastError());
       return mrk_comm_flags_finish(ctx, slot);
@@ -2313,6 +2358,10 @@ extern "C" int mrk_shard_exchange_orows(mrk_ctx* ctx, mrk_batch* batch, const ui
 extern "C" int mrk_shard_exchange_grows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* grows, uint32_t n_queries, uint32_t k, uint64_t* out_grows,
                                         uint32_t slot) {
   return shard_exchange(ctx, batch, grows, n_queries, k, out_grows, slot, ROWS_GROUP);
+}
+extern "C" int mrk_shard_exchange_arows(mrk_ctx* ctx, mrk_batch* batch, const uint64_t* arows, uint32_t n_queries, uint32_t k, uint64_t* out_arows,
+                                        uint32_t slot) {
+  return shard_exchange(ctx, batch, arows, n_queries, k, out_arows, slot, ROWS_AGGR);
 }
 extern "C" int mrk_shard_slice(uint32_t n_queries, int n_ranks, int rank, uint32_t* first, uint32_t* count) {
   if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return mrk_fail(MRK_E_INVAL, "mrk_shard_slice: rank %d of %d", rank, n_ranks);

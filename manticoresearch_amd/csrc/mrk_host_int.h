@@ -30,7 +30,7 @@ struct mrk_ctx {
   hipStream_t merge_stream = nullptr; // mrk_topk_merge: never queued behind the scans of a following batch
   hipEvent_t merge_done[MRK_MERGE_SLOTS] = {};
   bool merge_used[MRK_MERGE_SLOTS] = {};
-  uint64_t* gmerge = nullptr;     // group-row merges (mrk_topk_merge_grows*): the scratch arena of their tables, one per query of a call, ...
+  uint64_t* gmerge = nullptr;     // group- and aggregate-row merges (mrk_topk_merge_grows* / _arows*): the scratch arena of their tables, one per query of a call, ...
   size_t gmerge_words = 0;        // ... grown on demand, cleared on merge_stream in front of every merge
   int64_t item_bytes = 128 << 10; // target doclist bytes per work item
   int path = 0;                   // 0 = packed doclists when the segment has them, 1 = VLB (.spd) direct, 2 = packed only
@@ -273,6 +273,11 @@ inline uint32_t query_decline_mask(int status, uint32_t sort_bits, uint32_t orde
 // relevance queries and declines the rest -- a query the planner declined, and a sorted or ordered one.  It implies the narrow bit.
 inline uint32_t group_row_decline_bit(int status, uint32_t sort_bits, uint32_t order) {
   return status != MRK_OK || sort_bits != 0 || order != 0 ? 1u << ROWS_GROUP : 0u;
+}
+// The fifth bit: an AGGREGATE row (MRK_AROW_WORDS) carries what a GROUP row carries and a grouped query's aggregates with it, so a
+// query's aggregates do not set it (the batch ORs the GROUP bit for them; this bit it leaves as this function gives it).
+inline uint32_t aggr_row_decline_bit(int status, uint32_t sort_bits, uint32_t order) {
+  return status != MRK_OK || sort_bits != 0 || order != 0 ? 1u << ROWS_AGGR : 0u;
 }
 
 // Least and largest field-weight sum over the masks of the first nwf (<= 32) fields, the empty mask counting as 1

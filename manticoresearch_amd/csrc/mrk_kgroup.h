@@ -225,6 +225,54 @@ MRK_GHD uint32_t group_row_head(const uint64_t* row, uint64_t& tword, uint64_t& 
 }
 MRK_GHD bool group_row_has_say(uint64_t tword, uint64_t spec) { return !(tword & MRK_ROW_DECLINED) || spec != 0ull; }
 
+// The AGGREGATE row (MRK_AROW_WORDS, include/mrk.h): a GROUP row's first 2 G + 2 words, then MRK_MAX_AGGRS planes of G aggregate
+// VALUES (what aggr_unmap gives: the accumulators' mapping does not travel), the group spec word and the aggregate spec word --
+// what every merger of the query's aggregates must agree on and nothing of where a segment stores the column.  0 = no aggregates.
+//   bit 0 set | bits 1-3 n | bits 4-6 1 + the ordering aggregate (0 = none) | per aggregate a, bits 8 + 4 a ..: func (2 bits) |
+//   the source is a signed 64 | an INT source widened
+constexpr int AROW_WORDS = MRK_AROW_WORDS;
+constexpr int AROW_AGGR = GROW_PLANE + GROW_GROUPS, AROW_GSPEC = AROW_WORDS - 2, AROW_ASPEC = AROW_WORDS - 1; // (plane a: AROW_AGGR + a * GROW_GROUPS)
+struct AggrSpec {
+  uint32_t n, order; // order: 1 + the aggregate whose merged 32-bit value orders the groups, 0 = the group spec's sort_by does
+};
+MRK_GHD uint32_t aggr_spec_nibble(uint32_t op) { return aggr_func(op) | ((op & AGGR_SRC64) ? 4u : 0u) | ((op & AGGR_WIDEN) ? 8u : 0u); }
+// aggregate a's op word from its nibble, shift and bits 0: all that aggr_map / aggr_unmap / group_aggr_update read of it
+MRK_GHD uint32_t aggr_spec_op(uint64_t w, uint32_t a) {
+  const uint32_t nib = (uint32_t)(w >> (8u + 4u * a)) & 15u;
+  return aggr_op_word(nib & 3u, 0u, 0u, (nib & 4u) != 0u, (nib & 8u) != 0u);
+}
+MRK_GHD uint64_t aggr_spec_word(uint32_t n, uint32_t order, const uint32_t* ops) {
+  uint64_t w = 1ull | ((uint64_t)(n & 7u) << 1) | ((uint64_t)(order & 7u) << 4);
+  for (uint32_t a = 0; a < n && a < (uint32_t)MRK_MAX_AGGRS; ++a) w |= (uint64_t)aggr_spec_nibble(ops[a]) << (8u + 4u * a);
+  return w;
+}
+// false: not a word aggr_spec_word writes for a query this library answers next to a group spec with this sort_by -- a stray bit, n out
+// of range, func 0 inside n or a field beyond it, both width bits, an order that names a 64-bit result or no aggregate, an order next
+// to another sort_by
+MRK_GHD bool aggr_spec_unpack(uint64_t w, uint32_t group_sort_by, AggrSpec& s) {
+  s.n = (uint32_t)(w >> 1) & 7u, s.order = (uint32_t)(w >> 4) & 7u;
+  if (!(w & 1ull) || (w >> 24) != 0ull || (w & 0x80ull) || s.n < 1u || s.n > (uint32_t)MRK_MAX_AGGRS || s.order > s.n) return false;
+  for (uint32_t a = 0; a < (uint32_t)MRK_MAX_AGGRS; ++a) {
+    const uint32_t nib = (uint32_t)(w >> (8u + 4u * a)) & 15u;
+    if (a < s.n ? (nib & 3u) == 0u || (nib & 12u) == 12u : nib != 0u) return false;
+  }
+  if (s.order && ((((uint32_t)(w >> (8u + 4u * (s.order - 1u))) & 12u) != 0u) || group_sort_by != (uint32_t)MRK_GROUPSORT_KEY)) return false;
+  return true;
+}
+// The reader of an aggregate row, the only way into one for merge_arows_kernel and tests/cpp/aggr_merge.cpp: group_row_head's
+// contract over both spec words.  Hostile -- more entries than a row holds, a group spec that does not unpack, an aggregate spec that
+// does not unpack next to it or stands over group spec 0 -- reads as MRK_ROW_DECLINED with no entries and both spec words 0, so nothing
+// behind it indexes by an unchecked field.  (group_row_has_say over the group spec word tells whether the list takes part in the election.)
+MRK_GHD uint32_t aggr_row_head(const uint64_t* row, uint64_t& tword, uint64_t& gspec, uint64_t& aspec) {
+  const uint64_t c = row[GROW_CNT], t = row[GROW_TOTAL], gsp = row[AROW_GSPEC], asp = row[AROW_ASPEC];
+  GroupSpec gs;
+  AggrSpec as;
+  const bool hostile = c > (uint64_t)GROW_GROUPS || (gsp != 0ull && !group_spec_unpack(gsp, gs)) || (asp != 0ull && (gsp == 0ull || !aggr_spec_unpack(asp, gs.sort_by, as)));
+  tword = hostile ? (t & MRK_ROW_RERUN) | MRK_ROW_DECLINED : t;
+  gspec = hostile ? 0ull : gsp, aspec = hostile ? 0ull : asp;
+  return hostile ? 0u : (uint32_t)c;
+}
+
 #if defined(__HIPCC__)
 struct GroupDevOps {
   static __device__ uint64_t load64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

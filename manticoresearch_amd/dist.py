@@ -349,9 +349,151 @@ def merge_grows_np(grows_all: np.ndarray, k: int) -> np.ndarray:
     return out
 
 
+# MRK_AROW_WORDS, the aggregate row that carries a grouped query WITH its aggregates (api.Aggr): a group row's first 2 G + 2 words |
+#   MAX_AGGRS planes of GROW_GROUPS aggregate values (plane a at AROW_AGGR + a * GROW_GROUPS) | group spec word | aggregate spec word
+AROW_WORDS = _lib.AROW_WORDS
+AROW_AGGR, AROW_GSPEC, AROW_ASPEC = GROW_PLANE + GROW_GROUPS, AROW_WORDS - 2, AROW_WORDS - 1  # word offsets
+MAX_AGGRS = _lib.MRK_MAX_AGGRS
+_M64, _SIGN = 0xFFFFFFFFFFFFFFFF, 1 << 63
+
+
+def aggr_spec_word(aggrs, order_by: int = -1) -> int:
+    """The aggregate spec word of a grouped query's aggregate row (mrk_kgroup.h, aggr_spec_word): bit 0 set | bits 1-3 n | bits 4-6
+    1 + order_by | per aggregate a, bits 8 + 4 a ..: func (2 bits) | a signed 64-bit source | widened.  0 = no aggregates.
+    aggrs: api.Aggr-like objects (func, kind, widen)."""
+    if not aggrs:
+        return 0
+    w = 1 | ((len(aggrs) & 7) << 1) | (((int(order_by) + 1) & 7) << 4)
+    for a, g in enumerate(aggrs[:MAX_AGGRS]):
+        w |= ((int(g.func) & 3) | (4 if int(g.kind) == 2 else 0) | (8 if g.widen else 0)) << (8 + 4 * a)
+    return w
+
+
+def aggr_spec_unpack(spec: int, group_sort_by: int = 0):
+    """(n, order_by, [(func, signed 64-bit source, widened)] * n) of an aggregate spec word next to a group spec with this sort_by, or
+    None where it is not one the library writes: a stray bit, n outside 1..MAX_AGGRS, func 0 inside n or a nonzero field beyond it,
+    both width bits, an order that names a 64-bit result or an index >= n, an order next to a sort_by other than GROUPSORT_KEY."""
+    spec = int(spec)
+    n, order = (spec >> 1) & 7, (spec >> 4) & 7
+    if not spec & 1 or spec >> 24 or spec & 0x80 or not 1 <= n <= MAX_AGGRS or order > n:
+        return None
+    nibs = [(spec >> (8 + 4 * a)) & 15 for a in range(MAX_AGGRS)]
+    for a, nib in enumerate(nibs):
+        if (nib & 3 == 0 or nib & 12 == 12) if a < n else nib:
+            return None
+    if order and (nibs[order - 1] & 12 or group_sort_by != 0):
+        return None
+    return n, order - 1, [(nib & 3, bool(nib & 4), bool(nib & 8)) for nib in nibs[:n]]
+
+
+def _arow_head(row):
+    """mrk_kgroup.h aggr_row_head: (entries, total word, group spec, aggregate spec); a hostile row reads declined, empty, specs 0"""
+    c, t, gsp, asp = int(row[GROW_CNT]), int(row[GROW_TOTAL]), int(row[AROW_GSPEC]), int(row[AROW_ASPEC])
+    gs = group_spec_unpack(gsp) if gsp else None
+    if c > GROW_GROUPS or (gsp and gs is None) or (asp and (not gsp or aggr_spec_unpack(asp, gs[0]) is None)):
+        return 0, (t & ROW_RERUN) | ROW_DECLINED, 0, 0
+    return c, t, gsp, asp
+
+
+def arow_groups(row: np.ndarray):
+    """An aggregate row's answer -> grow_groups' tuple (head rowid, head weight, group key, @count, total_found) plus the aggregates'
+    values, uint64 (n, n_aggrs): the first min(n, max_matches) entries.  A row without aggregates gives an (n, 0) array."""
+    row = np.asarray(row, dtype=np.uint64)
+    as_group = np.concatenate([row[:AROW_AGGR], row[AROW_GSPEC:AROW_GSPEC + 1]])
+    rowid, weight, gkey, gcnt, total = grow_groups(as_group)
+    asp = int(row[AROW_ASPEC])
+    un = aggr_spec_unpack(asp, (int(row[AROW_GSPEC]) >> 1) & 3) if asp else None
+    n_aggrs = un[0] if un else 0
+    vals = np.stack([row[AROW_AGGR + a * GROW_GROUPS:AROW_AGGR + a * GROW_GROUPS + len(rowid)] for a in range(n_aggrs)], axis=1) if n_aggrs else np.zeros((len(rowid), 0), np.uint64)
+    return rowid, weight, gkey, gcnt, total, vals
+
+
+def merge_arows_np(arows_all: np.ndarray, k: int) -> np.ndarray:
+    """What merge_arows_kernel computes, in numpy, word for word: arows_all uint64 [n_lists, nq, AROW_WORDS] -> [nq, AROW_WORDS].
+    merge_grows_np's rules over both spec words: the election is the group spec's, the answering lists' aggregate spec words must be
+    equal in every bit too ("without aggregates" next to "with" is a mismatch), a hostile list (_arow_head) reads declined under spec
+    words 0.  Per group value counts add, the largest head stays and every aggregate merges as its accumulator does: SUM adds modulo
+    2^64 (a 32-bit result is the low dword), MIN / MAX compare unsigned for INT sources and signed for INT64 ones.  The groups leave
+    by the group spec's order, or by the ordering aggregate's merged 32-bit value in its direction, then by head rowid ascending."""
+    arows_all = np.ascontiguousarray(arows_all, dtype=np.uint64)
+    n_lists, nq, _ = arows_all.shape
+    out = np.zeros((nq, AROW_WORDS), dtype=np.uint64)
+    fmask = ROW_RERUN | ROW_DECLINED
+    for q in range(nq):
+        rows = arows_all[:, q]
+        heads_ = [_arow_head(rows[l]) for l in range(n_lists)]
+        cnt, tw = [h[0] for h in heads_], [h[1] for h in heads_]
+        flags = 0
+        for t in tw:
+            flags |= t & fmask
+        answering = [(h[2], h[3]) for h in heads_ if not h[1] & ROW_DECLINED or h[2]]  # (declined without a spec: no say)
+        spec, aspec = answering[0] if answering else (0, 0)
+        mismatch = any(sa != (spec, aspec) for sa in answering)
+        if mismatch:
+            flags |= ROW_DECLINED
+        out[q, AROW_GSPEC], out[q, AROW_ASPEC] = np.uint64(spec), np.uint64(aspec)
+        if spec == 0:
+            total = sum(t & ~fmask for t in tw) & _M64
+            out[q, GROW_TOTAL] = np.uint64((total & ~fmask) | flags)
+            if mismatch:
+                continue
+            keys = np.concatenate([rows[l, :min(cnt[l], MRK_MAX_K)] for l in range(n_lists)])
+            n = min(len(keys), k)
+            out[q, :n] = np.sort(keys)[::-1][:n]
+            out[q, GROW_CNT] = np.uint64(n)
+            continue
+        sort_by, desc, _bits, kq = group_spec_unpack(spec)
+        n_aggrs, order_by, kinds = aggr_spec_unpack(aspec, sort_by) if aspec else (0, -1, [])
+        if kq > k:
+            flags |= ROW_DECLINED
+        if not flags:
+            heads = np.concatenate([rows[l, :cnt[l]] for l in range(n_lists)])
+            plane = np.concatenate([rows[l, GROW_PLANE:GROW_PLANE + cnt[l]] for l in range(n_lists)])
+            values, inv = np.unique((plane >> np.uint64(32)).astype(np.uint32), return_inverse=True)
+            inv = inv.reshape(-1)
+            counts = np.zeros(len(values), np.uint64)
+            np.add.at(counts, inv, plane & np.uint64(0xFFFFFFFF))
+            head = np.zeros(len(values), np.uint64)
+            np.maximum.at(head, inv, heads)
+            merged = np.zeros((n_aggrs, len(values)), np.uint64)
+            for a, (func, src64, widen) in enumerate(kinds):  # the accumulator's arithmetic (mrk_kgroup.h aggr_map / aggr_unmap) over a zero word
+                at = AROW_AGGR + a * GROW_GROUPS
+                v = np.concatenate([rows[l, at:at + cnt[l]] for l in range(n_lists)])
+                sign = np.uint64(_SIGN if src64 else 0)
+                if func == 1:
+                    np.add.at(merged[a], inv, v)  # (uint64: modulo 2^64)
+                elif func == 3:
+                    np.maximum.at(merged[a], inv, v ^ sign)
+                    merged[a] ^= sign
+                else:
+                    np.maximum.at(merged[a], inv, ~(v ^ sign))
+                    merged[a] = ~merged[a] ^ sign
+                if not (src64 or widen):
+                    merged[a] &= np.uint64(0xFFFFFFFF)
+            if len(values) > GROUPBY_FACTOR * kq or (len(values) and int(counts.max()) > 0xFFFFFFFF):
+                flags |= ROW_DECLINED
+            else:
+                if order_by >= 0:
+                    p = merged[order_by].astype(np.uint32)
+                    okeys = ((p if desc else ~p).astype(np.uint64) << np.uint64(32)) | (head & np.uint64(0xFFFFFFFF))
+                else:
+                    okeys = group_order_keys(sort_by, desc, values, counts.astype(np.uint32), head)
+                order = np.argsort(okeys)[::-1]
+                n = len(values)
+                out[q, :n] = head[order]
+                out[q, GROW_PLANE:GROW_PLANE + n] = (values[order].astype(np.uint64) << np.uint64(32)) | counts[order]
+                for a in range(n_aggrs):
+                    out[q, AROW_AGGR + a * GROW_GROUPS:AROW_AGGR + a * GROW_GROUPS + n] = merged[a][order]
+                out[q, GROW_CNT] = np.uint64(n)
+                out[q, GROW_TOTAL] = np.uint64(n)
+        if flags:
+            out[q, GROW_TOTAL] = np.uint64(flags)
+    return out
+
+
 def exchange_rows(rows):
     """ONE all-gather of [nq, W] result rows -> [world, nq, W] (gloo on CPU tensors, RCCL on device); W = ROW_WORDS, SROW_WORDS,
-    OROW_WORDS or GROW_WORDS: the row width is the tensor's."""
+    OROW_WORDS, GROW_WORDS or AROW_WORDS: the row width is the tensor's."""
     import torch
     import torch.distributed as dist
 
