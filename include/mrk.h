@@ -242,6 +242,40 @@ typedef struct {
   int32_t desc;                  /* 1 = descending */
 } mrk_group;
 
+/* GROUP BY a multi-value attribute (a 32-bit MVA, SPH_ATTR_UINT32SET, in the blob pool): one group per VALUE -- the facet over tags,
+   SELECT ..., COUNT(*) FROM idx WHERE MATCH('...') GROUP BY tags.  The reference: MVAGroupSorter_T::Push (sphinxsort.cpp:4113-4156)
+   calls PushEx(match, value) for every value of the match's MVA, into the same CSphKBufferGroupSorter a row attribute's groups go to.
+   mrk_batch_submit_mva names the attribute as an MVA filter does (mrk_filter: mva_bits, blob_attr_id, n_blob_attrs) next to the
+   query's mrk_group, whose sort_by / desc hold and whose bit_offset / bit_count are ignored.
+   Pushes: a match that reaches the sorter (past dead rows, attribute filters and weight filters; the weight carries index_weight) is
+     pushed once per STORED value of its MVA, into that value's group.  The stored values are neither de-duplicated nor re-sorted: a
+     value stored twice counts twice, as the reference's loop does.  A doc without values joins no group.  An MVA filter on the same
+     attribute decides whether the doc reaches the sorter, not which of its values form groups: all of them do.
+   Per group: the head is the best match by weight DESC, then global rowid ASC; @count is the number of pushes.
+   Result: total_found = the number of groups; the best min(groups, max_matches) of them in the order sort_by / desc name.
+     mrk_result is unchanged: group_key the value, group_count @count, rowid / weight the head's.
+   Limit: more than 4 * max_matches distinct values -- counted over all docs, also when one doc alone carries them -- is declined
+     while the query runs, exactly as for a row attribute (MRK_E_UNSUPPORTED, the message names the limit, MRK_ROW_DECLINED).
+   Ties: the ONE place where the reference's answer is open.  Groups of a row attribute have distinct heads, so (order part, head
+     rowid) is a total order.  One doc may head several groups of an MVA; ordered by @count or by the head's weight, two such groups
+     compare equal in MatchGeneric1_fn, and the reference leaves their order -- and which of them falls off at max_matches -- to its
+     unstable sort and to the order the matches arrived in.  The device's rule: AMONG GROUPS WHOSE ORDER KEY IS EQUAL THE SMALLER GROUP
+     VALUE COMES FIRST, whatever desc says; the same rule decides which group falls off at max_matches, and the merges of group rows
+     apply it too, so sharded == unsharded holds under ties.  (Declining ties would decline the ordinary facet: two rare tags on one
+     doc tie at count 1.)
+   MRK_E_INVAL before a row is read: mva_bits other than 32 / 64, blob_attr_id / n_blob_attrs out of range or not the segment's, rows
+   without a blob locator, an mrk_group_mva without an mrk_group, and the group's unknown sort_by / desc.  MRK_E_UNSUPPORTED per query:
+   mva_bits == 64 (the group key has 32 bits), a segment without a blob pool (never set, or dropped by a later mrk_segment_set_attrs),
+   aggregates next to it (the accumulators would need a slot per pushed value), and everything that declines a group.  GROUP N BY and
+   JSON arrays are out of scope.
+   Exchange rows: the query leaves in GROUP rows under the spec word of a 32-bit key and is merged as every grouped query is -- counts
+   add per value, the better head wins; the other four row kinds decline it. */
+typedef struct {
+  int32_t mva_bits;     /* 32 (64: declined) */
+  int32_t blob_attr_id; /* which of the row's blob attributes */
+  int32_t n_blob_attrs; /* how many the row has: the segment's mrk_segment_set_blobs */
+} mrk_group_mva;
+
 /* Aggregates of a grouped query: SUM / MIN / MAX of one integer row attribute over the group's matches that reached the sorter --
    the set @count counts.  The reference's grouping sorter carries a list of aggregate functions next to the counter (m_dAggregates,
    sphinxsort.cpp:2608-2693) and updates them on every push (AggrSum_t / AggrMin_t / AggrMax_t, :1902-1979).  Typing, as the
@@ -496,6 +530,10 @@ int mrk_batch_submit_grouped(mrk_batch* b, mrk_segment* seg, const mrk_query* qu
 /* ... and with aggregates per grouped query (mrk_aggrs, above): aggrs[i] == NULL = query i has none; aggrs == NULL =
    mrk_batch_submit_grouped.  Aggregates without a group are MRK_E_INVAL */
 int mrk_batch_submit_aggr(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, const mrk_aggrs* const* aggrs, uint32_t n_queries);
+/* ... and with a multi-value group attribute per grouped query (mrk_group_mva, above): mvas[i] == NULL = query i as before; mvas ==
+   NULL = mrk_batch_submit_aggr.  mvas[i] without groups[i] is MRK_E_INVAL */
+int mrk_batch_submit_mva(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, const mrk_aggrs* const* aggrs,
+                         const mrk_group_mva* const* mvas, uint32_t n_queries);
 /* The aggregates of query i's returned rows, after mrk_batch_wait: *values = n x *n_aggrs words, row-major, in the order of the result's
    rows (mrk_batch_result); a 32-bit result zero-extended, a 64-bit one the integer's bits.  NULL / 0 for every query without
    aggregates and for a failed one.  Valid until the batch is resubmitted or destroyed */

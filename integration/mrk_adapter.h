@@ -37,13 +37,14 @@
 // items besides @count / @groupby, no m_iGroupbyLimit (one head per group), the within-group order left at relevance
 // (m_sSortBy "@weight desc" / SPH_SORT_RELEVANCE) and m_sGroupSortBy one of "@groupby" / "@count" / "@weight" (weight()) asc or
 // desc -- exact while the query has at most 4 * max_matches distinct groups, declined (MRK_E_UNSUPPORTED) beyond.  Those are the
-// settings MrkEligible COULD pass.  It does not yet: the frame replay feeds rows to the reference's own sorter and a grouping sorter
+// settings MrkEligible COULD pass -- and, with mrk_group_mva / mrk_batch_submit_mva, the same settings over m_sGroupBy naming a 32-bit MVA
+// (SPH_ATTR_UINT32SET: MVAGroupSorter_T, one PushEx per value of the match's MVA; a bigint MVA stays on the CPU).  It does not yet: the frame replay feeds rows to the reference's own sorter and a grouping sorter
 // needs every match, not one head per group, so a grouped query needs a result path of its own (rows from mrk_result.group_key /
 // group_count straight into the result set).  For an index of several chunks that path starts from GROUP rows (MRK_GROW_WORDS):
 // mrk_batch_export_grows after each chunk's mrk_batch_wait, one mrk_topk_merge_grows over the chunks' rows where QueryDiskChunks
 // folds the chunks' sorters together (mrk_shard_exchange_grows across shards) -- the merged row holds what ONE grouping sorter over
 // all chunks holds before it cuts, or MRK_ROW_DECLINED past 4 * max_matches groups.  Until that exists MrkEligible declines every sorter with IsGroupby(), as before, and
-// all other group settings (group functions over time, MVA and JSON keys, DISTINCT, aggregates, GROUP n BY, WITHIN GROUP ORDER BY)
+// all other group settings (group functions over time, bigint MVA and JSON keys, DISTINCT, aggregates, GROUP n BY, WITHIN GROUP ORDER BY)
 // stay on the CPU for good reasons of their own.
 #pragma once
 

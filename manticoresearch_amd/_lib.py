@@ -80,6 +80,11 @@ class Group(C.Structure):  # mrk_group
 
 GROUPSORT_KEY, GROUPSORT_COUNT, GROUPSORT_WEIGHT = 0, 1, 2  # MRK_GROUPSORT_*
 
+
+class GroupMva(C.Structure):  # mrk_group_mva
+    _fields_ = [("mva_bits", C.c_int32), ("blob_attr_id", C.c_int32), ("n_blob_attrs", C.c_int32)]
+
+
 AGGR_SUM, AGGR_MIN, AGGR_MAX = 1, 2, 3  # MRK_AGGR_*
 AGGR_WIDEN = 1                          # MRK_AGGR_WIDEN (mrk_aggr.flags)
 MRK_MAX_AGGRS = 4
@@ -183,6 +188,8 @@ SYMBOLS = [
     ("mrk_batch_submit", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Query), C.c_uint32]),
     ("mrk_batch_submit_grouped", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Query), C.POINTER(C.POINTER(Group)), C.c_uint32]),
     ("mrk_batch_submit_aggr", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Query), C.POINTER(C.POINTER(Group)), C.POINTER(C.POINTER(Aggrs)), C.c_uint32]),
+    ("mrk_batch_submit_mva", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Query), C.POINTER(C.POINTER(Group)), C.POINTER(C.POINTER(Aggrs)), C.POINTER(C.POINTER(GroupMva)),
+                                       C.c_uint32]),
     ("mrk_batch_result_aggrs", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int32)]),
     ("mrk_batch_wait", C.c_int, [C.c_void_p]),
     ("mrk_batch_test", C.c_int, [C.c_void_p]),

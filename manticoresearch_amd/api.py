@@ -378,11 +378,17 @@ class Group:
     """GROUP BY one integer row attribute (mrk_group, include/mrk.h): groupfunc = attr.  The head of a group is its best match by
     relevance (weight DESC, rowid ASC), @count its matches; the groups leave ordered by sort_by (GROUPSORT_KEY = the group value,
     GROUPSORT_COUNT, GROUPSORT_WEIGHT = the head's weight), desc or asc, then the head's rowid ascending.  Answered exactly for up
-    to 4 * max_matches distinct values; beyond that the query is declined (status MRK_E_UNSUPPORTED)."""
+    to 4 * max_matches distinct values; beyond that the query is declined (status MRK_E_UNSUPPORTED).
+    mva_bits != 0: GROUP BY a multi-value attribute in the blob pool instead (mrk_group_mva; named as Filter names an MVA: mva_bits = 32,
+    blob_attr_id of n_blob_attrs) -- one group per stored value of a match's MVA, duplicates counted; bit_offset / bit_count are ignored.
+    Groups whose order key is equal (one doc heads several of them) leave with the smaller group value first."""
     bit_offset: int
     bit_count: int
     sort_by: int = GROUPSORT_KEY
     desc: bool = True
+    mva_bits: int = 0
+    blob_attr_id: int = 0
+    n_blob_attrs: int = 0
 
 
 AGGR_SUM, AGGR_MIN, AGGR_MAX = _lib.AGGR_SUM, _lib.AGGR_MIN, _lib.AGGR_MAX  # MRK_AGGR_*
@@ -437,6 +443,9 @@ class _CQueries:
         self.aggrs = (C.POINTER(_lib.Aggrs) * max(1, len(queries)))() if any(q.aggrs is not None for q in queries) else None
         if self.aggrs is not None and self.groups is None:
             self.groups = (C.POINTER(_lib.Group) * max(1, len(queries)))()
+        # ... and the fourth, of multi-value group attributes, only when some group names one: every other list of queries is submitted by the
+        # call it always was
+        self.mvas = (C.POINTER(_lib.GroupMva) * max(1, len(queries)))() if any(q.group is not None and q.group.mva_bits for q in queries) else None
         for qi, q in enumerate(queries):
             nodes: List[XQNode] = []
             kids_of: List[List[int]] = []
@@ -520,6 +529,10 @@ class _CQueries:
                 cg = _lib.Group(int(q.group.bit_offset), int(q.group.bit_count), int(q.group.sort_by), int(desc))
                 self.groups[qi] = C.pointer(cg)
                 self.keep.append(cg)
+                if q.group.mva_bits:
+                    cm = _lib.GroupMva(int(q.group.mva_bits), int(q.group.blob_attr_id), int(q.group.n_blob_attrs))
+                    self.mvas[qi] = C.pointer(cm)
+                    self.keep.append(cm)
             if q.aggrs is not None:
                 ca = _lib.Aggrs()
                 ca.n, ca.order_by = len(q.aggrs), int(q.aggr_order)  # (more than MAX_AGGRS, or none: n says so and the library refuses)
@@ -705,7 +718,9 @@ class Batch:
         self._submit(seg, self._cq, self._n)
 
     def _submit(self, seg: Segment, cq: "_CQueries", n: int) -> None:
-        if cq.aggrs is not None:
+        if getattr(cq, "mvas", None) is not None:
+            check(lib().mrk_batch_submit_mva(self._h, seg._h, cq.arr, cq.groups, cq.aggrs, cq.mvas, n))
+        elif cq.aggrs is not None:
             check(lib().mrk_batch_submit_aggr(self._h, seg._h, cq.arr, cq.groups, cq.aggrs, n))
         elif cq.groups is not None:
             check(lib().mrk_batch_submit_grouped(self._h, seg._h, cq.arr, cq.groups, n))

@@ -301,7 +301,8 @@ struct DevQuery {
   uint32_t grp_item, grp_shift, grp_bits; // the group-by attribute: dword of the row, bit offset inside it, width
   uint32_t grp_sort_by, grp_desc;         // MRK_GROUPSORT_*, 1 = descending: the groups' order (group_select_kernel)
   uint32_t grp_slots;                     // slots of the table, a power of two >= 2 * (4 k + 1) ...
-  uint32_t grp_pad;
+  uint32_t grp_pad;                       // the MVA word of a query grouped by a multi-value attribute (mrk_group_mva; coded as DevFilter::mva: width |
+                                          // blob attribute id << 16 | blob attributes of the row << 24); 0 = a row attribute.  grp_item / shift / bits are 0 / 0 / 32 then
   uint64_t grp_off;                       // ... and its offset in ScanArgs::gtab, in u64 words
   // ... with aggregates (mrk_aggrs, mrk_kgroup.h): grp_naggr u64 accumulator planes behind the table's counts.  All zero otherwise
   uint32_t grp_naggr;
@@ -412,7 +413,8 @@ struct ScanArgs {
   uint64_t* scand;          // candidates of the batch's sorted queries: [2 * i] = hi, [2 * i + 1] = lo (mrk_sortkey.h); NULL = the batch holds none
   uint64_t* gtab;           // group tables of the batch's grouped queries (mrk_kgroup.h), DevQuery::grp_off words in; NULL = the batch holds none
                             // (a batch with grouped queries has scand set too: the update lives in the instances that carry the sort)
-  uint32_t grp_aggr;        // the batch holds a grouped query with aggregates (DevQuery::grp_naggr): the sort instances with the accumulators' flush
+  uint32_t grp_aggr;        // the batch holds a grouped query whose flush reads the rows again -- aggregates (DevQuery::grp_naggr) or a multi-value group
+                            // (DevQuery::grp_pad): the sort instances with those flushes (the AGGR template flag)
   uint32_t grp_aggr_pad;
 };
 

@@ -12,7 +12,8 @@
 // A query with aggregates (mrk_aggrs) may order its groups by an aggregate's 32-bit value in the place of that part, and the best k
 // rows' aggregates leave next to them, the accumulators' mapping undone.
 // 4096 x (8-byte key + 4-byte slot index) = 48 KB of the 64 KB static LDS.  Slots are compacted in whatever order the atomics fall;
-// the order keys are distinct (heads are distinct rows), so the sorted result is the same from run to run.
+// the order keys of a row attribute's groups are distinct (heads are distinct rows), and equal keys -- groups of a multi-value
+// attribute that one doc heads -- leave by the smaller group value (group_sort_desc), so the sorted result is the same from run to run.
 // The same compaction and sort (group_compact_sort) serve the GROUP rows further down: pack_grows_kernel writes all the groups of a
 // query's table as its exchange row, merge_grows_kernel adds up to 8 such rows into one table and writes the merged row.
 // The AGGREGATE rows behind them carry a query's aggregates too: pack_arows_kernel writes the groups with their aggregates' values,
@@ -30,9 +31,13 @@ struct __align__(16) GroupSelSmem {
   uint32_t n;
 };
 
-// s.key / s.idx [0, n), n <= GRP_MAX_GROUPS, sorted descending by (key, the lower idx first), by the whole workgroup.  The entries are
-// written and the workgroup in step when it is called; it ends behind a barrier.
-__device__ __forceinline__ void group_sort_desc(GroupSelSmem& s, uint32_t n) {
+// s.key / s.idx [0, n), n <= GRP_MAX_GROUPS, sorted by the whole workgroup: key descending; among equal keys the SMALLER GROUP VALUE
+// first, read from tkeys[idx] (the table's key plane) on that rare branch; padding last.  Equal keys of real entries occur only
+// between groups of a multi-value attribute that one doc heads (include/mrk.h, mrk_group_mva): the reference leaves their order
+// open, and the table slot -- which depends on the hash and on who won a claim -- must not decide it.  tkeys == NULL (the narrow
+// merge of relevance keys, whose idx are all 0): equal keys stay in either order, they are the same word.  The entries are written
+// and the workgroup in step when it is called; it ends behind a barrier.
+__device__ __forceinline__ void group_sort_desc(GroupSelSmem& s, uint32_t n, const uint64_t* __restrict__ tkeys = nullptr) {
   const uint32_t tid = threadIdx.x;
   uint32_t len = 64;
   while (len < n) len <<= 1;
@@ -45,7 +50,9 @@ __device__ __forceinline__ void group_sort_desc(GroupSelSmem& s, uint32_t n) {
         const bool down = (i & k) == 0;
         const uint64_t ak = s.key[i], bk = s.key[p];
         const uint32_t ai = s.idx[i], bi = s.idx[p];
-        const bool b_gt = bk > ak || (bk == ak && bi < ai);
+        bool b_gt = bk > ak;
+        if (bk == ak) // (padding's idx is the largest: it loses to every real entry, whose values are read only when both are real)
+          b_gt = tkeys && ai != 0xFFFFFFFFu && bi != 0xFFFFFFFFu ? (uint32_t)tkeys[bi] < (uint32_t)tkeys[ai] : bi < ai;
         if (b_gt == down) s.key[i] = bk, s.idx[i] = bi, s.key[p] = ak, s.idx[p] = ai;
       }
       __syncthreads();
@@ -73,7 +80,7 @@ __device__ __forceinline__ uint32_t group_compact_sort(GroupSelSmem& s, const Gr
   }
   __syncthreads();
   const uint32_t n = s.n < GRP_MAX_GROUPS ? s.n : GRP_MAX_GROUPS;
-  group_sort_desc(s, n);
+  group_sort_desc(s, n, T.keys);
   return n;
 }
 

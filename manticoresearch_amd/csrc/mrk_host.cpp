@@ -1073,7 +1073,8 @@ static int launch_gen_rank(mrk::ScanArgs& sa, bool nearn, hipStream_t st) {
   return MRK_OK;
 }
 
-static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups = nullptr, const mrk_aggrs* const* aggrs = nullptr);
+static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups = nullptr, const mrk_aggrs* const* aggrs = nullptr,
+                                 const mrk_group_mva* const* mvas = nullptr);
 static int mrk_batch_wait_impl(mrk_batch* b);
 static int mrk_batch_result_impl(mrk_batch* b, uint32_t q, mrk_result* out);
 
@@ -1147,15 +1148,16 @@ static int bind_sorted(mrk_batch* b, uint32_t n, bool prox, mrk::ScanArgs& sa, h
 // ... and its grouped queries: the arena of their tables (`words` u64), cleared on st in front of the scan -- every submit, and the
 // rerun of one query, starts from empty tables: a rerun over the submit's table would double its counts.  The rows' value and count
 // planes come with it; aggr: the scan holds a query with aggregates -- the rows' value plane and its pinned mirror too (the
-// accumulators are part of the tables: `words` counts them, and the one memset clears them)
-static int bind_groups(mrk_batch* b, uint64_t words, bool aggr, mrk::ScanArgs& sa, hipStream_t st) {
+// accumulators are part of the tables: `words` counts them, and the one memset clears them); mva: the scan holds a query grouped by a
+// multi-value attribute -- with either, the scan and rank instances whose flush reads the rows again (ScanArgs::grp_aggr)
+static int bind_groups(mrk_batch* b, uint64_t words, bool aggr, bool mva, mrk::ScanArgs& sa, hipStream_t st) {
   int rc;
   const size_t rows = (size_t)b->max_queries * KCAP;
   if ((rc = b->d_gtab.reserve(words)) || (rc = b->d_out_gkey.reserve(rows)) || (rc = b->d_out_gcnt.reserve(rows)) || (rc = b->h_gkey.reserve(rows)) || (rc = b->h_gcnt.reserve(rows))) return rc;
   if (aggr && ((rc = b->d_out_aggr.reserve(rows * MRK_MAX_AGGRS)) || (rc = b->h_aggr.reserve(rows * MRK_MAX_AGGRS)))) return rc;
   HIP_TRY(hipMemsetAsync(b->d_gtab.p, 0, words * 8, st));
   sa.gtab = b->d_gtab.p;
-  sa.grp_aggr = aggr ? 1u : 0u;
+  sa.grp_aggr = aggr || mva ? 1u : 0u;
   return MRK_OK;
 }
 
@@ -1271,7 +1273,8 @@ static void launch_pack_rows(const mrk_batch* b, RowKind kind, uint64_t* rows, u
   launch_pack_xrows(kind, pa, st);
 }
 
-static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups, const mrk_aggrs* const* aggrs) {
+static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, uint32_t n, const mrk_group* const* groups, const mrk_aggrs* const* aggrs,
+                                 const mrk_group_mva* const* mvas) {
   if (!b || !seg || (!queries && n)) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: NULL argument");
   if (n > b->max_queries) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: %u queries > batch capacity %u", n, b->max_queries);
   if (seg->ctx != b->ctx) return mrk_fail(MRK_E_INVAL, "mrk_batch_submit: segment and batch belong to different contexts");
@@ -1303,12 +1306,14 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   uint32_t max_terms = 1;
   bool any_ext = false; // position modifiers, BEFORE, attribute filters
   bool any_aggr = false; // a grouped query with aggregates
+  bool any_mva = false;  // a query grouped by a multi-value attribute
   if (b->ctx->path == 2 && !seg->has_packed) return mrk_fail(MRK_E_UNSUPPORTED, "path=packed but the segment has no packed doclists");
   const bool use_packed = seg->has_packed && b->ctx->path != 1;
   for (uint32_t i = 0; i < n; ++i) {
     const mrk::BatchPlan::Mark before = plan.mark();
     const mrk_group* group = groups ? groups[i] : nullptr;
-    int rc = plan_query(seg, queries[i], b->ctx->item_bytes, use_packed, b->h_queries.p[i], n, i, plan, rowid_max.empty() || group ? 0xFFFFFFFFu : rowid_max[i], group, aggrs ? aggrs[i] : nullptr);
+    int rc = plan_query(seg, queries[i], b->ctx->item_bytes, use_packed, b->h_queries.p[i], n, i, plan, rowid_max.empty() || group ? 0xFFFFFFFFu : rowid_max[i], group, aggrs ? aggrs[i] : nullptr,
+                        mvas ? mvas[i] : nullptr);
     b->status[i] = rc;
     if (rc == MRK_E_INVAL) return rc;
     if (rc != MRK_OK) { // unsupported: reported per query, runs no device work
@@ -1318,10 +1323,12 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
       b->h_queries.p[i].sort_on = 0;
       b->h_queries.p[i].grp_on = 0;
       b->h_queries.p[i].grp_naggr = 0;
+      b->h_queries.p[i].grp_pad = 0;
     }
     b->grouped[i] = rc == MRK_OK && b->h_queries.p[i].grp_on != 0;
     b->n_aggr[i] = b->grouped[i] ? (uint8_t)b->h_queries.p[i].grp_naggr : 0;
     any_aggr = any_aggr || b->n_aggr[i] != 0;
+    any_mva = any_mva || (b->grouped[i] && b->h_queries.p[i].grp_pad != 0);
     max_terms = std::max(max_terms, b->h_queries.p[i].n_terms);
     any_ext = any_ext || (b->h_queries.p[i].tree_flags & (mrk::TF_TERMPOS | mrk::TF_ORDER | mrk::TF_PHRASE_LEAF | mrk::TF_NOTNEAR)) != 0 || b->h_queries.p[i].n_filters != 0 || b->h_queries.p[i].n_wfilters != 0 ||
               b->h_queries.p[i].rowid_max != 0xFFFFFFFFu || b->h_queries.p[i].sort_on != 0 || b->h_queries.p[i].grp_on != 0;
@@ -1420,7 +1427,7 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   bind_scan(b, seg, sa);
   sa.n_items = (uint32_t)n_items; // (the VLB path's one launch; launch_packed sets its sections')
   if (shape.sort && (rc = bind_sorted(b, n, shape.prox, sa, st))) return rc;
-  if (shape.group && (rc = bind_groups(b, plan.group_total, b->any_aggr, sa, st))) return rc;
+  if (shape.group && (rc = bind_groups(b, plan.group_total, b->any_aggr, any_mva, sa, st))) return rc;
   // (submit only: the weight bounds' buffers -- a rerun's list holds every doc its drivers can deliver, it runs without this pruning)
   if (use_packed && shape.prox && b->ctx->prox_prune) { // pruning in front of the hit pass (mrk_kprune.h, prox_bounds)
     const size_t words = (size_t)n * (2 * NBINS + mrk::QSTRIDE);
@@ -1580,7 +1587,7 @@ static int rerun_overflowed(mrk_batch* b, uint32_t qi) {
   if (shape.sort && (rc = bind_sorted(r, 1, shape.prox, sa, st))) return rc;
   const uint32_t n_aggr = grouped ? passes[0].grp_naggr : 0u; // (the accumulators ride behind the table: cleared with it, copied back with it)
   r->any_aggr = n_aggr != 0;
-  if (grouped && (rc = bind_groups(r, mrk::group_table_words(passes[0].grp_slots, n_aggr), n_aggr != 0, sa, st))) return rc;
+  if (grouped && (rc = bind_groups(r, mrk::group_table_words(passes[0].grp_slots, n_aggr), n_aggr != 0, grouped && passes[0].grp_pad != 0, sa, st))) return rc;
   // match queues for every doc a pass can match (no cap: this run must not overflow), every pass charged the whole rerun's items
   uint64_t chunks[3] = {0, 0, 0};
   for (const DevQuery& P : passes) {
@@ -2130,6 +2137,10 @@ extern "C" int mrk_batch_submit_grouped(mrk_batch* b, mrk_segment* seg, const mr
 }
 extern "C" int mrk_batch_submit_aggr(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, const mrk_aggrs* const* aggrs, uint32_t n) {
   return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_submit_impl(b, seg, queries, n, groups, aggrs); });
+}
+extern "C" int mrk_batch_submit_mva(mrk_batch* b, mrk_segment* seg, const mrk_query* queries, const mrk_group* const* groups, const mrk_aggrs* const* aggrs,
+                                    const mrk_group_mva* const* mvas, uint32_t n) {
+  return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_submit_impl(b, seg, queries, n, groups, aggrs, mvas); });
 }
 extern "C" int mrk_batch_result_aggrs(mrk_batch* b, uint32_t i, const uint64_t** values, int32_t* n_aggrs) {
   return on_worker(b ? b->ctx : nullptr, [&] { return mrk_batch_result_aggrs_impl(b, i, values, n_aggrs); });

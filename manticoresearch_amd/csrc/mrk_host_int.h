@@ -160,8 +160,11 @@ struct BatchPlan {
 // query gets a table of plan.group_total's arena instead of a candidate list (DevQuery::grp_*; all zero for every other query).
 // aggrs: the grouped query's mrk_aggrs (mrk_batch_submit_aggr) or NULL -- its table gets one accumulator plane per aggregate behind the
 // counts (DevQuery::grp_naggr, grp_aggr_*, grp_order_aggr); a query without them plans word for word as without the argument.
+// mva: the grouped query's mrk_group_mva (mrk_batch_submit_mva) or NULL -- the group's values are a multi-value attribute's
+// (DevQuery::grp_pad, the MVA word; grp_item / grp_shift / grp_bits 0 / 0 / 32); the table, the routing and the rerun are a group's.
 int plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
-               BatchPlan& plan, uint32_t rowid_max = 0xFFFFFFFFu, const mrk_group* group = nullptr, const mrk_aggrs* aggrs = nullptr);
+               BatchPlan& plan, uint32_t rowid_max = 0xFFFFFFFFu, const mrk_group* group = nullptr, const mrk_aggrs* aggrs = nullptr,
+               const mrk_group_mva* mva = nullptr);
 
 // Groups of a batch's scan_bm queries for the grouped bitmap kernel ("bm_group", mrk_batch_submit).  A member names its two
 // keywords (key: bitmap offset + idf bits, so that members sharing a key share its tfidf table too), the bytes a walk of each

@@ -1,4 +1,5 @@
-// mrk_kgroup.h -- GROUP BY one integer row attribute: the per-query group table and its update.
+// mrk_kgroup.h -- GROUP BY one integer row attribute, or one 32-bit multi-value attribute (a group per value: blob_mva_span and
+// group_flush_wave_mva below): the per-query group table and its update.
 //
 // Stands in for CSphKBufferGroupSorter (sphinxsort.cpp:2961-3310) while it has not cut: PushEx (:3148-3205) finds the match's group
 // in a hash of group keys; a new group gets the match as its head and a count of 1 (++m_iTotal), an existing one
@@ -179,8 +180,35 @@ MRK_GHD bool group_update(const GroupTable& T, uint32_t value, uint32_t count, u
   return true;
 }
 
+// ---- GROUP BY a multi-value attribute (mrk_group_mva, include/mrk.h; MVAGroupSorter_T::Push, sphinxsort.cpp:4113-4156): a match is
+// pushed once per STORED value of its MVA, in the stored order and with every duplicate.  The MVA word (DevQuery::grp_pad) is coded as
+// DevFilter::mva is: width in bits | blob attribute id << 16 | blob attributes of the row << 24.
+// blob_mva_span: where the values of a row's MVA lie in the pool, with row_passes_filters' arithmetic (mrk_dev.h; the blob row of
+// attribute.cpp:495-513: length-size byte, n_blob cumulative lengths, data).  Every blob row was bounds-checked at load
+// (mrk_blobrow.h), so nothing here is checked again.  The data is not aligned: the header and the values are read byte-wise.
+struct MvaSpan {
+  const uint8_t* data;
+  uint32_t n; // values of the MVA's width
+};
+MRK_GHD uint32_t group_mva_word(uint32_t bits, uint32_t blob_attr_id, uint32_t n_blob_attrs) { return (bits & 0xffu) | ((blob_attr_id & 0xffu) << 16) | (n_blob_attrs << 24); }
+MRK_GHD uint64_t blob_read_le(const uint8_t* p, uint32_t nb) {
+  uint64_t x = 0;
+  for (uint32_t i = 0; i < nb; ++i) x |= (uint64_t)p[i] << (8u * i);
+  return x;
+}
+MRK_GHD MvaSpan blob_mva_span(const uint8_t* blobs, const uint32_t* row, uint32_t mva) {
+  const uint32_t w = (mva & 0xffu) >> 3, id = (mva >> 16) & 0xffu, nblob = mva >> 24;
+  const uint8_t* br = blobs + ((uint64_t)row[2] | ((uint64_t)row[3] << 32)); // sphGetBlobRowOffset: the 2nd attribute
+  const uint32_t sz = br[0] == 0 ? 1u : br[0] == 1 ? 2u : 4u;
+  const uint64_t l1 = blob_read_le(br + 1 + id * sz, sz), l0 = id ? blob_read_le(br + 1 + (id - 1u) * sz, sz) : 0ull;
+  return MvaSpan{br + 1 + (uint64_t)nblob * sz + l0, w ? (uint32_t)((l1 - l0) / w) : 0u};
+}
+MRK_GHD uint32_t blob_mva_value32(const MvaSpan& s, uint32_t i) { return (uint32_t)blob_read_le(s.data + 4ull * i, 4u); }
+
 // The groups' order (MatchGeneric1_fn, sphinxsort.cpp:4708-4720): one of group value / count / head weight, ascending or
-// descending, then the head's global rowid ascending.  Larger = better; heads are distinct rows, so no two groups tie.
+// descending, then the head's global rowid ascending.  Larger = better.  Heads of a row attribute's groups are distinct rows, so no
+// two of them tie; one doc may head several groups of a multi-value attribute, and groups whose keys are equal leave with the
+// smaller group value first (group_sort_desc, mrk_groupsel.hip; include/mrk.h has the why).
 MRK_GHD uint64_t group_order_key(uint32_t sort_by, uint32_t desc, uint32_t value, uint32_t count, uint64_t head) {
   const uint32_t p = sort_by == MRK_GROUPSORT_COUNT ? count : sort_by == MRK_GROUPSORT_KEY ? value : (uint32_t)(head >> 32);
   return ((uint64_t)(desc ? p : ~p) << 32) | (uint32_t)head;
@@ -453,6 +481,66 @@ __device__ __forceinline__ bool group_flush_wave_aggr(const GroupTable& T, uint6
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   return all_ok;
+}
+
+// ---- the flush of a query grouped by a MULTI-VALUE attribute (the MVA word, DevQuery::grp_pad: see blob_mva_span).  Chosen by a
+// uniform branch on that word where the kernels publish, in the AGGR instances only -- the flag means "the flush reads the rows
+// again" -- so that every other instance stays as it is.  cbuf holds the matches' keys; what the scan buffered in cbuf2 is ignored.
+// Steps: every lane takes the keys of its <= 2 entries into registers (from here on the two buffers are free: no key is read from
+// LDS again, so nothing unread is ever overwritten) and finds their MVAs' spans in the pool, row = key_rowid(key) - rowid_base; a
+// wave prefix sum of the value counts numbers the expanded (key, value) pairs, entries in buffer order and values in stored order;
+// then, in rounds of up to 128 pairs, the lanes write their pairs of the round into the buffers and group_flush_wave takes the
+// round to the table as it takes a row attribute's buffer -- equal values combined to one count and one head, one lane per distinct
+// value in group_update, so a hot tag costs one atomic per round and not one per match.  A doc with more values than a round holds
+// spreads over several rounds (the lane keeps key and span in registers); an entry without values writes nothing.  Offsets are 64-bit:
+// 128 spans of one pool may add up to more than 2^32 values.  false (uniform) = some update found the table full.
+__device__ __forceinline__ uint64_t group_wave_scan64(uint64_t v, uint64_t& total) { // inclusive prefix sum over the lanes; total = lane 63's
+  v = group_dpp_add64<0x111, 0xf>(v);
+  v = group_dpp_add64<0x112, 0xf>(v);
+  v = group_dpp_add64<0x114, 0xf>(v);
+  v = group_dpp_add64<0x118, 0xf>(v);
+  v = group_dpp_add64<0x142, 0xa>(v);
+  v = group_dpp_add64<0x143, 0xc>(v);
+  total = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+  return v;
+}
+constexpr uint32_t GRP_MVA_ROUND = 128; // pairs per round: what cbuf / cbuf2 hold (MRK_CBUF, RK_CBUF)
+
+__device__ __forceinline__ bool group_flush_wave_mva(const GroupTable& T, uint64_t* cbuf, uint64_t* cbuf2, uint32_t cn, uint32_t lane, const uint32_t* __restrict__ attrs,
+                                                     uint32_t attr_stride, uint32_t rowid_base, const uint8_t* __restrict__ blobs, uint32_t mva) {
+  const bool v0 = lane < cn, v1 = lane + 64u < cn;
+  const uint64_t k0 = v0 ? cbuf[lane] : 0ull, k1 = v1 ? cbuf[lane + 64u] : 0ull;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  MvaSpan s0{nullptr, 0u}, s1{nullptr, 0u};
+  if (v0) s0 = blob_mva_span(blobs, attrs + (uint64_t)(key_rowid(k0) - rowid_base) * attr_stride, mva);
+  if (v1) s1 = blob_mva_span(blobs, attrs + (uint64_t)(key_rowid(k1) - rowid_base) * attr_stride, mva);
+  uint64_t t0, t1;
+  const uint64_t o0 = group_wave_scan64(s0.n, t0) - s0.n;      // the lane's first entry: its first pair's number
+  const uint64_t o1 = t0 + group_wave_scan64(s1.n, t1) - s1.n; // ... and its second entry's, behind all the first ones
+  const uint64_t total = t0 + t1;
+  bool ok = true;
+  for (uint64_t base = 0; base < total; base += GRP_MVA_ROUND) { // (uniform)
+    auto fill = [&](uint64_t o, const MvaSpan& s, uint64_t k) {  // the entry's pairs numbered [base, base + GRP_MVA_ROUND)
+      const uint64_t lo = base > o ? base - o : 0ull;
+      const uint64_t room = o >= base + GRP_MVA_ROUND ? 0ull : base + GRP_MVA_ROUND - o;
+      const uint64_t hi = room < s.n ? room : s.n;
+      for (uint64_t i = lo; i < hi; ++i) {
+        const uint32_t at = (uint32_t)(o + i - base); // (< GRP_MVA_ROUND)
+        cbuf[at] = k;
+        cbuf2[at] = blob_mva_value32(s, (uint32_t)i);
+      }
+    };
+    fill(o0, s0, k0);
+    fill(o1, s1, k1);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const uint64_t left = total - base;
+    ok = group_flush_wave(T, cbuf, cbuf2, left < GRP_MVA_ROUND ? (uint32_t)left : GRP_MVA_ROUND, lane) && ok; // (ends behind a fence: the buffers are free again)
+  }
+  return ok;
 }
 #endif // __HIPCC__
 

@@ -776,6 +776,7 @@ struct PlanState {
   const uint32_t qi;
   const mrk_group* const group; // mrk_batch_submit_grouped's spec for this query, or NULL
   const mrk_aggrs* const aggrs; // mrk_batch_submit_aggr's aggregates for this (grouped) query, or NULL
+  const mrk_group_mva* const mva; // mrk_batch_submit_mva's multi-value group attribute for this (grouped) query, or NULL
   // what the stages work out, in their order
   KeySpec order;
   bool filtered = false; // the query reads attribute rows: the packed block scan's EXT instances only
@@ -883,12 +884,34 @@ struct PlanState {
     if (G.sort_by != MRK_GROUPSORT_KEY && G.sort_by != MRK_GROUPSORT_COUNT && G.sort_by != MRK_GROUPSORT_WEIGHT)
       return mrk_fail(MRK_E_INVAL, "query %u: group sort_by %d", qi, G.sort_by);
     if (G.desc != 0 && G.desc != 1) return mrk_fail(MRK_E_INVAL, "query %u: group desc %d (0 or 1)", qi, G.desc);
+    if (mva) return resolve_group_mva();
     if (G.bit_offset < 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: group by a blob-stored or computed attribute (no row locator)", qi);
     if (G.bit_count == 64 && (G.bit_offset & 31) == 0 && seg->dev.attrs && (uint64_t)G.bit_offset + 64 <= (uint64_t)seg->dev.attr_stride * 32)
       return mrk_fail(MRK_E_UNSUPPORTED, "query %u: group by a 64-bit attribute (device path: <= 32 bits)", qi);
     if (int rc = check_key_locator(qi, "group", "group key", MRK_SORTKEY_INT, G.bit_offset, G.bit_count)) return rc;
     if (seg->dev.attrs && seg->dev.attr_stride)
       if (int rc = check_key_in_row(seg, qi, "group", G.bit_offset, G.bit_count)) return rc;
+    if (q.sort || q.order) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: a group next to mrk_query.sort / mrk_query.order (the within-group order is relevance)", qi);
+    if (!seg->dev.attrs || seg->h_attrs.empty())
+      return mrk_fail(MRK_E_UNSUPPORTED, "query %u: grouping by an attribute needs the segment's attribute rows (mrk_segment_set_attrs)", qi);
+    if (!use_packed) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: grouped queries run on the packed path only", qi);
+    if (q.cutoff > 0) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: cutoff next to a group (which rows count depends on the scan order)", qi);
+    return MRK_OK;
+  }
+  // mrk_group_mva: the group's attribute is a multi-value attribute in the blob pool; mrk_group's locator is ignored, its order was
+  // checked above.  The tests and the wording of an MVA filter (translate_filter), then what the device declines, then what declines
+  // every group
+  int resolve_group_mva() const {
+    const mrk_group_mva& M = *mva;
+    if (M.mva_bits != 32 && M.mva_bits != 64) return mrk_fail(MRK_E_INVAL, "query %u: MVA width %d", qi, M.mva_bits);
+    if (M.n_blob_attrs < 1 || M.n_blob_attrs > 255 || M.blob_attr_id < 0 || M.blob_attr_id >= M.n_blob_attrs)
+      return mrk_fail(MRK_E_INVAL, "query %u: blob attribute %d of %d (the segment's rows hold %u)", qi, M.blob_attr_id, M.n_blob_attrs, seg->n_blob_attrs);
+    if (!seg->dev.blobs) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: grouping by an MVA needs the segment's blob pool (mrk_segment_set_blobs)", qi);
+    if ((uint32_t)M.n_blob_attrs != seg->n_blob_attrs)
+      return mrk_fail(MRK_E_INVAL, "query %u: blob attribute %d of %d (the segment's rows hold %u)", qi, M.blob_attr_id, M.n_blob_attrs, seg->n_blob_attrs);
+    if (seg->dev.attr_stride < 4) return mrk_fail(MRK_E_INVAL, "query %u: rows of %u dwords hold no blob locator", qi, seg->dev.attr_stride);
+    if (M.mva_bits == 64) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: group by a 64-bit MVA (device path: the group key has 32 bits)", qi);
+    if (aggrs) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: aggregates next to a group by an MVA (one accumulator slot per match, not per pushed value)", qi);
     if (q.sort || q.order) return mrk_fail(MRK_E_UNSUPPORTED, "query %u: a group next to mrk_query.sort / mrk_query.order (the within-group order is relevance)", qi);
     if (!seg->dev.attrs || seg->h_attrs.empty())
       return mrk_fail(MRK_E_UNSUPPORTED, "query %u: grouping by an attribute needs the segment's attribute rows (mrk_segment_set_attrs)", qi);
@@ -945,6 +968,8 @@ struct PlanState {
     dq.cand_cap = dq.sort_cap = 0;
     dq.grp_on = 1;
     dq.grp_item = (uint32_t)G.bit_offset >> 5, dq.grp_shift = (uint32_t)G.bit_offset & 31u, dq.grp_bits = (uint32_t)G.bit_count;
+    if (mva) // the values come from the blob pool at the flush: the scan's read of the group dword reads the row's first, and is ignored
+      dq.grp_item = 0, dq.grp_shift = 0, dq.grp_bits = 32, dq.grp_pad = group_mva_word((uint32_t)mva->mva_bits, (uint32_t)mva->blob_attr_id, (uint32_t)mva->n_blob_attrs);
     dq.grp_sort_by = (uint32_t)G.sort_by, dq.grp_desc = (uint32_t)G.desc;
     dq.grp_slots = group_slots_for((uint32_t)q.max_matches);
     dq.grp_off = plan.group_total;
@@ -1638,9 +1663,10 @@ struct PlanState {
 };
 
 int mrk::plan_query(const mrk_segment* seg, const mrk_query& q, int64_t item_bytes, bool use_packed, DevQuery& dq, uint32_t n_queries, uint32_t qi,
-                    BatchPlan& plan, uint32_t rowid_max, const mrk_group* group, const mrk_aggrs* aggrs) {
+                    BatchPlan& plan, uint32_t rowid_max, const mrk_group* group, const mrk_aggrs* aggrs, const mrk_group_mva* mva) {
   memset(&dq, 0, sizeof dq);
-  PlanState S{seg, q, use_packed, qi, group, aggrs};
+  PlanState S{seg, q, use_packed, qi, group, aggrs, mva};
+  if (mva && !group) return mrk_fail(MRK_E_INVAL, "query %u: a multi-value group attribute without a group", qi);
   // validate: hostile order / sort specs are MRK_E_INVAL before a row is read
   if (int rc = S.resolve_order()) return rc;
   dq.item_first = (uint32_t)plan.items.size();

@@ -36,7 +36,8 @@ struct __align__(16) RkSmem {
 // WIDE: a segment with 9-32 fields -- 32 field weights and ranker bytes; queues 0 / 1 carry the doc's whole field mask in one more
 // plane behind the narrow entry (the generic evaluator reads it from pk_fmask itself)
 // SORT: the batch holds queries ordered by a row attribute (mrk_query.sort); instances of their own (see scan_pk_kernel)
-// AGGR: the batch holds grouped queries with aggregates: the SORT instances once more with the accumulators' flush (see scan_pk_kernel)
+// AGGR: the batch holds grouped queries with aggregates or a multi-value group: the SORT instances once more with the flushes that read
+// the rows again (see scan_pk_kernel)
 template <int MODE, bool WIDE = false, bool SORT = false, bool AGGR = false>
 __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   constexpr bool FAT = MODE == 1, GEN = MODE == 2;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
   bool grouped = false;
   uint32_t gr_item = 0, gr_shift = 0, gr_bits = 32;
   GroupTable gtable = group_table_at(nullptr, 8u);
-  const DevQuery* gr_q = a.queries; // the descriptor the aggregates' locators are read from at a flush (any pass of the query holds them)
+  const DevQuery* gr_q = a.queries; // the descriptor the aggregates' locators and the MVA word are read from at a flush (any pass of the query holds them)
   uint32_t *ghist = nullptr, *gcount = nullptr, *gtaubin = nullptr;
 
   auto publish = [&]() __attribute__((always_inline)) { // (always_inline: with the aggregates' flush in it the AGGR instances would call it, closure and kernel arguments in scratch)
@@ -92,6 +93,11 @@ __global__ __launch_bounds__(WG) void rank_kernel(ScanArgs a) {
           if (cn && gr_q->grp_naggr) { // (uniform) ... and the aggregates' accumulators behind them, from the rows
             if (!group_flush_wave_aggr(gtable, L.cbuf, L.cbuf2, cn, lane, a.seg.attrs, a.seg.attr_stride, a.seg.rowid_base, gr_q->grp_naggr, gr_q->grp_aggr_item, gr_q->grp_aggr_op) && lane == 0)
               atomicOr(a.q_flags + cur_oq, QF_GROUPS);
+            cn = 0;
+            return;
+          }
+          if (cn && gr_q->grp_pad) { // (uniform) grouped by a multi-value attribute: one push per stored value, from the rows' blob rows
+            if (!group_flush_wave_mva(gtable, L.cbuf, L.cbuf2, cn, lane, a.seg.attrs, a.seg.attr_stride, a.seg.rowid_base, a.seg.blobs, gr_q->grp_pad) && lane == 0) atomicOr(a.q_flags + cur_oq, QF_GROUPS);
             cn = 0;
             return;
           }

@@ -80,8 +80,9 @@ struct __align__(16) PkSmem {
 // batches launch stay as they are
 // (the WIDE instance that carries the sort sat at 168 VGPRs, the most that lets three waves share a SIMD; the group update's two more
 // would cost it the third wave, so that instance asks the register allocator for three -- every other instance is compiled as before)
-// AGGR: the batch holds grouped queries with aggregates (mrk_aggrs): the SORT instances once more with the accumulators' flush
-// (group_flush_wave_aggr), so that the ones every other sorted or grouped batch launches stay as they are
+// AGGR: the batch holds grouped queries whose flush reads the rows again -- aggregates (mrk_aggrs, group_flush_wave_aggr) or a group by
+// a multi-value attribute (mrk_group_mva, group_flush_wave_mva): the SORT instances once more with those flushes, so that the ones every
+// other sorted or grouped batch launches stay as they are
 template <bool PROX, bool TREE, bool EXT = false, int NREF = MAX_PROX_TERMS, bool WIDE = false, bool SORT = false, bool AGGR = false>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE && SORT && !AGGR && NREF == MAX_PROX_TERMS ? 3 : 1))) void scan_pk_kernel(ScanArgs a) {
   constexpr int NF = WIDE ? 32 : 8;
@@ -215,6 +216,13 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WIDE && SORT
           if (cn && Q->grp_naggr) { // (uniform) ... and the aggregates' accumulators behind them, from the rows
             if (!group_flush_wave_aggr(group_table_at(a.gtab + Q->grp_off, Q->grp_slots), L.cbuf, L.cbuf2, cn, lane, a.seg.attrs, a.seg.attr_stride, a.seg.rowid_base, Q->grp_naggr,
                                        Q->grp_aggr_item, Q->grp_aggr_op) &&
+                lane == 0)
+              atomicOr(a.q_flags + oq, QF_GROUPS);
+            cn = 0;
+            return;
+          }
+          if (cn && Q->grp_pad) { // (uniform) grouped by a multi-value attribute: one push per stored value, from the rows' blob rows
+            if (!group_flush_wave_mva(group_table_at(a.gtab + Q->grp_off, Q->grp_slots), L.cbuf, L.cbuf2, cn, lane, a.seg.attrs, a.seg.attr_stride, a.seg.rowid_base, a.seg.blobs, Q->grp_pad) &&
                 lane == 0)
               atomicOr(a.q_flags + oq, QF_GROUPS);
             cn = 0;
@@ -1016,7 +1024,7 @@ void launch_scan_pk(const ScanArgs& a, uint32_t max_terms, bool prox, bool tree,
   if (max_terms < 1) max_terms = 1;
   const size_t tail = (size_t)(max_terms - 1) * 256 * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (a.scand && a.grp_aggr) { // ... and grouped queries with aggregates: the same instances with the accumulators' flush
+  if (a.scand && a.grp_aggr) { // ... and grouped queries with aggregates or a multi-value group: the same instances with the flushes that read the rows again
     if (a.seg.pk_fmask)
       gen ? launch_pk<true, true, true, MRK_MAX_AND_TERMS, true, true, true>(a, tail, st) : launch_pk<true, true, true, MAX_PROX_TERMS, true, true, true>(a, tail, st);
     else

@@ -338,7 +338,8 @@ def merge_grows_np(grows_all: np.ndarray, k: int) -> np.ndarray:
             if len(values) > GROUPBY_FACTOR * kq or (len(values) and int(counts.max()) > 0xFFFFFFFF):
                 flags |= ROW_DECLINED
             else:
-                order = np.argsort(group_order_keys(sort_by, desc, values, counts.astype(np.uint32), head))[::-1]
+                # (descending by the order key; equal keys -- groups of a multi-value attribute that one doc heads -- the smaller value first)
+                order = np.lexsort((values, ~group_order_keys(sort_by, desc, values, counts.astype(np.uint32), head)))
                 n = len(values)
                 out[q, :n] = head[order]
                 out[q, GROW_PLANE:GROW_PLANE + n] = (values[order].astype(np.uint64) << np.uint64(32)) | counts[order]
@@ -478,7 +479,7 @@ def merge_arows_np(arows_all: np.ndarray, k: int) -> np.ndarray:
                     okeys = ((p if desc else ~p).astype(np.uint64) << np.uint64(32)) | (head & np.uint64(0xFFFFFFFF))
                 else:
                     okeys = group_order_keys(sort_by, desc, values, counts.astype(np.uint32), head)
-                order = np.argsort(okeys)[::-1]
+                order = np.lexsort((values, ~okeys))  # (descending by the order key, equal keys the smaller value first: as merge_grows_np)
                 n = len(values)
                 out[q, :n] = head[order]
                 out[q, GROW_PLANE:GROW_PLANE + n] = (values[order].astype(np.uint64) << np.uint64(32)) | counts[order]
