@@ -427,7 +427,11 @@ int mrk_ctx_destroy(mrk_ctx* ctx);
    kernel over bitmap words are cut into, defaults 2^20 / 6144) and "bm_min_windows" (windows per work item of the AND kernel, default
    256; 128 before "bm_place": since work items of different queries interleave -- "item_order", a mask: 1 block scan, 2 bitmap AND, 4 bitmap trees, 8 also in
    batches that feed the hit pass; default 7 -- small items are the fast ones); "pk_min_items" (a batch with fewer block-scan work items
-   has its block ranges cut finer, default 2048);
+   has its block ranges cut finer, default 2048; 1 = the planner's items stay as they are);
+   "p2_max_blocks" (a launch on the lean block-scan instance -- "pair_scan" -- keeps no work item longer than this many driver blocks,
+   a multiple of the 4 waves of a workgroup: a wave there is a chain of dependent round trips per driver block, and the launch lasts as
+   long as its longest waves; part of the same recut as "pk_min_items", so off with pk_min_items = 1; 0 = no cap; default 4, one block per
+   wave; read at submit; a speed hint only);
    "pair_scan" (1 = a batch whose block-scan launch needs none of the generic kernel's machinery -- queries of one or two keywords under
    NONE / BM25 / single-keyword PROXIMITY, no trees, phrases, position modifiers, filters or sort, a segment of <= 8 fields packed with
    bitmap_inv != 0 -- runs that launch on a lean instance of the kernel: twice the waves per SIMD and a shorter chain of dependent loads per

@@ -360,6 +360,11 @@ extern "C" int mrk_ctx_set(mrk_ctx* c, const char* key, int64_t value) {
     c->pk_min_items = (int)value;
     return MRK_OK;
   }
+  if (!strcmp(key, "p2_max_blocks")) {
+    if (value < 0 || value > (1 << 20)) return mrk_fail(MRK_E_INVAL, "p2_max_blocks must be 0 .. 2^20");
+    c->p2_max_blocks = (int)value;
+    return MRK_OK;
+  }
   if (!strcmp(key, "pair_scan")) {
     if (value < 0 || value > 1) return mrk_fail(MRK_E_INVAL, "pair_scan must be 0 or 1");
     c->pair_scan = (int)value;
@@ -1345,13 +1350,16 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   b->gen_progs.swap(plan.gen_progs); // (copied to the device below: they live until the next submit)
   // ---- launch layout (mrk_plan.cpp): the items in launch order, the scan_bm groups, the match queues' sizes
   const mrk_ctx* c = b->ctx;
-  const mrk::LayoutKnobs knobs{c->pk_min_items, c->item_order, c->bm_target_items, c->bm_min_windows, c->bt_target_items, c->bm_group, c->mq_max_chunks};
+  LaunchShape shape{max_terms, plan.any_prox, plan.any_tree, any_ext, use_packed && (plan.sort_total != 0 || plan.group_total != 0), false, use_packed && plan.group_total != 0};
+  // (the lean instance's chains of round trips want short items: the cap rides with the recut pass, which pk_min_items = 1 turns off)
+  const bool lean = use_packed && lean_scan_ok(c, seg, shape);
+  const mrk::LayoutKnobs knobs{c->pk_min_items, c->item_order, c->bm_target_items, c->bm_min_windows, c->bt_target_items, c->bm_group, c->mq_max_chunks,
+                               lean && c->pk_min_items > 1 ? c->p2_max_blocks : 0};
   mrk::BatchLayout lay;
   mrk::layout_batch(b->h_queries.p, n, plan, use_packed, seg->dev.pk_attr1 != nullptr, knobs, lay);
   const float plan_ms = std::chrono::duration<float, std::milli>(lay.t_block_items - t_submit0).count(); // (up to the block-scan section in order)
   const size_t n_items = lay.items.size(), n_items_pk = lay.n_items_pk;
   const uint64_t cand_total = plan.cand_total;
-  LaunchShape shape{max_terms, plan.any_prox, plan.any_tree, any_ext, use_packed && (plan.sort_total != 0 || plan.group_total != 0), false, use_packed && plan.group_total != 0};
   b->any_grouped = shape.group;
   b->any_aggr = shape.group && any_aggr;
   for (uint32_t i = 0; i < n && !b->gen_progs.empty(); ++i) shape.nearn = shape.nearn || (b->h_queries.p[i].tree_flags & mrk::TF_GEN_NEARN) != 0;
@@ -1448,7 +1456,6 @@ static int mrk_batch_submit_impl(mrk_batch* b, mrk_segment* seg, const mrk_query
   HIP_TRY(hipEventRecord(b->ev_scan0, st));
   b->stats.pk_lean = 0;
   if (use_packed) {
-    const bool lean = lean_scan_ok(c, seg, shape);
     b->stats.pk_lean = lean && n_items_pk ? 1u : 0u;
     if ((rc = launch_packed(sa, n_items_pk, lay.n_items_kind, mq_chunks, shape, n_group_slots ? (const BmGroup*)(b->d_items.p + n_items) : nullptr, lean, st))) return rc;
   } else

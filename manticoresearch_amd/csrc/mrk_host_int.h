@@ -46,6 +46,7 @@ struct mrk_ctx {
   int bm_group = 1;               // two-bitmap AND kernel: queries that share a keyword run in one workgroup, a wave per member (0 = a workgroup per query)
   int pair_scan = 1;              // block-scan launches of plain one- and two-keyword queries take the lean instance (mrk_scan_p2.hip); 0 = the generic one
   int pk_min_items = 2048;        // block-scan kernel: a batch with fewer work items has its block ranges cut finer (>= one block per wave)
+  int p2_max_blocks = 4;          // ... and a launch on the lean instance keeps no work item longer than this many driver blocks (a multiple of the 4 waves; 0 = no cap; pk_min_items = 1 turns the whole recut off, this cap included)
   int exchange_part = 1;          // mrk_shard_exchange partitions the merge by query (all-to-all of row slices); 0 = all-gather, every rank merges everything
   int prox_prune = 1;             // proximity rankers: matches whose weight upper bound cannot reach the top K skip the hit pass (counted, not ranked)
   int exchange_self_rccl = 0;     // one rank: still send the rows to itself through RCCL (rehearsal of the collective path)
@@ -193,6 +194,7 @@ uint64_t pass_max_matches(const DevQuery& P);
 // queries that share a keyword put in groups, the match queues sized.
 struct LayoutKnobs { // the context's settings of the same names
   int pk_min_items, item_order, bm_target_items, bm_min_windows, bt_target_items, bm_group, mq_max_chunks;
+  int p2_max_blocks; // longest block-scan item, in driver blocks (0 = no cap): mrk_batch_submit sets it for launches on the lean instance
 };
 struct BatchLayout {
   std::vector<DevItem> items;       // launch order: block-scan items, then kind 0 (scan_bm), kind 1 (scan_bt), kind 2 (generic evaluator)

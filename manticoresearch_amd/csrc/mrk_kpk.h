@@ -69,4 +69,48 @@ __device__ __forceinline__ void decode_pk(const PkRaw& raw, uint32_t w, uint32_t
   r1 = bp1 + o1;
 }
 
+// ---- one doc of a block on its own: offsets are stored at a fixed width from the block base, so slot i needs no other slot.
+// (host code too: tests/cpp/pk_probe.cpp runs these against the plain decode)
+
+// the window of `sh` + 32 bits that decode_pk reads
+__host__ __device__ inline uint32_t pk_alignbit(uint32_t hi, uint32_t lo, uint32_t sh) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_alignbit(hi, lo, sh);
+#else
+  return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31u));
+#endif
+}
+
+// offset from the block base of doc i (0 .. 127) of the block whose words start at dp; w: its width.  A narrow block's doc i
+// lives in value slot 2 * (i & 63) + (i >> 6); the two-word read stays inside the block's 4 * w + 1 words.  w == 0: one doc, offset 0
+// (slots past the block's docs hold zeros: the caller compares i with the doc count)
+__host__ __device__ inline uint32_t pk_doc_off(const uint32_t* __restrict__ dp, uint32_t w, uint32_t i) {
+  if (w == PK_WIDE) return dp[i];
+  if (w == 0) return 0u;
+  const uint32_t bit = (2u * (i & 63u) + (i >> 6)) * w;
+  struct __attribute__((packed, aligned(4))) Pair {
+    uint32_t lo, hi;
+  };
+  const Pair pr = *reinterpret_cast<const Pair*>(dp + (bit >> 5));
+  return pk_alignbit(pr.hi, pr.lo, bit & 31u) & ((1u << w) - 1u);
+}
+
+// one step of the lower bound below: doc `at`'s offset against `want`; a doc index past the block's docs compares as +infinity
+__host__ __device__ inline bool pk_doc_below(uint32_t off_at, uint32_t at, uint32_t nd, uint32_t want) { return at < nd && off_at < want; }
+
+// Lower bound over the docs of one block in seven fixed steps: the number of docs among the block's first 127 whose offset is below
+// `want`, i.e. min(index of the first doc with offset >= want, 127).  A hit is pos < nd && pk_doc_off(pos) == want; with all 128 docs
+// below `want` the result is 127, whose offset differs from `want`.
+// This function is the host-side model of the kernel's loop, not the loop itself: scan_p2_kernel writes the same seven steps out
+// for a lane's two docs side by side, so that both docs' reads of a step are in flight together.  What the two share, and what
+// tests/cpp/pk_probe.cpp therefore checks of the device code, are the step's parts: pk_doc_off and pk_doc_below.
+__host__ __device__ inline uint32_t pk_lower_bound(const uint32_t* __restrict__ dp, uint32_t w, uint32_t nd, uint32_t want) {
+  uint32_t pos = 0;
+  for (uint32_t step = DEVBLK / 2; step; step >>= 1) {
+    const uint32_t at = pos + step - 1;
+    if (pk_doc_below(pk_doc_off(dp, w, at), at, nd, want)) pos += step;
+  }
+  return pos;
+}
+
 } // namespace mrk

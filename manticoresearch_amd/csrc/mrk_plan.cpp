@@ -2173,11 +2173,19 @@ void mrk::layout_batch(DevQuery* head, uint32_t n, BatchPlan& plan, bool use_pac
   // A small batch (one-eighth shards, selective keywords, a lone query): the planner cuts a driver doclist into ~item_bytes
   // pieces whatever the batch holds, and 280 workgroups that each walk 70 blocks per wave one after the other leave the chip
   // idle for 0.1 ms.  Cut the block ranges finer until the launch has pk_min_items work items (never under one block per wave).
-  if (use_packed && !items.empty() && items.size() < (size_t)knobs.pk_min_items) {
+  // A launch on the lean instance (p2_max_blocks): a wave there is a chain of dependent round trips per driver block, and the launch
+  // lasts as long as its longest waves, so no item keeps more than the cap's blocks however many items the launch already has.
+  // The piece length is the smaller of the two rules', a multiple of T0_BLOCKS.
+  const bool few = items.size() < (size_t)knobs.pk_min_items;
+  if (use_packed && !items.empty() && (few || knobs.p2_max_blocks > 0)) {
     uint64_t total_blocks = 0;
     for (const DevItem& it : items) total_blocks += it.blk_end - it.blk_begin;
-    uint64_t per = (total_blocks + (uint64_t)knobs.pk_min_items - 1) / (uint64_t)knobs.pk_min_items;
-    per = std::max<uint64_t>(T0_BLOCKS, (per + T0_BLOCKS - 1) / T0_BLOCKS * T0_BLOCKS);
+    uint64_t per = ~0ull;
+    if (few) {
+      per = (total_blocks + (uint64_t)knobs.pk_min_items - 1) / (uint64_t)knobs.pk_min_items;
+      per = std::max<uint64_t>(T0_BLOCKS, (per + T0_BLOCKS - 1) / T0_BLOCKS * T0_BLOCKS);
+    }
+    if (knobs.p2_max_blocks > 0) per = std::min<uint64_t>(per, std::max<uint64_t>(T0_BLOCKS, (uint64_t)knobs.p2_max_blocks / T0_BLOCKS * T0_BLOCKS));
     std::vector<DevItem> cut;
     cut.reserve(items.size() + (size_t)(total_blocks / per) + 1);
     std::vector<uint32_t> per_pass((size_t)n + extra.size(), 0);

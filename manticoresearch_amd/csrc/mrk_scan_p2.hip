@@ -9,8 +9,11 @@
 //   * no per-workgroup tables and no workgroup barrier: tfidf(tf) is the reference's three fp32 operations per doc and
 //     the field-weight sum a loop over <= 8 scalars, both cheaper here than a table fill for 128 docs;
 //   * no LDS histogram and no direct rowid -> slot map: candidates' bins go to the query's histogram with one atomic per
-//     distinct bin (hist_add_keys), a slot of a decoded block is found by binary search.  A keyword dense enough for the
-//     map carries a bitmap and is probed through it.  LDS is 7 KB per workgroup;
+//     distinct bin (hist_add_keys).  A keyword dense enough for the map carries a bitmap and is probed through it;
+//   * a sparse second keyword is never decoded block by block: each driver doc finds its own block in the register chunk of
+//     the block index and its slot by a lower bound over the packed words themselves (mrk_kpk.h, pk_doc_off), so a driver
+//     block costs the same chain of round trips whether its docs fall into one block of that keyword or into sixty.  LDS is
+//     the candidate buffer alone, 4 KB per workgroup;
 //   * the wave's first loads -- overflow flag, threshold word, block-index chunk -- are requested together;
 //   * the dense probe asks for the rank-directory word only in lanes whose bit is set (a second 128-byte line per driver
 //     doc otherwise, needed by the few that match): one more dependent round trip, measured 11 % faster than asking for it
@@ -26,9 +29,7 @@ namespace {
 constexpr int P2_CBUF = 128; // candidates a wave collects before it publishes them
 
 struct __align__(16) P2WaveLds {
-  uint64_t cbuf[P2_CBUF];      // candidates not yet published to the query's global list
-  uint32_t tj_rowid[DEVBLK];   // the decoded block of the other keyword: rowids by slot ...
-  uint32_t tj_attr[64];        // ... and its tf / field words
+  uint64_t cbuf[P2_CBUF]; // candidates not yet published to the query's global list
 };
 
 // LDS hand-off between lanes of ONE wave.  A wave's DS instructions execute in issue order, so wavefront-scope fences --
@@ -39,6 +40,9 @@ __device__ __forceinline__ void p2_lds_fence() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+// v of lane l (0 .. 63), l a per-lane value; the source lane must be active
+__device__ __forceinline__ uint32_t lane_read(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l << 2), (int)v); }
 
 } // namespace
 
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(WG, 8) void scan_p2_kernel(ScanArgs a) {
 
   uint32_t total = 0, cn = 0, flush_at = 64;
   cj.first = NOBLK;
-  uint32_t slot_blk = NOBLK, kj = 0;
+  uint32_t kj = 0;
   uint32_t gt_new = 0;
 
   // publish the wave's buffered candidates: reserve a slice of the query's list with ONE atomic, write it coalesced, add
@@ -251,6 +255,11 @@ __global__ __launch_bounds__(WG, 8) void scan_p2_kernel(ScanArgs a) {
           }
         }
       } else {
+        // Sparse keyword: every waiting doc finds its OWN block in the register chunk and its slot in that block by a lower
+        // bound straight over the packed words (pk_doc_off: any slot of any block can be read on its own) -- the depth of the
+        // chain is the same whether the driver block's docs fall into one block of this keyword or into sixty.
+        // The shared threshold word rides along once per driver block.
+        gt_new = __hip_atomic_load(gtaubin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         for (;;) {
           // smallest driver rowid still waiting for this keyword (docs are in rowid order lane by lane)
           const uint64_t p0 = __ballot(!done[0]), p1 = __ballot(!done[1]);
@@ -260,75 +269,73 @@ __global__ __launch_bounds__(WG, 8) void scan_p2_kernel(ScanArgs a) {
           if (cj.first == NOBLK || kj < cj.first || kj - cj.first >= (uint32_t)CHUNK) load_pk_chunk(cj, a.seg, Tj, kj);
           {
             const uint64_t le = __ballot(cj.bp1 <= r_min);
-            uint32_t p = le ? 63u - (uint32_t)__builtin_clzll(le) : 0u;
+            const uint32_t p = le ? 63u - (uint32_t)__builtin_clzll(le) : 0u;
             if (p >= (uint32_t)CHUNK) { // beyond this chunk: wave-wide 64-ary search, then reload
               kj = wave_find_block(a.seg.pk_base + Tj.blk_first, cj.first + CHUNK - 1, Tj.nblocks, r_min);
               load_pk_chunk(cj, a.seg, Tj, kj);
-              p = 0;
-            }
-            const uint32_t k_new = cj.first + p;
-            if (k_new > kj) kj = k_new;
+            } else if (cj.first + p > kj)
+              kj = cj.first + p;
           }
-          const uint32_t ci = kj - cj.first;
-          const uint32_t bp1_k = rdlane(cj.bp1, ci), bp1_n = rdlane(cj.bp1, ci + 1);
-          if (slot_blk != kj) {
-            const PkRaw rj = issue_pk(a.seg, Tj, cj, ci);
-            // the shared threshold word rides along with the block
-            gt_new = __hip_atomic_load(gtaubin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t wj = rdlane(cj.w, ci);
-            const uint32_t leftj = Tj.docs - kj * DEVBLK;
-            const uint32_t ndj = leftj < (uint32_t)DEVBLK ? leftj : (uint32_t)DEVBLK;
-            uint32_t e0, e1, f0, f1;
-            bool k0, k1;
-            decode_pk(rj, wj, bp1_k, ndj, e0, e1, f0, f1, k0, k1);
-            L.tj_rowid[lane] = k0 ? e0 : INF_ROWID;
-            L.tj_rowid[lane + 64] = k1 ? e1 : INF_ROWID;
-            L.tj_attr[lane] = rj.attr;
-            slot_blk = kj;
-            p2_lds_fence();
+          // own block: p = the chunk's last entry with bp1 <= row, six fixed steps over the chunk's registers (the loop is
+          // wave-uniform: every source lane is active).  Entry 63 only bounds block 62: a doc with p == 63 waits for the next
+          // pass, whose chunk starts at or behind its block.
+          uint32_t p[2] = {0u, 0u}, bp[2];
+          bp[0] = bp[1] = rdlane(cj.bp1, 0);
+#pragma unroll
+          for (uint32_t step = 32; step; step >>= 1) {
+            uint32_t v[2];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) v[r] = lane_read(cj.bp1, p[r] + step);
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+              if (v[r] <= row[r]) p[r] += step, bp[r] = v[r];
           }
-          // probe: driver docs that fall into [bp1_k, bp1_n).  Both docs of a lane go through the dependent LDS reads side
-          // by side (binary search -> {rowid, attr}) instead of one after the other.
-          {
-            bool inr[2];
-            uint32_t pos[2] = {0u, 0u}, want[2];
+          bool act[2];
+          uint32_t wj[2], want[2], ndj[2], pos[2] = {0u, 0u};
+          const uint32_t* __restrict__ dp[2];
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-              inr[r] = !done[r] && row[r] >= bp1_k && row[r] < bp1_n;
-              done[r] = done[r] || inr[r];
-              want[r] = inr[r] ? row[r] : 0u;
-            }
+          for (int r = 0; r < 2; ++r) {
+            wj[r] = lane_read(cj.w, p[r]);
+            dp[r] = a.seg.pk_delta + lane_read(cj.doff, p[r]);
+            const bool here = !done[r] && p[r] < (uint32_t)CHUNK;
+            done[r] = done[r] || here;
+            act[r] = here && row[r] >= bp[r]; // (a row below the chunk's first block cannot happen: the cursor only moves forward)
+            want[r] = row[r] - bp[r];
+            const uint32_t leftj = Tj.docs - (cj.first + p[r]) * DEVBLK;
+            ndj[r] = act[r] ? (leftj < (uint32_t)DEVBLK ? leftj : (uint32_t)DEVBLK) : 0u;
+          }
+          // slot in the block: both docs of a lane go through the dependent reads side by side
 #pragma unroll
-            for (uint32_t step = DEVBLK / 2; step; step >>= 1) {
-              uint32_t probe[2];
+          for (uint32_t step = DEVBLK / 2; step; step >>= 1) {
+            uint32_t o[2] = {0u, 0u};
 #pragma unroll
-              for (int r = 0; r < 2; ++r) probe[r] = L.tj_rowid[pos[r] + step - 1];
+            for (int r = 0; r < 2; ++r)
+              if (act[r]) o[r] = pk_doc_off(dp[r], wj[r], pos[r] + step - 1);
 #pragma unroll
-              for (int r = 0; r < 2; ++r)
-                if (probe[r] < want[r]) pos[r] += step;
-            }
-            uint32_t rid[2], aw[2];
+            for (int r = 0; r < 2; ++r)
+              if (pk_doc_below(o[r], pos[r] + step - 1, ndj[r], want[r])) pos[r] += step;
+          }
+          uint32_t fo[2] = {0u, 0u}, aw[2] = {0u, 0u};
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-              rid[r] = L.tj_rowid[pos[r]];
-              aw[r] = L.tj_attr[pos[r] & 63u];
-            }
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-              const uint32_t sh = (pos[r] >> 6) * 8;
-              const uint32_t tfj = (aw[r] >> sh) & 0xffu;
-              const uint32_t fj = (aw[r] >> (16 + sh)) & 0xffu & Tj.queried32;
-              if (inr[r] && rid[r] == row[r] && fj != 0) {
-                hit[r] = true;
-                const float tvx = term_tfidf(tfj == 255u ? exc_tf(a.seg, Tj, row[r]) : tfj, Tj.idf);
-                acc[r] = acc[r] + tvx;
-                fld[r] |= fj;
-              }
+          for (int r = 0; r < 2; ++r) {
+            act[r] = act[r] && pos[r] < ndj[r];
+            if (act[r]) {
+              fo[r] = pk_doc_off(dp[r], wj[r], pos[r]);
+              aw[r] = a.seg.pk_attr[(uint64_t)(Tj.blk_first + cj.first + p[r]) * 64 + (pos[r] & 63u)];
             }
           }
 #pragma unroll
-          for (int r = 0; r < 2; ++r)
-            if (!done[r] && row[r] < bp1_k) done[r] = true; // cannot happen (cursor only moves forward)
+          for (int r = 0; r < 2; ++r) {
+            const uint32_t sh = (pos[r] >> 6) * 8;
+            const uint32_t tfj = (aw[r] >> sh) & 0xffu;
+            const uint32_t fj = (aw[r] >> (16 + sh)) & 0xffu & Tj.queried32;
+            if (act[r] && fo[r] == want[r] && fj != 0) {
+              hit[r] = true;
+              const float tvx = term_tfidf(tfj == 255u ? exc_tf(a.seg, Tj, row[r]) : tfj, Tj.idf);
+              acc[r] = acc[r] + tvx;
+              fld[r] |= fj;
+            }
+          }
         }
       }
       live[0] = live[0] && hit[0];
